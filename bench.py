@@ -8,7 +8,8 @@ global batch 24) on N MI355X of one node.
 A "step" = teacher forward (eval) + student forward/backward + UnbiasedCE + contrastive/100 + 10*UnbiasedKD
 + gradient all-reduce + SGD + PolyLR on a device-resident synthetic batch (train.py:95-151 of the
 reference).  Rank 0 prints ONE JSON line; see DESIGN.md "Measurement" for the roofline and cpu_baseline
-definitions.
+definitions.  --dump-outputs DIR also writes what the last timed step computed as DIR/<name>.npy (the inputs are seeded: two
+builds run with the same arguments can be compared file for file).
 """
 import argparse
 import json
@@ -75,12 +76,18 @@ def parse():
     p.add_argument("--no_kernel_timing", action="store_true")
     p.add_argument("--no_miopen_find", action="store_true", help="skip the MIOpen solver search (default: search; ~2 min of warm-up, 25 % faster convolutions)")
     p.add_argument("--pixcon_precision", default=None, choices=["f32", "f16"])
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last one computed (its losses, a fixed sample of the student's "
+                        "updated state) as DIR/<name>.npy")
     # test hooks: run the N > 1 code path with several ranks on ONE GPU (RCCL refuses that; gloo carries CUDA tensors)
     p.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help=argparse.SUPPRESS)
     p.add_argument("--device", type=int, default=None, help=argparse.SUPPRESS)
     p.add_argument("--check_lockstep", action="store_true", help=argparse.SUPPRESS)   # test hook: ranks compare weights / statistics
     p.add_argument("--first_step_losses", action="store_true", help=argparse.SUPPRESS)   # test hook: losses of the very first iteration
-    return p.parse_args()
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
+    return args
 
 
 def build(args, device, per_rank_batch, rank):
@@ -167,6 +174,32 @@ def kernel_timing(trainer, optimizer, scheduler, images, labels, steps):
                                         "frac": staged / (ms * 1e-3) / 1e9 / STAGING_ROOF_GBS}
     out["_event_pair_overhead_us"] = 1e3 * overhead_ms
     return out
+
+
+DUMP_PER_TENSOR = 4096      # state entries larger than this are sampled (VOC 15-5: 677k elements, 2.7 MB of float32 in all)
+
+
+def dump_outputs(trainer, out_dir):
+    """What a caller of the timed step holds after its last iteration: the losses train_step returned (float64, one file each) and
+    the student's state the step updated, parameters and running statistics, as one float32 vector (student_state.npy) in
+    state_dict order.  An entry of more than DUMP_PER_TENSOR elements contributes that many elements at seeded positions of its
+    logical (NCHW) order, so the same arguments sample the same elements whatever the memory format or the build."""
+    import numpy as np
+    torch.cuda.synchronize()
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in trainer.last.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), np.asarray(float(v), dtype=np.float64))
+    net = trainer.model.module if hasattr(trainer.model, "module") else trainer.model
+    rng = np.random.default_rng(20261015)
+    parts = []
+    for t in net.state_dict().values():
+        if not t.is_floating_point():
+            continue
+        flat = t.detach().reshape(-1)
+        if flat.numel() > DUMP_PER_TENSOR:
+            flat = flat[torch.from_numpy(rng.choice(flat.numel(), DUMP_PER_TENSOR, replace=False)).to(flat.device)]
+        parts.append(flat.float().cpu())
+    np.save(os.path.join(out_dir, "student_state.npy"), torch.cat(parts).numpy())
 
 
 def cpu_baseline(args, classes):
@@ -314,6 +347,9 @@ def main():
                 if dt2 < dt:
                     dt, graphed = dt2, True
     last = {k: float(v) for k, v in trainer.last.items()}
+    if args.dump_outputs and rank == 0:
+        # before the instrumented pass below trains on; a multi-rank run's third (mailbox) phase comes later and is not in the dump
+        dump_outputs(trainer, args.dump_outputs)
     # device memory of this rank up to the end of the timed phases (the instrumented pass and the CPU baseline come later): the
     # captured step's pool included; the weight gradients' side stream keeps every layer's dZ until its join
     memory = {"peak_allocated_gb": round(torch.cuda.max_memory_allocated(device) / 2 ** 30, 2),

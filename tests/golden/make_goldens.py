@@ -3,6 +3,7 @@
 (ucd_amd.synth).  Only numeric inputs/outputs are stored; no reference source travels.
 
     python tests/golden/make_goldens.py            # writes the .npz files next to this script
+    python tests/golden/make_goldens.py check      # re-runs the fast entry points and compares with the committed files
 
 Import recipe: utils/loss.py and utils/loss_new.py load by file path with
 torch only; models/ + modules/ import with sys.path=/root/reference (models first); the third-party
@@ -91,7 +92,7 @@ def import_reference_model():
     return models, modules, segmentation_module
 
 
-OUT_DIR = os.environ.get("UCD_GOLDEN_OUT", HERE)      # the regeneration test writes into a scratch directory
+OUT_DIR = os.environ.get("UCD_GOLDEN_OUT", HERE)      # check() writes into a scratch directory
 
 
 def save(name, **arrays):
@@ -508,12 +509,41 @@ def gold_traj513(steps=20, name="ucd_traj_513_cal.npz"):
          upd2=upd2[0], upd2_norm=upd2[1], upd=upd[0], upd_norm=upd[1])
 
 
+def check():
+    """The committed recipe must run as committed (VERDICT r3 / ADVICE r3): its fast entry points are re-run into a scratch
+    directory and every array must equal the committed .npz bit for bit.  The 20-step trajectory golden takes ~4
+    minutes to regenerate; its first two iterations are re-run and must equal the committed file's prefix: per-step losses, anchor
+    / contrast counts and the sampled two-step updates + their lengths."""
+    global OUT_DIR
+    import tempfile
+    with tempfile.TemporaryDirectory(prefix="ucd_golden_check_") as OUT_DIR:
+        gold_pixcon(); gold_logit_losses(); gold_v1_losses(); gold_model(); gold_traj513(2, "ucd_traj_513_cal_head.npz")
+        made = sorted(f for f in os.listdir(OUT_DIR) if f.endswith(".npz"))
+        assert {"pixcon_voc_15_5.npz", "logit_losses.npz", "v1_losses.npz", "model_full.npz", "model_blocks.npz", "ucd_step.npz",
+                "ucd_traj_513_cal_head.npz"} <= set(made), made
+        head, full = np.load(os.path.join(OUT_DIR, "ucd_traj_513_cal_head.npz")), np.load(os.path.join(HERE, "ucd_traj_513_cal.npz"))
+        for k in ("ce", "con", "lkd", "A", "C"):
+            assert np.array_equal(head[k], full[k][:2]), k
+        for k in ("upd2", "upd2_norm"):
+            assert np.array_equal(head[k], full[k]), k
+        assert full["upd"].shape == head["upd"].shape == (8, 512) and full["upd_norm"].shape == (8,)
+        made.remove("ucd_traj_513_cal_head.npz")
+        for f in made:
+            new, old = np.load(os.path.join(OUT_DIR, f)), np.load(os.path.join(HERE, f))
+            assert sorted(new.files) == sorted(old.files), f
+            for k in new.files:
+                assert np.array_equal(new[k], old[k]), (f, k)
+        print(f"check: {len(made)} regenerated files equal the committed fixtures, the trajectory prefix too")
+
+
 if __name__ == "__main__":
     which = sys.argv[1:] or ["pixcon", "logit", "v1", "model", "cfg0", "step513", "heads", "aspp_eval", "step513_cal", "cfg3_ade",
                              "cfg4_city", "traj513"]
+    if "check" in which:                 # python tests/golden/make_goldens.py check   (writes nothing under tests/golden)
+        check()
     if "traj513" in which:
         gold_traj513()
-    if "traj513_head" in which:          # the first two iterations only (the regeneration test: equal to the committed file's prefix)
+    if "traj513_head" in which:          # the first two iterations only (check(): equal to the committed file's prefix)
         gold_traj513(2, "ucd_traj_513_cal_head.npz")
     if "cfg0" in which:
         gold_cfg0()

@@ -321,6 +321,41 @@ def test_bench_forced_collectives_on_one_gpu_match_the_plain_run(tmp_path):
     assert a["execution"]["eager_ms"] is None and a["execution"]["graph_ms"] is None      # a plain run has one phase
 
 
+def test_bench_dump_outputs_are_the_last_timed_step_and_repeat(tmp_path):
+    """bench.py --dump-outputs DIR at the benchmarked shape: after exactly --steps timed iterations it writes the losses of the last
+    one (the numbers of the JSON line) and a fixed sample of the student's updated state as float .npy files, under 64 MB.  Two runs
+    with the same arguments start from the same inputs (first-iteration losses; deterministic statistics path, UCD_STAT_ATOMIC=0) and
+    dump the same elements.  Their values are not bit-equal even on that path (measured: the first iteration's losses agree, the
+    state after the later steps does not; the random-weight network amplifies last-bit differences step by step), so the sampled state
+    is held to a relative L2 distance: measured 6e-4 between two default runs of 20 timed + 6 warm-up steps."""
+    import json
+    runs = []
+    for k in range(2):
+        d = tmp_path / f"dump{k}"
+        env = dict(os.environ, UCD_STAT_ATOMIC="0")
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "3", "--no_cpu_baseline",
+                            "--no_kernel_timing", "--first_step_losses", "--dump-outputs", str(d)],
+                           capture_output=True, text=True, env=env, timeout=600)
+        assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        out = json.loads(lines[0])
+        assert out["steps"] == 2 and out["ms_per_step"] > 0
+        files = {f: np.load(d / f) for f in os.listdir(d)}
+        assert set(files) == {f"{k}.npy" for k in out["losses"]} | {"student_state.npy"}, sorted(files)
+        assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+        assert sum(a.nbytes for a in files.values()) <= 64 << 20
+        for name, v in out["losses"].items():
+            assert float(files[f"{name}.npy"]) == v, name
+        runs.append((out, files))
+    (a, fa), (b, fb) = runs
+    for k, v in a["first_step_losses"].items():
+        assert abs(b["first_step_losses"][k] - v) <= 1e-5 * max(1.0, abs(v)), k
+    sa, sb = fa["student_state.npy"].astype(np.float64), fb["student_state.npy"].astype(np.float64)
+    assert sa.shape == sb.shape
+    assert np.linalg.norm(sa - sb) <= 1e-2 * np.linalg.norm(sa), np.linalg.norm(sa - sb) / np.linalg.norm(sa)
+
+
 def test_aborted_backward_leaves_no_widening_copies_behind():
     """at world 1 the bf16 -> fp32 widening copies of the gradient buckets are queued and flushed in finish().  A
     backward that stops before finish() (an exception inside a later node, a whole-step capture that fails) must not leave its
