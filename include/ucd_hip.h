@@ -524,8 +524,9 @@ typedef struct ucd_conv1x1_desc {
  * test_conv1x1_fused_gpu.py::test_every_pipeline_form... holds every form bit-exact on integers): single LDS stage at four workgroups
  * per CU (full grids), double buffer at two (<= 640 tiles, out_mode 4), and since round 4 the loader-wave forms - MFMA waves that
  * only multiply and loader waves that only stage - on 128-row tiles for grids of <= 256 tiles and on 256-row tiles for grids of
- * 257 .. 640 tiles that fit the chip as 256-row tiles.  The environment variable UCD_CONV_PIPE (read once per process: 2x64, 4x32,
- * 4x64, lw32, lw64, lw64x2, lw256) forces one form for every double-buffer-eligible launch; it exists for probes and A/B runs.
+ * 257 .. 640 tiles that fit the chip as 256-row tiles.  The environment variable UCD_CONV_PIPE (read once per process: 2x64, lw64,
+ * lw256; auto or unset = by the grid) forces one form for every double-buffer-eligible launch; it exists for probes and A/B runs.
+ * Any other value makes every ucd_conv1x1 call fail with UCD_EINVAL.
  * Launches of at most 128 (128 x 128) tiles (3 - 6 images per GPU) run on 128 x 64 tiles - same outputs bit for bit, twice the
  * workgroups; UCD_CONV_BN64_TILES (read once per process) sets that bound, 0 = never. */
 int ucd_conv1x1_row_tiles(int M);
@@ -618,12 +619,12 @@ int ucd_conv_wgrad_strided(const void* dz, int ld_dz, const void* x, int ld_x, i
  * SIDE STREAM (round 6, mode bit 1 / flags bit 1): nothing in a backward pass waits for a weight gradient before the optimiser, yet on
  * the caller's stream each one sits in the chain of input-gradient products - ~190 of the ~850 dependent launches of a step, which at
  * 3 - 6 images per GPU fill a quarter of the chip each.  Under ucd_conv_wgrad_defer(mode) with mode & 2, a call with flags & 2 runs
- * on a stream owned by the library (lowest priority; UCD_WGRAD_STREAM_PRIO=normal: the default priority), forked behind `stream`
+ * on a stream owned by the library (lowest priority), forked behind `stream`
  * and joined back into `stream` by ucd_conv_wgrad_flush(stream) / ucd_conv_wgrad_drop(stream); under stream capture fork and join
  * become the graph's edges.  An accepted call records its fork point on `stream` at once, its launches go out at the NEXT accepted
  * call or at the flush: in a replayed graph the branch created first keeps the fork point's hardware queue and the other one hops
- * behind a cross-queue signal - launched at the fork, the weight gradients make the CALLER's chain the one that hops, ~8 us per
- * call (UCD_WGRAD_STREAM_LATE=0; UCD_WGRAD_STREAM_GROUP=n: n calls per fork point).  flags & 2 promises: dz, x, dw / dw32 and `workspace` stay allocated and untouched by other
+ * behind a cross-queue signal - launched at the fork, the weight gradients would make the CALLER's chain the one that hops, ~8 us
+ * per call.  flags & 2 promises: dz, x, dw / dw32 and `workspace` stay allocated and untouched by other
  * streams until that flush, `workspace` is not the one of a call without the flag, and dw is not read before the flush; an error
  * of a launch made later is returned by the call that triggers it.  Results are the same bits either way (the same kernels on the
  * same operands).

@@ -1272,10 +1272,10 @@ def test_atomic_links_survive_an_arena_reset_and_refuse_a_second_fill():
         assert torch.isfinite(b).all() and _rel(b, a) < 8e-2
 
 
-@pytest.mark.parametrize("pipe", ["2x64", "4x32", "4x64", "lw32", "lw64", "lw64x2", "lw256"])
+@pytest.mark.parametrize("pipe", ["2x64", "lw64", "lw256"])
 def test_every_pipeline_form_of_the_gemm_kernel_is_exact_on_integers(pipe):
-    """The GEMM / implicit-GEMM kernel has seven pipeline forms since round 4 (double buffer, two four-stage forms, loader waves on
-    128-row tiles with 2 / 3 / 4 stages and on 256-row tiles); the library picks by grid, ``UCD_CONV_PIPE`` forces one.  Each form runs
+    """The GEMM / implicit-GEMM kernel has three forceable pipeline forms (double buffer, loader waves on 128-row tiles and on 256-row
+    tiles; the 64-row loader-wave form is taken by grid only); the library picks by grid, ``UCD_CONV_PIPE`` forces one.  Each form runs
     the plain, statistics and affine + residual + activation epilogues on sparse small integers (every output exactly representable:
     bit-exact against fp32 products, the per-tile statistics partials included) at ragged row counts, in a process of its own."""
     import subprocess
@@ -1284,6 +1284,40 @@ def test_every_pipeline_form_of_the_gemm_kernel_is_exact_on_integers(pipe):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, "-c", _PIPE_CHILD % {"root": root}], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and r.stdout.strip().endswith("ok"), (pipe, r.stdout[-500:], r.stderr[-1500:])
+
+
+_PIPE_UNKNOWN_CHILD = r"""
+import sys, torch
+sys.path.insert(0, %(root)r)
+from ucd_amd import hip
+dev = torch.device("cuda:0")
+a = torch.empty(256, 128, device=dev, dtype=torch.bfloat16)      # torch.empty: no kernel of the child runs before the call
+w = torch.empty(128, 128, device=dev, dtype=torch.bfloat16)
+y = torch.empty(256, 128, device=dev, dtype=torch.bfloat16)
+try:
+    hip.conv1x1(a, w, y)
+except RuntimeError as e:
+    print("refused:", e)
+else:
+    print("accepted")
+"""
+
+
+def test_an_unknown_pipeline_form_is_refused():
+    """A ``UCD_CONV_PIPE`` value that names no form (here ``lw128``, a form that never existed) makes
+    ``ucd_conv1x1`` fail with UCD_EINVAL before it launches anything, naming the accepted values - not fall back to the grid's
+    choice while ``bench.py``'s ``own_kernels`` reports the value.  In a process of its own: the switch is read once per process."""
+    import subprocess
+    import sys
+    env = dict(os.environ, UCD_CONV_PIPE="lw128")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, "-c", _PIPE_UNKNOWN_CHILD % {"root": root}], env=env, capture_output=True, text=True,
+                       timeout=300)
+    assert r.returncode == 0, (r.stdout[-500:], r.stderr[-1500:])
+    out = r.stdout.strip()
+    assert out.startswith("refused:") and "code -1" in out and "UCD_CONV_PIPE=lw128" in out, out
+    assert all(name in out for name in ("auto", "2x64", "lw64", "lw256")), out
+
 
 _BN64_VS_BN128 = r"""
 import sys, torch

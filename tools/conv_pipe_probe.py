@@ -1,7 +1,7 @@
-"""GPU probe: the pipeline forms of the double-buffered GEMM / implicit-GEMM kernel (csrc/conv1x1.hip: UCD_CONV_PIPE = 2x64 | 4x32 |
-4x64, read once per process - run this script once per setting) on the layer shapes of the step at 24 and at 3 images: result
+"""GPU probe: the pipeline forms of the double-buffered GEMM / implicit-GEMM kernel (csrc/conv1x1.hip: UCD_CONV_PIPE = 2x64 | lw64 |
+lw256, read once per process - run this script once per setting) on the layer shapes of the step at 24 and at 3 images: result
 against an fp32 product and time per call.
-usage: UCD_CONV_PIPE=4x32 python tools/conv_pipe_probe.py"""
+usage: UCD_CONV_PIPE=lw64 python tools/conv_pipe_probe.py"""
 import os
 import sys
 

@@ -1,6 +1,6 @@
 """GPU probe (round 6): graph-replayed time per launch of the GEMM / implicit-GEMM kernel at the per-rank shapes of the multi-GPU
 split (3 and 6 images) and at 24 images - the kernel alone, no launch gaps (96 launches in one replay).  Environment switches of
-csrc/conv1x1.hip (UCD_CONV_LW_PF, UCD_CONV_LW_NL, UCD_CONV_PIPE, ...) are read once per process: run once per setting.
+csrc/conv1x1.hip (UCD_CONV_PIPE, UCD_CONV_BN64_TILES, UCD_CONV_LW64_TILES) are read once per process: run once per setting.
 usage: [UCD_...=..] python tools/lw_probe.py [batches, default 3,24]"""
 import os
 import sys

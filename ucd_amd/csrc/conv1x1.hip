@@ -49,7 +49,9 @@ typedef __hip_bfloat16 bf16;
 constexpr int kThreads = 256;
 constexpr int kBM = 128;
 
-constexpr int kBK = 64;
+constexpr int kBK = 64;        // K step of every form
+constexpr int kDbStages = 2;   // LDS stages of the DB form
+constexpr int kLwStages = 3;   // LDS stages of the loader-wave form
 
 struct Args {
   const bf16* A; int lda;
@@ -84,13 +86,8 @@ __device__ __forceinline__ float act_grad_rt(float z, float slope) { return z > 
 // s ^ ((r >> 1) & 7).  Two rows share a 256-byte bank row; with this XOR the 16 lanes of every ds_read_b128 group
 // (rows 0-3,12-15,20-27 / 4-11,16-19,28-31 of a 32-row fragment) hit 16 different slots: conflict-free without padding,
 // which is what lets the tile be filled by global_load_lds (lane-linear destination, swizzle on the SOURCE address).
-__device__ __forceinline__ int swz(int row, int slot) { return row * 128 + ((slot ^ ((row >> 1) & 7)) << 4); }
-// The same for K steps of 32 (64-byte rows, four rows per 256-byte bank row): slot s of row r at s ^ ((r >> 2) & 3) - the rows
-// of one ds_read_b128 group that share r & 3 (the same 64-byte quarter of a bank row) differ in (r >> 2) & 3.
-template <int BK>
-__device__ __forceinline__ int swz_fn(int row) { return BK == 64 ? ((row >> 1) & 7) : ((row >> 2) & 3); }
-template <int BK>
-__device__ __forceinline__ int swzk(int row, int slot) { return row * (BK * 2) + ((slot ^ swz_fn<BK>(row)) << 4); }
+__device__ __forceinline__ int swz_fn(int row) { return (row >> 1) & 7; }
+__device__ __forceinline__ int swz(int row, int slot) { return row * 128 + ((slot ^ swz_fn(row)) << 4); }
 
 typedef __attribute__((address_space(1))) const void* gptr_t;
 typedef __attribute__((address_space(3))) void* lptr_t;
@@ -118,12 +115,8 @@ typedef __attribute__((address_space(3))) void* lptr_t;
 template <int OUT> constexpr int kEpilogueBarriers = 4 + (OUT >= 2 ? 2 : 0);
 template <int OUT, int HALVES> constexpr int kEpilogueBarriersH = 2 * HALVES + (OUT >= 2 ? 2 : 0);
 
-// Pipeline depth of the DB form (round 4): NST stages of K steps of BK columns, fills NST - 1 steps ahead behind counted vmcnt
-// waits.  <64, 2> is the original double buffer (64 KB, two workgroups per CU); <32, 4> keeps two workgroups per CU (4 x 16 KB
-// stages each: 96 KB of fills in flight per CU instead of 64, three steps of latency cover instead of one) for the grids of
-// 257 .. 640 workgroups (every 33 x 33 layer at B = 24); <64, 4> (128 KB, ONE workgroup per CU) is for grids that give a CU at most
-// one workgroup anyway (the 3 - 6 images per GPU of the multi-GPU split: 26 - 104 workgroups, where a K step is one exposed
-// memory round trip - 36 of them in a row for a 256-channel 3x3 layer).
+// (Deeper DB pipelines - four stages of 32-column K steps, four stages of 64 at one workgroup per CU - measured slower than or level
+// with the loader-wave forms below and were removed: DESIGN.md sections 3.1 and 10, profiles/r04_conv_pipe_probe.txt.)
 // CONV3, stride 1: the contiguous range of kernel ROWS of a 3 x 3 tap grid that can meet the map for a tile of consecutive output rows
 // [m0, m1) (raster order over the images).  Kernel row kh shifts every pixel by dy = (kh - 1) d; with d >= the tile's distance
 // from the map's top / bottom edge all of its rows read padding and the whole kernel row contributes nothing - at the ASPP
@@ -139,18 +132,15 @@ __device__ __forceinline__ void live_taps(int m0, int m1, int ohw, int oW, int i
   if (ymin >= iH - dil) ntap -= 3;                         // dy = +d
 }
 
-template <int BN, bool PRO, int OUT, bool CONV3 = false, bool DB = false, int BK = 64, int NST = 2>
-__global__ __launch_bounds__(kThreads, DB ? (BK * NST >= 256 ? 1 : 2) : ((PRO || OUT >= 3) && BN == 128 ? 3 : 4)) void conv1x1_kernel(Args p) {
+template <int BN, bool PRO, int OUT, bool CONV3 = false, bool DB = false>
+__global__ __launch_bounds__(kThreads, DB ? 2 : ((PRO || OUT >= 3) && BN == 128 ? 3 : 4)) void conv1x1_kernel(Args p) {
   static_assert(!DB || !PRO, "the double-buffered form has no input transform");
-  static_assert(DB || (BK == 64 && NST == 2), "pipeline parameters belong to the DB form");
-  static_assert(BK == 64 || BK == 32, "K steps of 64 or 32");
-  static_assert(NST == 2 || NST == 4, "two or four stages");
-  constexpr int kStage = (kBM + BN) * BK * 2;   // bytes of one LDS stage (A tile + W tile)
+  constexpr int kStage = (kBM + BN) * kBK * 2;  // bytes of one LDS stage (A tile + W tile)
   constexpr int WN = BN / 2;           // columns per wave
   constexpr int TN = WN / 32;          // 32-wide accumulator tiles per wave along N
   extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
   unsigned char* As = smem;                            // [128][64] bf16, swizzled
-  unsigned char* Bs = smem + kBM * BK * 2;             // [BN][BK]
+  unsigned char* Bs = smem + kBM * kBK * 2;            // [BN][64]
   float* Ps = reinterpret_cast<float*>(smem + p.param_off);   // PRO: [3][K] input-transform constants, loaded once
 
   // tile of this workgroup: column tiles of one strip on the same XCD
@@ -174,7 +164,7 @@ __global__ __launch_bounds__(kThreads, DB ? (BK * NST >= 256 ? 1 : 2) : ((PRO ||
   // ---- staging addresses -------------------------------------------------------------------------------------------
   // LDS-DMA: wave-instruction c covers tile rows 8c .. 8c+7 (1 KiB); lane l lands on (row 8c + l/8, slot l%8) and
   // therefore FETCHES logical slot (l%8) ^ ((row >> 1) & 7) of that row.  Rows past M are clamped (never stored).
-  constexpr int RPC = 1024 / (BK * 2), SPR = BK / 8;    // rows per 1 KiB chunk (8 | 16), 16-byte slots per row (8 | 4)
+  constexpr int RPC = 1024 / (kBK * 2), SPR = kBK / 8;  // rows per 1 KiB chunk (8), 16-byte slots per row (8)
   constexpr int CA = kBM / RPC / 4, CB = BN / RPC / 4;  // chunks per wave: A kBM / RPC chunks, B BN / RPC chunks, 4 waves
   const bf16* ga[CA];
   const bf16* gb[CB];
@@ -182,7 +172,7 @@ __global__ __launch_bounds__(kThreads, DB ? (BK * NST >= 256 ? 1 : 2) : ((PRO ||
 #pragma unroll
   for (int i = 0; i < CA; ++i) {
     const int row = RPC * (wave * CA + i) + lane / SPR;
-    const int slot = ((lane % SPR) ^ swz_fn<BK>(row)) << 3;
+    const int slot = ((lane % SPR) ^ swz_fn(row)) << 3;
     ga[i] = p.A + (size_t)min(m0 + row, p.M - 1) * p.lda + slot;
     if (CONV3 || p.stride > 1) {
       const int m = m0 + row;
@@ -199,7 +189,7 @@ __global__ __launch_bounds__(kThreads, DB ? (BK * NST >= 256 ? 1 : 2) : ((PRO ||
 #pragma unroll
   for (int i = 0; i < CB; ++i) {
     const int row = RPC * (wave * CB + i) + lane / SPR;
-    gb[i] = p.W + (size_t)(n0 + row) * p.ldw + (((lane % SPR) ^ swz_fn<BK>(row)) << 3);
+    gb[i] = p.W + (size_t)(n0 + row) * p.ldw + (((lane % SPR) ^ swz_fn(row)) << 3);
   }
   // register path of A (PRO): thread -> 16-byte slot ks of rows srow + 32 i
   const int ks = tid & 7, srow = tid >> 3;
@@ -217,8 +207,7 @@ __global__ __launch_bounds__(kThreads, DB ? (BK * NST >= 256 ? 1 : 2) : ((PRO ||
     __syncthreads();
   }
   const int fr = lane & 31, fh = lane >> 5;
-  static_assert(!PRO || BK == 64, "the register-staged input transform walks K in steps of 64");
-  const int kpt = p.K / BK;                            // K steps per tap
+  const int kpt = p.K / kBK;                           // K steps per tap
   int tap0 = 0, ntap = 9;
   if (CONV3 && p.stride == 1) live_taps(m0, min(m0 + kBM, p.M), p.ohw, p.oW, p.iH, p.dil, tap0, ntap);
   const int nk = CONV3 ? ntap * kpt : kpt;             // K steps of the live taps; step kb belongs to tap tap0 + kb / kpt
@@ -256,7 +245,7 @@ __global__ __launch_bounds__(kThreads, DB ? (BK * NST >= 256 ? 1 : 2) : ((PRO ||
   };
   auto fill3 = [&](int kb, unsigned char* Ad, unsigned char* Bd) {   // LDS-DMA fill of step kb (double-buffered form)
     const int kt = CONV3 ? kb / kpt : 0, tap = tap0 + kt;
-    const int k0 = (kb - kt * kpt) * BK;
+    const int k0 = (kb - kt * kpt) * kBK;
     if (CONV3) {
       if (tap != atap) set_tap(tap);
 #pragma unroll
@@ -273,12 +262,12 @@ __global__ __launch_bounds__(kThreads, DB ? (BK * NST >= 256 ? 1 : 2) : ((PRO ||
   };
   if (DB) {
 #pragma unroll
-    for (int st = 0; st < NST - 1; ++st)
+    for (int st = 0; st < kDbStages - 1; ++st)
       if (st < nk) fill3(st, As + st * kStage, Bs + st * kStage);
   }
   for (int kb = 0; kb < nk; ++kb) {
     const int kt = CONV3 ? kb / kpt : 0, tap = tap0 + kt;
-    const int k0 = (kb - kt * kpt) * BK;
+    const int k0 = (kb - kt * kpt) * kBK;
     const int wk0 = CONV3 ? tap * p.K + k0 : k0;       // column offset inside a weight row (pitch 9 K)
     if (kb) {                                          // the previous step's fragment reads are done
       if (DB) {   // raw barrier: __syncthreads() would wait for the fill in flight as well
@@ -288,19 +277,17 @@ __global__ __launch_bounds__(kThreads, DB ? (BK * NST >= 256 ? 1 : 2) : ((PRO ||
         __syncthreads();
       }
     }
-    const unsigned char* Ac = As + (DB ? (kb & (NST - 1)) * kStage : 0);
-    const unsigned char* Bc = Bs + (DB ? (kb & (NST - 1)) * kStage : 0);
+    const unsigned char* Ac = As + (DB ? (kb & (kDbStages - 1)) * kStage : 0);
+    const unsigned char* Bc = Bs + (DB ? (kb & (kDbStages - 1)) * kStage : 0);
     if (DB) {
-      // the stage read in step kb - 1 is free (barrier above): the fill of step kb + NST - 1 goes there; then wait until only
-      // the fills BEHIND this step's are still in flight (a counted vmcnt: r younger fills of CA + CB loads each)
-      if (kb + NST - 1 < nk) {
-        const int st = (kb + NST - 1) & (NST - 1);
-        fill3(kb + NST - 1, As + st * kStage, Bs + st * kStage);
+      // the stage read in step kb - 1 is free (barrier above): the fill of step kb + 1 goes there; then wait until only that fill
+      // is still in flight (a counted vmcnt of CA + CB loads)
+      if (kb + kDbStages - 1 < nk) {
+        const int st = (kb + kDbStages - 1) & (kDbStages - 1);
+        fill3(kb + kDbStages - 1, As + st * kStage, Bs + st * kStage);
       }
-      const int r = min(NST - 1, nk - 1 - kb);          // wave-uniform
-      if (NST == 4 && r >= 3) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(3 * (CA + CB)) : "memory");
-      else if (NST == 4 && r == 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * (CA + CB)) : "memory");
-      else if (r >= 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(CA + CB) : "memory");
+      const int r = min(kDbStages - 1, nk - 1 - kb);    // wave-uniform
+      if (r >= 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(CA + CB) : "memory");
       else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();
     } else if (PRO) {
@@ -359,14 +346,14 @@ __global__ __launch_bounds__(kThreads, DB ? (BK * NST >= 256 ? 1 : 2) : ((PRO ||
       bf16x8 af[2][2], bfr[2][TN];
       auto read_slice = [&](int set, int kk) {
 #pragma unroll
-        for (int a = 0; a < 2; ++a) af[set][a] = *reinterpret_cast<const bf16x8*>(Ac + swzk<BK>(wm * 64 + a * 32 + fr, 2 * kk + fh));
+        for (int a = 0; a < 2; ++a) af[set][a] = *reinterpret_cast<const bf16x8*>(Ac + swz(wm * 64 + a * 32 + fr, 2 * kk + fh));
 #pragma unroll
-        for (int b = 0; b < TN; ++b) bfr[set][b] = *reinterpret_cast<const bf16x8*>(Bc + swzk<BK>(wn * WN + b * 32 + fr, 2 * kk + fh));
+        for (int b = 0; b < TN; ++b) bfr[set][b] = *reinterpret_cast<const bf16x8*>(Bc + swz(wn * WN + b * 32 + fr, 2 * kk + fh));
       };
       read_slice(0, 0);
 #pragma unroll
-      for (int kk = 0; kk < BK / 16; ++kk) {
-        if (kk + 1 < BK / 16) read_slice((kk + 1) & 1, kk + 1);
+      for (int kk = 0; kk < kBK / 16; ++kk) {
+        if (kk + 1 < kBK / 16) read_slice((kk + 1) & 1, kk + 1);
         __builtin_amdgcn_sched_barrier(0);                   // the reads above stay above these MFMAs
 #pragma unroll
         for (int a = 0; a < 2; ++a)
@@ -399,8 +386,8 @@ __global__ __launch_bounds__(kThreads, DB ? (BK * NST >= 256 ? 1 : 2) : ((PRO ||
 // LDS-DMA: a `buffer_load_dwordx4 ... lds` piece (1 KiB) holds the issuing wave for 60 - 185 cycles (MI355X_MICROARCH.md, cycle
 // constants), 8 pieces per wave and K step = 800 - 1500 cycles next to 16 MFMAs = 512: a wave of the DB form is ~34 % MFMA-busy, and
 // two per SIMD reach ~67 % (profiles/r03_conv3x3_sq.txt).  Here the roles are split: waves 0 - 3 hold the 2 x 2 wave tiles and do
-// nothing but {barrier; 16 ds_read_b128 + 16 MFMA} per K step; waves 4 - 7 only stage - they issue the fill of step kb + NST - 1
-// right after barrier kb (the stage of step kb - 1 is free then), wait with a counted vmcnt until the fill of step kb + 1 has
+// nothing but {barrier; 16 ds_read_b128 + 16 MFMA} per K step; waves 4 - 7 only stage, into three LDS stages - they issue the fill
+// of step kb + 2 right after barrier kb (the stage of step kb - 1 is free then), wait with a counted vmcnt until the fill of step kb + 1 has
 // landed and join barrier kb + 1.  ONE barrier per K step, no DMA issue in an MFMA wave's instruction stream.
 // BM = 256 (round 4): EIGHT MFMA waves (4 x 2 wave tiles of 64 x 64, two per SIMD) and eight loader waves on a 256 x BN workgroup
 // tile, one workgroup per CU: a quarter less staged bytes per MFMA than two 128-row workgroups, and the MFMA waves of a SIMD take
@@ -413,24 +400,22 @@ __global__ __launch_bounds__(kThreads, DB ? (BK * NST >= 256 ? 1 : 2) : ((PRO ||
 // 128 x 64 tile stages 24 KB and takes ~750 cycles with 256 cycles of MFMA in it - so the time of such a launch is the bytes ONE
 // workgroup stages, whatever the number of workgroups (3 and 6 images: the same 12.9 / 13.6 us for the 3x3 256 -> 256 layer).
 // 64-row tiles stage 16 KB per step on twice as many CUs.
-template <int BM, int BN, int OUT, bool CONV3, int BK, int NST>
-__global__ __launch_bounds__(BM == 64 ? 384 : BM * 4, (BM + BN) * BK * 2 * NST > 80 * 1024 ? 1 : 2) void conv_lw_kernel(Args p) {
+template <int BM, int BN, int OUT, bool CONV3>
+__global__ __launch_bounds__(BM == 64 ? 384 : BM * 4, (BM + BN) * kBK * 2 * kLwStages > 80 * 1024 ? 1 : 2) void conv_lw_kernel(Args p) {
   static_assert(BM == 64 || BM == 128 || BM == 256, "64-, 128- or 256-row workgroup tiles");
   static_assert(BM != 64 || BN == 64, "the 64-row form runs its epilogue on 128 threads: 64-column tiles");
   constexpr int NC = BM / 32, NL = BM == 64 ? 4 : BM / 32;   // MFMA waves (2 per 64 rows), loader waves
-  static_assert(BK == 64 || BK == 32, "K steps of 64 or 32");
-  static_assert(NST >= 2 && NST <= 4, "two to four stages");
-  constexpr int kStage = (BM + BN) * BK * 2;
+  constexpr int kStage = (BM + BN) * kBK * 2;
   constexpr int WN = BN / 2, TN = WN / 32;
   extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
   unsigned char* As = smem;
-  unsigned char* Bs = smem + BM * BK * 2;
+  unsigned char* Bs = smem + BM * kBK * 2;
   const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
   const int tmw = (j / p.tiles_n) * 8 + xcd, tn = j % p.tiles_n;      // workgroup tile (BM rows)
   if (tmw >= p.tiles_m) return;
   const int m0w = tmw * BM, n0 = tn * BN;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int kpt = p.K / BK;
+  const int kpt = p.K / kBK;
   int tap0 = 0, ntap = 9;
   if (CONV3 && p.stride == 1) live_taps(m0w, min(m0w + BM, p.M), p.ohw, p.oW, p.iH, p.dil, tap0, ntap);
   const int nk = CONV3 ? ntap * kpt : kpt;             // K steps of the live taps (loader and MFMA waves count the same steps)
@@ -439,14 +424,14 @@ __global__ __launch_bounds__(BM == 64 ? 384 : BM * 4, (BM + BN) * BK * 2 * NST >
     // ================================ loader waves ================================
     const int lw = wave - NC;
     const int m0 = m0w;
-    constexpr int RPC = 1024 / (BK * 2), SPR = BK / 8;
+    constexpr int RPC = 1024 / (kBK * 2), SPR = kBK / 8;
     constexpr int CA = BM / RPC / NL, CB = BN / RPC / NL;
     int py[CA], px[CA], pimg[CA], pslot[CA];
     unsigned a1off[CA], boff[CB];
 #pragma unroll
     for (int i = 0; i < CA; ++i) {
       const int row = RPC * (lw * CA + i) + lane / SPR;
-      const int slot = ((lane % SPR) ^ swz_fn<BK>(row)) << 3;
+      const int slot = ((lane % SPR) ^ swz_fn(row)) << 3;
       a1off[i] = (unsigned)(((size_t)min(m0 + row, p.M - 1) * p.lda + slot) * 2);
       if (CONV3 || p.stride > 1) {
         const int m = m0 + row;
@@ -463,7 +448,7 @@ __global__ __launch_bounds__(BM == 64 ? 384 : BM * 4, (BM + BN) * BK * 2 * NST >
 #pragma unroll
     for (int i = 0; i < CB; ++i) {
       const int row = RPC * (lw * CB + i) + lane / SPR;
-      boff[i] = (unsigned)(((size_t)(n0 + row) * p.ldw + (((lane % SPR) ^ swz_fn<BK>(row)) << 3)) * 2);
+      boff[i] = (unsigned)(((size_t)(n0 + row) * p.ldw + (((lane % SPR) ^ swz_fn(row)) << 3)) * 2);
     }
     const auto rsW = __builtin_amdgcn_make_buffer_rsrc((void*)p.W, 0, (int)((size_t)p.N * p.ldw * 2), 0x00020000);
     const auto rsA = __builtin_amdgcn_make_buffer_rsrc((void*)p.A, 0, (int)((size_t)p.a_rows * p.lda * 2), 0x00020000);
@@ -484,7 +469,7 @@ __global__ __launch_bounds__(BM == 64 ? 384 : BM * 4, (BM + BN) * BK * 2 * NST >
       unsigned char* Ad = As + st * kStage;
       unsigned char* Bd = Bs + st * kStage;
       const int kt = CONV3 ? kb / kpt : 0, tap = tap0 + kt;
-      const int k0 = (kb - kt * kpt) * BK;
+      const int k0 = (kb - kt * kpt) * kBK;
       if (CONV3) {
         if (tap != atap) set_tap(tap);
 #pragma unroll
@@ -500,18 +485,17 @@ __global__ __launch_bounds__(BM == 64 ? 384 : BM * 4, (BM + BN) * BK * 2 * NST >
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rsW, (lptr_t)(Bd + (lw * CB + i) * 1024), 16, (int)boff[i], (tap * p.K + k0) * 2, 0, 0);
     };
 #pragma unroll
-    for (int st = 0; st < NST - 1; ++st)
+    for (int st = 0; st < kLwStages - 1; ++st)
       if (st < nk) fill(st, st);
-    int wst = NST - 1;                                  // stage the next fill goes to: (kb + NST - 1) % NST
+    int wst = kLwStages - 1;                            // stage the next fill goes to: (kb + 2) % 3
     for (int kb = 0; kb < nk; ++kb) {
-      // fills issued so far: 0 .. min(kb + NST - 2, nk - 1); the fill of step kb has to have landed: r younger ones stay in flight
-      const int r = min(NST - 2, nk - 1 - kb);
-      if (r >= 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * (CA + CB)) : "memory");
-      else if (r == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(CA + CB) : "memory");
+      // fills issued so far: 0 .. min(kb + 1, nk - 1); the fill of step kb has to have landed: r younger ones stay in flight
+      const int r = min(kLwStages - 2, nk - 1 - kb);
+      if (r == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(CA + CB) : "memory");
       else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();                      // barrier kb: the MFMA waves are done with step kb - 1, step kb is in LDS
-      if (kb + NST - 1 < nk) fill(kb + NST - 1, wst);
-      wst = wst + 1 == NST ? 0 : wst + 1;
+      if (kb + kLwStages - 1 < nk) fill(kb + kLwStages - 1, wst);
+      wst = wst + 1 == kLwStages ? 0 : wst + 1;
     }
 #pragma unroll
     for (int b = 0; b < kEpilogueBarriersH<OUT, BM == 64 ? 1 : 2>; ++b) __syncthreads();
@@ -528,24 +512,24 @@ __global__ __launch_bounds__(BM == 64 ? 384 : BM * 4, (BM + BN) * BK * 2 * NST >
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
   const int fr = lane & 31, fh = lane >> 5;
-  int rst = 0;                                          // stage of step kb: kb % NST
+  int rst = 0;                                          // stage of step kb: kb % 3
   for (int kb = 0; kb < nk; ++kb) {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the previous step's fragment reads have returned
     __builtin_amdgcn_s_barrier();
     const unsigned char* Ac = As + rst * kStage;
     const unsigned char* Bc = Bs + rst * kStage;
-    rst = rst + 1 == NST ? 0 : rst + 1;
+    rst = rst + 1 == kLwStages ? 0 : rst + 1;
     bf16x8 af[2][2], bfr[2][TN];
     auto read_slice = [&](int set, int kk) {
 #pragma unroll
-      for (int a = 0; a < 2; ++a) af[set][a] = *reinterpret_cast<const bf16x8*>(Ac + swzk<BK>(wmw * 64 + a * 32 + fr, 2 * kk + fh));
+      for (int a = 0; a < 2; ++a) af[set][a] = *reinterpret_cast<const bf16x8*>(Ac + swz(wmw * 64 + a * 32 + fr, 2 * kk + fh));
 #pragma unroll
-      for (int b = 0; b < TN; ++b) bfr[set][b] = *reinterpret_cast<const bf16x8*>(Bc + swzk<BK>(wn * WN + b * 32 + fr, 2 * kk + fh));
+      for (int b = 0; b < TN; ++b) bfr[set][b] = *reinterpret_cast<const bf16x8*>(Bc + swz(wn * WN + b * 32 + fr, 2 * kk + fh));
     };
     read_slice(0, 0);
 #pragma unroll
-    for (int kk = 0; kk < BK / 16; ++kk) {
-      if (kk + 1 < BK / 16) read_slice((kk + 1) & 1, kk + 1);
+    for (int kk = 0; kk < kBK / 16; ++kk) {
+      if (kk + 1 < kBK / 16) read_slice((kk + 1) & 1, kk + 1);
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int a = 0; a < 2; ++a)
@@ -901,13 +885,13 @@ int pick_wgrad_chunks(int M, int N, int K) {
 }
 
 
-// Launch of the DB form with one of its three pipelines (see the kernel's header): 0 = <64, 2>, 1 = <32, 4>, 2 = <64, 4>.
+// Launch of a DB-eligible product in the form pick_pipe / ucd_conv1x1 chose: 0 = the DB kernel, 4 / 5 / 7 = loader waves on 128- /
+// 256- / 64-row tiles.
 template <int BN, int OUT, bool CONV3>
 int launch_db(int pipe, int grid, hipStream_t s, const Args& a, const char* fn) {
-  (void)fn;
   constexpr size_t kOut = (size_t)64 * (BN + 4) * 4, kRed = (size_t)(kThreads / (BN / 8)) * 2 * BN * 4;
-  auto lds_of = [&](int bk, int nst) {
-    size_t l = (size_t)(kBM + BN) * bk * 2 * nst;
+  auto lds_of = [&](int nst) {
+    size_t l = (size_t)(kBM + BN) * kBK * 2 * nst;
     if (l < kOut) l = kOut;
     if (l < kRed) l = kRed;
     return l;
@@ -917,17 +901,10 @@ int launch_db(int pipe, int grid, hipStream_t s, const Args& a, const char* fn) 
       Args b = a;
       b.tiles_m = ceil_div(a.M, 256);
       const int grid256 = ceil_div(b.tiles_m, 8) * 8 * b.tiles_n;
-      size_t lds = (size_t)(256 + BN) * 64 * 2 * 3;
+      size_t lds = (size_t)(256 + BN) * kBK * 2 * kLwStages;
       if (lds < kOut) lds = kOut;
-      UCD_TRY_LDS((conv_lw_kernel<256, BN, OUT, CONV3, 64, 3>), (int)lds);
-      conv_lw_kernel<256, BN, OUT, CONV3, 64, 3><<<grid256, 1024, lds, s>>>(b);
-      return 0;
-    }
-    pipe = 0;
-  }
-  if (pipe == 6) {                  // loader waves, TWO 32 KB stages, two workgroups (16 waves) per CU: OUT 0 .. 2 (128 registers)
-    if constexpr (OUT <= 2) {
-      conv_lw_kernel<128, BN, OUT, CONV3, 64, 2><<<grid, 2 * kThreads, lds_of(64, 2), s>>>(a);
+      UCD_TRY_LDS((conv_lw_kernel<256, BN, OUT, CONV3>), (int)lds);
+      conv_lw_kernel<256, BN, OUT, CONV3><<<grid256, 1024, lds, s>>>(b);
       return 0;
     }
     pipe = 0;
@@ -937,34 +914,19 @@ int launch_db(int pipe, int grid, hipStream_t s, const Args& a, const char* fn) 
       Args b = a;
       b.tiles_m = ceil_div(a.M, 64);
       const int grid64 = ceil_div(b.tiles_m, 8) * 8 * b.tiles_n;
-      const size_t lds64 = (size_t)(64 + BN) * 64 * 2 * 3;
-      conv_lw_kernel<64, BN, OUT, CONV3, 64, 3><<<grid64, 384, lds64, s>>>(b);
+      const size_t lds64 = (size_t)(64 + BN) * kBK * 2 * kLwStages;
+      conv_lw_kernel<64, BN, OUT, CONV3><<<grid64, 384, lds64, s>>>(b);
       return 0;
     }
     pipe = 4;
   }
   if (pipe == 4) {                  // loader waves, three 32 KB stages, one workgroup (8 waves) per CU: every epilogue fits
-    const size_t lds = lds_of(64, 3);
-    UCD_TRY_LDS((conv_lw_kernel<128, BN, OUT, CONV3, 64, 3>), (int)lds);
-    conv_lw_kernel<128, BN, OUT, CONV3, 64, 3><<<grid, 2 * kThreads, lds, s>>>(a);
+    const size_t lds = lds_of(kLwStages);
+    UCD_TRY_LDS((conv_lw_kernel<128, BN, OUT, CONV3>), (int)lds);
+    conv_lw_kernel<128, BN, OUT, CONV3><<<grid, 2 * kThreads, lds, s>>>(a);
     return 0;
   }
-  if (pipe == 3) {
-    if constexpr (OUT <= 2) {       // two workgroups per CU: the epilogues of OUT 3 / 4 need more registers than 16 waves leave
-      conv_lw_kernel<128, BN, OUT, CONV3, 32, 4><<<grid, 2 * kThreads, lds_of(32, 4), s>>>(a);
-      return 0;
-    }
-    pipe = 0;
-  }
-  if (pipe == 1) {
-    conv1x1_kernel<BN, false, OUT, CONV3, true, 32, 4><<<grid, kThreads, lds_of(32, 4), s>>>(a);
-  } else if (pipe == 2) {
-    const size_t lds = lds_of(64, 4);
-    UCD_TRY_LDS((conv1x1_kernel<BN, false, OUT, CONV3, true, 64, 4>), (int)lds);
-    conv1x1_kernel<BN, false, OUT, CONV3, true, 64, 4><<<grid, kThreads, lds, s>>>(a);
-  } else {
-    conv1x1_kernel<BN, false, OUT, CONV3, true, 64, 2><<<grid, kThreads, lds_of(64, 2), s>>>(a);
-  }
+  conv1x1_kernel<BN, false, OUT, CONV3, true><<<grid, kThreads, lds_of(kDbStages), s>>>(a);
   return 0;
 }
 
@@ -985,16 +947,20 @@ int launch_db_out(int out_mode, int pipe, int grid, hipStream_t s, const Args& a
   }
 }
 
-// Pipeline of a DB launch: UCD_CONV_PIPE = 2x64 | 4x32 | 4x64 overrides (probes / A-B); else by the grid (measured:
-// tools/conv3x3_probe.py, tools/conv1x1_probe.py, profiles/r04_conv_pipe_probe.txt).
-int pick_pipe(int M, int tiles_n, int BN, int nk64, int out_mode) {
-  static int forced = -2;
-  if (forced == -2) {
+// UCD_CONV_PIPE (read once per process; probes / A-B): the form every DB-eligible launch takes - 2x64 (the DB kernel, 0), lw64 (4) or
+// lw256 (5); unset, empty or auto: by the grid (-1).  -2: the value names no form, and ucd_conv1x1 refuses every call.
+int forced_pipe() {
+  static const int forced = [] {
     const char* e = getenv("UCD_CONV_PIPE");
-    forced = !e ? -1 : !strcmp(e, "2x64") ? 0 : !strcmp(e, "4x32") ? 1 : !strcmp(e, "4x64") ? 2 : !strcmp(e, "lw32") ? 3 :
-             !strcmp(e, "lw64") ? 4 : !strcmp(e, "lw256") ? 5 : !strcmp(e, "lw64x2") ? 6 : -1;
-  }
-  if (forced >= 0) return forced;
+    return !e || !*e || !strcmp(e, "auto") ? -1 : !strcmp(e, "2x64") ? 0 : !strcmp(e, "lw64") ? 4 : !strcmp(e, "lw256") ? 5 : -2;
+  }();
+  return forced;
+}
+
+// Pipeline of a DB launch: forced_pipe(), else by the grid (measured: tools/conv3x3_probe.py, tools/conv1x1_probe.py,
+// profiles/r04_conv_pipe_probe.txt).
+int pick_pipe(int M, int tiles_n, int BN, int nk64, int out_mode) {
+  if (forced_pipe() >= 0) return forced_pipe();
   const long long wg128 = (long long)ceil_div(M, 128) * tiles_n, wg256 = (long long)ceil_div(M, 256) * tiles_n;
   // grids that give a CU at most one workgroup (3 - 6 images per GPU, the multi-GPU split): the loader-wave form - 3x3 256 -> 256 at
   // 3 images 26.8 -> 17.3 us, 512 -> 512 49 -> 30, the ASPP branches 169 -> 100, 1x1 1024 -> 256 12.2 -> 9.5 (profiles/r04_conv_pipe_probe.txt)
@@ -1027,6 +993,8 @@ int ucd_conv1x1_stat_replicas(int M) {
 
 int ucd_conv1x1(const ucd_conv1x1_desc* d, ucd_stream_t stream) {
   static const char* fn = "ucd_conv1x1";
+  UCD_REQUIRE(forced_pipe() != -2, UCD_EINVAL, "%s: UCD_CONV_PIPE=%s names no form (accepted: auto, 2x64, lw64, lw256)", fn,
+              getenv("UCD_CONV_PIPE"));
   UCD_REQUIRE(d && d->a && d->w && d->y, UCD_EINVAL, "%s: NULL operand", fn);
   UCD_REQUIRE(d->M > 0 && d->N > 0 && d->K > 0, UCD_EINVAL, "%s: empty product", fn);
   UCD_REQUIRE(d->K % kBK == 0 && d->N % 64 == 0, UCD_EUNSUPPORTED, "%s: K (%d) and N (%d) must be multiples of 64", fn, d->K, d->N);

@@ -24,8 +24,8 @@
 // Workgroup -> work: all tiles and taps of one row chunk sit on one XCD (ids congruent mod 8 share an L2), so a chunk's rows
 // of dZ and X leave HBM once and are re-read by its tiles from that L2.
 #include <map>
-#include <vector>
 #include <mutex>
+#include <optional>
 #include <type_traits>
 
 #include "common.h"
@@ -770,8 +770,8 @@ SumArgs take_pending(hipStream_t s) {
 // per fork 0.5 ms faster.  The form kept: the call only RECORDS its fork point on the caller's stream; the launches go out at the
 // NEXT accepted call (or the flush), by when the caller has created its chain's next nodes - the weight gradients are the branch
 // that hops, and nothing waits for them: 3 images 8.95 -> 7.95 ms, 6 images 12.0 -> 10.65, 24 images 28.95 -> 28.45
-// (profiles/r06_side_stream.md).  UCD_WGRAD_STREAM_GROUP (default 1) calls share a fork point, UCD_WGRAD_STREAM_LATE=0 launches at
-// the fork (the slower forms, kept for the A/B).
+// (profiles/r06_side_stream.md).  So each accepted call launches the call armed before it behind that call's fork point, records its
+// own fork point and arms itself; the flush launches the last armed call.
 struct ExArgs {
   const void* dz; int ld_dz; const void* x; int ld_x; int M, N, K, taps, H, W, dilation, stride;
   void* dw; float* dw32; int accumulate32; void* workspace; size_t workspace_bytes; int flags;
@@ -782,33 +782,22 @@ int wgrad_launch_on(const ExArgs& q, hipStream_t s);
 struct Side {
   hipStream_t s = nullptr;
   hipEvent_t fork = nullptr, join = nullptr;
-  bool active = false;      // work since the last join
-  std::vector<ExArgs> queue;   // accepted calls not launched yet
-  std::vector<ExArgs> armed;   // a full group whose fork point is recorded, launched at the next call (UCD_WGRAD_STREAM_LATE)
+  bool active = false;             // work since the last join
+  std::optional<ExArgs> armed;     // an accepted call whose fork point is recorded, launched at the next call or the flush
 };
-bool side_late() {
-  static const bool on = [] { const char* e = getenv("UCD_WGRAD_STREAM_LATE"); return !(e && e[0] == '0'); }();
-  return on;
-}
-int side_group() {
-  static const int g = [] { const char* e = getenv("UCD_WGRAD_STREAM_GROUP"); const int v = e ? atoi(e) : 1; return v < 1 ? 1 : v; }();
-  return g;
-}
 std::map<hipStream_t, Side> g_side;     // by the caller's stream; under g_pend_mu
 
-// the side stream of `main`, forked behind its current position; nullptr (with the error set) when HIP refuses
-// phase bit 0: record the fork point on `main`; bit 1: let the side stream wait for the recorded point
-hipStream_t side_fork(hipStream_t main, const char* fn, int phase = 3) {
+// the side stream of `main`; nullptr (with the error set) when HIP refuses
+// phase 1: record the fork point on `main`; phase 2: let the side stream wait for the recorded point
+hipStream_t side_fork(hipStream_t main, const char* fn, int phase) {
   std::lock_guard<std::mutex> lock(g_pend_mu);
   Side& sd = g_side[main];
   if (!sd.s) {
     int least = 0, greatest = 0;
-    const char* e = getenv("UCD_WGRAD_STREAM_PRIO");
-    const bool low = !(e && e[0] == 'n');                 // "normal": the caller's priority; default: the lowest (the chain goes first)
     hipStream_t st = nullptr;
     hipEvent_t f = nullptr, j = nullptr;
-    bool ok = hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess &&
-              hipStreamCreateWithPriority(&st, hipStreamNonBlocking, low ? least : 0) == hipSuccess &&
+    bool ok = hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess &&     // the lowest priority: the chain goes first
+              hipStreamCreateWithPriority(&st, hipStreamNonBlocking, least) == hipSuccess &&
               hipEventCreateWithFlags(&f, hipEventDisableTiming) == hipSuccess &&
               hipEventCreateWithFlags(&j, hipEventDisableTiming) == hipSuccess;
     if (!ok) {
@@ -818,12 +807,12 @@ hipStream_t side_fork(hipStream_t main, const char* fn, int phase = 3) {
     }
     sd.s = st; sd.fork = f; sd.join = j;
   }
-  if ((phase & 1) && hipEventRecord(sd.fork, main) != hipSuccess) {
+  if (phase == 1 && hipEventRecord(sd.fork, main) != hipSuccess) {
     (void)hipGetLastError();
     set_error("%s: cannot record the fork point on the caller's stream", fn);
     return nullptr;
   }
-  if (phase & 2) {
+  if (phase == 2) {
     if (hipStreamWaitEvent(sd.s, sd.fork, 0) != hipSuccess) {
       (void)hipGetLastError();
       set_error("%s: cannot fork the side stream behind the caller's", fn);
@@ -852,62 +841,32 @@ int side_join(hipStream_t main, const char* fn) {
   return 0;
 }
 
-// launch the queued calls of `main` on its side stream behind one fork
-int side_drain(hipStream_t main, const char* fn) {
-  std::vector<ExArgs> todo;
-  {
-    std::lock_guard<std::mutex> lock(g_pend_mu);
-    auto it = g_side.find(main);
-    if (it == g_side.end() || it->second.queue.empty()) return 0;
-    todo.swap(it->second.queue);
-  }
-  hipStream_t sd = side_fork(main, fn);
-  if (!sd) return (int)hipErrorUnknown;
-  for (const ExArgs& q : todo) {
-    const int rc = wgrad_launch_on(q, sd);
-    if (rc) return rc;
-  }
-  return 0;
-}
-// launch a group whose fork point was recorded earlier (the caller's stream has moved on since)
+// launch the armed call of `main` on its side stream, behind the fork point it recorded (the caller's stream has moved on since)
 int side_launch_armed(hipStream_t main, const char* fn) {
-  std::vector<ExArgs> todo;
+  ExArgs q;
   {
     std::lock_guard<std::mutex> lock(g_pend_mu);
     auto it = g_side.find(main);
-    if (it == g_side.end() || it->second.armed.empty()) return 0;
-    todo.swap(it->second.armed);
+    if (it == g_side.end() || !it->second.armed) return 0;
+    q = *it->second.armed;
+    it->second.armed.reset();
   }
   hipStream_t sd = side_fork(main, fn, 2);
   if (!sd) return (int)hipErrorUnknown;
-  for (const ExArgs& q : todo) {
-    const int rc = wgrad_launch_on(q, sd);
-    if (rc) return rc;
-  }
-  return 0;
+  return wgrad_launch_on(q, sd);
 }
 int side_enqueue(hipStream_t main, const ExArgs& q, const char* fn) {
-  const int rc = side_launch_armed(main, fn);
+  const int rc = side_launch_armed(main, fn);                    // the previous call, behind its fork point
   if (rc) return rc;
-  size_t n;
-  {
-    std::lock_guard<std::mutex> lock(g_pend_mu);
-    Side& sd = g_side[main];
-    sd.queue.push_back(q);
-    n = sd.queue.size();
-  }
-  if (n < (size_t)side_group()) return 0;
-  if (!side_late()) return side_drain(main, fn);
-  if (!side_fork(main, fn, 1)) return (int)hipErrorUnknown;      // the fork point now, the launches at the next call
+  if (!side_fork(main, fn, 1)) return (int)hipErrorUnknown;      // this call's fork point now, its launch at the next call
   std::lock_guard<std::mutex> lock(g_pend_mu);
-  Side& sd = g_side[main];
-  sd.armed.swap(sd.queue);
+  g_side[main].armed = q;
   return 0;
 }
 void side_forget(hipStream_t main) {
   std::lock_guard<std::mutex> lock(g_pend_mu);
   auto it = g_side.find(main);
-  if (it != g_side.end()) { it->second.queue.clear(); it->second.armed.clear(); }
+  if (it != g_side.end()) it->second.armed.reset();
 }
 
 int plan_target(int N, int K, int taps) {
@@ -962,8 +921,7 @@ int ucd_conv_wgrad_flush(ucd_stream_t stream) {
   static const char* fn = "ucd_conv_wgrad_flush";
   const hipStream_t main = (hipStream_t)stream;
   {
-    int rc = side_launch_armed(main, fn);              // a group waiting for its launch
-    if (!rc) rc = side_drain(main, fn);                // calls still waiting for their group
+    const int rc = side_launch_armed(main, fn);        // the last accepted call
     if (rc) return rc;
   }
   if (hipStream_t sd = side_active(main)) {            // the side stream: its pending sum, then the join
@@ -985,7 +943,7 @@ int ucd_conv_wgrad_flush(ucd_stream_t stream) {
 int ucd_conv_wgrad_drop(ucd_stream_t stream) {
   const hipStream_t main = (hipStream_t)stream;
   (void)take_pending(main);
-  side_forget(main);                                   // calls not launched yet never are
+  side_forget(main);                                   // a call not launched yet never is
   if (hipStream_t sd = side_active(main)) {            // launched work cannot be taken back: join it (a capture must not end forked)
     (void)take_pending(sd);
     return side_join(main, "ucd_conv_wgrad_drop");
@@ -1014,7 +972,7 @@ int ucd_conv_wgrad_ex(const void* dz, int ld_dz, const void* x, int ld_x, int M,
               UCD_EALIGN, "%s: operands must be 16-byte aligned with leading dimensions that are multiples of 8", fn);
   ExArgs q{dz, ld_dz, x, ld_x, M, N, K, taps, H, W, dilation, stride, dw, dw32, accumulate32, workspace, workspace_bytes, flags};
   {
-    // enough workspace?  (checked here, at the call, also for a launch that waits in the side stream's queue)
+    // enough workspace?  (checked here, at the call, also for a call armed on the side stream)
     Plan pl = make_plan(M, N, K, taps, plan_target(N, K, taps));
     int chunks = pl.chunks;
     if (wgrad_three(q, oW, oH)) chunks = make_plan3(M, N, K).chunks;
