@@ -651,6 +651,29 @@ int ucd_flip_weights_batched64(const void* src_flat, void* dst_flat, const int* 
 /* dst[cols, rows] = src[rows, cols]^T (bf16): the [K, N] weight of the input-gradient product. */
 int ucd_transpose_bf16(const void* src, int rows, int cols, void* dst, ucd_stream_t stream);
 
+/* ---- fp32 stride-1 convolutions (the fp32 training mode, --opt_level O0; csrc/conv_f32.hip) ---------------------------
+ * PRECISION: every fp32 operand is split as x = hi + lo, hi = bf16_rn(x), lo = bf16_rn(x - hi), and each product is
+ * accumulated in fp32 as hi*hi + hi*lo + lo*hi on the bf16 matrix cores (three MFMAs per product).  The error per product is
+ * about 3 * 2^-18 ~ 1e-5 relative (the rounding of each lo part plus the dropped lo*lo term) - ~100x below a bf16 product.
+ * Inputs are assumed finite (an inf makes its lo part NaN).  On integer-valued operands whose partial sums stay below 2^24 the
+ * result is exact.
+ * All operands are fp32 row matrices with a row pitch in elements (multiple of 4, 16-byte aligned bases); rows past the end,
+ * 3x3 halo positions and channel tails are read as zeros through range-checked loads - nothing outside an operand is touched.
+ * No allocation, no host synchronisation: the calls capture into graphs.  UCD_EINVAL for shapes the kernels do not take (K or
+ * N not a multiple of 32, unaligned pitch or base, an operand beyond 2 GB).
+ *
+ * ucd_conv_f32:  y[M][N] (+)= im2col(a)[M][taps K] . w[N][taps K]^T.  taps = 1: the 1x1 product; taps = 9: the 3x3 convolution
+ * (stride 1, padding = dilation) over the [B, H, W, K] map behind a (M = B*H*W), w the channels-last weight [N][kh][kw][K].
+ * accumulate != 0: y += the product.  The input gradient is the same call on w^T (1x1) or on w.flip(2, 3).transpose(0, 1) (3x3).
+ * ucd_conv_f32_wgrad:  dw[N][taps K] = sum_m dz[m][n] * x[shift_t(m)][k] (taps 1 / 9 as above, dw dense in the weight's
+ * channels-last order), written (not accumulated).  Row chunks reduce into ucd_conv_f32_wgrad_workspace_bytes(M, N, K, taps)
+ * bytes of fp32 slabs (0: none needed), summed in a fixed order on the same stream: no atomics, bit-reproducible. */
+int ucd_conv_f32(const float* a, int lda, const float* w, int ldw, float* y, int ldy, int M, int N, int K, int taps, int H, int W,
+                 int dilation, int accumulate, ucd_stream_t stream);
+size_t ucd_conv_f32_wgrad_workspace_bytes(int M, int N, int K, int taps);
+int ucd_conv_f32_wgrad(const float* dz, int ld_dz, const float* x, int ld_x, int M, int N, int K, int taps, int H, int W,
+                       int dilation, float* dw, void* workspace, size_t workspace_bytes, ucd_stream_t stream);
+
 /* ---- optimiser step -------------------------------------------------------------------------------------------------
  * Replaces `optim.step()` (train.py:147) of the reference's torch.optim.SGD(params, lr, momentum=0.9, nesterov=True) with
  * per-group weight decay (run.py:175-186) by ONE launch over every parameter tensor; the bf16 working copy of a

@@ -244,11 +244,125 @@ def _stride_one_conv(x, w, d, wt=None, own_fwd=False, own_dgrad=False):
     return _StrideOneConvFn.apply(x, w, d, wt, bool(own_fwd), bool(own_dgrad))
 
 
+def _own_f32_conv(M, K, N, taps):
+    """Shape gate of the fp32 split-bf16 kernels (csrc/conv_f32.hip) against MIOpen fp32, a pure function of the product's shape:
+    M = B*H*W rows, K -> N channels, taps 1 (1x1) or 9 (3x3).  Channels on the kernels' grid (multiples of 32, at least 64) and
+    maps that give the chip some tiles (M >= 1024: the image-pooling branch's [B, C, 1, 1] products stay on the library).  Measured
+    per shape at B = 24 (tools/conv_f32_probe.py, profiles/r07_conv_f32_probe.txt, forward / input gradient us, own vs MIOpen
+    fp32): 1.1 - 2.5x faster on every stride-1 layer (ASPP branches 774 - 860 vs 1753 - 1772, 2048 -> 512 239 vs 472, 3x3
+    128 -> 128 at 65^2 128 vs 283) except the 64 -> 64 1x1 layer at 129^2 (51.5 vs 43.7 forward, 54.3 vs 54.7 input gradient),
+    which stays on the library.  Measured at B = 24 only; the gate applies the same verdict at any M >= 1024.  The weight gradient
+    has a gate of its own (``_own_f32_wgrad``)."""
+    if not (taps in (1, 9) and K % 32 == 0 and N % 32 == 0 and K >= 64 and N >= 64 and M >= 1024):
+        return False
+    return not (taps == 1 and K == 64 and N == 64)
+
+
+def _own_f32_wgrad(M, K, N, taps):
+    """Weight gradient of a layer that passed ``_own_f32_conv``: on ucd_conv_f32_wgrad when both channel counts fill the 128-wide
+    tile; the 64-channel layers (129^2: 64 -> 256 173 vs 141 us, 256 -> 64 180 vs 143, 3x3 64 -> 64 666 vs 303;
+    profiles/r07_conv_f32_probe.txt) keep MIOpen's weight-gradient solvers.  Every other shape of that table is 1.25 - 1.95x
+    faster on the own kernel (2048 -> 512 224 vs 436, ASPP branches 1319 - 1409 vs 1807 - 1811).  Measured at B = 24 only; the
+    gate applies the same verdict at any M >= 1024."""
+    return _own_f32_conv(M, K, N, taps) and min(K, N) >= 128
+
+
+def _f32_conv_ok(conv, x):
+    """Does this stride-1 layer call run on the fp32 split-bf16 kernels?  ``UCD_F32_OWN_CONV=1`` and a channels-last fp32 GPU map
+    with a 16-byte aligned base and autocast off, no bias, stride 1, 1x1 with padding 0 or 3x3 with padding = dilation, and the
+    shape gate ``_own_f32_conv``."""
+    if _env("UCD_F32_OWN_CONV", "0") != "1":
+        return False
+    if not (x.is_cuda and x.dim() == 4 and x.dtype == torch.float32 and not torch.is_autocast_enabled() and conv.bias is None
+            and conv.weight.dtype == torch.float32 and conv.groups == 1 and conv.stride == (1, 1)
+            and x.is_contiguous(memory_format=torch.channels_last) and not (x.data_ptr() & 15)):
+        return False
+    if conv.kernel_size == (1, 1):
+        if conv.padding != (0, 0):
+            return False
+        taps = 1
+    elif conv.kernel_size == (3, 3) and conv.padding == conv.dilation and conv.dilation[0] == conv.dilation[1]:
+        taps = 9
+    else:
+        return False
+    return _own_f32_conv(x.shape[0] * x.shape[2] * x.shape[3], conv.in_channels, conv.out_channels, taps)
+
+
+def _f32_rows(t):
+    """[B, C, H, W] fp32 map -> its channels-last [B*H*W, C] row matrix (a view of a channels-last tensor, else a copy)."""
+    if not t.is_contiguous(memory_format=torch.channels_last):
+        t = t.contiguous(memory_format=torch.channels_last)
+    return t.permute(0, 2, 3, 1).reshape(t.shape[0] * t.shape[2] * t.shape[3], t.shape[1])
+
+
+def _f32_conv_fwd(x, w, d):
+    """y = conv2d(x, w, stride 1, padding d, dilation d) (d = 0: 1x1) on ucd_conv_f32; y channels-last fp32."""
+    from . import hip
+    B, K, H, W = x.shape
+    N = w.shape[0]
+    y = torch.empty((B, N, H, W), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+    wm = w.permute(0, 2, 3, 1).reshape(N, -1)            # [N, taps K] in the weight's channels-last order
+    if wm.stride(1) != 1 or (wm.data_ptr() & 15):
+        wm = wm.contiguous()
+    hip.conv_f32(_f32_rows(x), wm, _f32_rows(y), conv3=(H, W, d) if d > 0 else None)
+    return y
+
+
+class _F32ConvFn(torch.autograd.Function):
+    """fp32 stride-1 convolution (1x1, or 3x3 with padding = dilation d) with forward, input gradient and weight gradient on the
+    split-bf16 kernels (csrc/conv_f32.hip; ~1e-5 relative per product; the weight gradient of the 64-channel layers on MIOpen,
+    ``_own_f32_wgrad``).  Like ``_StrideOneConvFn`` the input gradient is the
+    forward product on the rearranged weight: w^T (1x1) or w.flip(2, 3).transpose(0, 1) (3x3)."""
+
+    @staticmethod
+    def forward(ctx, x, w, d):
+        ctx.d = d
+        ctx.save_for_backward(x, w)
+        return _f32_conv_fwd(x, w, d)
+
+    @staticmethod
+    def backward(ctx, dy):
+        from . import hip
+        x, w = ctx.saved_tensors
+        d = ctx.d
+        dy = dy.contiguous(memory_format=torch.channels_last)
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            wt = (w.transpose(0, 1) if d == 0 else w.flip(2, 3).transpose(0, 1)).contiguous(memory_format=torch.channels_last)
+            dx = _f32_conv_fwd(dy, wt, d)
+        if ctx.needs_input_grad[1]:
+            B, K, H, W = x.shape
+            N = w.shape[0]
+            k = 3 if d > 0 else 1
+            if _own_f32_wgrad(B * H * W, K, N, k * k):
+                dwm = torch.empty((N, k * k * K), dtype=torch.float32, device=x.device)
+                hip.conv_f32_wgrad(_f32_rows(dy), _f32_rows(x), dwm, conv3=(H, W, d) if d > 0 else None)
+                dw = dwm.view(N, k, k, K).permute(0, 3, 1, 2)
+                if not w.is_contiguous(memory_format=torch.channels_last):
+                    dw = dw.contiguous()
+            else:
+                dl = max(d, 1)
+                dw = torch.ops.aten.convolution_backward(dy, x, w, None, [1, 1], [d, d], [dl, dl], False, [0, 0], 1,
+                                                         [False, True, False])[1]
+        return dx, dw, None
+
+
+def _f32_conv(conv, x):
+    """The layer on the fp32 split-bf16 kernels (after ``_f32_conv_ok``): autograd node when anything needs a gradient, else the
+    plain forward (the frozen teacher)."""
+    d = conv.dilation[0] if conv.kernel_size == (3, 3) else 0
+    if torch.is_grad_enabled() and (x.requires_grad or conv.weight.requires_grad):
+        return _F32ConvFn.apply(x, conv.weight, d)
+    return _f32_conv_fwd(x, conv.weight, d)
+
+
 class Conv3x3(Conv2d):
     """3x3, stride 1, padding = dilation: the bottleneck conv2 layers and the ASPP branches (modules/residual.py:69,
     modules/deeplab.py:27-29).  Same parameters and state_dict keys as nn.Conv2d."""
 
     def forward(self, x):
+        if _f32_conv_ok(self, x):
+            return _f32_conv(self, x)
         M = x.shape[0] * x.shape[2] * x.shape[3] if x.dim() == 4 else 0
         own = _own3x3_ok(self, x) and self.weight.is_contiguous(memory_format=torch.channels_last)
         if (x.is_cuda and torch.is_grad_enabled() and self.weight.requires_grad and self.bias is None
@@ -296,6 +410,8 @@ class Conv1x1(Conv2d):
         self.link_dgrad = False
 
     def forward(self, x):
+        if _f32_conv_ok(self, x):          # UCD_F32_OWN_CONV=1: the fp32 mode's layers on csrc/conv_f32.hip
+            return _f32_conv(self, x)
         # bf16 activations only: in the fp32 parity mode (--opt_level O0) every convolution stays on one code
         # path (MIOpen), which is what the 1e-3 logit comparison with the reference was validated on
         if not (self.as_gemm and x.is_cuda and x.dim() == 4 and (x.dtype != torch.float32 or torch.is_autocast_enabled())):

@@ -129,6 +129,9 @@ SIGNATURES = {
     "ucd_conv_wgrad_flush": (_i, [_p]),
     "ucd_conv_wgrad_drop": (_i, [_p]),
     "ucd_transpose_bf16": (_i, [_p, _i, _i, _p, _p]),
+    "ucd_conv_f32": (_i, [_p, _i, _p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "ucd_conv_f32_wgrad_workspace_bytes": (_z, [_i, _i, _i, _i]),
+    "ucd_conv_f32_wgrad": (_i, [_p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _z, _p]),
     "ucd_flip_weights_batched": (_i, [_p, _p, _p, _i, _p, _p]),
     "ucd_flip_weights_batched64": (_i, [_p, _p, _p, _i, _p, _p]),
     "ucd_sgd_chunk": (_i, []),
@@ -747,6 +750,40 @@ def conv_wgrad(dz, x, dw=None, conv3=None, dw32=None, accumulate32=False, stride
                                      ptr(dw32), 1 if accumulate32 else 0, ptr(ws), nbytes, (1 if defer else 0) | (2 if side else 0), stream()),
                "ucd_conv_wgrad")
     return dw if dw is not None else dw32
+
+
+def conv_f32(a, w, y, conv3=None, accumulate=False):
+    """fp32 stride-1 convolution on the split-bf16 kernels (ucd_conv_f32): ``y[M, N] (+)= a[M, K] . w[N, K]^T``, all fp32 row
+    matrices; ``conv3 = (H, W, dilation)``: the 3x3 convolution (padding = dilation) of the [B, H, W, K] map behind ``a`` with the
+    channels-last weight given as its [N, 9 K] row matrix.  ``accumulate``: y += the product."""
+    lib = load()
+    M, K = a.shape
+    N = w.shape[0]
+    taps = 9 if conv3 is not None else 1
+    H, W, d = (int(conv3[0]), int(conv3[1]), int(conv3[2])) if conv3 is not None else (0, 0, 0)
+    # roofline work of the instrumented bench pass: algorithmic bytes (bench.py counts only its listed call types as MFMA-bound)
+    work = 4 * (M * K + N * taps * K + M * N * (2 if accumulate else 1))
+    with _timed("ucd_conv3x3_f32" if conv3 is not None else "ucd_conv1x1_f32", work):
+        _check(lib.ucd_conv_f32(ptr(a), a.stride(0), ptr(w), w.stride(0), ptr(y), y.stride(0), M, N, K, taps, H, W, d,
+                                1 if accumulate else 0, stream()), "ucd_conv_f32")
+    return y
+
+
+def conv_f32_wgrad(dz, x, dw, conv3=None):
+    """Weight gradient of an fp32 stride-1 convolution (ucd_conv_f32_wgrad): ``dz`` [M, N] and ``x`` [M, K] fp32 row matrices ->
+    ``dw`` [N, taps * K] fp32 (written, channels-last weight order [N][kh][kw][K]); ``conv3 = (H, W, dilation)`` for the 3x3
+    layers.  The slab workspace comes from torch's allocator (stream-ordered, graph-capturable)."""
+    lib = load()
+    M, N = dz.shape
+    K = x.shape[1]
+    taps = 9 if conv3 is not None else 1
+    H, W, d = (int(conv3[0]), int(conv3[1]), int(conv3[2])) if conv3 is not None else (0, 0, 0)
+    nbytes = lib.ucd_conv_f32_wgrad_workspace_bytes(M, N, K, taps)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dz.device) if nbytes else None
+    with _timed("ucd_conv3x3_f32_wgrad" if conv3 is not None else "ucd_conv1x1_f32_wgrad", 4 * (M * N + M * K + N * taps * K)):
+        _check(lib.ucd_conv_f32_wgrad(ptr(dz), dz.stride(0), ptr(x), x.stride(0), M, N, K, taps, H, W, d, ptr(dw), ptr(ws), nbytes,
+                                      stream()), "ucd_conv_f32_wgrad")
+    return dw
 
 
 def transpose_bf16(src, dst):
