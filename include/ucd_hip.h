@@ -703,6 +703,44 @@ int ucd_sgd_hyper_store(ucd_sgd_hyper* device_hyper, const ucd_sgd_hyper* hyper,
 int ucd_sgd_step_dev(const ucd_sgd_tensor* table, const int* blocks, int n_blocks, const ucd_sgd_hyper* device_hyper,
                      ucd_stream_t stream);
 
+/* ---- EWC / PI / RW regulariser ----------------------------------------------------------------------------------------
+ * The weight-space penalty of the reference's other baselines (utils/regularizer.py, train.py:139-145) as ONE pass over every
+ * trainable tensor, run between the gradient all-reduce and the optimiser step.  Per element, with g the data gradient:
+ *   EWC:  F = a g^2 + b F
+ *   PI:   if counter > 0: delta += g (temp - p);  temp = p
+ *   RW:   if counter % iterations == 0 { if counter > 0: score += g (temp - p) / (0.5 F (p - temp)^2 + 1e-8);  temp = p }
+ *         F = a g^2 + b F
+ *   then, where `penalize` is set:  sum += omega (p - p_old)^2;  g += (lambda omega) (2 (p - p_old))
+ * (fp32, one rounding per operation, IEEE division: the reference's torch ops bit for bit; a = float(alpha),
+ * b = float(1 - alpha), lambda = float(reg_importance)).  Entry `score` holds PI's delta or RW's score.  State pointers a
+ * method does not use may be NULL; p_old and omega may be NULL where penalize == 0.  All arrays of an entry share one dense
+ * layout of n elements.  blocks [n_blocks][2] (device, int32) = {table entry, chunk of ucd_reg_chunk() elements}.
+ * The hyper-parameters and the update counter live in device memory (written once by ucd_reg_hyper_store); the second launch
+ * of ucd_reg_step adds the per-block fp64 partials (device, n_blocks doubles) in a fixed order, writes
+ * penalty[0] = float(reg_importance * sum) and increments the counter, so a captured step graph advances it on every replay.
+ * No allocation, no host synchronisation.  UCD_EINVAL: n_blocks < 0, NULL table / blocks / hyper / partials / penalty with
+ * n_blocks > 0, unknown method.  n_blocks == 0: no-op. */
+#define UCD_REG_EWC 0
+#define UCD_REG_PI 1
+#define UCD_REG_RW 2
+typedef struct ucd_reg_tensor {
+  float* p;  float* g;  const float* p_old;  const float* omega;
+  float* fisher;  float* score;  float* temp;
+  long long n;
+  int penalize;  int pad;
+} ucd_reg_tensor;
+typedef struct ucd_reg_hyper {
+  double reg_importance;
+  float alpha, one_minus_alpha, lambda_f;
+  int iterations;
+  int counter;
+  int pad;
+} ucd_reg_hyper;
+int ucd_reg_chunk(void);
+int ucd_reg_hyper_store(ucd_reg_hyper* device_hyper, const ucd_reg_hyper* hyper, ucd_stream_t stream);
+int ucd_reg_step(const ucd_reg_tensor* table, const int* blocks, int n_blocks, int method, ucd_reg_hyper* device_hyper,
+                 double* partials, float* penalty, ucd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -77,7 +77,7 @@ _ARGS = [
     _flag("--test", **_ON), _flag("--ckpt", default=None, type=str),
     # distillation (ILT)
     _flag("--freeze", **_ON), _flag("--loss_de", type=float, default=0.), _flag("--loss_kd", type=float, default=0.),
-    # regularisers (EWC / RW / PI): accepted for CLI compatibility, not on the UCD path
+    # regularisers (EWC / RW / PI; --method EWC|RW|PI): ucd_amd.regularizer, after the UCD step
     _flag("--regularizer", default=None, type=str, choices=["ewc", "rw", "pi"]),
     _flag("--reg_importance", type=float, default=1.), _flag("--reg_alpha", type=float, default=0.9),
     _flag("--reg_no_normalize", **_ON), _flag("--reg_iterations", type=int, default=10),

@@ -212,18 +212,20 @@ def main(opts):
     scheduler = PolyLR(optimizer, max_iters=opts.epochs * len(train_loader), power=opts.lr_power)
     model = DistributedDataParallel(model, delay_allreduce=True,
                                     bf16_weights=getattr(opts, "opt_level", "O0") != "O0" and getattr(opts, "bf16_weights", True))
+    trainer_state = None
     if opts.step > 0:
         path = opts.step_ckpt or f"checkpoints/step/{task_name}_{opts.name}_{opts.step - 1}.pth"
         if os.path.exists(path):
             ckpt = torch.load(path, map_location="cpu")
             load_step_checkpoint(opts, model, model_old, ckpt["model_state"], device)
+            trainer_state = ckpt.get("trainer_state")                     # run.py:236-243 (the regulariser's state)
             logger.info(f"[!] Previous model loaded from {path}")
         elif not opts.debug:
             raise FileNotFoundError(path)
         for p in model_old.parameters():
             p.requires_grad = False
         model_old.eval()
-    trainer = Trainer(model, model_old, device=device, opts=opts, classes=classes)
+    trainer = Trainer(model, model_old, device=device, opts=opts, trainer_state=trainer_state, classes=classes)
     # validation set + streaming metrics (run.py:161-164, 304-338): synthetic images carrying every class seen so far
     n_classes = sum(classes)
     seen = [l for l in (list(labels_old) + list(labels)) if l != 0] or [1]
@@ -239,6 +241,8 @@ def main(opts):
         optimizer.load_state_dict(ckpt["optimizer_state"])
         scheduler.load_state_dict(ckpt["scheduler_state"])
         cur_epoch, best_score = ckpt["epoch"] + 1, ckpt["best_score"]
+        if "trainer_state" in ckpt:                                       # run.py:258-259
+            trainer.load_state_dict(ckpt["trainer_state"])
     ckpt_path = f"checkpoints/step/{task_name}_{opts.name}_{opts.step}.pth"
     while cur_epoch < opts.epochs and not opts.test:
         epoch_loss = trainer.train(cur_epoch=cur_epoch, optim=optimizer, train_loader=train_loader,

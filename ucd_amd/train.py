@@ -16,8 +16,8 @@ What changed for the hardware: activations are channels-last bf16 (``--opt_level
 the contrastive term is one fused HIP operation with no host round trip; the per-iteration ``.item()``
 reads (train.py:153-157, >= 5 device syncs) are replaced by device-side accumulators read once per
 ``print_int`` iterations; gradient averaging overlaps the backward (ucd_amd.ddp).
-Out of scope on this path (raise ``NotImplementedError``): BCE/iCaRL losses and the EWC/RW/PI
-regularisers of the other baselines.
+EWC / PI / RW (``--method EWC|PI|RW``) add the weight-space penalty of ucd_amd.regularizer between the gradient
+all-reduce and the optimiser (train.py:139-145).  Out of scope on this path (raise ``NotImplementedError``): BCE/iCaRL.
 """
 from __future__ import annotations
 
@@ -49,8 +49,6 @@ class Trainer:
         if opts.bce or opts.icarl:
             raise NotImplementedError("BCE / iCaRL (--bce, --icarl, --method LWF-MC) are other baselines, "
                                       "outside the UCD hot path")
-        if getattr(opts, "regularizer", None) is not None:
-            raise NotImplementedError("EWC / RW / PI regularisers are outside the UCD hot path")
         self.temperature = opts.temperature
         self.pixcon_weight = getattr(opts, "pixcon_weight", 0.01)      # the reference hard-codes /100 (train.py:116)
         # the reference clamps down-sampled labels at the VOC bound 20 (utils/utils.py:267-268); datasets
@@ -66,7 +64,6 @@ class Trainer:
         self.lkd = opts.loss_kd
         self.lkd_flag = self.lkd > 0. and model_old is not None
         self.lkd_loss = (UnbiasedKnowledgeDistillationLoss if opts.unkd else KnowledgeDistillationLoss)(alpha=opts.alpha)
-        self.regularizer, self.regularizer_flag = None, False
         # The frozen teacher (eval mode, no gradients, no collectives) is replayed from a hipGraph after two eager
         # warm-up steps: ~330 kernel launches of host work per step disappear, which matters once the per-GPU batch
         # is small (8-GPU regime: the step is launch-bound, not GPU-bound).
@@ -93,6 +90,15 @@ class Trainer:
         if self.amp and device.type == "cuda" and model_old is not None and getattr(opts, "bf16_weights", True):
             from .master import Bf16Weights
             self._teacher_w16 = Bf16Weights(model_old, trainable=False)
+        # EWC / PI / RW (train.py:69-72): the whole UCD step, then the weight-space penalty (ucd_amd.regularizer).  Built after
+        # the teacher's Bf16Weights, which moves its fp32 convolution weights into one flat buffer: theta_old then points at
+        # the storage the teacher keeps, not at a copy it dropped
+        self.regularizer, self.regularizer_flag = None, False
+        if getattr(opts, "regularizer", None) is not None:
+            from .regularizer import get_regularizer
+            reg_state = trainer_state["regularizer"] if trainer_state is not None else None
+            self.regularizer = get_regularizer(model, model_old, device, opts, reg_state)
+            self.regularizer_flag = self.regularizer is not None
         self.last = {}
         # The WHOLE iteration (teacher + student forward, losses, backward, gradient buckets, optimiser) as one hipGraph,
         # captured after the eager warm-up iterations and replayed from then on: at the per-rank batch of the 8-GPU run
@@ -182,13 +188,16 @@ class Trainer:
         one-launch optimiser with its tables in place (its hyper-parameters can then live on the device)."""
         from .optim import SGD
         return (hasattr(self.model, "finish_grad_sync") and hasattr(self.model, "zero_grad") and isinstance(optim, SGD)
-                and optim.plan_is_current())
+                and optim.plan_is_current() and self._reg_plan_is_current())
+
+    def _reg_plan_is_current(self):
+        return not self.regularizer_flag or self.regularizer.plan_is_current()
 
     def _graph_step(self, images, labels, optim, scheduler):
         """Replay (or capture, then replay) the iteration; None when this call has to run eagerly."""
         key = (tuple(images.shape), tuple(labels.shape), images.dtype, labels.dtype, id(optim), self.model.training)
         sg = self._sg
-        if sg is not None and sg["key"] == key and not optim.plan_is_current():
+        if sg is not None and sg["key"] == key and not (optim.plan_is_current() and self._reg_plan_is_current()):
             # parameters / gradients / momentum buffers moved (load_state_dict, add_param_group, a re-wrapped model): the captured
             # optimiser launch holds the old addresses - drop the graph, run eagerly, capture again after the warm-up count
             self._sg, self._sg_seen, sg = None, 0, None
@@ -302,11 +311,16 @@ class Trainer:
         loss_tot.backward()
         if hasattr(model, "finish_grad_sync"):
             model.finish_grad_sync()
+        if self.regularizer_flag:
+            # train.py:139-145: update the importance from the reduced data gradient, add reg_importance * penalty's gradient
+            l_reg = self.regularizer.step()
         optim.step()
         if scheduler is not None:
             scheduler.step()
         self.last = {"loss": loss.detach(), "lkd": lkd.detach(), "lde": lde.detach(), "ce": ce.detach(),
                      "con": con.detach()}
+        if self.regularizer_flag:
+            self.last["reg"] = l_reg.detach()
         return self.last
 
     def train(self, cur_epoch, optim, train_loader, scheduler=None, print_int=10, logger=None):
@@ -326,6 +340,9 @@ class Trainer:
             epoch_loss += r["loss"]
             reg_loss += r["lkd"] + r["lde"]
             interval += r["loss"] + r["lkd"] + r["lde"]
+            if "reg" in r:                                      # train.py:154-157: l_reg counts as regularisation loss
+                reg_loss += r["reg"]
+                interval += r["reg"]
             n += 1
             if (cur_step + 1) % print_int == 0:
                 value = (interval / print_int).item()           # the only host sync of the interval
@@ -399,7 +416,8 @@ class Trainer:
         return (class_loss, reg_loss), score, []
 
     def state_dict(self):
-        return {"regularizer": None}
+        return {"regularizer": self.regularizer.state_dict() if self.regularizer_flag else None}
 
     def load_state_dict(self, state):
-        pass
+        if state["regularizer"] is not None and self.regularizer is not None:
+            self.regularizer.load_state_dict(state["regularizer"])
