@@ -619,7 +619,7 @@ int ucd_conv_wgrad_strided(const void* dz, int ld_dz, const void* x, int ld_x, i
  * SIDE STREAM (round 6, mode bit 1 / flags bit 1): nothing in a backward pass waits for a weight gradient before the optimiser, yet on
  * the caller's stream each one sits in the chain of input-gradient products - ~190 of the ~850 dependent launches of a step, which at
  * 3 - 6 images per GPU fill a quarter of the chip each.  Under ucd_conv_wgrad_defer(mode) with mode & 2, a call with flags & 2 runs
- * on a stream owned by the library (lowest priority), forked behind `stream`
+ * on a stream owned by the library (lowest priority, one per caller stream), forked behind `stream`
  * and joined back into `stream` by ucd_conv_wgrad_flush(stream) / ucd_conv_wgrad_drop(stream); under stream capture fork and join
  * become the graph's edges.  An accepted call records its fork point on `stream` at once, its launches go out at the NEXT accepted
  * call or at the flush: in a replayed graph the branch created first keeps the fork point's hardware queue and the other one hops
@@ -628,7 +628,12 @@ int ucd_conv_wgrad_strided(const void* dz, int ld_dz, const void* x, int ld_x, i
  * streams until that flush, `workspace` is not the one of a call without the flag, and dw is not read before the flush; an error
  * of a launch made later is returned by the call that triggers it.  Results are the same bits either way (the same kernels on the
  * same operands).
- * ucd_conv_wgrad_defer(mode): bit 0 deferral, bit 1 side stream; returns the previous mode.  ucd_conv_wgrad_mode(): the mode. */
+ *
+ * The library keeps one record per CALLER stream: its pending sum, its side stream with the armed call and that stream's pending
+ * sum.  ucd_conv_wgrad_flush(stream) launches the armed call and the pending sums of the record and joins its side stream;
+ * ucd_conv_wgrad_drop(stream) forgets the pending sums and the armed call and joins launched side work.
+ * ucd_conv_wgrad_defer(mode): bit 0 deferral, bit 1 side stream; returns the previous mode (process-wide).  ucd_conv_wgrad_mode():
+ * the mode. */
 int ucd_conv_wgrad_ex(const void* dz, int ld_dz, const void* x, int ld_x, int M, int N, int K, int taps, int H, int W, int dilation,
                       int stride, void* dw, float* dw32, int accumulate32, void* workspace, size_t workspace_bytes, int flags,
                       ucd_stream_t stream);
@@ -636,6 +641,9 @@ int ucd_conv_wgrad_defer(int mode);
 int ucd_conv_wgrad_mode(void);
 int ucd_conv_wgrad_flush(ucd_stream_t stream);
 int ucd_conv_wgrad_drop(ucd_stream_t stream);
+/* ucd_conv_wgrad_drop on every caller stream the library holds state for (an aborted backward whose streams the caller no longer
+ * knows, e.g. a failed capture); the mode is kept; returns the first error (a NULL stream cannot mean "all": it is the default stream). */
+int ucd_conv_wgrad_drop_all(void);
 
 /* The weights of the input-gradient convolutions of ALL stride-1 layers in one launch: for table entry e = {src offset,
  * dst offset, Co, Ci, KH*KW} (elements into the flat bf16 buffers; 4-D weights in channels-last memory order

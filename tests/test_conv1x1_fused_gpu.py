@@ -1746,3 +1746,128 @@ def test_deferred_weight_gradients_are_final_when_any_backward_pass_ends():
         finally:
             hip.wgrad_drop()
             hip.wgrad_defer(0)
+
+
+def test_drop_all_forgets_the_weight_gradient_work_of_every_stream():
+    """ucd_conv_wgrad_drop_all (include/ucd_hip.h): deferred and armed weight-gradient work that an aborted backward left on two caller
+    streams is forgotten on both - a flush of either stream afterwards is a no-op, no dropped sum lands in its gradient (nor rides in
+    a later launch), and the mode stays."""
+    from ucd_amd import hip
+    g = torch.Generator(DEV).manual_seed(23)
+    M, K, N = 3267, 256, 256
+    dz = (torch.randn(M, N, device=DEV, generator=g) * 0.1).bfloat16()
+    x = torch.randn(M, K, device=DEV, generator=g).bfloat16()
+    want = hip.conv_wgrad(dz, x, dw=torch.empty(N, K, device=DEV, dtype=torch.bfloat16)).clone()
+    lib = hip.load()
+    sa, sb = torch.cuda.Stream(DEV), torch.cuda.Stream(DEV)
+    torch.cuda.synchronize()
+    assert hip.wgrad_defer(3) == 0
+    try:
+        dropped, plain = [], []
+        with torch.cuda.stream(sa):                                   # a deferred sum pending on stream a
+            dropped.append(torch.full_like(want, float("nan")))
+            hip.conv_wgrad(dz, x, dw=dropped[-1], defer=True)
+        with torch.cuda.stream(sb):                                   # stream b: one call launched on its side stream with its sum
+            for _ in range(2):                                        # pending there, one armed
+                dropped.append(torch.full_like(want, float("nan")))
+                hip.conv_wgrad(dz, x, dw=dropped[-1], defer=True, side=True)
+        assert hip.wgrad_drop_all() == 0
+        assert lib.ucd_conv_wgrad_mode() == 3
+        for s in (sa, sb):
+            with torch.cuda.stream(s):
+                hip.wgrad_flush()                                     # nothing left: a no-op
+                plain.append(hip.conv_wgrad(dz, x, dw=torch.empty_like(want)))   # a pending sum would ride in this launch
+        torch.cuda.synchronize()
+        assert all(bool(torch.isnan(d.float()).all()) for d in dropped)
+        assert all(torch.equal(p, want) for p in plain)
+    finally:
+        hip.wgrad_drop_all()
+        assert hip.wgrad_defer(0) == 3
+
+
+def _stride1_chain(seed):
+    """Three 3x3 layers (256 channels, dilation 2) on the C++ node, every product on the own kernels (deterministic: mode 0 gives
+    the same bits run to run); None when the node is not built."""
+    from ucd_amd import abn as _abn
+    node = _abn._abn_node()
+    if node is None or not hasattr(node, "conv_stride1"):
+        return None, None, None
+    g = torch.Generator(DEV).manual_seed(seed)
+    x = torch.randn(3, 256, 33, 33, device=DEV, generator=g).bfloat16().contiguous(memory_format=torch.channels_last)
+    ws = [(torch.randn(256, 256, 3, 3, device=DEV, generator=g) * 0.02).bfloat16().contiguous(memory_format=torch.channels_last)
+          .requires_grad_() for _ in range(3)]
+    return node, x, ws
+
+
+def test_a_backward_pass_that_died_leaves_the_next_one_its_end_of_pass_flush():
+    """The end-of-pass flush belongs to the autograd pass (csrc/abn_node.cpp: by graph task).  A pass stopped by an exception after
+    its first deferring call never runs its callback; the next ``torch.autograd.grad`` pass under the same mode still queues one,
+    runs it exactly once and returns the bits of mode 0."""
+    from ucd_amd import hip
+    node, x, ws = _stride1_chain(6)
+    if node is None:
+        pytest.skip("C++ autograd nodes not built")
+
+    class Stop(Exception):
+        pass
+
+    def stop(grad):
+        raise Stop()
+
+    def grads(hook=None):
+        y = x
+        for i, w in enumerate(ws):
+            y = node.conv_stride1(y, w, 2, None, True, True, hip.stream(), True)
+            if i == 1 and hook is not None:
+                y.register_hook(hook)                         # runs behind the last layer's backward, its weight gradient included
+        return torch.autograd.grad(y.float().square().mean(), ws)
+
+    want = grads()                                            # mode 0 (kept alive: no later buffer inherits its bits)
+    torch.cuda.synchronize()
+    assert hip.wgrad_defer(3) == 0
+    try:
+        n0 = node.pass_flushes()
+        with pytest.raises(Stop):
+            grads(stop)
+        assert node.pass_flushes() == n0                      # the dead pass ran no callback
+        got = grads()
+        assert node.pass_flushes() == n0 + 1
+        torch.cuda.synchronize()
+        assert all(torch.equal(a, b) for a, b in zip(got, want))
+    finally:
+        hip.wgrad_drop_all()
+        assert hip.wgrad_defer(0) == 3
+
+
+def test_the_end_of_pass_flush_covers_every_stream_of_the_pass():
+    """One backward pass whose deferring calls run on two streams (the middle layer's forward - hence its backward - on a stream of
+    its own): its single end-of-pass callback flushes both, and the gradients are the bits of mode 0."""
+    from ucd_amd import hip
+    node, x, ws = _stride1_chain(7)
+    if node is None:
+        pytest.skip("C++ autograd nodes not built")
+    other = torch.cuda.Stream(DEV)
+
+    def grads():
+        main = torch.cuda.current_stream()
+        y1 = node.conv_stride1(x, ws[0], 2, None, True, True, hip.stream(), True)
+        other.wait_stream(main)
+        with torch.cuda.stream(other):
+            y2 = node.conv_stride1(y1, ws[1], 2, None, True, True, hip.stream(), True)
+        main.wait_stream(other)
+        y3 = node.conv_stride1(y2, ws[2], 2, None, True, True, hip.stream(), True)
+        got = torch.autograd.grad(y3.float().square().mean(), ws)
+        torch.cuda.synchronize()                              # (the forward maps stay referenced until both streams are done)
+        return got
+
+    want = grads()                                            # mode 0
+    n0 = node.pass_flushes()
+    for i, mode in enumerate((1, 3)):
+        assert hip.wgrad_defer(mode) == 0
+        try:
+            got = grads()
+            assert node.pass_flushes() == n0 + i + 1          # one callback ...
+            assert all(torch.equal(a, b) for a, b in zip(got, want)), mode   # ... that flushed both streams
+        finally:
+            hip.wgrad_drop_all()
+            assert hip.wgrad_defer(0) == mode

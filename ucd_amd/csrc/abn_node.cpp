@@ -11,10 +11,12 @@
 // The reference reaches the same work through inplace_abn's autograd Functions (segmentation_module.py:15-20).
 #include <torch/extension.h>
 #include <torch/csrc/autograd/engine.h>
+#include <torch/csrc/autograd/graph_task.h>
 
 #include <cstring>
 #include <map>
 #include <mutex>
+#include <set>
 
 #include "../../include/ucd_hip.h"
 
@@ -32,10 +34,10 @@ std::mutex g_mu;
 std::map<std::pair<int, int64_t>, at::Tensor> g_ws;
 
 // Tensors that kernels on the library's SIDE stream (weight gradients, include/ucd_hip.h ucd_conv_wgrad_ex flags & 2) still read or
-// write: the caching allocator knows nothing of that stream, so the operands stay referenced here until the join
-// (wgrad_side_release, called behind ucd_conv_wgrad_flush / _drop) - a block freed on the compute stream before that could be handed
-// to a later kernel of that stream while the side stream is still reading it.
-std::vector<at::Tensor> g_side_hold;
+// write, by the caller's stream: the caching allocator knows nothing of the side stream, so the operands stay referenced here until
+// a join of that stream succeeded (wgrad_side_release) - a block freed on the compute stream before that could be handed to a later
+// kernel of that stream while the side stream is still reading it.
+std::map<int64_t, std::vector<at::Tensor>> g_side_hold;
 constexpr int kWsTags = 8;     // tags 0 / 1 scratch of the nodes, 2 / 3 slab workspaces in turn, 4 / 5 the same for side-stream calls
 
 void* workspace(const at::Tensor& like, size_t bytes, int64_t stream, int tag = 0) {
@@ -44,41 +46,55 @@ void* workspace(const at::Tensor& like, size_t bytes, int64_t stream, int tag = 
   auto it = g_ws.find(key);
   if (it == g_ws.end() || (size_t)it->second.numel() < bytes) {
     size_t n = bytes < ((size_t)1 << 20) ? ((size_t)1 << 20) : bytes;
-    if (it != g_ws.end() && tag >= 4) g_side_hold.push_back(it->second);     // the side stream may still be in the old buffer
+    if (it != g_ws.end() && tag >= 4) g_side_hold[stream].push_back(it->second);     // the side stream may still be in the old buffer
     g_ws[key] = at::empty({(int64_t)n}, like.options().dtype(at::kByte));
     it = g_ws.find(key);
   }
   return it->second.data_ptr();
 }
 
-int64_t g_pass_flushes = 0;      // test hook: end-of-pass flushes run so far
-bool g_pass_cb_queued = false;   // under g_mu: this backward pass already has its end-of-pass flush queued
-
-void wgrad_side_release() {
-  std::vector<at::Tensor> gone;
+// the operands held for the side work of `stream` (every stream: nullopt) - call only behind a join that succeeded
+void wgrad_side_release(c10::optional<int64_t> stream) {
+  std::map<int64_t, std::vector<at::Tensor>> gone;
   {
     std::lock_guard<std::mutex> lock(g_mu);
-    gone.swap(g_side_hold);
-    g_pass_cb_queued = false;      // (a pass that died before its callbacks ran must not leave the flag behind)
+    if (!stream) gone.swap(g_side_hold);
+    else if (auto it = g_side_hold.find(*stream); it != g_side_hold.end()) gone.insert(g_side_hold.extract(it));
   }
 }   // the tensors are released outside the lock
+
+int64_t g_pass_flushes = 0;                      // test hook: end-of-pass flushes run so far
+std::map<int, std::set<int64_t>> g_pass_streams;  // under g_mu: by autograd graph task, the streams its deferring calls ran on
 
 // A weight-gradient call that may be deferred / moved to the side stream is final only behind ucd_conv_wgrad_flush.  The
 // gradient-bucket wrapper flushes in front of its copies - but a pass it does not see to its end (torch.autograd.grad under the
 // wrapper: no AccumulateGrad, no hook) would hand out gradients whose last slab sum never ran.  So the first such call of a backward
 // pass queues the flush as an engine callback: it runs when the pass ends, whoever started it, in stream order before the caller
-// gets its gradients (a second flush by the wrapper is a no-op).
+// gets its gradients, and flushes every stream the pass's calls ran on (a second flush by the wrapper is a no-op).  A pass that dies
+// never runs its callback (its entry stays behind, a few bytes); the next pass is another graph task and queues its own.
 void queue_end_of_pass_flush(int64_t stream) {
+  const int task = torch::autograd::get_current_graph_task_id();
   {
     std::lock_guard<std::mutex> lock(g_mu);
-    if (g_pass_cb_queued) return;
-    g_pass_cb_queued = true;
+    auto [it, first] = g_pass_streams.try_emplace(task);
+    it->second.insert(stream);
+    if (!first) return;
   }
-  torch::autograd::Engine::get_default_engine().queue_callback([stream]() {
+  torch::autograd::Engine::get_default_engine().queue_callback([task]() {
     ++g_pass_flushes;
-    const int rc = ucd_conv_wgrad_flush((ucd_stream_t)stream);
-    wgrad_side_release();
-    TORCH_CHECK(rc == 0, "ucd_conv_wgrad_flush failed at the end of the backward pass (code ", rc, "): ", ucd_last_error());
+    std::set<int64_t> streams;
+    {
+      std::lock_guard<std::mutex> lock(g_mu);
+      streams = std::move(g_pass_streams.at(task));
+      g_pass_streams.erase(task);
+    }
+    std::string err;
+    for (int64_t s : streams) {
+      const int rc = ucd_conv_wgrad_flush((ucd_stream_t)s);
+      if (rc == 0) wgrad_side_release(s);
+      else if (err.empty()) err = "code " + std::to_string(rc) + ": " + ucd_last_error();
+    }
+    TORCH_CHECK(err.empty(), "ucd_conv_wgrad_flush failed at the end of the backward pass (", err, ")");
   });
 }
 
@@ -205,9 +221,10 @@ int wgrad_flags(const at::Tensor& w4, bool* side) {
   *side = (ucd_conv_wgrad_mode() & 2) != 0;
   return *side ? 3 : 1;
 }
-void hold_for_side(std::initializer_list<at::Tensor> ts) {
+void hold_for_side(int64_t stream, std::initializer_list<at::Tensor> ts) {
   std::lock_guard<std::mutex> lock(g_mu);
-  for (const auto& t : ts) g_side_hold.push_back(t);
+  auto& held = g_side_hold[stream];
+  held.insert(held.end(), ts);
 }
 
 // May the slab sum of this weight gradient wait for the next weight-gradient launch?  Only when nothing reads the gradient before the
@@ -224,7 +241,7 @@ at::Tensor own_wgrad(const at::Tensor& dz, const at::Tensor& x, const at::Tensor
   const size_t wsb = ucd_conv_wgrad_workspace_bytes((int)M, (int)N, (int)K, taps);
   bool side;
   const int flags = wgrad_flags(w4, &side);
-  if (side) hold_for_side({dz, x, dw});
+  if (side) hold_for_side(stream, {dz, x, dw});
   if (flags && ucd_conv_wgrad_mode()) queue_end_of_pass_flush(stream);
   check(ucd_conv_wgrad_ex(dz.data_ptr(), (int)N, x.data_ptr(), (int)K, (int)M, (int)N, (int)K, taps, (int)H, (int)W,
                           (int)(dilation > 0 ? dilation : 1), (int)stride, dw.data_ptr(), nullptr, 0,
@@ -344,7 +361,7 @@ at::Tensor own_wgrad_rows(const at::Tensor& dy, const at::Tensor& rows, int64_t 
   const size_t wsb = ucd_conv_wgrad_workspace_bytes((int)M, (int)Co, (int)Ci, 1);
   bool side;
   const int flags = wgrad_flags(w4, &side);
-  if (side) hold_for_side({dy, rows, dw});
+  if (side) hold_for_side(stream, {dy, rows, dw});
   if (flags && ucd_conv_wgrad_mode()) queue_end_of_pass_flush(stream);
   check(ucd_conv_wgrad_ex(dy.data_ptr(), (int)Co, rows.data_ptr(), (int)Ci, (int)M, (int)Co, (int)Ci, 1, 0, 0, 1, 1, dw.data_ptr(), nullptr, 0,
                           wgrad_workspace(rows, wsb, stream, side), wsb, flags, (ucd_stream_t)stream),
@@ -1080,7 +1097,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "C++ autograd node of the training-mode ABN layer over libucd_hip.so";
   m.def("poison_workspaces", &poison_workspaces);
   m.def("pass_flushes", []() { return g_pass_flushes; }, "number of end-of-pass flushes the nodes' engine callbacks have run (test hook)");
-  m.def("wgrad_side_release", &wgrad_side_release, "drop the operands held for the side stream of the weight gradients (after the join)");
+  m.def("wgrad_side_release", &wgrad_side_release, py::arg("stream") = py::none(),
+        "drop the operands held for the side work of a stream (None: every stream) - only after its join succeeded");
   m.def("stat_arena_reset", &stat_arena_reset, "zero the used part of the statistics arena of a device and start a new generation");
   m.def("abn_train", &abn_train, "y = act(BN_batch(x) [+ residual]) with autograd in C++");
   m.def("dense_channels_last", &dense_channels_last);

@@ -730,13 +730,7 @@ bool wgrad3_enabled() {
   return !(e && e[0] == '0');
 }
 
-// ---- deferred slab sums: host state (see SumArgs above) ---------------------------------------------------------------------------
-// One pending sum per stream; ucd_conv_wgrad_ex(flags & 1) under ucd_conv_wgrad_defer(mode & 1) leaves its sum pending and carries the
-// previous one of that stream in its launch.  g_defer holds the mode: bit 0 deferral, bit 1 the side stream (below).
-std::mutex g_pend_mu;
-std::map<hipStream_t, SumArgs> g_pend;
-int g_defer = 0;
-
+// ---- deferred slab sums and the side stream: host state (see SumArgs above) --------------------------------------------------------
 SumArgs make_sum(const void* workspace, int chunks, size_t total, void* dw, float* dw32, int accumulate32) {
   SumArgs q;
   q.partial = (const float*)workspace; q.chunks = chunks; q.total = total; q.dW = (bf16*)dw; q.dW32 = dw32; q.accumulate = accumulate32;
@@ -747,21 +741,13 @@ SumArgs make_sum(const void* workspace, int chunks, size_t total, void* dw, floa
   else { q.cl = 1; q.blocks = (int)((groups8 + kThreads - 1) / kThreads); }
   return q;
 }
-SumArgs take_pending(hipStream_t s) {
-  std::lock_guard<std::mutex> lock(g_pend_mu);
-  SumArgs q{};
-  auto it = g_pend.find(s);
-  if (it != g_pend.end()) { q = it->second; g_pend.erase(it); }
-  return q;
-}
 
-// ---- side stream (round 6) ----------------------------------------------------------------------------------------------------------
-// Nothing in the backward pass waits for a weight gradient before the optimiser, but on the caller's stream every one of them sits in
-// the chain of input-gradient products: at 3 - 6 images per GPU (the per-rank batch of the 8-GPU run) a step is ~850 launches of
-// ~10 us, each waiting for the one before, on a chip the small launches fill to a quarter.  A call that allows it (flags & 2, mode
-// bit 1) runs on a stream of the library instead: forked behind the caller's stream at the call (the operands are ready there),
-// joined back by ucd_conv_wgrad_flush / _drop.  Under stream capture the fork and the join become the graph's edges.  The caller
-// keeps dz, x, dw and the workspace alive until the join and does not touch dw before it.
+// Side stream (round 6).  Nothing in the backward pass waits for a weight gradient before the optimiser, but on the caller's stream
+// every one of them sits in the chain of input-gradient products: at 3 - 6 images per GPU (the per-rank batch of the 8-GPU run) a
+// step is ~850 launches of ~10 us, each waiting for the one before, on a chip the small launches fill to a quarter.  A call that
+// allows it (flags & 2, mode bit 1) runs on a stream of the library instead: forked behind the caller's stream at the call (the
+// operands are ready there), joined back by ucd_conv_wgrad_flush / _drop / _drop_all.  Under stream capture the fork and the join
+// become the graph's edges.  The caller keeps dz, x, dw and the workspace alive until the join and does not touch dw before it.
 //
 // A fork can cost the CALLER's chain: in a replayed graph ROCm keeps the branch whose first node was created FIRST on the hardware
 // queue of the fork point and continues the other branch on another queue, behind a cross-queue signal (~8 us).  Launching the side
@@ -777,63 +763,30 @@ struct ExArgs {
   void* dw; float* dw32; int accumulate32; void* workspace; size_t workspace_bytes; int flags;
 };
 bool wgrad_three(const ExArgs& q, int oW, int oH);
-int wgrad_launch_on(const ExArgs& q, hipStream_t s);
+int wgrad_launch_on(const ExArgs& q, hipStream_t s, SumArgs& pending);
 
-struct Side {
-  hipStream_t s = nullptr;
+// Everything the library keeps for one CALLER stream.  A launch on a stream carries that stream's pending sum (ucd_conv_wgrad_ex
+// flags & 1 under mode bit 0 leaves its own there instead of launching it); the side stream's pending sum lives in the record of
+// its caller, so no state is keyed by a stream of the library.
+struct StreamState {
+  SumArgs pending{};               // the sum the next launch on the caller's stream carries (blocks 0: none)
+  hipStream_t side = nullptr;      // the side stream, created at the first call that takes it, with its fork / join events
   hipEvent_t fork = nullptr, join = nullptr;
-  bool active = false;             // work since the last join
+  bool active = false;             // side work since the last join
   std::optional<ExArgs> armed;     // an accepted call whose fork point is recorded, launched at the next call or the flush
+  SumArgs side_pending{};          // the sum the next launch on the side stream carries
 };
-std::map<hipStream_t, Side> g_side;     // by the caller's stream; under g_pend_mu
+// One lock over all of it, held across the launches it orders (calls on one stream are ordered anyway).  The mode is process-wide:
+// bit 0 deferral, bit 1 the side stream (ucd_conv_wgrad_defer).
+std::mutex g_mu;
+std::map<hipStream_t, StreamState> g_streams;      // by the caller's stream
+int g_mode = 0;
 
-// the side stream of `main`; nullptr (with the error set) when HIP refuses
-// phase 1: record the fork point on `main`; phase 2: let the side stream wait for the recorded point
-hipStream_t side_fork(hipStream_t main, const char* fn, int phase) {
-  std::lock_guard<std::mutex> lock(g_pend_mu);
-  Side& sd = g_side[main];
-  if (!sd.s) {
-    int least = 0, greatest = 0;
-    hipStream_t st = nullptr;
-    hipEvent_t f = nullptr, j = nullptr;
-    bool ok = hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess &&     // the lowest priority: the chain goes first
-              hipStreamCreateWithPriority(&st, hipStreamNonBlocking, least) == hipSuccess &&
-              hipEventCreateWithFlags(&f, hipEventDisableTiming) == hipSuccess &&
-              hipEventCreateWithFlags(&j, hipEventDisableTiming) == hipSuccess;
-    if (!ok) {
-      (void)hipGetLastError();
-      set_error("%s: cannot create the side stream of the weight gradients", fn);
-      return nullptr;
-    }
-    sd.s = st; sd.fork = f; sd.join = j;
-  }
-  if (phase == 1 && hipEventRecord(sd.fork, main) != hipSuccess) {
-    (void)hipGetLastError();
-    set_error("%s: cannot record the fork point on the caller's stream", fn);
-    return nullptr;
-  }
-  if (phase == 2) {
-    if (hipStreamWaitEvent(sd.s, sd.fork, 0) != hipSuccess) {
-      (void)hipGetLastError();
-      set_error("%s: cannot fork the side stream behind the caller's", fn);
-      return nullptr;
-    }
-    sd.active = true;
-  }
-  return sd.s;
-}
-// the side stream of `main` when it holds work since the last join, else nullptr
-hipStream_t side_active(hipStream_t main) {
-  std::lock_guard<std::mutex> lock(g_pend_mu);
-  auto it = g_side.find(main);
-  return it != g_side.end() && it->second.active ? it->second.s : nullptr;
-}
-int side_join(hipStream_t main, const char* fn) {
-  std::lock_guard<std::mutex> lock(g_pend_mu);
-  auto it = g_side.find(main);
-  if (it == g_side.end() || !it->second.active) return 0;
-  it->second.active = false;
-  if (hipEventRecord(it->second.join, it->second.s) != hipSuccess || hipStreamWaitEvent(main, it->second.join, 0) != hipSuccess) {
+// ---- under g_mu ----
+int join_side(StreamState& st, hipStream_t main, const char* fn) {
+  if (!st.active) return 0;
+  st.active = false;
+  if (hipEventRecord(st.join, st.side) != hipSuccess || hipStreamWaitEvent(main, st.join, 0) != hipSuccess) {
     (void)hipGetLastError();
     set_error("%s: cannot join the side stream of the weight gradients", fn);
     return (int)hipErrorUnknown;
@@ -841,32 +794,77 @@ int side_join(hipStream_t main, const char* fn) {
   return 0;
 }
 
-// launch the armed call of `main` on its side stream, behind the fork point it recorded (the caller's stream has moved on since)
-int side_launch_armed(hipStream_t main, const char* fn) {
-  ExArgs q;
-  {
-    std::lock_guard<std::mutex> lock(g_pend_mu);
-    auto it = g_side.find(main);
-    if (it == g_side.end() || !it->second.armed) return 0;
-    q = *it->second.armed;
-    it->second.armed.reset();
+// launch the armed call on the side stream, behind the fork point it recorded (the caller's stream has moved on since)
+int launch_armed(StreamState& st, const char* fn) {
+  if (!st.armed) return 0;
+  const ExArgs q = *st.armed;
+  st.armed.reset();
+  if (hipStreamWaitEvent(st.side, st.fork, 0) != hipSuccess) {
+    (void)hipGetLastError();
+    set_error("%s: cannot fork the side stream behind the caller's", fn);
+    return (int)hipErrorUnknown;
   }
-  hipStream_t sd = side_fork(main, fn, 2);
-  if (!sd) return (int)hipErrorUnknown;
-  return wgrad_launch_on(q, sd);
+  st.active = true;
+  return wgrad_launch_on(q, st.side, st.side_pending);
 }
-int side_enqueue(hipStream_t main, const ExArgs& q, const char* fn) {
-  const int rc = side_launch_armed(main, fn);                    // the previous call, behind its fork point
+
+// an accepted side call: the previous one goes out behind its fork point, this one records its fork point now and is armed
+int side_enqueue(StreamState& st, hipStream_t main, const ExArgs& q, const char* fn) {
+  const int rc = launch_armed(st, fn);
   if (rc) return rc;
-  if (!side_fork(main, fn, 1)) return (int)hipErrorUnknown;      // this call's fork point now, its launch at the next call
-  std::lock_guard<std::mutex> lock(g_pend_mu);
-  g_side[main].armed = q;
+  if (!st.side) {
+    int least = 0, greatest = 0;
+    hipStream_t s = nullptr;
+    hipEvent_t f = nullptr, j = nullptr;
+    const bool ok = hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess &&     // the lowest priority: the chain goes first
+                    hipStreamCreateWithPriority(&s, hipStreamNonBlocking, least) == hipSuccess &&
+                    hipEventCreateWithFlags(&f, hipEventDisableTiming) == hipSuccess &&
+                    hipEventCreateWithFlags(&j, hipEventDisableTiming) == hipSuccess;
+    if (!ok) {
+      (void)hipGetLastError();
+      set_error("%s: cannot create the side stream of the weight gradients", fn);
+      return (int)hipErrorUnknown;
+    }
+    st.side = s; st.fork = f; st.join = j;
+  }
+  if (hipEventRecord(st.fork, main) != hipSuccess) {
+    (void)hipGetLastError();
+    set_error("%s: cannot record the fork point on the caller's stream", fn);
+    return (int)hipErrorUnknown;
+  }
+  st.armed = q;
   return 0;
 }
-void side_forget(hipStream_t main) {
-  std::lock_guard<std::mutex> lock(g_pend_mu);
-  auto it = g_side.find(main);
-  if (it != g_side.end()) it->second.armed.reset();
+
+// the last armed call, the side stream's pending sum and the join, then the caller's pending sum
+int flush(StreamState& st, hipStream_t main, const char* fn) {
+  int rc = launch_armed(st, fn);
+  if (rc) return rc;
+  if (st.active) {
+    const SumArgs q = st.side_pending;
+    st.side_pending = SumArgs{};
+    if (q.blocks > 0) {
+      wgrad_sum_kernel<<<q.blocks, kThreads, 0, st.side>>>(q);
+      rc = check_launch(fn);
+      if (rc) { (void)join_side(st, main, fn); return rc; }
+    }
+    rc = join_side(st, main, fn);
+    if (rc) return rc;
+  }
+  const SumArgs q = st.pending;
+  st.pending = SumArgs{};
+  if (q.blocks <= 0) return 0;
+  wgrad_sum_kernel<<<q.blocks, kThreads, 0, main>>>(q);
+  return check_launch(fn);
+}
+
+// pending sums are forgotten and an armed call is never launched; launched side work cannot be taken back: it is joined (a capture
+// must not end forked)
+int drop(StreamState& st, hipStream_t main, const char* fn) {
+  st.pending = SumArgs{};
+  st.side_pending = SumArgs{};
+  st.armed.reset();
+  return join_side(st, main, fn);
 }
 
 int plan_target(int N, int K, int taps) {
@@ -906,49 +904,39 @@ int ucd_conv_wgrad_strided(const void* dz, int ld_dz, const void* x, int ld_x, i
 }
 
 int ucd_conv_wgrad_defer(int mode) {
-  std::lock_guard<std::mutex> lock(g_pend_mu);
-  const int was = g_defer;
-  g_defer = mode & 3;
+  std::lock_guard<std::mutex> lock(g_mu);
+  const int was = g_mode;
+  g_mode = mode & 3;
   return was;
 }
 
 int ucd_conv_wgrad_mode(void) {
-  std::lock_guard<std::mutex> lock(g_pend_mu);
-  return g_defer;
+  std::lock_guard<std::mutex> lock(g_mu);
+  return g_mode;
 }
 
 int ucd_conv_wgrad_flush(ucd_stream_t stream) {
-  static const char* fn = "ucd_conv_wgrad_flush";
   const hipStream_t main = (hipStream_t)stream;
-  {
-    const int rc = side_launch_armed(main, fn);        // the last accepted call
-    if (rc) return rc;
-  }
-  if (hipStream_t sd = side_active(main)) {            // the side stream: its pending sum, then the join
-    const SumArgs q = take_pending(sd);
-    if (q.blocks > 0) {
-      wgrad_sum_kernel<<<q.blocks, kThreads, 0, sd>>>(q);
-      const int rc = check_launch(fn);
-      if (rc) { (void)side_join(main, fn); return rc; }
-    }
-    const int rc = side_join(main, fn);
-    if (rc) return rc;
-  }
-  const SumArgs q = take_pending(main);
-  if (q.blocks <= 0) return 0;
-  wgrad_sum_kernel<<<q.blocks, kThreads, 0, main>>>(q);
-  return check_launch(fn);
+  std::lock_guard<std::mutex> lock(g_mu);
+  auto it = g_streams.find(main);
+  return it == g_streams.end() ? 0 : flush(it->second, main, "ucd_conv_wgrad_flush");
 }
 
 int ucd_conv_wgrad_drop(ucd_stream_t stream) {
   const hipStream_t main = (hipStream_t)stream;
-  (void)take_pending(main);
-  side_forget(main);                                   // a call not launched yet never is
-  if (hipStream_t sd = side_active(main)) {            // launched work cannot be taken back: join it (a capture must not end forked)
-    (void)take_pending(sd);
-    return side_join(main, "ucd_conv_wgrad_drop");
+  std::lock_guard<std::mutex> lock(g_mu);
+  auto it = g_streams.find(main);
+  return it == g_streams.end() ? 0 : drop(it->second, main, "ucd_conv_wgrad_drop");
+}
+
+int ucd_conv_wgrad_drop_all(void) {
+  std::lock_guard<std::mutex> lock(g_mu);
+  int first = 0;
+  for (auto& [main, st] : g_streams) {
+    const int rc = drop(st, main, "ucd_conv_wgrad_drop_all");
+    if (rc && !first) first = rc;
   }
-  return 0;
+  return first;
 }
 
 int ucd_conv_wgrad_ex(const void* dz, int ld_dz, const void* x, int ld_x, int M, int N, int K, int taps, int H, int W, int dilation,
@@ -978,9 +966,11 @@ int ucd_conv_wgrad_ex(const void* dz, int ld_dz, const void* x, int ld_x, int M,
     if (wgrad_three(q, oW, oH)) chunks = make_plan3(M, N, K).chunks;
     UCD_REQUIRE(workspace_bytes >= (size_t)chunks * N * taps * K * sizeof(float), UCD_EWORKSPACE, "%s: workspace too small", fn);
   }
-  hipStream_t s = (hipStream_t)stream;
-  if ((flags & 2) && (ucd_conv_wgrad_mode() & 2)) return side_enqueue(s, q, fn);      // off the caller's chain (see Side above)
-  return wgrad_launch_on(q, s);
+  const hipStream_t s = (hipStream_t)stream;
+  std::lock_guard<std::mutex> lock(g_mu);
+  StreamState& st = g_streams[s];
+  if ((flags & 2) && (g_mode & 2)) return side_enqueue(st, s, q, fn);      // off the caller's chain (see StreamState above)
+  return wgrad_launch_on(q, s, st.pending);
 }
 
 }  // extern "C"
@@ -996,7 +986,8 @@ bool wgrad_three(const ExArgs& q, int oW, int oH) {
          q.M >= 8192 && wgrad3_enabled();      // (small maps, 3 images per GPU: level with the 9-tap form or behind it)
 }
 
-int wgrad_launch_on(const ExArgs& q, hipStream_t s) {
+// under g_mu: the product on `s` carrying the sum `pending` holds, this call's own sum left there or launched behind the product
+int wgrad_launch_on(const ExArgs& q, hipStream_t s, SumArgs& pending) {
   static const char* fn = "ucd_conv_wgrad";
   const void *dz = q.dz, *x = q.x;
   void *dw = q.dw, *workspace = q.workspace;
@@ -1030,7 +1021,8 @@ int wgrad_launch_on(const ExArgs& q, hipStream_t s) {
   const size_t lds = (size_t)2 * kRows * (pl.bno + pl.bko) * 2;
   // the pending slab sum of this stream (a deferred earlier call) rides behind this launch's own workgroups; this call's own sum
   // is left pending when the caller allows it (flags & 1) and deferral is on, else launched right behind the product
-  const SumArgs pend = take_pending(s);
+  const SumArgs pend = pending;
+  pending = SumArgs{};
   const int extra = pend.blocks > 0 ? pend.blocks : 0;
 #define UCD_WG_LAUNCH(BN_, BK_)                                                             \
   {                                                                                         \
@@ -1068,13 +1060,10 @@ int wgrad_launch_on(const ExArgs& q, hipStream_t s) {
   int rc = check_launch(fn);
   if (rc) return rc;
   const SumArgs mine = make_sum(workspace, pl.chunks, total, dw, dw32, accumulate32);
-  bool defer;
-  {
-    std::lock_guard<std::mutex> lock(g_pend_mu);
-    defer = (g_defer & 1) && (flags & 1);
-    if (defer) g_pend[s] = mine;
+  if ((g_mode & 1) && (flags & 1)) {
+    pending = mine;
+    return 0;
   }
-  if (defer) return 0;
   wgrad_sum_kernel<<<mine.blocks, kThreads, 0, s>>>(mine);
   return check_launch(fn);
 }

@@ -199,7 +199,7 @@ class GradReducer:
         self._late_dst, self._late_src = [], []
         if self._wgrad_mode():
             from . import hip
-            hip.wgrad_drop()                                    # ... nor the slab sum its last weight gradient left pending
+            hip.wgrad_drop_all()                                # ... nor the slab sums its weight gradients left, on any stream
 
     def prepare_step(self):
         """Called by the wrapper's forward: if the caller cleared the gradients with ``optim.zero_grad()`` (set_to_none:
@@ -224,7 +224,7 @@ class GradReducer:
             return
         from . import hip
         if on:
-            hip.wgrad_drop()                                    # of a backward that never finished
+            hip.wgrad_drop_all()                                # of a backward that never finished
         # bit 1: the nodes' weight gradients leave the compute stream for the library's side stream until the next flush (include/
         # ucd_hip.h) - nothing waits for them before the bucket copies, and off the chain of input-gradient products they cost the
         # small-batch step (3 - 6 images per GPU) a fifth of its dependent launches less

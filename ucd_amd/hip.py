@@ -128,6 +128,7 @@ SIGNATURES = {
     "ucd_conv_wgrad_mode": (_i, []),
     "ucd_conv_wgrad_flush": (_i, [_p]),
     "ucd_conv_wgrad_drop": (_i, [_p]),
+    "ucd_conv_wgrad_drop_all": (_i, []),
     "ucd_transpose_bf16": (_i, [_p, _i, _i, _p, _p]),
     "ucd_conv_f32": (_i, [_p, _i, _p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
     "ucd_conv_f32_wgrad_workspace_bytes": (_z, [_i, _i, _i, _i]),
@@ -694,29 +695,40 @@ def wgrad_defer(mode):
     return int(load().ucd_conv_wgrad_defer(int(mode) & 3))
 
 
-def _wgrad_side_release():
-    # the C++ nodes hold the operands of their side-stream calls until the join (csrc/abn_node.cpp: g_side_hold)
+def _wgrad_side_release(stream=None):
+    # the C++ nodes hold the operands of their side-stream calls, by caller stream (None: every stream), until a join succeeded
+    # (csrc/abn_node.cpp: g_side_hold)
     from . import abn as _abn
     node = _abn._abn_node()
-    if node is not None and hasattr(node, "wgrad_side_release"):
-        node.wgrad_side_release()
+    if node is not None:
+        node.wgrad_side_release(stream)
 
 
 def wgrad_flush():
     """Launch the pending slab sum of the current stream, if any, and join the side stream of the weight gradients back into it
-    (``ucd_conv_wgrad_flush``)."""
-    try:
-        _check(load().ucd_conv_wgrad_flush(stream()), "ucd_conv_wgrad_flush")
-    finally:
-        _wgrad_side_release()
+    (``ucd_conv_wgrad_flush``); the operands held for that side work are released once the join succeeded."""
+    s = stream()
+    _check(load().ucd_conv_wgrad_flush(s), "ucd_conv_wgrad_flush")
+    _wgrad_side_release(s)
 
 
 def wgrad_drop():
-    """Forget the pending slab sum of the current stream (an aborted backward); side-stream work already launched is joined."""
-    try:
-        load().ucd_conv_wgrad_drop(stream())
-    finally:
+    """Forget the pending slab sum of the current stream (an aborted backward); side-stream work already launched is joined.
+    Returns the library's code (0: joined, and its held operands released)."""
+    s = stream()
+    rc = load().ucd_conv_wgrad_drop(s)
+    if rc == 0:
+        _wgrad_side_release(s)
+    return rc
+
+
+def wgrad_drop_all():
+    """``wgrad_drop`` for every stream the library holds weight-gradient state for (``ucd_conv_wgrad_drop_all``: a backward that
+    died on a stream the caller no longer knows, such as a failed capture's); the mode stays.  Returns the first error code."""
+    rc = load().ucd_conv_wgrad_drop_all()
+    if rc == 0:
         _wgrad_side_release()
+    return rc
 
 
 _wgrad_turn = {}
