@@ -2,14 +2,18 @@
 global batch 24) on N MI355X of one node.
 
     python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
 A "step" = teacher forward (eval) + student forward/backward + UnbiasedCE + contrastive/100 + 10*UnbiasedKD
 + gradient all-reduce + SGD + PolyLR on a device-resident synthetic batch (train.py:95-151 of the
-reference).  Rank 0 prints ONE JSON line; see DESIGN.md "Measurement" for the roofline and cpu_baseline
-definitions.  --dump-outputs DIR also writes what the last timed step computed as DIR/<name>.npy (the inputs are seeded: two
-builds run with the same arguments can be compared file for file).
+reference).  Rank 0 prints ONE JSON line.  A plain run does only what that line's headline figure needs: set-up, warm-up, the
+timed steps, the dump below; its `roofline`, `cpu_baseline` and `kernels` are null.  --full adds the measurements that take runs
+of their own after the timed steps: the instrumented per-call pass with its roofline (not with --no_kernel_timing) and the CPU
+oracle baseline (not with --no_cpu_baseline); see DESIGN.md "Measurement" for their definitions.  --dump-outputs DIR also writes
+what the last timed step computed as DIR/<name>.npy (the inputs are seeded: two builds run with the same arguments can be compared
+file for file).
 """
 import argparse
 import json
@@ -72,9 +76,12 @@ def parse():
     p.add_argument("--task", default="15-5")
     p.add_argument("--dataset", default="voc")
     p.add_argument("--step", type=int, default=1)
-    p.add_argument("--no_cpu_baseline", action="store_true")
-    p.add_argument("--no_kernel_timing", action="store_true")
-    p.add_argument("--no_miopen_find", action="store_true", help="skip the MIOpen solver search (default: search; ~2 min of warm-up, 25 % faster convolutions)")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run the instrumented per-call pass (kernels, roofline) and the CPU oracle "
+                        "baseline (cpu_baseline, one-process runs); a plain run reports them as null")
+    p.add_argument("--no_cpu_baseline", action="store_true", help="with --full: no CPU oracle baseline")
+    p.add_argument("--no_kernel_timing", action="store_true", help="with --full: no instrumented per-call pass")
+    p.add_argument("--no_miopen_find", action="store_true", help="skip the MIOpen solver search (default: search; ~2 min of warm-up, 25 %% faster convolutions)")
     p.add_argument("--pixcon_precision", default=None, choices=["f32", "f16"])
     p.add_argument("--dump-outputs", metavar="DIR", default=None,
                    help="after the timed steps, write what the last one computed (its losses, a fixed sample of the student's "
@@ -386,7 +393,7 @@ def main():
         return same
 
     roof, kernels = None, None
-    if not args.no_kernel_timing:
+    if args.full and not args.no_kernel_timing:
         kernels = kernel_timing(trainer, optimizer, scheduler, images, labels, min(args.steps, 3))
         ev_us = kernels.pop("_event_pair_overhead_us")
         for kname, kv in kernels.items():                    # per-call-type roofline fractions
@@ -430,7 +437,7 @@ def main():
                 pass
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             cpu = cpu_baseline(args, classes)
         except Exception as e:  # the baseline is a reported extra: never lose the GPU measurement over it

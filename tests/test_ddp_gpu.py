@@ -238,7 +238,7 @@ def test_bench_multi_rank_path_two_ranks_one_gpu(tmp_path, mailbox):
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
                         "--master-addr", "127.0.0.1", "--master-port", port, os.path.join(ROOT, "bench.py"),
                         "--gpus", "2", "--steps", "3", "--warmup", "3", "--global_batch", "4", "--crop", "129",
-                        "--backend", "gloo", "--device", "0", "--no_miopen_find", "--no_cpu_baseline", "--check_lockstep"],
+                        "--backend", "gloo", "--device", "0", "--no_miopen_find", "--full", "--no_cpu_baseline", "--check_lockstep"],
                        capture_output=True, text=True, env=env, timeout=900)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -354,6 +354,31 @@ def test_bench_dump_outputs_are_the_last_timed_step_and_repeat(tmp_path):
     sa, sb = fa["student_state.npy"].astype(np.float64), fb["student_state.npy"].astype(np.float64)
     assert sa.shape == sb.shape
     assert np.linalg.norm(sa - sb) <= 1e-2 * np.linalg.norm(sa), np.linalg.norm(sa - sb) / np.linalg.norm(sa)
+
+
+def test_bench_full_adds_what_a_plain_run_leaves_out(tmp_path):
+    """A plain bench.py run does only what its headline figure needs: its line has the same keys as a --full one, with the
+    per-call table, its roofline and the CPU oracle baseline null.  --full measures those after the timed steps (small crop and
+    batch: the mechanics, not the numbers)."""
+    import json
+    out = {}
+    for mode, extra in (("plain", []), ("full", ["--full"])):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "3", "--global_batch", "2",
+                            "--crop", "129", "--no_miopen_find"] + extra,
+                           capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        out[mode] = json.loads(lines[0])
+    a, b = out["plain"], out["full"]
+    assert set(a) == set(b)
+    for d in (a, b):
+        assert d["steps"] == 2 and d["value"] > 0 and d["ms_per_step"] > 0 and d["unit"] == "images/sec" and d["higher_is_better"]
+        assert all(np.isfinite(v) for v in d["losses"].values())
+    assert a["kernels"] is None and a["roofline"] is None and a["cpu_baseline"] is None and a["kernel_table_config"] is None
+    assert b["kernels"] and b["kernel_table_config"] and b["roofline"]["kernel"] in b["kernels"] and b["roofline"]["frac"] > 0
+    assert "error" not in b["cpu_baseline"], b["cpu_baseline"]
+    assert b["cpu_baseline"]["value"] > 0 and np.isfinite(b["cpu_baseline"]["loss"])
 
 
 def test_aborted_backward_leaves_no_widening_copies_behind():

@@ -1,7 +1,7 @@
 # The bench line, the kernel trace and the per-rank batches of the FINAL commit (the full collection: tools/measure_round.sh)
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}; O=$R/gpurun_out/r05f; mkdir -p $O
 cd $R
-timeout 900 python bench.py --steps 20 --warmup 6 > $O/bench_final.json 2> $O/bench_final.err
+timeout 900 python bench.py --steps 20 --warmup 6 --full > $O/bench_final.json 2> $O/bench_final.err
 brief() { python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$1', 'ms_per_step', round(d['ms_per_step'],3), 'img/s', round(d['value'],1), 'step_graph', d['execution']['step_graph'])"; }
 (for gb in 12 6 3; do UCD_STEP_GRAPH=auto timeout 300 python bench.py --steps 16 --warmup 6 --global_batch $gb --no_cpu_baseline --no_kernel_timing 2>/dev/null | brief "global_batch $gb"; done) > $O/small_batch.txt 2>&1
 cd /tmp && export TMPDIR=/tmp

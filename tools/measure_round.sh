@@ -2,7 +2,7 @@
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}; O=$R/gpurun_out/r06; mkdir -p $O
 cd $R
 if [ -z "$SKIP_TESTS" ]; then timeout 3000 python -m pytest tests -m gpu -q 2>&1 | tail -5 > $O/gputests.log; fi
-timeout 900 python bench.py --steps 20 --warmup 6 > $O/bench_final.json 2> $O/bench_final.err
+timeout 900 python bench.py --steps 20 --warmup 6 --full > $O/bench_final.json 2> $O/bench_final.err
 brief() { python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$1', 'ms_per_step', round(d['ms_per_step'],3), 'img/s', round(d['value'],1), 'step_graph', d['execution']['step_graph'])"; }
 # the per-rank batches of the multi-GPU split on one GPU, with the captured step and without
 (for gb in 24 12 6 3; do for sg in auto 0; do UCD_STEP_GRAPH=$sg timeout 300 python bench.py --steps 16 --warmup 6 --global_batch $gb --no_cpu_baseline --no_kernel_timing 2>/dev/null | brief "global_batch $gb UCD_STEP_GRAPH=$sg"; done; done) > $O/small_batch.txt 2>&1
