@@ -12,6 +12,7 @@
 #include <torch/extension.h>
 #include <torch/csrc/autograd/engine.h>
 #include <torch/csrc/autograd/graph_task.h>
+#include <torch/csrc/autograd/utils/grad_layout_contract.h>
 
 #include <cstring>
 #include <map>
@@ -64,6 +65,7 @@ void wgrad_side_release(c10::optional<int64_t> stream) {
 }   // the tensors are released outside the lock
 
 int64_t g_pass_flushes = 0;                      // test hook: end-of-pass flushes run so far
+int64_t g_wgrad_calls[2] = {0, 0};               // test hook: own weight-gradient calls of the nodes, those of them issued with flags
 std::map<int, std::set<int64_t>> g_pass_streams;  // under g_mu: by autograd graph task, the streams its deferring calls ran on
 
 // A weight-gradient call that may be deferred / moved to the side stream is final only behind ucd_conv_wgrad_flush.  The
@@ -213,13 +215,18 @@ void* wgrad_workspace(const at::Tensor& like, size_t bytes, int64_t stream, bool
 
 // flags of a node's weight-gradient call (ucd_conv_wgrad_ex): bit 0 the slab sum may wait, bit 1 the call may leave the compute
 // stream - both only for a gradient nothing reads before the wrapper's flush (sum_may_wait below); with bit 1 in force the operands
-// are held until that flush
-int sum_may_wait(const at::Tensor& w4);
-int wgrad_flags(const at::Tensor& w4, bool* side) {
+// are held until that flush.  dw: the tensor the node returns as the weight's gradient.
+int sum_may_wait(const at::Tensor& w4, const at::Tensor& dw);
+int wgrad_flags(const at::Tensor& w4, const at::Tensor& dw, bool* side) {
   *side = false;
-  if (!sum_may_wait(w4)) return 0;
+  if (!sum_may_wait(w4, dw)) return 0;
   *side = (ucd_conv_wgrad_mode() & 2) != 0;
   return *side ? 3 : 1;
+}
+void count_wgrad_call(int flags) {
+  std::lock_guard<std::mutex> lock(g_mu);
+  ++g_wgrad_calls[0];
+  if (flags & 3) ++g_wgrad_calls[1];
 }
 void hold_for_side(int64_t stream, std::initializer_list<at::Tensor> ts) {
   std::lock_guard<std::mutex> lock(g_mu);
@@ -227,27 +234,61 @@ void hold_for_side(int64_t stream, std::initializer_list<at::Tensor> ts) {
   held.insert(held.end(), ts);
 }
 
-// May the slab sum of this weight gradient wait for the next weight-gradient launch?  Only when nothing reads the gradient before the
-// wrapper's flush: the weight is a LEAF (the flat bf16 working copy of ucd_amd/master.py: AccumulateGrad adopts the tensor without
-// touching it - the layout contract is met, dw comes out in the weight's own strides).  A weight that is the output of autocast's
-// per-call cast has a ToCopyBackward node behind it that reads the gradient at once.
-int sum_may_wait(const at::Tensor& w4) { return w4.defined() && w4.is_leaf() && w4.requires_grad() ? 1 : 0; }
+// bf16 working copies of ucd_amd.master.Bf16Weights (by tensor; a weak reference keeps the address from being reused): their one
+// post-accumulate-grad hook is the gradient-bucket wrapper's (ucd_amd/ddp.py _on_grad), which reads no gradient values - the code
+// that consumes them (_complete / finish) flushes first
+std::map<const c10::TensorImpl*, c10::weak_intrusive_ptr<c10::TensorImpl>> g_working;   // under g_mu
+
+void wgrad_register_working(const std::vector<at::Tensor>& ts) {
+  std::lock_guard<std::mutex> lock(g_mu);
+  for (auto it = g_working.begin(); it != g_working.end();) it = it->second.expired() ? g_working.erase(it) : std::next(it);
+  for (const auto& t : ts) g_working.insert_or_assign(t.unsafeGetTensorImpl(), c10::weak_intrusive_ptr<c10::TensorImpl>(t.getIntrusivePtr()));
+}
+
+bool registered_working(const at::Tensor& w) {
+  std::lock_guard<std::mutex> lock(g_mu);
+  auto it = g_working.find(w.unsafeGetTensorImpl());
+  return it != g_working.end() && !it->second.expired();
+}
+
+// May the slab sum of this weight gradient wait for the next weight-gradient launch (and the product leave the compute stream)?
+// Only when AccumulateGrad will adopt the returned tensor untouched and nothing reads it before the wrapper's / the end-of-pass
+// flush (torch/csrc/autograd/functions/accumulate_grad.h, case 1.1):
+//  - the weight is a leaf that requires its gradient (the output of autocast's per-call cast has a ToCopyBackward node behind it
+//    that reads the gradient at once);
+//  - it has no .grad yet (otherwise AccumulateGrad adds into it: the gradient-bucket views of ucd_amd/ddp.py are such a .grad);
+//  - grad mode is off (backward(create_graph=True): AccumulateGrad clones);
+//  - dw obeys the gradient layout contract with the weight (otherwise AccumulateGrad re-strides it into a copy);
+//  - no tensor hook (it receives dw before AccumulateGrad) and no post-accumulate-grad hook (it reads .grad before the flush),
+//    except the wrapper's own on a registered working copy.
+// Everywhere else the call runs exactly as with deferral off.  Not seen here: a weight used by two nodes of one graph, whose two
+// gradients the engine adds before AccumulateGrad - no model of this project shares a convolution weight.
+int sum_may_wait(const at::Tensor& w4, const at::Tensor& dw) {
+  if (!(w4.defined() && w4.is_leaf() && w4.requires_grad())) return 0;
+  if (w4.grad().defined() || at::GradMode::is_enabled()) return 0;
+  if (!torch::autograd::utils::obeys_layout_contract(dw, w4)) return 0;
+  if (!torch::autograd::impl::hooks(w4).empty()) return 0;
+  if (torch::autograd::impl::post_acc_grad_hooks(w4) && !registered_working(w4)) return 0;
+  return 1;
+}
 
 at::Tensor own_wgrad(const at::Tensor& dz, const at::Tensor& x, const at::Tensor& w4, int64_t dilation, int64_t stream,
                      int64_t stride = 1) {
   const int64_t B = x.size(0), K = x.size(1), H = x.size(2), W = x.size(3), N = w4.size(0), M = B * dz.size(2) * dz.size(3);
   const int taps = dilation > 0 ? 9 : 1;
   at::Tensor dw = at::empty({N, taps == 9 ? 3 : 1, taps == 9 ? 3 : 1, K}, x.options().memory_format(c10::nullopt));
+  at::Tensor ret = dw.permute({0, 3, 1, 2});      // [N, K, kh, kw] with channels-last strides: the weight's own memory order
   const size_t wsb = ucd_conv_wgrad_workspace_bytes((int)M, (int)N, (int)K, taps);
   bool side;
-  const int flags = wgrad_flags(w4, &side);
+  const int flags = wgrad_flags(w4, ret, &side);
+  count_wgrad_call(flags);
   if (side) hold_for_side(stream, {dz, x, dw});
   if (flags && ucd_conv_wgrad_mode()) queue_end_of_pass_flush(stream);
   check(ucd_conv_wgrad_ex(dz.data_ptr(), (int)N, x.data_ptr(), (int)K, (int)M, (int)N, (int)K, taps, (int)H, (int)W,
                           (int)(dilation > 0 ? dilation : 1), (int)stride, dw.data_ptr(), nullptr, 0,
                           wgrad_workspace(x, wsb, stream, side), wsb, flags, (ucd_stream_t)stream),
         "ucd_conv_wgrad");
-  return dw.permute({0, 3, 1, 2});      // [N, K, kh, kw] with channels-last strides: the weight's own memory order
+  return ret;
 }
 
 class ABNTrainNode : public torch::autograd::Function<ABNTrainNode> {
@@ -358,15 +399,18 @@ bool own_wgrad_rows_ok(const at::Tensor& dy, const at::Tensor& rows) {
 at::Tensor own_wgrad_rows(const at::Tensor& dy, const at::Tensor& rows, int64_t stream, const at::Tensor& w4) {
   const int64_t M = rows.size(0), Ci = rows.size(1), Co = dy.size(1);
   at::Tensor dw = at::empty({Co, Ci}, rows.options());
+  // the weight-shaped view the node returns; the side-stream hold keeps the base, so that AccumulateGrad may still adopt the view
+  at::Tensor ret = dw.as_strided(w4.sizes(), w4.strides());
   const size_t wsb = ucd_conv_wgrad_workspace_bytes((int)M, (int)Co, (int)Ci, 1);
   bool side;
-  const int flags = wgrad_flags(w4, &side);
+  const int flags = wgrad_flags(w4, ret, &side);
+  count_wgrad_call(flags);
   if (side) hold_for_side(stream, {dy, rows, dw});
   if (flags && ucd_conv_wgrad_mode()) queue_end_of_pass_flush(stream);
   check(ucd_conv_wgrad_ex(dy.data_ptr(), (int)Co, rows.data_ptr(), (int)Ci, (int)M, (int)Co, (int)Ci, 1, 0, 0, 1, 1, dw.data_ptr(), nullptr, 0,
                           wgrad_workspace(rows, wsb, stream, side), wsb, flags, (ucd_stream_t)stream),
         "ucd_conv_wgrad");
-  return dw;
+  return ret;
 }
 
 // ---- wide 1x1 convolution as a row-matrix GEMM (ucd_amd/blocks.py::_Gemm1x1 is the Python twin) ------------------
@@ -1097,6 +1141,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "C++ autograd node of the training-mode ABN layer over libucd_hip.so";
   m.def("poison_workspaces", &poison_workspaces);
   m.def("pass_flushes", []() { return g_pass_flushes; }, "number of end-of-pass flushes the nodes' engine callbacks have run (test hook)");
+  m.def("wgrad_calls", []() {
+    std::lock_guard<std::mutex> lock(g_mu);
+    return std::make_pair(g_wgrad_calls[0], g_wgrad_calls[1]);
+  }, "(own weight-gradient calls of the nodes, those issued deferred / for the side stream) so far (test hook)");
+  m.def("wgrad_register_working", &wgrad_register_working,
+        "weights whose only post-accumulate-grad hook is the gradient-bucket wrapper's (ucd_amd.master.Bf16Weights working copies)");
   m.def("wgrad_side_release", &wgrad_side_release, py::arg("stream") = py::none(),
         "drop the operands held for the side work of a stream (None: every stream) - only after its join succeeded");
   m.def("stat_arena_reset", &stat_arena_reset, "zero the used part of the statistics arena of a device and start a new generation");

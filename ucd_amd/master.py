@@ -65,6 +65,13 @@ class Bf16Weights:
                 if trainable:
                     _WORKING[w] = (s, weakref.ref(self))
                 off += n
+        if trainable:
+            # the working copies' one post-accumulate-grad hook is the gradient-bucket wrapper's, which reads no values before its
+            # flush: the C++ nodes may defer their weight gradients (csrc/abn_node.cpp sum_may_wait)
+            from . import abn
+            node = abn._abn_node()
+            if node is not None:
+                node.wgrad_register_working(list(self.shadow_of.values()))
         self._build_flip_table()
         self._seen = None
         self._dirty = True
