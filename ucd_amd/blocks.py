@@ -105,21 +105,7 @@ class _Gemm1x1(torch.autograd.Function):
         dx = None
         if ctx.needs_input_grad[0]:
             dx = dy @ w if lib is None else lib.gemm_bf16(1, dy, w, torch.empty_like(rows))
-        dw = None
-        if ctx.needs_input_grad[1]:
-            M, Co = dy.shape
-            S = _wgrad_split(M)
-            if (_own_wgrad() and dy.dtype == torch.bfloat16 and rows.dtype == torch.bfloat16 and Co % 64 == 0
-                    and rows.shape[1] % 64 == 0 and rows.is_contiguous()):
-                from . import hip
-                dw = hip.conv_wgrad(dy, rows, torch.empty(Co, rows.shape[1], dtype=dy.dtype, device=dy.device))
-            elif S > 1:      # K = B*H*W is long: 8 batched chunks + a sum beat every single-kernel candidate (41 vs 96 us)
-                dw = torch.bmm(dy.view(S, M // S, Co).transpose(1, 2), rows.view(S, M // S, rows.shape[1])).sum(0)
-            elif lib is None:
-                dw = dy.t() @ rows
-            else:
-                dw = lib.gemm_bf16(2, dy, rows, torch.empty(Co, rows.shape[1], dtype=dy.dtype, device=dy.device))
-            dw = dw.as_strided(w4.shape, w4.stride())     # [Co, Ci, 1, 1] is one memory order in either format
+        dw = _conv_wgrad(dy, rows, w4, 1, WGRAD_OWN, WGRAD_SPLIT, lib) if ctx.needs_input_grad[1] else None
         return dx, dw
 
 
@@ -185,34 +171,55 @@ class _StrideOneConvFn(torch.autograd.Function):
                 dx = _own3x3(dy.contiguous(memory_format=torch.channels_last), wt, d)
             else:
                 dx = F.conv2d(dy, wt, None, 1, pad, d)
-        if ctx.needs_input_grad[1]:
-            dw = _own_wgrad_4d(dy, x, w, d if w.shape[2] == 3 else 0)
-            if dw is None:
-                dw = torch.ops.aten.convolution_backward(dy, x, w, None, [1, 1], [pad, pad], [d, d], False, [0, 0], 1,
-                                                         [False, True, False])[1]
+        dw = _conv_wgrad(dy, x, w, d, WGRAD_OWN, WGRAD_LIBRARY) if ctx.needs_input_grad[1] else None
         return dx, dw, None, None, None, None
 
 
-def _own_wgrad_4d(dz, x, w4, dilation):
-    """Weight gradient of a stride-1 convolution (dilation 0: 1x1) on the own kernel, as a tensor with the weight's sizes and
-    channels-last strides; None when the layer is not one it takes (alignment, dtype, UCD_OWN_WGRAD=0)."""
-    if not (_own_wgrad() and dz.is_cuda and dz.dtype == torch.bfloat16 and x.dtype == torch.bfloat16 and w4.shape[0] % 64 == 0
-            and w4.shape[1] % 64 == 0 and x.shape[2] > 1 and x.shape[3] > 1 and x.is_contiguous(memory_format=torch.channels_last)
-            and x.shape[0] * x.shape[2] * x.shape[3] < (1 << 22)):
-        return None
-    if dilation > 0 and not (tuple(w4.shape[2:]) == (3, 3) and w4.is_contiguous(memory_format=torch.channels_last)):
-        return None
-    from . import hip
-    if not dz.is_contiguous(memory_format=torch.channels_last):
-        dz = dz.contiguous(memory_format=torch.channels_last)
-    N, K = w4.shape[0], w4.shape[1]
-    B, _, H, W = x.shape
-    rows = lambda t: t.permute(0, 2, 3, 1).reshape(B * H * W, t.shape[1])
-    taps = 9 if dilation > 0 else 1
-    dw = torch.empty((N, taps * K), dtype=x.dtype, device=x.device)
-    hip.conv_wgrad(rows(dz), rows(x), dw, conv3=(H, W, dilation) if dilation > 0 else None)
-    k = 3 if dilation > 0 else 1
-    return dw.view(N, k, k, K).permute(0, 3, 1, 2)
+# Route of a layer's weight gradient (the same values as csrc/abn_node.cpp WgradRoute): the batched split-M library products (1x1
+# layers only: a 3x3 layer takes the library instead), MIOpen's weight-gradient solver, or the own kernel (csrc/wgrad.hip)
+WGRAD_SPLIT, WGRAD_LIBRARY, WGRAD_OWN = 0, 1, 2
+
+
+def _conv_wgrad(dz, x, w4, d, route, fallback, lib=None):
+    """Weight gradient of a stride-1 convolution of dilation ``d`` (Python twin of csrc/abn_node.cpp::conv_wgrad): ``dz`` / ``x``
+    the gradient of the output and the input, maps or (a 1x1 layer) [M, C] row matrices, ``w4`` the weight.  ``WGRAD_OWN`` takes the
+    own kernel where the layer is one it takes and UCD_OWN_WGRAD is on, else the ``fallback`` route; the split products of an M too
+    short to split run on ``lib``'s hipBLASLt entry point, or through torch when it is None.  The gradient has the weight's sizes,
+    in the weight's own memory order on the own and split routes."""
+    N, K, k = w4.shape[0], w4.shape[1], w4.shape[2]
+    rows = lambda t: t.permute(0, 2, 3, 1).reshape(t.shape[0] * t.shape[2] * t.shape[3], t.shape[1])
+    if route == WGRAD_OWN:
+        if x.dim() == 2:
+            ok = x.is_contiguous()
+        else:
+            ok = (dz.is_cuda and x.shape[2] > 1 and x.shape[3] > 1 and x.is_contiguous(memory_format=torch.channels_last)
+                  and x.shape[0] * x.shape[2] * x.shape[3] < (1 << 22)
+                  and (k == 1 or (tuple(w4.shape[2:]) == (3, 3) and w4.is_contiguous(memory_format=torch.channels_last))))
+        if ok and _own_wgrad() and dz.dtype == torch.bfloat16 and x.dtype == torch.bfloat16 and N % 64 == 0 and K % 64 == 0:
+            from . import hip
+            dw = torch.empty((N, k * k * K), dtype=x.dtype, device=x.device)
+            if x.dim() == 2:
+                hip.conv_wgrad(dz, x, dw)
+                return dw.as_strided(w4.shape, w4.stride())
+            if not dz.is_contiguous(memory_format=torch.channels_last):
+                dz = dz.contiguous(memory_format=torch.channels_last)
+            H, W = x.shape[2], x.shape[3]
+            hip.conv_wgrad(rows(dz), rows(x), dw, conv3=(H, W, d) if k == 3 else None)
+            return dw.view(N, k, k, K).permute(0, 3, 1, 2)
+        route = fallback
+    if route == WGRAD_SPLIT and k == 1:
+        dzr, xr = (dz, x) if x.dim() == 2 else (rows(dz), rows(x))
+        M = dzr.shape[0]
+        S = _wgrad_split(M)
+        if S > 1:      # K = B*H*W is long: 8 batched chunks + a sum beat every single-kernel candidate (41 vs 96 us)
+            dw = torch.bmm(dzr.view(S, M // S, N).transpose(1, 2), xr.view(S, M // S, K)).sum(0)
+        elif lib is None:
+            dw = dzr.t() @ xr
+        else:
+            dw = lib.gemm_bf16(2, dzr, xr, torch.empty(N, K, dtype=dz.dtype, device=dz.device))
+        return dw.as_strided(w4.shape, w4.stride())     # [N, K, 1, 1] is one memory order in either format
+    return torch.ops.aten.convolution_backward(dz, x, w4, None, [1, 1], [d * (k // 2)] * 2, [d, d], False, [0, 0], 1,
+                                               [False, True, False])[1]
 
 
 def _own3x3(x, w, d):
@@ -608,8 +615,8 @@ class _ConvABNFunction(torch.autograd.Function):
             lflag[2] = dx._version
             return dict(out_mode=3, out_norm=(lbuf[3 * C:4 * C], lbuf[5 * C:], lbias, lbuf[4 * C:5 * C], lact & hip.ACT_MASK, lslope),
                         residual=rows(lz), partial=lpart)
+        dx = None
         if dilation > 0:
-            dx = dw = None
             if ctx.needs_input_grad[0]:
                 if wflip is None:
                     wflip = w4.flip(2, 3).transpose(0, 1).contiguous(memory_format=torch.channels_last)
@@ -619,15 +626,7 @@ class _ConvABNFunction(torch.autograd.Function):
                                 **(link_args(dx) if link is not None else {}))
                 else:
                     dx = F.conv2d(dz, wflip, None, 1, dilation, dilation)
-            if ctx.needs_input_grad[1]:
-                dw = _own_wgrad_4d(dz, x, w4, dilation) if wgrad_conv == 2 else None
-                if dw is None:
-                    dw = torch.ops.aten.convolution_backward(dz, x, w4, None, [1, 1], [dilation, dilation], [dilation, dilation],
-                                                             False, [0, 0], 1, [False, True, False])[1]
-            return dx, dw, sums[N:], sums[:N], dres, None, None, None, None, None, None, None, None, None, None, None, None, None, None, None
-        w2 = w4.reshape(N, K)
-        dx = dw = None
-        if ctx.needs_input_grad[0]:
+        elif ctx.needs_input_grad[0]:
             fold = (dskip is not None and dskip.dtype == x.dtype
                     and dskip.is_contiguous(memory_format=torch.channels_last) and own_dgrad and wflip is not None)
             dx = dskip if fold else torch.empty_like(x)
@@ -642,23 +641,11 @@ class _ConvABNFunction(torch.autograd.Function):
                     extra = link_args(dx)
                 hip.conv1x1(rows(dz), wflip.reshape(K, N), rows(dx), accumulate=fold, **extra)
             else:
-                hip.gemm_bf16(1, rows(dz), w2, rows(dx))
+                hip.gemm_bf16(1, rows(dz), w4.reshape(N, K), rows(dx))
             if dskip is not None and not fold:
                 dx = dx + dskip
-        if ctx.needs_input_grad[1] and wgrad_conv == 2:
-            dw = _own_wgrad_4d(dz, x, w4, 0)
-            if dw is None:
-                wgrad_conv = 1
-        if dw is not None:
-            pass
-        elif ctx.needs_input_grad[1] and wgrad_conv == 1:
-            dw = torch.ops.aten.convolution_backward(dz, x, w4, None, [1, 1], [0, 0], [1, 1], False, [0, 0], 1,
-                                                     [False, True, False])[1]
-        elif ctx.needs_input_grad[1]:
-            S = _wgrad_split(M)
-            dzr, xr = rows(dz), rows(x)
-            dw = (torch.bmm(dzr.view(S, M // S, N).transpose(1, 2), xr.view(S, M // S, K)).sum(0) if S > 1 else dzr.t() @ xr)
-            dw = dw.as_strided(w4.shape, w4.stride())
+        # the own kernel's fallback is MIOpen here, where the C++ node falls back to the split products on a 1x1 layer
+        dw = _conv_wgrad(dz, x, w4, dilation or 1, wgrad_conv, WGRAD_LIBRARY) if ctx.needs_input_grad[1] else None
         return dx, dw, sums[N:], sums[:N], dres, None, None, None, None, None, None, None, None, None, None, None, None, None, None, None
 
 
@@ -688,14 +675,13 @@ def _conv_abn_train(conv, bn, x, residual=None, activation=None, activation_para
             and _is_fused_abn(bn) and bn.training and bn.weight is not None and torch.is_grad_enabled() and x.is_cuda
             and x.dim() == 4 and x.dtype == torch.bfloat16 and conv.in_channels % 64 == 0 and conv.out_channels % 64 == 0):
         return None
-    dilation, wflip, fused, own_dgrad, wgrad_conv = 0, None, None, False, 0      # wgrad_conv: 0 batched products, 1 MIOpen, 2 own
+    dilation, wflip, fused, own_dgrad, wgrad_conv = 0, None, None, False, WGRAD_LIBRARY
     if stride:
         # the strided layers of a stage's first block: forward (+ statistics) and weight gradient on the own kernels, the input
         # gradient stays with the library's backward-data solver; no link consumed (the producer falls back to its own reduction)
         if is3 and not conv.weight.is_contiguous(memory_format=torch.channels_last):
             return None
         dilation, fused, link, blink = (conv.dilation[0] if is3 else 0), True, None, None
-        wgrad_conv = 1
     elif is3:
         if not (conv.stride == (1, 1) and conv.padding == conv.dilation and conv.dilation[0] == conv.dilation[1]
                 and conv.groups == 1 and not with_skip and conv.weight.is_contiguous(memory_format=torch.channels_last)):
@@ -712,9 +698,10 @@ def _conv_abn_train(conv, bn, x, residual=None, activation=None, activation_para
         own_dgrad = conv.own_dgrad or (link is not None and conv.link_dgrad and not with_skip) or (blink is not None and conv.link_dgrad)
         # the transposed weight: cached with the bf16 working copies, else made per call below (same kernels either way)
         wflip = conv._w16_flip if (own_dgrad and conv.working_weight() is not None) else None
-        wgrad_conv = 0 if conv.wide else 1
+        # narrow layers (<= 512 channels at 65^2 / 129^2): MIOpen's weight-gradient solver beats the split-M products
+        wgrad_conv = WGRAD_SPLIT if conv.wide else WGRAD_LIBRARY
     if _own_wgrad():
-        wgrad_conv = 2
+        wgrad_conv = WGRAD_OWN
     if link is not None and (not own_dgrad or with_skip):
         link = None                              # the consumer's input gradient does not run on the own kernel: no link
     if blink is not None and (not own_dgrad or is3):

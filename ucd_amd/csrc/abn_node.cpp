@@ -185,20 +185,6 @@ int dtype_code(const at::Tensor& x) {
 
 const float* fptr(const at::Tensor& t) { return t.defined() ? t.data_ptr<float>() : nullptr; }
 
-// Weight gradient of a stride-1 convolution on the own kernel (ucd_conv_wgrad, csrc/wgrad.hip): dz [B, N, H, W] and x [B, K, H, W]
-// dense channels-last bf16 -> a tensor with the weight's sizes and (channels-last) strides.  dilation 0: 1x1.
-bool own_wgrad_ok(const at::Tensor& dz, const at::Tensor& x, const at::Tensor& w4, int64_t dilation) {
-  return dz.defined() && dense_channels_last(dz) && dense_channels_last(x) && dz.scalar_type() == at::kBFloat16 &&
-         x.scalar_type() == at::kBFloat16 && w4.size(0) % 64 == 0 && w4.size(1) % 64 == 0 && dz.size(1) == w4.size(0) &&
-         x.size(1) == w4.size(1) && x.size(0) * x.size(2) * x.size(3) < (1 << 22) &&
-         (dilation == 0 ? (w4.size(2) == 1 && w4.size(3) == 1)
-                        // every stride-1 3x3 layer (tools/wgrad_probe2.py, profiles/r03_wgrad_probe.txt: 64-256 channel layers
-                        // 50-58 vs 80-100 us for MIOpen's solver, 512 -> 512 213 vs 215, the ASPP branches 392 vs 372 - plus the
-                        // ~35 us of zero-fill / cast kernels MIOpen wraps around its solver on the step)
-                        : (w4.size(2) == 3 && w4.size(3) == 3));
-}
-
-// stride > 1 (the first block of a stage: conv2 3x3 / proj_conv 1x1 with stride 2): dz is the smaller output map
 // Slab workspace of a weight-gradient call.  The calls of the autograd nodes allow the library to DEFER their slab sum into the next
 // weight-gradient launch of the stream (ucd_conv_wgrad_ex, flags bit 0: the gradient goes to AccumulateGrad and is first read by the
 // bucket copies, in front of which ucd_amd/ddp.py flushes) - so a call's slabs must outlive the NEXT call: two scratch buffers, taken
@@ -272,23 +258,90 @@ int sum_may_wait(const at::Tensor& w4, const at::Tensor& dw) {
   return 1;
 }
 
-at::Tensor own_wgrad(const at::Tensor& dz, const at::Tensor& x, const at::Tensor& w4, int64_t dilation, int64_t stream,
-                     int64_t stride = 1) {
-  const int64_t B = x.size(0), K = x.size(1), H = x.size(2), W = x.size(3), N = w4.size(0), M = B * dz.size(2) * dz.size(3);
-  const int taps = dilation > 0 ? 9 : 1;
-  at::Tensor dw = at::empty({N, taps == 9 ? 3 : 1, taps == 9 ? 3 : 1, K}, x.options().memory_format(c10::nullopt));
-  at::Tensor ret = dw.permute({0, 3, 1, 2});      // [N, K, kh, kw] with channels-last strides: the weight's own memory order
-  const size_t wsb = ucd_conv_wgrad_workspace_bytes((int)M, (int)N, (int)K, taps);
-  bool side;
-  const int flags = wgrad_flags(w4, ret, &side);
-  count_wgrad_call(flags);
-  if (side) hold_for_side(stream, {dz, x, dw});
-  if (flags && ucd_conv_wgrad_mode()) queue_end_of_pass_flush(stream);
-  check(ucd_conv_wgrad_ex(dz.data_ptr(), (int)N, x.data_ptr(), (int)K, (int)M, (int)N, (int)K, taps, (int)H, (int)W,
-                          (int)(dilation > 0 ? dilation : 1), (int)stride, dw.data_ptr(), nullptr, 0,
-                          wgrad_workspace(x, wsb, stream, side), wsb, flags, (ucd_stream_t)stream),
-        "ucd_conv_wgrad");
-  return ret;
+// ---- weight gradients of the convolution nodes -------------------------------------------------------------------------------------
+// Route of a layer's weight gradient (the same values as ucd_amd/blocks.py WGRAD_*): the batched split-M library products (stride-1
+// 1x1 layers only: any other layer takes the library instead), MIOpen's weight-gradient solver, or the own kernel (ucd_conv_wgrad,
+// csrc/wgrad.hip) where the layer is one it takes, else the caller's fallback route.
+enum WgradRoute : int64_t { kWgradSplit = 0, kWgradLibrary = 1, kWgradOwn = 2 };
+
+// Number of K-chunks of the split products over M rows: the weight gradient of a long M is eight batched K-chunks + a sum (41 us
+// against 96 for the best single-kernel candidate at M = 26136).
+int64_t wgrad_split(int64_t M) {
+  if (M >= 8192)
+    for (int64_t S : {8, 4, 12, 6, 3, 2})
+      if (M % S == 0) return S;
+  return 1;
+}
+
+// Does the own kernel take this layer?  Row form (x 2-D, a 1x1 layer): dz [M, N] and x [M, K] contiguous 16-byte aligned bf16.  Map
+// form: dz [B, N, OH, OW] (the smaller output map of a strided layer) and x [B, K, H, W] dense channels-last bf16, a 1x1 weight or a
+// 3x3 weight in channels-last order - every 3x3 layer (tools/wgrad_probe2.py, profiles/r03_wgrad_probe.txt: 64-256 channel layers
+// 50-58 vs 80-100 us for MIOpen's solver, 512 -> 512 213 vs 215, the ASPP branches 392 vs 372 - plus the ~35 us of zero-fill / cast
+// kernels MIOpen wraps around its solver on the step) - and 128-aligned channels when strided.  Both: 64-aligned channels, M < 2^22.
+bool own_wgrad_ok(const at::Tensor& dz, const at::Tensor& x, const at::Tensor& w4, int64_t stride) {
+  if (x.dim() == 2)
+    return dz.dim() == 2 && dz.is_contiguous() && x.is_contiguous() && dz.scalar_type() == at::kBFloat16 &&
+           x.scalar_type() == at::kBFloat16 && dz.size(1) % 64 == 0 && x.size(1) % 64 == 0 && dz.size(0) < (1 << 22) &&
+           (reinterpret_cast<uintptr_t>(dz.data_ptr()) & 15) == 0 && (reinterpret_cast<uintptr_t>(x.data_ptr()) & 15) == 0;
+  const int64_t N = w4.size(0), K = w4.size(1);
+  return dz.defined() && dense_channels_last(dz) && dense_channels_last(x) && dz.scalar_type() == at::kBFloat16 &&
+         x.scalar_type() == at::kBFloat16 && N % 64 == 0 && K % 64 == 0 && dz.size(1) == N && x.size(1) == K &&
+         x.size(0) * x.size(2) * x.size(3) < (1 << 22) &&
+         ((w4.size(2) == 1 && w4.size(3) == 1) ||
+          (w4.size(2) == 3 && w4.size(3) == 3 && w4.is_contiguous(at::MemoryFormat::ChannelsLast))) &&
+         (stride == 1 || (N % 128 == 0 && K % 128 == 0));
+}
+
+// The weight gradient of a convolution node by `route`: dz the gradient of the output, x the input (both maps, or the row matrices of
+// a 1x1 layer), w4 the weight [N, K, k, k]; dilation and stride those of the convolution (padding dilation * (k / 2)).  Returns what
+// the node hands AccumulateGrad: the weight's sizes, in the weight's own memory order on the own and split routes.
+at::Tensor conv_wgrad(const at::Tensor& dz, const at::Tensor& x, const at::Tensor& w4, int64_t dilation, int64_t stride, int64_t route,
+                      WgradRoute fallback, int64_t stream) {
+  const bool rows = x.dim() == 2;
+  const int64_t N = w4.size(0), K = w4.size(1), k = w4.size(2);
+  if (route == kWgradOwn) {
+    // a bf16 map in another memory order is made dense channels-last for the own kernel (the other routes take it as it is)
+    const at::Tensor dzo = !rows && dz.scalar_type() == at::kBFloat16 && !dense_channels_last(dz)
+                               ? dz.contiguous(at::MemoryFormat::ChannelsLast) : dz;
+    if (own_wgrad_ok(dzo, x, w4, stride)) {
+      const int64_t M = rows ? x.size(0) : x.size(0) * dzo.size(2) * dzo.size(3);
+      at::Tensor dw = rows ? at::empty({N, K}, x.options()) : at::empty({N, k, k, K}, x.options());
+      // the tensor returned: [N, K, kh, kw] with channels-last strides (row form: the weight's strides) - the weight's own memory
+      // order; the side-stream hold keeps the base dw, so that AccumulateGrad may still adopt the view
+      at::Tensor ret = rows ? dw.as_strided(w4.sizes(), w4.strides()) : dw.permute({0, 3, 1, 2});
+      const size_t wsb = ucd_conv_wgrad_workspace_bytes((int)M, (int)N, (int)K, (int)(k * k));
+      bool side;
+      const int flags = wgrad_flags(w4, ret, &side);
+      count_wgrad_call(flags);
+      if (side) hold_for_side(stream, {dzo, x, dw});
+      if (flags && ucd_conv_wgrad_mode()) queue_end_of_pass_flush(stream);
+      check(ucd_conv_wgrad_ex(dzo.data_ptr(), (int)N, x.data_ptr(), (int)K, (int)M, (int)N, (int)K, (int)(k * k),
+                              rows ? 0 : (int)x.size(2), rows ? 0 : (int)x.size(3), (int)(k == 3 ? dilation : 1), (int)stride,
+                              dw.data_ptr(), nullptr, 0, wgrad_workspace(x, wsb, stream, side), wsb, flags, (ucd_stream_t)stream),
+            "ucd_conv_wgrad");
+      return ret;
+    }
+    route = fallback;
+  }
+  if (route == kWgradSplit && k == 1 && stride == 1) {
+    const int64_t M = rows ? x.size(0) : x.size(0) * x.size(2) * x.size(3);
+    const at::Tensor dz2 = rows ? dz : dz.permute({0, 2, 3, 1}).reshape({M, N}), x2 = rows ? x : x.permute({0, 2, 3, 1}).reshape({M, K});
+    const int64_t S = wgrad_split(M);
+    at::Tensor dw;
+    if (S > 1) {
+      dw = at::bmm(dz2.view({S, M / S, N}).transpose(1, 2), x2.view({S, M / S, K})).sum(0);
+    } else {
+      dw = at::empty({N, K}, x.options());
+      const size_t wsb = ucd_gemm_workspace_bytes();
+      check(ucd_gemm_bf16(2, (int)N, (int)K, (int)M, dz2.data_ptr(), (int)N, x2.data_ptr(), (int)K, dw.data_ptr(), (int)K,
+                          workspace(x, wsb, stream, 1), wsb, 1, (ucd_stream_t)stream),
+            "ucd_gemm_bf16");
+    }
+    return dw.as_strided(w4.sizes(), w4.strides());   // [N, K, 1, 1] is one memory order in either format
+  }
+  const int64_t pad = dilation * (k / 2);
+  return std::get<1>(at::convolution_backward(dz, x, w4, c10::nullopt, {stride, stride}, {pad, pad}, {dilation, dilation}, false,
+                                              {0, 0}, 1, {false, true, false}));
 }
 
 class ABNTrainNode : public torch::autograd::Function<ABNTrainNode> {
@@ -389,39 +442,8 @@ class ABNTrainNode : public torch::autograd::Function<ABNTrainNode> {
   }
 };
 
-// dw[Co, Ci] = dy[M, Co]^T rows[M, Ci] on the own kernel (2-D row matrices, contiguous bf16)
-bool own_wgrad_rows_ok(const at::Tensor& dy, const at::Tensor& rows) {
-  return dy.dim() == 2 && rows.dim() == 2 && dy.is_contiguous() && rows.is_contiguous() && dy.scalar_type() == at::kBFloat16 &&
-         rows.scalar_type() == at::kBFloat16 && dy.size(1) % 64 == 0 && rows.size(1) % 64 == 0 && dy.size(0) < (1 << 22) &&
-         (reinterpret_cast<uintptr_t>(dy.data_ptr()) & 15) == 0 && (reinterpret_cast<uintptr_t>(rows.data_ptr()) & 15) == 0;
-}
-
-at::Tensor own_wgrad_rows(const at::Tensor& dy, const at::Tensor& rows, int64_t stream, const at::Tensor& w4) {
-  const int64_t M = rows.size(0), Ci = rows.size(1), Co = dy.size(1);
-  at::Tensor dw = at::empty({Co, Ci}, rows.options());
-  // the weight-shaped view the node returns; the side-stream hold keeps the base, so that AccumulateGrad may still adopt the view
-  at::Tensor ret = dw.as_strided(w4.sizes(), w4.strides());
-  const size_t wsb = ucd_conv_wgrad_workspace_bytes((int)M, (int)Co, (int)Ci, 1);
-  bool side;
-  const int flags = wgrad_flags(w4, ret, &side);
-  count_wgrad_call(flags);
-  if (side) hold_for_side(stream, {dy, rows, dw});
-  if (flags && ucd_conv_wgrad_mode()) queue_end_of_pass_flush(stream);
-  check(ucd_conv_wgrad_ex(dy.data_ptr(), (int)Co, rows.data_ptr(), (int)Ci, (int)M, (int)Co, (int)Ci, 1, 0, 0, 1, 1, dw.data_ptr(), nullptr, 0,
-                          wgrad_workspace(rows, wsb, stream, side), wsb, flags, (ucd_stream_t)stream),
-        "ucd_conv_wgrad");
-  return ret;
-}
-
 // ---- wide 1x1 convolution as a row-matrix GEMM (ucd_amd/blocks.py::_Gemm1x1 is the Python twin) ------------------
-// y[M, Co] = rows[M, Ci] . w[Co, Ci]^T through ucd_gemm_bf16 (hipBLASLt, tuned once per shape); the weight gradient of a
-// long M is eight batched K-chunks + a sum (41 us against 96 for the best single-kernel candidate at M = 26136).
-int64_t wgrad_split(int64_t M) {
-  if (M >= 8192)
-    for (int64_t S : {8, 4, 12, 6, 3, 2})
-      if (M % S == 0) return S;
-  return 1;
-}
+// y[M, Co] = rows[M, Ci] . w[Co, Ci]^T through ucd_gemm_bf16 (hipBLASLt, tuned once per shape)
 
 class Gemm1x1Node : public torch::autograd::Function<Gemm1x1Node> {
  public:
@@ -457,20 +479,8 @@ class Gemm1x1Node : public torch::autograd::Function<Gemm1x1Node> {
                           wsb, 1, (ucd_stream_t)stream),
             "ucd_gemm_bf16");
     }
-    if (ctx->needs_input_grad(1)) {
-      const int64_t S = wgrad_split(M);
-      if (ctx->saved_data["own_wgrad"].toBool() && own_wgrad_rows_ok(dy, rows)) {
-        dw = own_wgrad_rows(dy, rows, stream, w4);
-      } else if (S > 1) {
-        dw = at::bmm(dy.view({S, M / S, Co}).transpose(1, 2), rows.view({S, M / S, Ci})).sum(0);
-      } else {
-        dw = at::empty({Co, Ci}, rows.options());
-        check(ucd_gemm_bf16(2, (int)Co, (int)Ci, (int)M, dy.data_ptr(), (int)Co, rows.data_ptr(), (int)Ci, dw.data_ptr(), (int)Ci,
-                            ws, wsb, 1, (ucd_stream_t)stream),
-              "ucd_gemm_bf16");
-      }
-      dw = dw.as_strided(w4.sizes(), w4.strides());   // [Co, Ci, 1, 1] is one memory order in either format
-    }
+    if (ctx->needs_input_grad(1))
+      dw = conv_wgrad(dy, rows, w4, 1, 1, ctx->saved_data["own_wgrad"].toBool() ? kWgradOwn : kWgradSplit, kWgradSplit, stream);
     return {dx, dw, at::Tensor(), at::Tensor()};
   }
 };
@@ -534,20 +544,8 @@ class Gemm1x1SkipNode : public torch::autograd::Function<Gemm1x1SkipNode> {
         dx = dskip;
       }
     }
-    if (ctx->needs_input_grad(1) && dy.defined()) {
-      const int64_t S = wgrad_split(M);
-      if (ctx->saved_data["own_wgrad"].toBool() && own_wgrad_rows_ok(dy, rows)) {
-        dw = own_wgrad_rows(dy, rows, stream, w4);
-      } else if (S > 1) {
-        dw = at::bmm(dy.view({S, M / S, Co}).transpose(1, 2), rows.view({S, M / S, Ci})).sum(0);
-      } else {
-        dw = at::empty({Co, Ci}, rows.options());
-        check(ucd_gemm_bf16(2, (int)Co, (int)Ci, (int)M, dy.data_ptr(), (int)Co, rows.data_ptr(), (int)Ci, dw.data_ptr(), (int)Ci,
-                            ws, wsb, 1, (ucd_stream_t)stream),
-              "ucd_gemm_bf16");
-      }
-      dw = dw.as_strided(w4.sizes(), w4.strides());
-    }
+    if (ctx->needs_input_grad(1) && dy.defined())
+      dw = conv_wgrad(dy, rows, w4, 1, 1, ctx->saved_data["own_wgrad"].toBool() ? kWgradOwn : kWgradSplit, kWgradSplit, stream);
     return {dx, dw, at::Tensor(), at::Tensor()};
   }
 };
@@ -605,17 +603,9 @@ class StrideOneConvNode : public torch::autograd::Function<StrideOneConvNode> {
         dx = at::conv2d(dy, wt, {}, {1, 1}, {pad, pad}, {d, d}, 1);
       }
     }
-    if (ctx->needs_input_grad(1)) {
-      const int64_t dil = w.size(2) == 3 ? d : 0;
-      at::Tensor dyc = dy;
-      if (ctx->saved_data["own_wgrad"].toBool() && dyc.scalar_type() == at::kBFloat16 && !dense_channels_last(dyc))
-        dyc = dyc.contiguous(at::MemoryFormat::ChannelsLast);
-      if (ctx->saved_data["own_wgrad"].toBool() && own_wgrad_ok(dyc, x, w, dil) && (dil == 0 || w.is_contiguous(at::MemoryFormat::ChannelsLast)))
-        dw = own_wgrad(dyc, x, w, dil, ctx->saved_data["stream"].toInt());
-      else
-        dw = std::get<1>(at::convolution_backward(dy, x, w, c10::nullopt, {1, 1}, {pad, pad}, {d, d}, false, {0, 0}, 1,
-                                                  {false, true, false}));
-    }
+    if (ctx->needs_input_grad(1))
+      dw = conv_wgrad(dy, x, w, d, 1, ctx->saved_data["own_wgrad"].toBool() ? kWgradOwn : kWgradLibrary, kWgradLibrary,
+                      ctx->saved_data["stream"].toInt());
     return {dx, dw, at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor()};
   }
 };
@@ -728,8 +718,8 @@ class ConvABNTrainNode : public torch::autograd::Function<ConvABNTrainNode> {
     // (make_link with a residual), B the first convolution of an identity-shortcut block (with_skip); lk_bias is unused.
     // dilation = 0: 1x1 convolution; dilation >= 1: 3x3, stride 1, padding = dilation (implicit GEMM, taps = 9), weight in
     // channels-last memory order; wflip = w.flip(2, 3).transpose(0, 1) (channels-last; for a 1x1 layer the transposed
-    // weight [Ci, Co]) for the input gradient through the own kernel (own_dgrad); wgrad_conv: weight gradient by 0 the batched
-    // split-M library products, 1 MIOpen, 2 the own kernel (ucd_conv_wgrad; 3x3 layers: 2 or MIOpen)
+    // weight [Ci, Co]) for the input gradient through the own kernel (own_dgrad); wgrad_conv: the WgradRoute of the weight gradient
+    // (conv_wgrad; a layer the own kernel does not take falls back to the split products, which a 3x3 / strided layer takes on MIOpen)
     TORCH_CHECK(dense_channels_last(x) && x.scalar_type() == at::kBFloat16, "ucd conv+abn node: x must be dense channels-last bf16");
     const bool conv3 = dilation > 0;
     TORCH_CHECK(w4.dim() == 4 && w4.scalar_type() == at::kBFloat16 && w4.size(1) == x.size(1) &&
@@ -1003,19 +993,9 @@ class ConvABNTrainNode : public torch::autograd::Function<ConvABNTrainNode> {
       if (ctx->needs_input_grad(0) && dz.defined())
         dx = std::get<0>(at::convolution_backward(dz, x, w4, c10::nullopt, {stride, stride}, {pad, pad}, {dil, dil}, false, {0, 0}, 1,
                                                   {true, false, false}));
-      if (ctx->needs_input_grad(1) && dz.defined()) {
-        if (ctx->saved_data["wgrad_conv"].toInt() == 2 && own_wgrad_ok(dz, x, w4, conv3 ? dilation : 0) && N % 128 == 0 && K % 128 == 0)
-          dw = own_wgrad(dz, x, w4, conv3 ? dilation : 0, stream, stride);
-        else
-          dw = std::get<1>(at::convolution_backward(dz, x, w4, c10::nullopt, {stride, stride}, {pad, pad}, {dil, dil}, false, {0, 0}, 1,
-                                                    {false, true, false}));
-      }
-      return {dx, dw, dweight, dbias, has_res ? dres : none, none, none, none, none, none, none, none, none, none, none, none, none,
-              none, none, none, none, none, none, none, none, none, none, none, none, none, none, none};
-    }
-    if (conv3) {
+    } else if (conv3) {
       // 3x3: input gradient = the same convolution on the flipped + transposed weight (own implicit GEMM, or MIOpen's
-      // FORWARD solver when the cached weight is missing / the map is too small to fill the chip); weight gradient: MIOpen
+      // FORWARD solver when the cached weight is missing / the map is too small to fill the chip)
       if (ctx->needs_input_grad(0) && dz.defined()) {
         if (!wflip.defined()) wflip = w4.flip({2, 3}).transpose(0, 1).contiguous(at::MemoryFormat::ChannelsLast);
         if (own_dgrad) {
@@ -1034,19 +1014,9 @@ class ConvABNTrainNode : public torch::autograd::Function<ConvABNTrainNode> {
           dx = at::conv2d(dz, wflip, {}, {1, 1}, {dilation, dilation}, {dilation, dilation}, 1);
         }
       }
-      if (ctx->needs_input_grad(1) && dz.defined()) {
-        if (ctx->saved_data["wgrad_conv"].toInt() == 2 && own_wgrad_ok(dz, x, w4, dilation))
-          dw = own_wgrad(dz, x, w4, dilation, stream);
-        else
-          dw = std::get<1>(at::convolution_backward(dz, x, w4, c10::nullopt, {1, 1}, {dilation, dilation}, {dilation, dilation}, false,
-                                                    {0, 0}, 1, {false, true, false}));
-      }
-      return {dx, dw, dweight, dbias, has_res ? dres : none, none, none, none, none, none, none, none, none, none, none, none, none,
-              none, none, none, none, none, none, none, none, none, none, none, none, none, none, none};
-    }
-    const size_t wsb = ucd_gemm_workspace_bytes();
-    void* gws = workspace(x, wsb, stream, 1);
-    if (ctx->needs_input_grad(0)) {
+    } else if (ctx->needs_input_grad(0)) {
+      const size_t wsb = ucd_gemm_workspace_bytes();
+      void* gws = workspace(x, wsb, stream, 1);
       const bool fold = dskip.defined() && dz.defined() && dskip.scalar_type() == at::kBFloat16;
       if (own_dgrad && dz.defined() && wflip.defined()) {
         // narrow / short-K layers: d x = d z . w through the own kernel on the cached transposed weight [Ci, Co]; the
@@ -1090,25 +1060,8 @@ class ConvABNTrainNode : public torch::autograd::Function<ConvABNTrainNode> {
         dx = dskip;
       }
     }
-    if (ctx->needs_input_grad(1) && dz.defined() && ctx->saved_data["wgrad_conv"].toInt() == 2 && own_wgrad_ok(dz, x, w4, 0)) {
-      dw = own_wgrad(dz, x, w4, 0, stream);
-    } else if (ctx->needs_input_grad(1) && dz.defined() && ctx->saved_data["wgrad_conv"].toInt() == 1) {
-      // narrow layers (<= 512 channels at 65^2 / 129^2): MIOpen's weight-gradient solver beats the split-M products
-      dw = std::get<1>(at::convolution_backward(dz, x, w4, c10::nullopt, {1, 1}, {0, 0}, {1, 1}, false, {0, 0}, 1,
-                                                {false, true, false}));
-    } else if (ctx->needs_input_grad(1) && dz.defined()) {
-      at::Tensor dz2 = dz.permute({0, 2, 3, 1}).reshape({M, N}), x2 = x.permute({0, 2, 3, 1}).reshape({M, K});
-      const int64_t S = wgrad_split(M);
-      if (S > 1) {
-        dw = at::bmm(dz2.view({S, M / S, N}).transpose(1, 2), x2.view({S, M / S, K})).sum(0);
-      } else {
-        dw = at::empty({N, K}, x.options().memory_format(c10::nullopt));
-        check(ucd_gemm_bf16(2, (int)N, (int)K, (int)M, dz2.data_ptr(), (int)N, x2.data_ptr(), (int)K, dw.data_ptr(), (int)K, gws, wsb, 1,
-                            (ucd_stream_t)stream),
-              "ucd_gemm_bf16");
-      }
-      dw = dw.as_strided(w4.sizes(), w4.strides());
-    }
+    if (ctx->needs_input_grad(1) && dz.defined())
+      dw = conv_wgrad(dz, x, w4, conv3 ? dilation : 1, stride, ctx->saved_data["wgrad_conv"].toInt(), kWgradSplit, stream);
     return {dx, dw, dweight, dbias, has_res ? dres : none, none, none, none, none, none, none, none, none, none, none, none, none,
             none, none, none, none, none, none, none, none, none, none, none, none, none, none, none};
   }
