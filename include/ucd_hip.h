@@ -410,8 +410,48 @@ int ucd_pixcon_scatter_grad(const float* grad_a, const float* chat, int ldc, con
  *   (sem_t may be NULL: cross entropy only; K = number of old classes incl. background, >= 1)
  *   loss_out[0] = mean CE, loss_out[1] = mean KD
  *   d_sem [B*h*w, ld_d] = d(ce_weight * CE + kd_weight * KD) / d sem_s   (overwritten)
- * The gradient is accumulated with float atomics (LDS, then global): its last bits depend on the
- * execution order; the loss values are summed in a fixed order. */
+ * Rows may be column slices of wider buffers: ld_s >= Ctot, ld_t >= K, ld_d >= Ctot in elements; columns past the class
+ * counts are never read, and those of d_sem come back as zeros (the whole [B*h*w, ld_d] block is cleared first).
+ *
+ * Forms (ucd_seg_losses_plan names the one a call gets; enum ucd_seg_form):
+ *   packed, Ctot <= 24:  (K <= 16, Ctot - K <= 8), (K <= 20, Ctot - K <= 4) or (K <= 12, Ctot - K <= 12), 64 x 64 pixel tiles;
+ *   register, Ctot <= 24: any other split, a d_sem that is not 16-byte aligned, UCD_SEG_PK=0 (environment, read once per
+ *            process), or a geometry whose packed form does not fit the LDS while this one does (21 classes at factor 8);
+ *   many-class, Ctot > 24: 32 x 64 pixel tiles.
+ * Gradient arithmetic.  The packed and the many-class form add every tile's contribution to a low-resolution cell as a 32-bit
+ * FIXED-POINT word: integer addition has no order, so d_sem has the same bits on every run.  The quantum of a word is
+ *   q = gmax / 2^17,  gmax = (|ce_weight| + 2 |kd_weight| / K) / (B H W)   (the largest gradient one pixel can contribute);
+ * a tile sums its pixels in fp64, rounds ONCE to the nearest word (error <= q / 2) and adds it; a cell receives one add from each
+ * tile that touches it, at most n_tiles = (ceil(2 f_y / tile_y) + 1) (ceil(2 f_x / 64) + 1) for up-sampling factors f_y, f_x
+ * (a cell's bilinear support is 2 f pixels wide).  The fixed-point error of an element is therefore at most (q / 2) n_tiles
+ * (4 q / 2 at factor 16), on top of the fp32 rounding of the per-pixel terms.  A cell collects bilinear weights of at most
+ * f_y f_x pixels: 64^2 x 2^17 = 2^29 < 2^31, which is why factors above 64 are refused.
+ * The register form, and the many-class form when d_sem is not 16-byte aligned, add with fp32 atomics instead (LDS, then
+ * global): no quantum, but the last bits depend on the execution order.  The loss values are summed in a fixed order always.
+ *
+ * Supported up-sampling factors: H / h and W / w in [4, 64], and the low-resolution cells under one tile must fit 150 KB of LDS
+ * in some form (at a 512-pixel crop: 21 classes down to about factor 7.5, 151 student + 101 teacher classes down to about 10;
+ * the count of cells depends on how the tiles fall on the source grid, so ask ucd_seg_losses_plan).
+ * Returns UCD_EINVAL (NULL sem_s / labels / loss_out / d_sem / workspace; a size < 1; K < 1 or K > Ctot; a leading dimension
+ * below its class count; H < h or W < w), UCD_EUNSUPPORTED (a factor below 4 or above 64; no form fits the LDS - the message
+ * names the factors and the bytes asked for), UCD_EWORKSPACE (workspace_bytes below ucd_seg_losses_workspace_bytes), or
+ * the hipError_t of a failed launch.  On a negative code nothing was launched and no output was written.
+ *
+ * ucd_seg_losses_plan touches no device (it answers on a machine without a GPU): for a geometry, a class split, has_teacher
+ * (sem_t != NULL), d_sem_aligned (16-byte) and pk (1 / 0: the packed forms allowed / not; -1: as UCD_SEG_PK says) it returns
+ * the code ucd_seg_losses would return for these arguments and, on 0, the form, the low-resolution cells ny x nx staged per
+ * tile and the bytes of dynamic LDS of the launch.  Output pointers may be NULL. */
+enum ucd_seg_form {
+  UCD_SEG_PK_16_8 = 1,   /* seg_losses_pk_kernel<16, 8>,  fixed-point words */
+  UCD_SEG_PK_20_4 = 2,   /* seg_losses_pk_kernel<20, 4>,  fixed-point words */
+  UCD_SEG_PK_12_12 = 3,  /* seg_losses_pk_kernel<12, 12>, fixed-point words */
+  UCD_SEG_REG_24_16 = 4, /* seg_losses_kernel<24, 16> (K <= 16), fp32 atomics */
+  UCD_SEG_REG_24_24 = 5, /* seg_losses_kernel<24, 24> (K > 16),  fp32 atomics */
+  UCD_SEG_WIDE_FIXED = 6, /* seg_losses_wide_kernel, fixed-point words */
+  UCD_SEG_WIDE_F32 = 7   /* seg_losses_wide_kernel, fp32 atomics (d_sem not 16-byte aligned) */
+};
+int ucd_seg_losses_plan(int H, int W, int h, int w, int Ctot, int K, int has_teacher, int d_sem_aligned, int pk, int* form,
+                        int* ny, int* nx, size_t* lds_bytes);
 size_t ucd_seg_losses_workspace_bytes(int B, int H, int W);
 int ucd_seg_losses(const float* sem_s, int ld_s, const float* sem_t, int ld_t, const int64_t* labels,
                    int B, int H, int W, int h, int w, int Ctot, int K, int ignore_index,

@@ -10,10 +10,12 @@
 // background + new classes), the teacher soft-max, the two losses and
 //   dCE/dz_c = softmax(z)_c - [label is bkg/old] [c < K] exp(z_c - LSE_old) - [label new] [c == label]
 //   dKD/dz_c = (softmax(z)_c - q_0 [c in {0} U [K,Ctot)] exp(z_c - LSE_bkgnew) - [1 <= c < K] q_c) / K
-// scattered to the 4 neighbours with their bilinear weights.  A 256-thread block owns a 16 x 64 pixel
-// tile; the <= 3 x 7 low-res cells under it are staged in LDS (logits in, gradient accumulators out, LDS
-// float atomics), then flushed with one global float atomic per cell and class (the summation order of
-// float atomics makes the last bits of the gradient run-dependent; the loss sums use a fixed order).
+// scattered to the 4 neighbours with their bilinear weights.  A 256-thread block owns a 64 x 64 pixel
+// tile (the many-class form: 32 x 64); the low-resolution cells under it (6 x 6 at 513 / 33; ucd_seg_losses_plan
+// computes the exact count) are staged in LDS (logits in, gradient accumulators out), then flushed with one
+// global atomic per cell and class: 32-bit fixed-point words in the packed and the many-class form (integer
+// addition has no order: the same bits on every run), fp32 atomics in the register form and for a d_sem that
+// is not 16-byte aligned (last bits run-dependent).  The loss sums use a fixed order in every form.
 #include "common.h"
 
 namespace ucd {
@@ -22,11 +24,18 @@ namespace {
 constexpr int kThreads = 256;
 constexpr int kTileY = 64, kTileX = 64;     // a thread walks kRows consecutive rows of one pixel column
 constexpr int kRows = kTileY / 4;
+// The sums over the class subsets (old classes; background + new classes) are taken from the exponentials relative to the maximum
+// over ALL classes.  A subset that trails that maximum by more than ~87 underflows to a zero sum (log -> -inf, 1 / sum -> inf):
+// below this threshold a pixel takes its subset sums again around each subset's own maximum (what torch.logsumexp does).  Rare in
+// training (a class set 70 below the leader), so a branch: the common path keeps its arithmetic.
+constexpr float kSubsetTiny = 1e-30f;
 
-__device__ __forceinline__ void up_src(int dst, int in_size, float scale, int& i0, int& i1, float& l0, float& l1) {
+// torch's align_corners=False source index.  Host and device: ucd_seg_losses_plan sizes the LDS with the very function the
+// kernels index it with (-ffp-contract=off on both sides: the same roundings)
+__host__ __device__ __forceinline__ void up_src(int dst, int in_size, float scale, int& i0, int& i1, float& l0, float& l1) {
   float src = scale * ((float)dst + 0.5f) - 0.5f;
   src = src < 0.f ? 0.f : src;
-  i0 = min((int)src, in_size - 1);
+  i0 = (int)src < in_size - 1 ? (int)src : in_size - 1;
   i1 = i0 + (i0 < in_size - 1 ? 1 : 0);
   l1 = src - (float)i0;
   l0 = 1.f - l1;
@@ -148,10 +157,31 @@ __global__ __launch_bounds__(kThreads) void seg_losses_kernel(
         z_lab = c == lab ? zc[c] : z_lab;
       }
       const float den = mz + kLn2 * __builtin_amdgcn_logf(s_all);
-      const float lse_old = mz + kLn2 * __builtin_amdgcn_logf(s_old), lse_bn = mz + kLn2 * __builtin_amdgcn_logf(s_bn);
+      float lse_old = mz + kLn2 * __builtin_amdgcn_logf(s_old), lse_bn = mz + kLn2 * __builtin_amdgcn_logf(s_bn);
+      float inv_old = 1.f / s_old, inv_bn = 1.f / s_bn;
+      const bool rescue = s_old < kSubsetTiny || s_bn < kSubsetTiny;
+      float m_o = 0.f, m_b = 0.f, r_o = 0.f, r_b = 0.f;
+      if (rescue) {
+        m_o = kNegBig; m_b = zc[0];
+#pragma unroll
+        for (int c = 0; c < CTA; ++c) {
+          m_o = c < K ? fmaxf(m_o, zc[c]) : m_o;
+          m_b = c >= K ? fmaxf(m_b, zc[c]) : m_b;
+        }
+        float so = 0.f, sb = 0.f;
+#pragma unroll
+        for (int c = 0; c < CTA; ++c) {
+          so += c < K ? __builtin_amdgcn_exp2f((zc[c] - m_o) * kL2e) : 0.f;
+          sb += (c == 0 || c >= K) ? __builtin_amdgcn_exp2f((zc[c] - m_b) * kL2e) : 0.f;
+        }
+        lse_old = m_o + kLn2 * __builtin_amdgcn_logf(so);
+        lse_bn = m_b + kLn2 * __builtin_amdgcn_logf(sb);
+        r_o = 1.f / so; r_b = 1.f / sb;
+        inv_old = 0.f; inv_bn = 0.f;                 // the subset terms of the gradient come from r_o / r_b below
+      }
       const float logp = lab == 0 ? lse_old - den : z_lab - den;
       if (!ignored) ce_sum += -logp;
-      const float inv_all = 1.f / s_all, inv_old = 1.f / s_old, inv_bn = 1.f / s_bn;
+      const float inv_all = 1.f / s_all;
       // teacher soft-max
       float te[KTA];
       float inv_st = 0.f, q0 = 0.f, kd_pix = 0.f;
@@ -192,6 +222,10 @@ __global__ __launch_bounds__(kThreads) void seg_losses_kernel(
           }
           const float bn = ec[c] * ((c == 0 || c >= K) ? q0bn : 0.f);
           g = __builtin_fmaf(kdw, p - bn - qc, g);
+        }
+        if (rescue) {
+          if (lab0 && c < K) g -= ce_w * r_o * __builtin_amdgcn_exp2f((zc[c] - m_o) * kL2e);
+          if (sem_t && (c == 0 || c >= K)) g -= kdw * q0 * r_b * __builtin_amdgcn_exp2f((zc[c] - m_b) * kL2e);
         }
         acc0[c] = __builtin_fmaf(ly0, g, acc0[c]);
         acc1[c] = __builtin_fmaf(ly1, g, acc1[c]);
@@ -502,10 +536,34 @@ __global__ __launch_bounds__(kThreads) void seg_losses_pk_kernel(
     const float s_old = so.x + so.y, s_new = sn.x + sn.y;
     const float s_all = s_old + s_new, s_bn = s_new + e[0].x;
     const float den = mz + kLn2 * __builtin_amdgcn_logf(s_all);
-    const float lse_old = mz + kLn2 * __builtin_amdgcn_logf(s_old), lse_bn = mz + kLn2 * __builtin_amdgcn_logf(s_bn);
+    float lse_old = mz + kLn2 * __builtin_amdgcn_logf(s_old), lse_bn = mz + kLn2 * __builtin_amdgcn_logf(s_bn);
+    float inv_old = 1.f / s_old, inv_bn = 1.f / s_bn;
+    const bool rescue = s_old < kSubsetTiny || s_bn < kSubsetTiny;
+    float m_o = 0.f, m_b = 0.f, r_o = 0.f, r_b = 0.f;
+    if (rescue) {
+      m_o = kNegBig; m_b = zpair(0).x;
+#pragma unroll
+      for (int p = 0; p < NP; ++p) {
+        const f32x2 zz = zpair(p);
+        if (p < KP) m_o = fmaxf(m_o, fmaxf(zz.x, zz.y));
+        else m_b = fmaxf(m_b, fmaxf(zz.x, zz.y));
+      }
+      const f32x2 MO = bc2(-m_o * kL2e), MB = bc2(-m_b * kL2e);
+      f32x2 so2 = bc2(0.f), sb2 = f32x2{__builtin_amdgcn_exp2f(__builtin_fmaf(zpair(0).x, kL2e, MB.x)), 0.f};
+#pragma unroll
+      for (int p = 0; p < NP; ++p) {
+        if (p < KP) so2 += exp2_2(fma2(zpair(p), L2E, MO));
+        else sb2 += exp2_2(fma2(zpair(p), L2E, MB));
+      }
+      const float so = so2.x + so2.y, sb = sb2.x + sb2.y;
+      lse_old = m_o + kLn2 * __builtin_amdgcn_logf(so);
+      lse_bn = m_b + kLn2 * __builtin_amdgcn_logf(sb);
+      r_o = 1.f / so; r_b = 1.f / sb;
+      inv_old = 0.f; inv_bn = 0.f;                   // the subset terms of the gradient come from r_o / r_b below
+    }
     const float logp = lab0 ? lse_old - den : z_lab - den;
     if (!ignored) ce_sum += -logp;
-    const float inv_all = 1.f / s_all, inv_old = 1.f / s_old, inv_bn = 1.f / s_bn;
+    const float inv_all = 1.f / s_all;
     const float ce_w = ignored ? 0.f : ce_scale;
     // teacher soft-max over the old classes; q_c = te_c / sum te
     f32x2 te[KP];
@@ -553,6 +611,15 @@ __global__ __launch_bounds__(kThreads) void seg_losses_pk_kernel(
       } else {
         const int j = 2 * (p - KP);
         g = e[p] * CNEW - f32x2{jlab == j ? ce_w : 0.f, jlab == j + 1 ? ce_w : 0.f};
+      }
+      if (rescue) {
+        const f32x2 zz = zpair(p);
+        if (p < KP) {
+          g -= bc2(lab0 ? ce_w * r_o : 0.f) * exp2_2(fma2(zz, L2E, bc2(-m_o * kL2e)));
+          if (p == 0) g.x -= kdw * q0 * r_b * __builtin_amdgcn_exp2f(__builtin_fmaf(zz.x, kL2e, -m_b * kL2e));
+        } else {
+          g -= bc2(kdw * q0 * r_b) * exp2_2(fma2(zz, L2E, bc2(-m_b * kL2e)));
+        }
       }
       acc0[p] = fma2(LY0p, g, acc0[p]);
       acc1[p] = fma2(LY1p, g, acc1[p]);
@@ -661,11 +728,13 @@ __global__ __launch_bounds__(kThreads) void seg_losses_wide_kernel(
   float ce_sum = 0.f, kd_sum = 0.f;
   // ---- phase A: per row, the normalisers and the loss values --------------------------------------------------------------
   float rmzl[kRW], ra_all[kRW], ra_old[kRW], rhot[kRW], rbbn[kRW], rmtl[kRW], rbq[kRW];
-  int rlab[kRW];
+  float rmo[kRW], rmb[kRW], rco[kRW], rcb[kRW];      // rows whose subset sums underflowed (kSubsetTiny): offsets and coefficients
+  int rlab[kRW], rescue_rows = 0;
 #pragma unroll
   for (int it = 0; it < kRW; ++it) {
     const int Y = Ybase + it;
     rmzl[it] = 0.f; ra_all[it] = 0.f; ra_old[it] = 0.f; rhot[it] = 0.f; rbbn[it] = 0.f; rmtl[it] = 0.f; rbq[it] = 0.f; rlab[it] = -1;
+    rmo[it] = 0.f; rmb[it] = 0.f; rco[it] = 0.f; rcb[it] = 0.f;
     if (X >= W || Y >= H) continue;
     int y0, y1;
     float ly0, ly1;
@@ -715,7 +784,36 @@ __global__ __launch_bounds__(kThreads) void seg_losses_wide_kernel(
       }
     }
     const float den = mz + kLn2 * __builtin_amdgcn_logf(s_all);
-    const float lse_old = mz + kLn2 * __builtin_amdgcn_logf(s_old), lse_bn = mz + kLn2 * __builtin_amdgcn_logf(s_bn);
+    float lse_old = mz + kLn2 * __builtin_amdgcn_logf(s_old), lse_bn = mz + kLn2 * __builtin_amdgcn_logf(s_bn);
+    float inv_old = 1.f / s_old, inv_bn = 1.f / s_bn, m_o = 0.f, m_b = 0.f, r_o = 0.f, r_b = 0.f;
+    const bool rescue = s_old < kSubsetTiny || s_bn < kSubsetTiny;
+    if (rescue) {
+      m_o = kNegBig; m_b = kNegBig;
+      for (int c = 0; c < CS; c += 4) {
+        const float4 v4 = interp4(s_log, s00, s01, s10, s11, c, lx0, lx1, ly0, ly1);
+        const float v[4] = {v4.x, v4.y, v4.z, v4.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          m_o = c + j < K ? fmaxf(m_o, v[j]) : m_o;
+          m_b = (c + j == 0 || c + j >= K) ? fmaxf(m_b, v[j]) : m_b;
+        }
+      }
+      float so = 0.f, sb = 0.f;
+      for (int c = 0; c < CS; c += 4) {
+        const float4 v4 = interp4(s_log, s00, s01, s10, s11, c, lx0, lx1, ly0, ly1);
+        const float v[4] = {v4.x, v4.y, v4.z, v4.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          so += c + j < K ? __builtin_amdgcn_exp2f((v[j] - m_o) * kL2e) : 0.f;
+          sb += (c + j == 0 || c + j >= K) ? __builtin_amdgcn_exp2f((v[j] - m_b) * kL2e) : 0.f;
+        }
+      }
+      lse_old = m_o + kLn2 * __builtin_amdgcn_logf(so);
+      lse_bn = m_b + kLn2 * __builtin_amdgcn_logf(sb);
+      r_o = 1.f / so; r_b = 1.f / sb;
+      inv_old = 0.f; inv_bn = 0.f;                   // the subset terms of the gradient come from rco / rcb in phase B
+      rescue_rows |= 1 << it;
+    }
     const bool lab0 = lab == 0;
     const float logp = lab0 ? lse_old - den : z_lab - den;
     if (!ignored) ce_sum += -logp;
@@ -729,10 +827,12 @@ __global__ __launch_bounds__(kThreads) void seg_losses_wide_kernel(
     }
     rmzl[it] = mzl;
     ra_all[it] = (ce_w + kdw) / s_all;
-    ra_old[it] = lab0 ? ce_w / s_old : 0.f;
+    ra_old[it] = lab0 ? ce_w * inv_old : 0.f;
     rhot[it] = lab0 ? 0.f : ce_w;
     rlab[it] = lab;
-    rbbn[it] = kdw * q0 / s_bn;
+    rbbn[it] = kdw * q0 * inv_bn;
+    rmo[it] = m_o; rmb[it] = m_b;
+    rco[it] = lab0 ? ce_w * r_o : 0.f; rcb[it] = kdw * q0 * r_b;
     rmtl[it] = mtl;
     rbq[it] = kdw * inv_st;
   }
@@ -791,6 +891,10 @@ __global__ __launch_bounds__(kThreads) void seg_losses_wide_kernel(
           if (c < KS) {
             const float te = __builtin_amdgcn_exp2f(__builtin_fmaf(tv[j], kL2e, -rmtl[it]));
             g = __builtin_fmaf(-rbq[it], (cc >= 1 && cc < K) ? te : 0.f, g);
+          }
+          if ((rescue_rows >> it) & 1) {
+            if (cc < K) g -= rco[it] * __builtin_amdgcn_exp2f((v[j] - rmo[it]) * kL2e);
+            if (cc == 0 || cc >= K) g -= rcb[it] * __builtin_amdgcn_exp2f((v[j] - rmb[it]) * kL2e);
           }
           acc0[4 * q + j] = __builtin_fmaf(ly0, g, acc0[4 * q + j]);
           acc1[4 * q + j] = __builtin_fmaf(ly1, g, acc1[4 * q + j]);
@@ -930,42 +1034,34 @@ size_t ucd_seg_losses_workspace_bytes(int B, int H, int W) {
   return (size_t)B * ceil_div(H, 4 * kRW) * ceil_div(W, kTileX) * 2 * sizeof(float);      // the finer tiling of the two kernels
 }
 
-int ucd_seg_losses(const float* sem_s, int ld_s, const float* sem_t, int ld_t, const int64_t* labels, int B, int H, int W,
-                   int h, int w, int Ctot, int K, int ignore_index, float ce_weight, float kd_weight, float* loss_out,
-                   float* d_sem, int ld_d, void* workspace, size_t workspace_bytes, ucd_stream_t stream) {
+// Host only, no device call: which kernel ucd_seg_losses launches for a geometry and a class split, on how many low-resolution
+// cells per tile and with how many bytes of dynamic LDS.  The one copy of that arithmetic: ucd_seg_losses calls it.
+int ucd_seg_losses_plan(int H, int W, int h, int w, int Ctot, int K, int has_teacher, int d_sem_aligned, int pk, int* form,
+                        int* ny_out, int* nx_out, size_t* lds_bytes) {
   static const char* fn = "ucd_seg_losses";
-  UCD_REQUIRE(sem_s && labels && loss_out && d_sem && workspace, UCD_EINVAL, "%s: NULL argument", fn);
-  UCD_REQUIRE(B > 0 && H > 0 && W > 0 && h > 0 && w > 0 && Ctot > 0 && K >= 1 && K <= Ctot, UCD_EINVAL, "%s: bad sizes", fn);
-  UCD_REQUIRE(ld_s >= Ctot && ld_d >= Ctot && (!sem_t || ld_t >= K), UCD_EINVAL, "%s: bad leading dimension", fn);
-  UCD_REQUIRE(H >= 8 * h || H >= h, UCD_EINVAL, "%s: bad scale", fn);
-  UCD_REQUIRE((float)H / h >= 4.f && (float)W / w >= 4.f, UCD_EUNSUPPORTED,
-              "%s: built for up-sampling factors >= 4 (the model's is 16)", fn);
+  UCD_REQUIRE(H > 0 && W > 0 && h > 0 && w > 0 && Ctot > 0 && K >= 1 && K <= Ctot, UCD_EINVAL, "%s: bad sizes", fn);
+  UCD_REQUIRE(H >= h && W >= w, UCD_EINVAL, "%s: bad scale (the label map %d x %d is smaller than the logits %d x %d)", fn, H, W, h, w);
+  const float fy = (float)H / h, fx = (float)W / w;
   // the fixed-point gradient words (scale 2^17 over one pixel's largest gradient) hold the bilinear weights of at most factor^2 pixels
   // per low-resolution cell: 64^2 x 2^17 = 2^29 < 2^31; beyond a factor of 64 an int32 word could wrap silently
-  UCD_REQUIRE((float)H / h <= 64.f && (float)W / w <= 64.f, UCD_EUNSUPPORTED, "%s: up-sampling factors above 64 are not supported", fn);
-  UCD_REQUIRE(workspace_bytes >= ucd_seg_losses_workspace_bytes(B, H, W), UCD_EWORKSPACE, "%s: workspace too small", fn);
-  hipStream_t s = (hipStream_t)stream;
+  UCD_REQUIRE(fy <= 64.f && fx <= 64.f, UCD_EUNSUPPORTED, "%s: up-sampling factors above 64 are not supported (%.4g x %.4g)", fn, fy, fx);
+  // below 4 the footprint arithmetic has never been checked against the kernels' (tests/test_seglosses_cpu.py sweeps 4 .. 64);
+  // between 4 and 64 the LDS budget below decides
+  UCD_REQUIRE(fy >= 4.f && fx >= 4.f, UCD_EUNSUPPORTED, "%s: up-sampling factors below 4 are not supported (%.4g x %.4g)", fn, fy, fx);
   const bool wide = Ctot > 24;                       // many classes (ADE): seg_losses_wide_kernel on 32 x 64 pixel tiles
   const int tile_y = wide ? 4 * kRW : kTileY;
-  const int tiles_x = ceil_div(W, kTileX), tiles_y = ceil_div(H, tile_y);
-  // worst-case LDS: (tile/scale + 3) cells per dimension
+  // worst-case footprint: (tile/scale + 3) cells per dimension
   int ny = (int)(tile_y * (float)h / H) + 3, nx = (int)(kTileX * (float)w / W) + 3;
   {
-    // the exact footprint instead of the bound: the kernels' own source-index arithmetic (up_src, same float operations) over
-    // every tile origin - 6 x 6 cells instead of 7 x 7 at 513 / 33, which is what lets two workgroups share a CU's LDS
-    auto lo = [](int dst, int in_size, float scale) {
-      float src = scale * ((float)dst + 0.5f) - 0.5f;
-      src = src < 0.f ? 0.f : src;
-      const int i0 = (int)src < in_size - 1 ? (int)src : in_size - 1;
-      return i0;
-    };
-    auto span = [&](int out, int in_size, float scale, int tile) {
-      int m = 1;
+    // the exact footprint instead of the bound: the kernels' own source-index function over the first and the last pixel of every
+    // tile (it is monotone in the pixel) - 6 x 6 cells instead of 7 x 7 at 513 / 33, which is what lets two workgroups share a
+    // CU's LDS
+    auto span = [](int out, int in_size, float scale, int tile) {
+      int m = 1, a, bnd, dummy;
+      float f0, f1;
       for (int t0 = 0; t0 < out; t0 += tile) {
-        const int a = lo(t0, in_size, scale);
-        const int last = (t0 + tile < out ? t0 + tile : out) - 1;
-        const int i0 = lo(last, in_size, scale);
-        const int bnd = i0 + (i0 < in_size - 1 ? 1 : 0);
+        up_src(t0, in_size, scale, a, dummy, f0, f1);
+        up_src((t0 + tile < out ? t0 + tile : out) - 1, in_size, scale, dummy, bnd, f0, f1);
         if (bnd - a + 1 > m) m = bnd - a + 1;
       }
       return m;
@@ -974,21 +1070,64 @@ int ucd_seg_losses(const float* sem_s, int ld_s, const float* sem_t, int ld_t, c
     if (ey < ny) ny = ey;
     if (ex < nx) nx = ex;
   }
-  const int CS = (Ctot + 3) & ~3, KS = sem_t ? ((K + 3) & ~3) : 0;
-  // few classes: the packed form with old / new classes in separate slot groups (UCD_SEG_PK=0: the round-3 register form, A/B)
-  static const int pk_on = getenv("UCD_SEG_PK") ? atoi(getenv("UCD_SEG_PK")) : 1;
-  int pk_kt = 0, pk_nt = 0;
-  if (pk_on && !wide && (reinterpret_cast<uintptr_t>(d_sem) & 15) == 0) {       // (its fixed-point words are converted four at a time)
-    const int nnew = Ctot - K;
-    if (K <= 16 && nnew <= 8) { pk_kt = 16; pk_nt = 8; }
-    else if (K <= 20 && nnew <= 4) { pk_kt = 20; pk_nt = 4; }
-    else if (K <= 12 && nnew <= 12) { pk_kt = 12; pk_nt = 12; }
+  const size_t ncell = (size_t)ny * nx, budget = 150 * 1024;
+  int f = 0;
+  size_t lds = 0;
+  if (wide) {
+    const size_t CS = (Ctot + 3) & ~3, KS = has_teacher ? ((K + 3) & ~3) : 0;
+    lds = (ncell * (CS + KS) + 8) * sizeof(float) + (size_t)kRepWD * (((ncell * CS + 31) & ~(size_t)31) + 4) * 8;
+    // the fixed-point words are converted four at a time: a d_sem off the 16-byte grid gets fp32 atomics
+    f = d_sem_aligned ? UCD_SEG_WIDE_FIXED : UCD_SEG_WIDE_F32;
+  } else {
+    // few classes: the packed form with old / new classes in separate slot groups (UCD_SEG_PK=0: the round-3 register form, A/B)
+    static const int pk_env = getenv("UCD_SEG_PK") ? atoi(getenv("UCD_SEG_PK")) : 1;
+    const int pk_on = pk < 0 ? pk_env : pk;
+    const size_t lds_reg = (ncell * (17 * (size_t)Ctot + K) + 8) * sizeof(float);
+    const int reg_form = K <= 16 ? UCD_SEG_REG_24_16 : UCD_SEG_REG_24_24;
+    int kt = 0, nt = 0;
+    if (pk_on && d_sem_aligned) {                       // (its fixed-point words are converted four at a time)
+      const int nnew = Ctot - K;
+      if (K <= 16 && nnew <= 8) { kt = 16; nt = 8; f = UCD_SEG_PK_16_8; }
+      else if (K <= 20 && nnew <= 4) { kt = 20; nt = 4; f = UCD_SEG_PK_20_4; }
+      else if (K <= 12 && nnew <= 12) { kt = 12; nt = 12; f = UCD_SEG_PK_12_12; }
+    }
+    if (f) {
+      lds = (size_t)kRepPk * (((ncell * (kt + nt) + 31) & ~(size_t)31) + 1) * 8 + 8 + (ncell * ((kt + nt) + kt + 2) + 8) * sizeof(float) +
+            kRows * kThreads;
+      // the eight accumulator copies of the packed form do not fit (VOC at an up-sampling factor of 8: 10 x 10 cells): the register
+      // form where it does - its gradient then comes from fp32 atomics, as under UCD_SEG_PK=0
+      if (lds > budget && lds_reg <= budget) f = 0;
+      else if (lds > budget && lds_reg < lds) lds = lds_reg;      // neither fits: report the smaller request
+    }
+    if (!f) { f = reg_form; lds = lds_reg; }
   }
-  const size_t lds = wide ? ((size_t)ny * nx * (CS + KS) + 8) * sizeof(float) + (size_t)kRepWD * (((ny * nx * CS + 31) & ~31) + 4) * 8
-                   : pk_kt ? (size_t)kRepPk * (((ny * nx * (pk_kt + pk_nt) + 31) & ~31) + 1) * 8 + 8
-                                 + ((size_t)ny * nx * ((pk_kt + pk_nt) + pk_kt + 2) + 8) * sizeof(float) + kRows * kThreads
-                          : ((size_t)ny * nx * (17 * Ctot + K) + 8) * sizeof(float);
-  UCD_REQUIRE(lds <= 150 * 1024, UCD_EUNSUPPORTED, "%s: %d classes exceed the LDS budget", fn, Ctot);
+  UCD_REQUIRE(lds <= budget, UCD_EUNSUPPORTED,
+              "%s: up-sampling factors %.4g x %.4g put %d x %d low-resolution cells under a tile: %zu bytes of LDS for %d classes, "
+              "over the budget of %zu - no form of the kernel serves this factor", fn, fy, fx, ny, nx, lds, Ctot, budget);
+  if (form) *form = f;
+  if (ny_out) *ny_out = ny;
+  if (nx_out) *nx_out = nx;
+  if (lds_bytes) *lds_bytes = lds;
+  return 0;
+}
+
+int ucd_seg_losses(const float* sem_s, int ld_s, const float* sem_t, int ld_t, const int64_t* labels, int B, int H, int W,
+                   int h, int w, int Ctot, int K, int ignore_index, float ce_weight, float kd_weight, float* loss_out,
+                   float* d_sem, int ld_d, void* workspace, size_t workspace_bytes, ucd_stream_t stream) {
+  static const char* fn = "ucd_seg_losses";
+  UCD_REQUIRE(sem_s && labels && loss_out && d_sem && workspace, UCD_EINVAL, "%s: NULL argument", fn);
+  UCD_REQUIRE(B > 0 && H > 0 && W > 0 && h > 0 && w > 0 && Ctot > 0 && K >= 1 && K <= Ctot, UCD_EINVAL, "%s: bad sizes", fn);
+  UCD_REQUIRE(ld_s >= Ctot && ld_d >= Ctot && (!sem_t || ld_t >= K), UCD_EINVAL, "%s: bad leading dimension", fn);
+  int form = 0, ny = 0, nx = 0;
+  size_t lds = 0;
+  int rc = ucd_seg_losses_plan(H, W, h, w, Ctot, K, sem_t != nullptr, (reinterpret_cast<uintptr_t>(d_sem) & 15) == 0, -1, &form, &ny,
+                               &nx, &lds);
+  if (rc) return rc;
+  UCD_REQUIRE(workspace_bytes >= ucd_seg_losses_workspace_bytes(B, H, W), UCD_EWORKSPACE, "%s: workspace too small", fn);
+  hipStream_t s = (hipStream_t)stream;
+  const bool wide = form == UCD_SEG_WIDE_FIXED || form == UCD_SEG_WIDE_F32;
+  const bool packed = form == UCD_SEG_PK_16_8 || form == UCD_SEG_PK_20_4 || form == UCD_SEG_PK_12_12;
+  const int tiles_x = ceil_div(W, kTileX), tiles_y = ceil_div(H, wide ? 4 * kRW : kTileY);
   UCD_TRY_LDS((seg_losses_pk_kernel<16, 8>), 150 * 1024);
   UCD_TRY_LDS((seg_losses_pk_kernel<20, 4>), 150 * 1024);
   UCD_TRY_LDS((seg_losses_pk_kernel<12, 12>), 150 * 1024);
@@ -1003,20 +1142,20 @@ int ucd_seg_losses(const float* sem_s, int ld_s, const float* sem_t, int ld_t, c
   // fixed-point scale of the packed form's gradient words: one pixel's gradient is at most ce + 2 kd / K in magnitude
   const float fx_gmax = fabsf(ce_weight * inv_pix) + 2.f * fabsf(kd_weight * inv_pix) / (float)K;
   const float fx_scale = fx_gmax > 0.f ? 131072.f / fx_gmax : 1.f;
-  const bool fx_wide = wide && (reinterpret_cast<uintptr_t>(d_sem) & 15) == 0;
+  const bool fx_wide = form == UCD_SEG_WIDE_FIXED;
 #define UCD_SEG_PK_LAUNCH(KT_, NT_)                                                                                              \
   seg_losses_pk_kernel<KT_, NT_><<<dim3(tiles_x, tiles_y, B), kThreads, lds, s>>>(                                               \
       sem_s, ld_s, sem_t, ld_t, labels, H, W, h, w, Ctot, K, ignore_index, (float)h / (float)H, (float)w / (float)W,             \
       ce_weight * inv_pix, kd_weight * inv_pix, part, d_sem, ld_d, tiles_x, tiles_y, ny * nx, fx_scale)
-  if (pk_kt == 16) UCD_SEG_PK_LAUNCH(16, 8);
-  else if (pk_kt == 20) UCD_SEG_PK_LAUNCH(20, 4);
-  else if (pk_kt == 12) UCD_SEG_PK_LAUNCH(12, 12);
+  if (form == UCD_SEG_PK_16_8) UCD_SEG_PK_LAUNCH(16, 8);
+  else if (form == UCD_SEG_PK_20_4) UCD_SEG_PK_LAUNCH(20, 4);
+  else if (form == UCD_SEG_PK_12_12) UCD_SEG_PK_LAUNCH(12, 12);
 #undef UCD_SEG_PK_LAUNCH
-  else if (Ctot <= 24 && K <= 16)
+  else if (form == UCD_SEG_REG_24_16)
     seg_losses_kernel<24, 16><<<dim3(tiles_x, tiles_y, B), kThreads, lds, s>>>(
         sem_s, ld_s, sem_t, ld_t, labels, H, W, h, w, Ctot, K, ignore_index, (float)h / (float)H, (float)w / (float)W,
         ce_weight * inv_pix, kd_weight * inv_pix, part, d_sem, ld_d, tiles_x, tiles_y);
-  else if (Ctot <= 24)
+  else if (form == UCD_SEG_REG_24_24)
     seg_losses_kernel<24, 24><<<dim3(tiles_x, tiles_y, B), kThreads, lds, s>>>(
         sem_s, ld_s, sem_t, ld_t, labels, H, W, h, w, Ctot, K, ignore_index, (float)h / (float)H, (float)w / (float)W,
         ce_weight * inv_pix, kd_weight * inv_pix, part, d_sem, ld_d, tiles_x, tiles_y);
@@ -1024,9 +1163,9 @@ int ucd_seg_losses(const float* sem_s, int ld_s, const float* sem_t, int ld_t, c
     seg_losses_wide_kernel<<<dim3(tiles_x, tiles_y, B), kThreads, lds, s>>>(
         sem_s, ld_s, sem_t, ld_t, labels, H, W, h, w, Ctot, K, ignore_index, (float)h / (float)H, (float)w / (float)W,
         ce_weight * inv_pix, kd_weight * inv_pix, part, d_sem, ld_d, tiles_x, tiles_y, fx_wide ? fx_scale : 0.f);
-  int rc = check_launch(fn);
+  rc = check_launch(fn);
   if (rc) return rc;
-  if (pk_kt || fx_wide) {
+  if (packed || fx_wide) {
     const size_t n = (size_t)B * h * w * ld_d;
     seg_grad_unfix_kernel<<<(unsigned)((n / 4 + kThreads) / kThreads), kThreads, 0, s>>>(d_sem, n, 1.0 / (double)fx_scale);
     rc = check_launch(fn);
