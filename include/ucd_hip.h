@@ -293,6 +293,20 @@ size_t ucd_attmap_workspace_bytes(int B, int HW);
 int ucd_attmap(const void* x, int ld_x, void* y, int ld_y, int dtype, int B, int HW, int C,
                void* workspace, size_t workspace_bytes, ucd_stream_t stream);
 
+/* ILT's encoder distillation term (train.py:129 of the reference) on the RAW maps, the attention weighting of both included:
+ *   att(x) = a * x with a as in ucd_attmap (detached);   loss_out[0] = mean over B HW C of (a_s x_s - a_t x_t)^2;
+ *   d_x = weight * 2 a_s (a_s x_s - a_t x_t) / (B HW C)   in the input dtype (the gradient of weight * loss w.r.t. x_s).
+ * x_s / x_t / d_x are channels-last rows [B*HW, C] (dtype UCD_F32 or UCD_BF16, the same for all three) with leading dimensions
+ * in elements; base pointers and row pitches 16-byte aligned, C itself is free (a scalar tail follows the 16-byte vectors).
+ * Three launches: per-pixel sums of squares of both maps, per-image norms, one pass that reads both maps once, writes d_x and
+ * reduces the loss in a fixed order (per-workgroup partials in the workspace, added in index order by the workgroup that
+ * finishes last; no float atomics): same inputs, same bits.  HBM traffic: 2 reads of each map + 1 write.
+ * Errors (checked on the host before any device call): UCD_EINVAL (NULL x_s / x_t / loss_out / d_x, unknown dtype, B / HW / C
+ * below 1, a leading dimension below C), UCD_EALIGN, UCD_EWORKSPACE (NULL or short workspace). */
+size_t ucd_attn_mse_workspace_bytes(int B, int HW);
+int ucd_attn_mse(const void* x_s, int ld_s, const void* x_t, int ld_t, int dtype, int B, int HW, int C, float weight,
+                 float* loss_out, void* d_x, int ld_d, void* workspace, size_t workspace_bytes, ucd_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Uncertainty-weighted pixel-contrastive distillation.  Replaces pre_contractive_pixel
  * (utils/utils.py:256-393; twin utils/loss.py:258-395) and PixelConLossV2.forward
@@ -421,6 +435,8 @@ int ucd_pixcon_scatter_grad(const float* grad_a, const float* chat, int ldc, con
  * Gradient arithmetic.  The packed and the many-class form add every tile's contribution to a low-resolution cell as a 32-bit
  * FIXED-POINT word: integer addition has no order, so d_sem has the same bits on every run.  The quantum of a word is
  *   q = gmax / 2^17,  gmax = (|ce_weight| + 2 |kd_weight| / K) / (B H W)   (the largest gradient one pixel can contribute);
+ *   (gmax is the same in every mode of ucd_seg_losses_ex: the plain distillation's per-pixel gradient |softmax_K(z)_c - q_c| / K is
+ *   below |kd_weight| / (K B H W) per element, inside the 2 |kd_weight| / K that the unbiased form needs, and alpha only changes q)
  * a tile sums its pixels in fp64, rounds ONCE to the nearest word (error <= q / 2) and adds it; a cell receives one add from each
  * tile that touches it, at most n_tiles = (ceil(2 f_y / tile_y) + 1) (ceil(2 f_x / 64) + 1) for up-sampling factors f_y, f_x
  * (a cell's bilinear support is 2 f pixels wide).  The fixed-point error of an element is therefore at most (q / 2) n_tiles
@@ -457,6 +473,29 @@ int ucd_seg_losses(const float* sem_s, int ld_s, const float* sem_t, int ld_t, c
                    int B, int H, int W, int h, int w, int Ctot, int K, int ignore_index,
                    float ce_weight, float kd_weight, float* loss_out, float* d_sem, int ld_d,
                    void* workspace, size_t workspace_bytes, ucd_stream_t stream);
+
+/* The same kernels for the other loss pairs of the reference's --method table (LWF, ILT, MiB / UCD at --alpha != 1, mixed pairs).
+ * ucd_seg_losses is this call with ce_old_cl = K, kd_mode = UCD_KD_UNBIASED, alpha = 1 (same launch, same bits).
+ *   ce_old_cl  the cross entropy pools the classes [0, ce_old_cl) into the background and maps labels below it to 0
+ *              (utils/loss.py:96-109); 1 is plain nn.CrossEntropyLoss.  With a teacher it must be 1 or K; without one it is the only
+ *              class split of the call and K is not used beyond its range check.
+ *   kd_mode    UCD_KD_UNBIASED, or UCD_KD_PLAIN: KnowledgeDistillationLoss (utils/loss.py:118-136),
+ *                KD = mean over pixels of -sum_{c<K} softmax(alpha t)_c log_softmax(z[:K])_c / K
+ *              - the student's soft-max is over the first K classes only; dKD/dz_c = (softmax_K(z)_c - q_c) / (K B H W) for
+ *              c < K and zero for the new classes.
+ *   alpha      multiplies the teacher logits (utils/loss.py:122, :158) - applied to the staged low-resolution rows, bilinear
+ *              up-sampling being linear.  Finite and non-zero.
+ * Every form serves every legal combination; form, cells and LDS bytes do not depend on kd_mode or alpha (ucd_seg_losses_plan_ex
+ * answers as ucd_seg_losses_plan does for the split the kernels use: K with a teacher, ce_old_cl without).
+ * Additional UCD_EINVAL: kd_mode not one of the two, alpha zero / NaN / infinite, ce_old_cl outside [1, Ctot], ce_old_cl not in
+ * {1, K} with a teacher - checked on the host before any device call; the message names the argument. */
+enum ucd_seg_kd_mode { UCD_KD_UNBIASED = 0, UCD_KD_PLAIN = 1 };
+int ucd_seg_losses_plan_ex(int H, int W, int h, int w, int Ctot, int K, int ce_old_cl, int kd_mode, int has_teacher,
+                           int d_sem_aligned, int pk, int* form, int* ny, int* nx, size_t* lds_bytes);
+int ucd_seg_losses_ex(const float* sem_s, int ld_s, const float* sem_t, int ld_t, const int64_t* labels,
+                      int B, int H, int W, int h, int w, int Ctot, int K, int ce_old_cl, int kd_mode, float alpha,
+                      int ignore_index, float ce_weight, float kd_weight, float* loss_out, float* d_sem, int ld_d,
+                      void* workspace, size_t workspace_bytes, ucd_stream_t stream);
 
 /* Validation on the device: bilinear up-sampling of the low-resolution logits
  * (segmentation_module.py:133), arg-max over the classes (train.py:242 `outputs.max(dim=1)`) and the confusion matrix of

@@ -18,6 +18,8 @@
 // is not 16-byte aligned (last bits run-dependent).  The loss sums use a fixed order in every form.
 #include "common.h"
 
+#include <cmath>
+
 namespace ucd {
 namespace {
 
@@ -45,11 +47,14 @@ __host__ __device__ __forceinline__ void up_src(int dst, int in_size, float scal
 // CT > 0: Ctot <= CT and the per-class gradient of a thread's pixel column is accumulated in 2*CT registers
 // over consecutive rows that share the same low-res row pair (8x fewer LDS atomics); CT == 0: any Ctot,
 // four LDS atomics per pixel and class.
-template <int CT, int KT = CT>
+// EX (CT > 0 only; see seg_losses_pk_kernel): cross entropy pooled over [0, kce), kce == K or 1; teacher rows staged times alpha;
+// kd_plain: KD = -sum_{c<K} q_c (z_c - LSE_old) / K.  EX == false keeps the arithmetic the kernel had.
+template <int CT, int KT = CT, bool EX = false>
 __global__ __launch_bounds__(kThreads) void seg_losses_kernel(
     const float* __restrict__ sem_s, int ld_s, const float* __restrict__ sem_t, int ld_t, const int64_t* __restrict__ labels,
     int H, int W, int h, int w, int Ctot, int K, int ignore_index, float scale_h, float scale_w, float ce_scale,
-    float kd_scale, float* __restrict__ loss_part, float* __restrict__ d_sem, int ld_d, int tiles_x, int tiles_y) {
+    float kd_scale, float* __restrict__ loss_part, float* __restrict__ d_sem, int ld_d, int tiles_x, int tiles_y, int kce,
+    int kd_plain, float alpha) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int b = blockIdx.z, ty0 = blockIdx.y * kTileY, tx0 = blockIdx.x * kTileX;
   // low-res footprint of the tile
@@ -79,13 +84,15 @@ __global__ __launch_bounds__(kThreads) void seg_losses_kernel(
     for (int i = threadIdx.x; i < ncell * K; i += kThreads) {
       const int cell = i / K, c = i - cell * K;
       const int cy = ya + cell / nx, cx = xa + cell % nx;
-      t_log[i] = sem_t[((size_t)(b * h + cy) * w + cx) * ld_t + c];
+      const float tv = sem_t[((size_t)(b * h + cy) * w + cx) * ld_t + c];
+      t_log[i] = EX ? alpha * tv : tv;
     }
   __syncthreads();
 
   float ce_sum = 0.f, kd_sum = 0.f;
   const int X = tx0 + (threadIdx.x & 63);
   const float invK = K > 0 ? 1.f / (float)K : 0.f;
+  const bool plain = EX && kd_plain != 0, pool = !EX || kce == K;
   constexpr int CTA = CT > 0 ? CT : 1;
   float acc0[CTA], acc1[CTA];          // sum over rows of ly0*g / ly1*g for the current low-res row pair
   int cur_y0 = -1, cur_y1 = -1, x0 = 0, x1 = 0;
@@ -127,7 +134,7 @@ __global__ __launch_bounds__(kThreads) void seg_losses_kernel(
     const int64_t lab64 = labels[((size_t)b * H + Y) * W + X];
     const bool ignored = lab64 == ignore_index;
     int lab = ignored ? 0 : (int)lab64;
-    if (lab < K) lab = 0;                                    // loss.py:104-105
+    if (lab < (EX ? kce : K)) lab = 0;                       // loss.py:104-105
     if (CT > 0) {
       // Register form (Ctot <= CT, K <= KT).  Every interpolated logit is formed once; the class-set tests (c < K,
       // c == 0 || c >= K, 1 <= c < K) are wave-uniform 0 / 1 multipliers, classes past Ctot / K carry -1e30 (their
@@ -179,7 +186,8 @@ __global__ __launch_bounds__(kThreads) void seg_losses_kernel(
         r_o = 1.f / so; r_b = 1.f / sb;
         inv_old = 0.f; inv_bn = 0.f;                 // the subset terms of the gradient come from r_o / r_b below
       }
-      const float logp = lab == 0 ? lse_old - den : z_lab - den;
+      const bool lab0 = EX ? pool && lab == 0 : lab == 0;     // the label is the pooled background (plain CE: a one-hot like any)
+      const float logp = lab0 ? lse_old - den : z_lab - den;
       if (!ignored) ce_sum += -logp;
       const float inv_all = 1.f / s_all;
       // teacher soft-max
@@ -202,12 +210,12 @@ __global__ __launch_bounds__(kThreads) void seg_losses_kernel(
         }
         inv_st = 1.f / st;
         q0 = te[0] * inv_st;
-        kd_pix = q0 * (lse_bn - den);
+        kd_pix = plain ? q0 * (zc[0] - lse_old) : q0 * (lse_bn - den);
       }
       const float ce_w = ignored ? 0.f : ce_scale;
       const float kdw = kd_scale * invK;
-      const bool lab0 = lab == 0;
       const float q0bn = q0 * inv_bn;
+      const float kd_ref = plain ? lse_old : den;      // what the old classes' log-probabilities are taken against
 #pragma unroll
       for (int c = 0; c < CTA; ++c) {
         const float p = ec[c] * inv_all;
@@ -218,14 +226,21 @@ __global__ __launch_bounds__(kThreads) void seg_losses_kernel(
           float qc = 0.f;
           if (c >= 1 && c < KTA) {                      // compile-time; the 1 <= c < K test is the uniform multiplier
             qc = te[c] * (c < K ? inv_st : 0.f);
-            kd_pix = __builtin_fmaf(qc, zc[c] - den, kd_pix);
+            kd_pix = __builtin_fmaf(qc, zc[c] - kd_ref, kd_pix);
           }
-          const float bn = ec[c] * ((c == 0 || c >= K) ? q0bn : 0.f);
-          g = __builtin_fmaf(kdw, p - bn - qc, g);
+          if (EX && plain) {                            // soft-max over the old classes against q, the background included
+            if (c == 0) qc = q0;
+            g = __builtin_fmaf(kdw, t_old - qc, g);
+          } else {
+            const float bn = ec[c] * ((c == 0 || c >= K) ? q0bn : 0.f);
+            g = __builtin_fmaf(kdw, p - bn - qc, g);
+          }
         }
         if (rescue) {
           if (lab0 && c < K) g -= ce_w * r_o * __builtin_amdgcn_exp2f((zc[c] - m_o) * kL2e);
-          if (sem_t && (c == 0 || c >= K)) g -= kdw * q0 * r_b * __builtin_amdgcn_exp2f((zc[c] - m_b) * kL2e);
+          if (EX && plain) {
+            if (c < K) g += kdw * r_o * __builtin_amdgcn_exp2f((zc[c] - m_o) * kL2e);
+          } else if (sem_t && (c == 0 || c >= K)) g -= kdw * q0 * r_b * __builtin_amdgcn_exp2f((zc[c] - m_b) * kL2e);
         }
         acc0[c] = __builtin_fmaf(ly0, g, acc0[c]);
         acc1[c] = __builtin_fmaf(ly1, g, acc1[c]);
@@ -376,12 +391,18 @@ __device__ __forceinline__ f32x2 fma2(f32x2 a, f32x2 b, f32x2 c) { return __buil
 __device__ __forceinline__ f32x4 fma4(f32x4 a, f32x4 b, f32x4 c) { return __builtin_elementwise_fma(a, b, c); }
 __device__ __forceinline__ f32x2 exp2_2(f32x2 a) { return f32x2{__builtin_amdgcn_exp2f(a.x), __builtin_amdgcn_exp2f(a.y)}; }
 
-template <int KT, int NT>
+// EX (ucd_seg_losses_ex with a teacher and anything but unbiased KD / alpha 1 / ce_old_cl == K): the cross entropy pools the classes
+// [0, kce) with kce == K or 1 (1: plain cross entropy - the label, an OLD class included, is a one-hot in its own slot), the teacher
+// rows are staged times alpha, and kd_plain distils with the student's soft-max over the old slots only (utils/loss.py:118-136):
+//   KD = -sum_{c<K} q_c (z_c - LSE_old) / K,   dKD/dz_c = [c < K] (e_c / sum_old - q_c) / K.
+// All three are block-uniform; the sums it needs (old slots, all slots) are the ones the unbiased pair takes already.  EX == false
+// keeps the arithmetic the kernel had (the same operations in the same order: the same bits).
+template <int KT, int NT, bool EX = false>
 __global__ __launch_bounds__(kThreads) void seg_losses_pk_kernel(
     const float* __restrict__ sem_s, int ld_s, const float* __restrict__ sem_t, int ld_t, const int64_t* __restrict__ labels,
     int H, int W, int h, int w, int Ctot, int K, int ignore_index, float scale_h, float scale_w, float ce_scale,
     float kd_scale, float* __restrict__ loss_part, float* __restrict__ d_sem, int ld_d, int tiles_x, int tiles_y, int cell_cap,
-    float fx_scale) {
+    float fx_scale, int kce, int kd_plain, float alpha) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   constexpr int CT = KT + NT, NP = CT / 2, KP = KT / 2, kRep = kRepPk;
   // logit rows in LDS are CT + 1 / KT + 1 floats apart: the lanes of a wave read from ~5 cells, sixteen lanes the same address - a
@@ -436,13 +457,15 @@ __global__ __launch_bounds__(kThreads) void seg_losses_pk_kernel(
     for (int i = threadIdx.x; i < ncell * KT; i += kThreads) {
       const int cell = i / KT, c = i - cell * KT;
       const int cy = ya + cell / nx, cx = xa + cell % nx;
-      t_log[cell * KTS + c] = c < K ? sem_t[((size_t)(b * h + cy) * w + cx) * ld_t + c] : kNegBig;
+      const float tv = c < K ? sem_t[((size_t)(b * h + cy) * w + cx) * ld_t + c] : kNegBig;
+      t_log[cell * KTS + c] = (EX && c < K) ? alpha * tv : tv;       // up-sampling is linear: alpha * up(t) = up(alpha * t)
     }
   __syncthreads();
 
   float ce_sum = 0.f, kd_sum = 0.f;
   const int X = tx0 + (threadIdx.x & 63);
   const float invK = 1.f / (float)K;
+  const bool plain = EX && kd_plain != 0, pool = !EX || kce == K;
   const float kdw = sem_t ? kd_scale * invK : 0.f;
   f32x2 acc0[NP], acc1[NP];            // sum over rows of ly0 * g / ly1 * g for the current low-resolution row pair, by slot pair
   int cur_y0 = -1, cur_y1 = -1, x0 = 0, x1 = 0;
@@ -504,9 +527,10 @@ __global__ __launch_bounds__(kThreads) void seg_losses_pk_kernel(
     const int code = lab_s[it * kThreads + threadIdx.x];
     const bool ignored = code == 0xFF;
     int lab = ignored ? 0 : code;
-    if (lab < K) lab = 0;                                    // loss.py:104-105
-    const bool lab0 = lab == 0;
-    const int jlab = lab - K;                                // the label's new-class slot (negative: background / old / ignored)
+    if (lab < (EX ? kce : K)) lab = 0;                       // loss.py:104-105
+    const bool lab0 = EX ? pool && lab == 0 : lab == 0;      // the label is the pooled background (EX, plain CE: never - a one-hot)
+    // the label's new-class slot (negative: background / old / ignored); EX: its slot among ALL slots, -1 when pooled
+    const int jlab = EX ? (lab0 ? -1 : lab < K ? lab : KT + lab - K) : lab - K;
 
     // z = h0 u_y0 + h1 u_y1 is two packed instructions per slot pair: formed for the maximum, formed again for the exponentials
     // (and for the old classes' KD term) instead of living in 24 registers
@@ -527,10 +551,14 @@ __global__ __launch_bounds__(kThreads) void seg_losses_pk_kernel(
       e[p] = exp2_2(fma2(zz, L2E, MZL));
       if (p < KP) {
         so += e[p];
+        if (EX) {
+          z_lab = jlab == 2 * p ? zz.x : z_lab;
+          z_lab = jlab == 2 * p + 1 ? zz.y : z_lab;
+        }
       } else {
         sn += e[p];
-        z_lab = jlab == 2 * (p - KP) ? zz.x : z_lab;
-        z_lab = jlab == 2 * (p - KP) + 1 ? zz.y : z_lab;
+        z_lab = jlab == (EX ? 2 * p : 2 * (p - KP)) ? zz.x : z_lab;
+        z_lab = jlab == (EX ? 2 * p : 2 * (p - KP)) + 1 ? zz.y : z_lab;
       }
     }
     const float s_old = so.x + so.y, s_new = sn.x + sn.y;
@@ -584,9 +612,10 @@ __global__ __launch_bounds__(kThreads) void seg_losses_pk_kernel(
       }
       inv_st = 1.f / (st2.x + st2.y);
       q0 = te[0].x * inv_st;
-      kd_pix = q0 * (lse_bn - den);
+      // plain KD: every old class, the background included, against the log-sum-exp of the old slots
+      kd_pix = q0 * ((plain ? zpair(0).x : lse_bn) - (plain ? lse_old : den));
       // old classes 1 .. K-1: q_c (z_c - den); unused slots carry q = 0 against a finite z
-      const f32x2 IST = bc2(inv_st), DEN = bc2(den);
+      const f32x2 IST = bc2(inv_st), DEN = bc2(plain ? lse_old : den);
       f32x2 kd2 = f32x2{0.f, te[0].y * inv_st} * (zpair(0) - DEN);
 #pragma unroll
       for (int p = 1; p < KP; ++p) kd2 = fma2(te[p] * IST, zpair(p) - DEN, kd2);
@@ -597,28 +626,37 @@ __global__ __launch_bounds__(kThreads) void seg_losses_pk_kernel(
     }
     // g_c = e_c [(ce_w + kdw) / sum_all - [c old] ce_w [label bkg/old] / sum_old - [c bkg/new] kdw q_0 / sum_bn]
     //       - ce_w [label new][c == label] - kdw q_c [1 <= c < K]
-    const float A = (ce_w + kdw) * inv_all, Bo = lab0 ? ce_w * inv_old : 0.f, Bb = kdw * q0 * inv_bn;
+    // EX: plain KD moves kdw from the sum over all slots to the sum over the old ones, drops the background + new term and gives
+    // slot 0 its q_0 like any old class; a one-hot label may sit in an old slot
+    const float A = EX ? (ce_w + (plain ? 0.f : kdw)) * inv_all : (ce_w + kdw) * inv_all;
+    const float Bo = EX ? (lab0 ? ce_w * inv_old : 0.f) - (plain ? kdw * inv_old : 0.f) : (lab0 ? ce_w * inv_old : 0.f);
+    const float Bb = (EX && plain) ? 0.f : kdw * q0 * inv_bn;
     const float coef_old = A - Bo, coef_new = A - Bb, nkq = -kdw * inv_st;
     const f32x2 COLD = bc2(coef_old), CNEW = bc2(coef_new), NKQ = bc2(nkq);
+    const float hot_w = (EX && lab0) ? 0.f : ce_w;           // (EX == false: the tests on jlab alone decide)
+    const float rc_old = EX ? (lab0 ? ce_w * r_o : 0.f) - (plain ? kdw * r_o : 0.f) : (lab0 ? ce_w * r_o : 0.f);
+    const float rc_bn = (EX && plain) ? 0.f : kdw * q0 * r_b;
 #pragma unroll
     for (int p = 0; p < NP; ++p) {
       f32x2 g;
       if (p == 0) {
         g = e[0] * f32x2{coef_old - Bb, coef_old};
-        g = fma2(te[0], f32x2{0.f, nkq}, g);
+        g = fma2(te[0], f32x2{(EX && plain) ? nkq : 0.f, nkq}, g);
+        if (EX) g -= f32x2{jlab == 0 ? hot_w : 0.f, jlab == 1 ? hot_w : 0.f};
       } else if (p < KP) {
         g = fma2(te[p], NKQ, e[p] * COLD);
+        if (EX) g -= f32x2{jlab == 2 * p ? hot_w : 0.f, jlab == 2 * p + 1 ? hot_w : 0.f};
       } else {
-        const int j = 2 * (p - KP);
-        g = e[p] * CNEW - f32x2{jlab == j ? ce_w : 0.f, jlab == j + 1 ? ce_w : 0.f};
+        const int j = EX ? 2 * p : 2 * (p - KP);
+        g = e[p] * CNEW - f32x2{jlab == j ? hot_w : 0.f, jlab == j + 1 ? hot_w : 0.f};
       }
       if (rescue) {
         const f32x2 zz = zpair(p);
         if (p < KP) {
-          g -= bc2(lab0 ? ce_w * r_o : 0.f) * exp2_2(fma2(zz, L2E, bc2(-m_o * kL2e)));
-          if (p == 0) g.x -= kdw * q0 * r_b * __builtin_amdgcn_exp2f(__builtin_fmaf(zz.x, kL2e, -m_b * kL2e));
+          g -= bc2(rc_old) * exp2_2(fma2(zz, L2E, bc2(-m_o * kL2e)));
+          if (p == 0) g.x -= rc_bn * __builtin_amdgcn_exp2f(__builtin_fmaf(zz.x, kL2e, -m_b * kL2e));
         } else {
-          g -= bc2(kdw * q0 * r_b) * exp2_2(fma2(zz, L2E, bc2(-m_b * kL2e)));
+          g -= bc2(rc_bn) * exp2_2(fma2(zz, L2E, bc2(-m_b * kL2e)));
         }
       }
       acc0[p] = fma2(LY0p, g, acc0[p]);
@@ -682,10 +720,14 @@ __device__ __forceinline__ float4 interp4(const float* base, int o00, int o01, i
                      ly0 * (lx0 * a.z + lx1 * b.z) + ly1 * (lx0 * d.z + lx1 * e.z), ly0 * (lx0 * a.w + lx1 * b.w) + ly1 * (lx0 * d.w + lx1 * e.w));
 }
 
+// EX (see seg_losses_pk_kernel): cross entropy pooled over [0, kce), kce == K or 1; teacher rows staged times alpha; kd_plain:
+// KD = -sum_{c<K} q_c (z_c - LSE_old) / K - the row constants of phase A change, phase B only widens its teacher mask to class 0.
+template <bool EX>
 __global__ __launch_bounds__(kThreads) void seg_losses_wide_kernel(
     const float* __restrict__ sem_s, int ld_s, const float* __restrict__ sem_t, int ld_t, const int64_t* __restrict__ labels,
     int H, int W, int h, int w, int Ctot, int K, int ignore_index, float scale_h, float scale_w, float ce_scale,
-    float kd_scale, float* __restrict__ loss_part, float* __restrict__ d_sem, int ld_d, int tiles_x, int tiles_y, float fx_scale) {
+    float kd_scale, float* __restrict__ loss_part, float* __restrict__ d_sem, int ld_d, int tiles_x, int tiles_y, float fx_scale,
+    int kce, int kd_plain, float alpha) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   constexpr int kTY = 4 * kRW;
   constexpr float kL2e = 1.4426950408889634f, kLn2 = 0.6931471805599453f, kNegBig = -1e30f;
@@ -714,10 +756,13 @@ __global__ __launch_bounds__(kThreads) void seg_losses_wide_kernel(
   for (int i = threadIdx.x; i < ncell * KS; i += kThreads) {
     const int cell = i / KS, c = i - cell * KS;
     const int cy = ya + cell / nx, cx = xa + cell % nx;
-    t_log[i] = c < K ? sem_t[((size_t)(b * h + cy) * w + cx) * ld_t + c] : kNegBig;
+    const float tv = c < K ? sem_t[((size_t)(b * h + cy) * w + cx) * ld_t + c] : kNegBig;
+    t_log[i] = (EX && c < K) ? alpha * tv : tv;
   }
   __syncthreads();
 
+  const bool plain = EX && kd_plain != 0, pool = !EX || kce == K;
+  const int q_lo = plain ? 0 : 1;                 // first class whose teacher probability enters the per-class KD terms
   const int X = tx0 + (threadIdx.x & 63), Ybase = ty0 + (threadIdx.x >> 6) * kRW;
   const float invK = K > 0 ? 1.f / (float)K : 0.f;
   const float kdw = sem_t ? kd_scale * invK : 0.f;
@@ -745,7 +790,7 @@ __global__ __launch_bounds__(kThreads) void seg_losses_wide_kernel(
     const int64_t lab64 = labels[((size_t)b * H + Y) * W + X];
     const bool ignored = lab64 == ignore_index;
     int lab = ignored ? 0 : (int)lab64;
-    if (lab < K) lab = 0;                                    // loss.py:104-105
+    if (lab < (EX ? kce : K)) lab = 0;                       // loss.py:104-105
     float mz = kNegBig, mt = kNegBig;
     for (int c = 0; c < CS; c += 4) {
       const float4 v = interp4(s_log, s00, s01, s10, s11, c, lx0, lx1, ly0, ly1);
@@ -777,7 +822,7 @@ __global__ __launch_bounds__(kThreads) void seg_losses_wide_kernel(
           const float te = __builtin_amdgcn_exp2f(__builtin_fmaf(tv[j], kL2e, -mtl));   // 0 for the padding classes
           st += te;
           te0 = cc == 0 ? te : te0;
-          const float tq = (cc >= 1 && cc < K) ? te : 0.f;
+          const float tq = (cc >= (EX ? q_lo : 1) && cc < K) ? te : 0.f;
           T0 += tq;
           T1 = __builtin_fmaf(tq, v[j], T1);
         }
@@ -814,7 +859,7 @@ __global__ __launch_bounds__(kThreads) void seg_losses_wide_kernel(
       inv_old = 0.f; inv_bn = 0.f;                   // the subset terms of the gradient come from rco / rcb in phase B
       rescue_rows |= 1 << it;
     }
-    const bool lab0 = lab == 0;
+    const bool lab0 = EX ? pool && lab == 0 : lab == 0;      // the label is the pooled background (plain CE: a one-hot like any)
     const float logp = lab0 ? lse_old - den : z_lab - den;
     if (!ignored) ce_sum += -logp;
     const float ce_w = ignored ? 0.f : ce_scale;
@@ -822,17 +867,19 @@ __global__ __launch_bounds__(kThreads) void seg_losses_wide_kernel(
     if (sem_t) {
       inv_st = 1.f / st;
       q0 = te0 * inv_st;
-      const float kd_pix = q0 * (lse_bn - den) + inv_st * (T1 - den * T0);
+      // plain: T0 / T1 hold every old class, and the log-probabilities are relative to the old classes' log-sum-exp
+      const float kd_pix = plain ? inv_st * (T1 - lse_old * T0) : q0 * (lse_bn - den) + inv_st * (T1 - den * T0);
       kd_sum += -kd_pix * invK;
     }
     rmzl[it] = mzl;
-    ra_all[it] = (ce_w + kdw) / s_all;
-    ra_old[it] = lab0 ? ce_w * inv_old : 0.f;
+    ra_all[it] = (ce_w + (plain ? 0.f : kdw)) / s_all;
+    ra_old[it] = EX ? (lab0 ? ce_w * inv_old : 0.f) - (plain ? kdw * inv_old : 0.f) : (lab0 ? ce_w * inv_old : 0.f);
     rhot[it] = lab0 ? 0.f : ce_w;
     rlab[it] = lab;
-    rbbn[it] = kdw * q0 * inv_bn;
+    rbbn[it] = plain ? 0.f : kdw * q0 * inv_bn;
     rmo[it] = m_o; rmb[it] = m_b;
-    rco[it] = lab0 ? ce_w * r_o : 0.f; rcb[it] = kdw * q0 * r_b;
+    rco[it] = EX ? (lab0 ? ce_w * r_o : 0.f) - (plain ? kdw * r_o : 0.f) : (lab0 ? ce_w * r_o : 0.f);
+    rcb[it] = plain ? 0.f : kdw * q0 * r_b;
     rmtl[it] = mtl;
     rbq[it] = kdw * inv_st;
   }
@@ -890,7 +937,7 @@ __global__ __launch_bounds__(kThreads) void seg_losses_wide_kernel(
           float g = e * coef - (cc == rlab[it] ? rhot[it] : 0.f);
           if (c < KS) {
             const float te = __builtin_amdgcn_exp2f(__builtin_fmaf(tv[j], kL2e, -rmtl[it]));
-            g = __builtin_fmaf(-rbq[it], (cc >= 1 && cc < K) ? te : 0.f, g);
+            g = __builtin_fmaf(-rbq[it], (cc >= (EX ? q_lo : 1) && cc < K) ? te : 0.f, g);
           }
           if ((rescue_rows >> it) & 1) {
             if (cc < K) g -= rco[it] * __builtin_amdgcn_exp2f((v[j] - rmo[it]) * kL2e);
@@ -1111,61 +1158,94 @@ int ucd_seg_losses_plan(int H, int W, int h, int w, int Ctot, int K, int has_tea
   return 0;
 }
 
-int ucd_seg_losses(const float* sem_s, int ld_s, const float* sem_t, int ld_t, const int64_t* labels, int B, int H, int W,
-                   int h, int w, int Ctot, int K, int ignore_index, float ce_weight, float kd_weight, float* loss_out,
-                   float* d_sem, int ld_d, void* workspace, size_t workspace_bytes, ucd_stream_t stream) {
-  static const char* fn = "ucd_seg_losses";
+}  // extern "C"
+
+namespace {
+
+// the argument rules of ucd_seg_losses_ex / ucd_seg_losses_plan_ex that ucd_seg_losses cannot break (host only, before anything else)
+int seg_ex_check(const char* fn, int Ctot, int K, int ce_old_cl, int kd_mode, float alpha, int has_teacher) {
+  UCD_REQUIRE(Ctot > 0 && K >= 1 && K <= Ctot, UCD_EINVAL, "%s: bad sizes", fn);
+  UCD_REQUIRE(ce_old_cl >= 1 && ce_old_cl <= Ctot, UCD_EINVAL, "%s: ce_old_cl = %d is outside [1, Ctot = %d]", fn, ce_old_cl, Ctot);
+  UCD_REQUIRE(kd_mode == UCD_KD_UNBIASED || kd_mode == UCD_KD_PLAIN, UCD_EINVAL,
+              "%s: kd_mode = %d is neither UCD_KD_UNBIASED (0) nor UCD_KD_PLAIN (1)", fn, kd_mode);
+  UCD_REQUIRE(std::isfinite(alpha) && alpha != 0.f, UCD_EINVAL, "%s: alpha = %g must be finite and non-zero", fn, (double)alpha);
+  UCD_REQUIRE(!has_teacher || ce_old_cl == 1 || ce_old_cl == K, UCD_EINVAL,
+              "%s: with a teacher ce_old_cl = %d must be 1 (plain cross entropy) or K = %d", fn, ce_old_cl, K);
+  return 0;
+}
+
+// opt every instantiation of one EX value in to the LDS budget, launch the planned form
+template <bool EX>
+int seg_launch(const char* fn, int form, dim3 grid, size_t lds, hipStream_t s, const float* sem_s, int ld_s, const float* sem_t, int ld_t,
+               const int64_t* labels, int H, int W, int h, int w, int Ctot, int K, int ignore_index, float ce_scale, float kd_scale,
+               float* part, float* d_sem, int ld_d, int cells, float fx_scale, int ce_old_cl, int kd_plain, float alpha) {
+  UCD_TRY_LDS((seg_losses_pk_kernel<16, 8, EX>), 150 * 1024);
+  UCD_TRY_LDS((seg_losses_pk_kernel<20, 4, EX>), 150 * 1024);
+  UCD_TRY_LDS((seg_losses_pk_kernel<12, 12, EX>), 150 * 1024);
+  UCD_TRY_LDS((seg_losses_kernel<24, 16, EX>), 150 * 1024);
+  UCD_TRY_LDS((seg_losses_kernel<24, 24, EX>), 150 * 1024);
+  UCD_TRY_LDS(seg_losses_wide_kernel<EX>, 150 * 1024);
+  hipError_t e = hipMemsetAsync(d_sem, 0, (size_t)grid.z * h * w * ld_d * sizeof(float), s);
+  if (e != hipSuccess) { set_error("%s: %s", fn, hipGetErrorString(e)); return (int)e; }
+  const int tiles_x = grid.x, tiles_y = grid.y;
+  // torch computes the up-sampling scale as float(in) / out
+#define UCD_SEG_ARGS                                                                                                               \
+  sem_s, ld_s, sem_t, ld_t, labels, H, W, h, w, Ctot, K, ignore_index, (float)h / (float)H, (float)w / (float)W, ce_scale, kd_scale, part, \
+      d_sem, ld_d, tiles_x, tiles_y
+  if (form == UCD_SEG_PK_16_8)
+    seg_losses_pk_kernel<16, 8, EX><<<grid, kThreads, lds, s>>>(UCD_SEG_ARGS, cells, fx_scale, ce_old_cl, kd_plain, alpha);
+  else if (form == UCD_SEG_PK_20_4)
+    seg_losses_pk_kernel<20, 4, EX><<<grid, kThreads, lds, s>>>(UCD_SEG_ARGS, cells, fx_scale, ce_old_cl, kd_plain, alpha);
+  else if (form == UCD_SEG_PK_12_12)
+    seg_losses_pk_kernel<12, 12, EX><<<grid, kThreads, lds, s>>>(UCD_SEG_ARGS, cells, fx_scale, ce_old_cl, kd_plain, alpha);
+  else if (form == UCD_SEG_REG_24_16)
+    seg_losses_kernel<24, 16, EX><<<grid, kThreads, lds, s>>>(UCD_SEG_ARGS, ce_old_cl, kd_plain, alpha);
+  else if (form == UCD_SEG_REG_24_24)
+    seg_losses_kernel<24, 24, EX><<<grid, kThreads, lds, s>>>(UCD_SEG_ARGS, ce_old_cl, kd_plain, alpha);
+  else
+    seg_losses_wide_kernel<EX><<<grid, kThreads, lds, s>>>(UCD_SEG_ARGS, form == UCD_SEG_WIDE_FIXED ? fx_scale : 0.f, ce_old_cl, kd_plain,
+                                                           alpha);
+#undef UCD_SEG_ARGS
+  return check_launch(fn);
+}
+
+// ucd_seg_losses and ucd_seg_losses_ex: one body, the messages carry the name of the entry that was called
+int seg_losses_impl(const char* fn, const float* sem_s, int ld_s, const float* sem_t, int ld_t, const int64_t* labels, int B, int H, int W,
+                    int h, int w, int Ctot, int K, int ce_old_cl, int kd_mode, float alpha, int ignore_index, float ce_weight,
+                    float kd_weight, float* loss_out, float* d_sem, int ld_d, void* workspace, size_t workspace_bytes,
+                    ucd_stream_t stream) {
   UCD_REQUIRE(sem_s && labels && loss_out && d_sem && workspace, UCD_EINVAL, "%s: NULL argument", fn);
   UCD_REQUIRE(B > 0 && H > 0 && W > 0 && h > 0 && w > 0 && Ctot > 0 && K >= 1 && K <= Ctot, UCD_EINVAL, "%s: bad sizes", fn);
   UCD_REQUIRE(ld_s >= Ctot && ld_d >= Ctot && (!sem_t || ld_t >= K), UCD_EINVAL, "%s: bad leading dimension", fn);
+  int rc = seg_ex_check(fn, Ctot, K, ce_old_cl, kd_mode, alpha, sem_t != nullptr);
+  if (rc) return rc;
+  // without a teacher the only class split is the cross entropy's; with one, the kernels split at K and take ce_old_cl beside it
+  if (!sem_t) K = ce_old_cl;
+  const bool ex = sem_t && (kd_mode != UCD_KD_UNBIASED || alpha != 1.f || ce_old_cl != K);
+  const int kd_plain = kd_mode == UCD_KD_PLAIN;
   int form = 0, ny = 0, nx = 0;
   size_t lds = 0;
-  int rc = ucd_seg_losses_plan(H, W, h, w, Ctot, K, sem_t != nullptr, (reinterpret_cast<uintptr_t>(d_sem) & 15) == 0, -1, &form, &ny,
-                               &nx, &lds);
+  rc = ucd_seg_losses_plan(H, W, h, w, Ctot, K, sem_t != nullptr, (reinterpret_cast<uintptr_t>(d_sem) & 15) == 0, -1, &form, &ny,
+                           &nx, &lds);
   if (rc) return rc;
   UCD_REQUIRE(workspace_bytes >= ucd_seg_losses_workspace_bytes(B, H, W), UCD_EWORKSPACE, "%s: workspace too small", fn);
   hipStream_t s = (hipStream_t)stream;
   const bool wide = form == UCD_SEG_WIDE_FIXED || form == UCD_SEG_WIDE_F32;
   const bool packed = form == UCD_SEG_PK_16_8 || form == UCD_SEG_PK_20_4 || form == UCD_SEG_PK_12_12;
   const int tiles_x = ceil_div(W, kTileX), tiles_y = ceil_div(H, wide ? 4 * kRW : kTileY);
-  UCD_TRY_LDS((seg_losses_pk_kernel<16, 8>), 150 * 1024);
-  UCD_TRY_LDS((seg_losses_pk_kernel<20, 4>), 150 * 1024);
-  UCD_TRY_LDS((seg_losses_pk_kernel<12, 12>), 150 * 1024);
-  UCD_TRY_LDS((seg_losses_kernel<24, 16>), 150 * 1024);
-  UCD_TRY_LDS((seg_losses_kernel<24, 24>), 150 * 1024);
-  UCD_TRY_LDS(seg_losses_wide_kernel, 150 * 1024);
-  hipError_t e = hipMemsetAsync(d_sem, 0, (size_t)B * h * w * ld_d * sizeof(float), s);
-  if (e != hipSuccess) { set_error("%s: %s", fn, hipGetErrorString(e)); return (int)e; }
   const float inv_pix = 1.f / ((float)B * H * W);
   float* part = (float*)workspace;
-  // torch computes the up-sampling scale as float(in) / out
-  // fixed-point scale of the packed form's gradient words: one pixel's gradient is at most ce + 2 kd / K in magnitude
+  // fixed-point scale of the packed form's gradient words: one pixel's gradient is at most ce + 2 kd / K in magnitude (unbiased KD;
+  // the plain mode's |softmax_K - q| / K stays below kd / K, so the same quantum serves it - include/ucd_hip.h)
   const float fx_gmax = fabsf(ce_weight * inv_pix) + 2.f * fabsf(kd_weight * inv_pix) / (float)K;
   const float fx_scale = fx_gmax > 0.f ? 131072.f / fx_gmax : 1.f;
-  const bool fx_wide = form == UCD_SEG_WIDE_FIXED;
-#define UCD_SEG_PK_LAUNCH(KT_, NT_)                                                                                              \
-  seg_losses_pk_kernel<KT_, NT_><<<dim3(tiles_x, tiles_y, B), kThreads, lds, s>>>(                                               \
-      sem_s, ld_s, sem_t, ld_t, labels, H, W, h, w, Ctot, K, ignore_index, (float)h / (float)H, (float)w / (float)W,             \
-      ce_weight * inv_pix, kd_weight * inv_pix, part, d_sem, ld_d, tiles_x, tiles_y, ny * nx, fx_scale)
-  if (form == UCD_SEG_PK_16_8) UCD_SEG_PK_LAUNCH(16, 8);
-  else if (form == UCD_SEG_PK_20_4) UCD_SEG_PK_LAUNCH(20, 4);
-  else if (form == UCD_SEG_PK_12_12) UCD_SEG_PK_LAUNCH(12, 12);
-#undef UCD_SEG_PK_LAUNCH
-  else if (form == UCD_SEG_REG_24_16)
-    seg_losses_kernel<24, 16><<<dim3(tiles_x, tiles_y, B), kThreads, lds, s>>>(
-        sem_s, ld_s, sem_t, ld_t, labels, H, W, h, w, Ctot, K, ignore_index, (float)h / (float)H, (float)w / (float)W,
-        ce_weight * inv_pix, kd_weight * inv_pix, part, d_sem, ld_d, tiles_x, tiles_y);
-  else if (form == UCD_SEG_REG_24_24)
-    seg_losses_kernel<24, 24><<<dim3(tiles_x, tiles_y, B), kThreads, lds, s>>>(
-        sem_s, ld_s, sem_t, ld_t, labels, H, W, h, w, Ctot, K, ignore_index, (float)h / (float)H, (float)w / (float)W,
-        ce_weight * inv_pix, kd_weight * inv_pix, part, d_sem, ld_d, tiles_x, tiles_y);
-  else
-    seg_losses_wide_kernel<<<dim3(tiles_x, tiles_y, B), kThreads, lds, s>>>(
-        sem_s, ld_s, sem_t, ld_t, labels, H, W, h, w, Ctot, K, ignore_index, (float)h / (float)H, (float)w / (float)W,
-        ce_weight * inv_pix, kd_weight * inv_pix, part, d_sem, ld_d, tiles_x, tiles_y, fx_wide ? fx_scale : 0.f);
-  rc = check_launch(fn);
+  const dim3 grid(tiles_x, tiles_y, B);
+  rc = ex ? seg_launch<true>(fn, form, grid, lds, s, sem_s, ld_s, sem_t, ld_t, labels, H, W, h, w, Ctot, K, ignore_index,
+                             ce_weight * inv_pix, kd_weight * inv_pix, part, d_sem, ld_d, ny * nx, fx_scale, ce_old_cl, kd_plain, alpha)
+          : seg_launch<false>(fn, form, grid, lds, s, sem_s, ld_s, sem_t, ld_t, labels, H, W, h, w, Ctot, K, ignore_index,
+                              ce_weight * inv_pix, kd_weight * inv_pix, part, d_sem, ld_d, ny * nx, fx_scale, ce_old_cl, kd_plain, alpha);
   if (rc) return rc;
-  if (packed || fx_wide) {
+  if (packed || form == UCD_SEG_WIDE_FIXED) {
     const size_t n = (size_t)B * h * w * ld_d;
     seg_grad_unfix_kernel<<<(unsigned)((n / 4 + kThreads) / kThreads), kThreads, 0, s>>>(d_sem, n, 1.0 / (double)fx_scale);
     rc = check_launch(fn);
@@ -1173,6 +1253,34 @@ int ucd_seg_losses(const float* sem_s, int ld_s, const float* sem_t, int ld_t, c
   }
   seg_losses_reduce_kernel<<<1, 1024, 0, s>>>(part, B * tiles_x * tiles_y, inv_pix, loss_out);
   return check_launch(fn);
+}
+
+}  // namespace
+
+extern "C" {
+
+// The staged rows, the tiles and the accumulators are the same in every mode: kd_mode only has to be legal.  The class split that
+// picks the form is the teacher's K, or - without a teacher - the cross entropy's pooled count.
+int ucd_seg_losses_plan_ex(int H, int W, int h, int w, int Ctot, int K, int ce_old_cl, int kd_mode, int has_teacher, int d_sem_aligned,
+                           int pk, int* form, int* ny_out, int* nx_out, size_t* lds_bytes) {
+  int rc = seg_ex_check("ucd_seg_losses_plan_ex", Ctot, K, ce_old_cl, kd_mode, 1.f, has_teacher);
+  if (rc) return rc;
+  return ucd_seg_losses_plan(H, W, h, w, Ctot, has_teacher ? K : ce_old_cl, has_teacher, d_sem_aligned, pk, form, ny_out, nx_out, lds_bytes);
+}
+
+int ucd_seg_losses(const float* sem_s, int ld_s, const float* sem_t, int ld_t, const int64_t* labels, int B, int H, int W,
+                   int h, int w, int Ctot, int K, int ignore_index, float ce_weight, float kd_weight, float* loss_out,
+                   float* d_sem, int ld_d, void* workspace, size_t workspace_bytes, ucd_stream_t stream) {
+  return seg_losses_impl("ucd_seg_losses", sem_s, ld_s, sem_t, ld_t, labels, B, H, W, h, w, Ctot, K, K, UCD_KD_UNBIASED, 1.f,
+                         ignore_index, ce_weight, kd_weight, loss_out, d_sem, ld_d, workspace, workspace_bytes, stream);
+}
+
+int ucd_seg_losses_ex(const float* sem_s, int ld_s, const float* sem_t, int ld_t, const int64_t* labels, int B, int H, int W,
+                      int h, int w, int Ctot, int K, int ce_old_cl, int kd_mode, float alpha, int ignore_index, float ce_weight,
+                      float kd_weight, float* loss_out, float* d_sem, int ld_d, void* workspace, size_t workspace_bytes,
+                      ucd_stream_t stream) {
+  return seg_losses_impl("ucd_seg_losses_ex", sem_s, ld_s, sem_t, ld_t, labels, B, H, W, h, w, Ctot, K, ce_old_cl, kd_mode, alpha,
+                         ignore_index, ce_weight, kd_weight, loss_out, d_sem, ld_d, workspace, workspace_bytes, stream);
 }
 
 int ucd_seg_confusion(const float* sem, int ld_s, const int64_t* labels, int B, int H, int W, int h, int w, int Ctot,

@@ -22,6 +22,7 @@ NORM_ABS_GAMMA = 0x100   # flag bit of `act`: gamma~ = |weight| + eps (InPlaceAB
 PIX_TILE = 128          # kPixTile of csrc/pixcon.h
 PIXCON_LD = 256         # feature rows of the contrast matrix are padded to 256 columns
 PIXCON_F32, PIXCON_F16, PIXCON_F16_SPLIT = 0, 1, 2
+KD_UNBIASED, KD_PLAIN = 0, 1              # enum ucd_seg_kd_mode
 # enum ucd_seg_form (include/ucd_hip.h): the kernel ucd_seg_losses_plan names
 SEG_FORMS = {1: "pk<16,8>", 2: "pk<20,4>", 3: "pk<12,12>", 4: "reg<24,16>", 5: "reg<24,24>", 6: "wide/fixed", 7: "wide/f32"}
 PIXCON_PRECISION = {"f32": PIXCON_F32, "fp32": PIXCON_F32, "f16": PIXCON_F16, "fp16": PIXCON_F16,
@@ -108,6 +109,8 @@ SIGNATURES = {
     "ucd_window_mean": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _i, _p, _i, _p, _z, _p]),
     "ucd_attmap_workspace_bytes": (_z, [_i, _i]),
     "ucd_attmap": (_i, [_p, _i, _p, _i, _i, _i, _i, _i, _p, _z, _p]),
+    "ucd_attn_mse_workspace_bytes": (_z, [_i, _i]),
+    "ucd_attn_mse": (_i, [_p, _i, _p, _i, _i, _i, _i, _i, _f, _p, _p, _i, _p, _z, _p]),
     "ucd_conv1x1_row_tiles": (_i, [_i]),
     "ucd_conv1x1_stats_partial_bytes": (_z, [_i, _i]),
     "ucd_conv1x1": (_i, [C.POINTER(Conv1x1Desc), _p]),
@@ -155,6 +158,8 @@ SIGNATURES = {
     "ucd_seg_losses_workspace_bytes": (_z, [_i, _i, _i]),
     "ucd_seg_losses_plan": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p]),
     "ucd_seg_losses": (_i, [_p, _i, _p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _p, _p, _i, _p, _z, _p]),
+    "ucd_seg_losses_plan_ex": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p]),
+    "ucd_seg_losses_ex": (_i, [_p, _i, _p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _f, _f, _p, _p, _i, _p, _z, _p]),
 }
 
 _lib = None

@@ -1,10 +1,11 @@
 """Losses of the ``--method UCD`` step, reference interface (utils/loss.py).
 
-``UnbiasedCrossEntropy`` (utils/loss.py:89-109) and ``UnbiasedKnowledgeDistillationLoss``
-(utils/loss.py:139-184) keep the reference's module interface on full-resolution logits (the unfused path:
-``--alpha`` != 1, plain KD, tests).  The training step itself calls ``fused_seg_losses``: bilinear x16
-up-sampling + UnbiasedCE + UnbiasedKD + the gradient w.r.t. the LOW-resolution logits in one HIP kernel
-(``ucd_seg_losses``, csrc/seglogit_loss.hip) - the ``[B, Ctot, H, W]`` tensors never exist.
+``UnbiasedCrossEntropy`` (utils/loss.py:89-109), ``KnowledgeDistillationLoss`` (:112-136) and
+``UnbiasedKnowledgeDistillationLoss`` (:139-184) keep the reference's module interface on full-resolution logits
+(the unfused path: the CPU, ``UCD_SEG_KD_EX=0``, tests).  The training step itself calls ``fused_seg_losses``: bilinear
+x16 up-sampling + (unbiased or plain) CE + (unbiased or plain) KD at any ``--alpha`` + the gradient w.r.t. the
+LOW-resolution logits in one HIP kernel (``ucd_seg_losses`` / ``ucd_seg_losses_ex``, csrc/seglogit_loss.hip; SURVEY.md
+section 8-f1) - the ``[B, Ctot, H, W]`` tensors never exist.
 The contrastive loss lives in :mod:`ucd_amd.contrastive`.
 """
 from __future__ import annotations
@@ -18,11 +19,12 @@ from .contrastive import PixelConLossV2, pre_contractive_pixel, ucd_contrastive_
 
 
 class _FusedSegLosses(torch.autograd.Function):
-    """total = ce_weight * mean(UnbiasedCE) + kd_weight * mean(UnbiasedKD) from the LOW-resolution logits;
-    the up-sampled [B, Ctot, H, W] tensors never exist (ucd_seg_losses)."""
+    """total = ce_weight * mean(CE) + kd_weight * mean(KD) from the LOW-resolution logits; the up-sampled
+    [B, Ctot, H, W] tensors never exist (ucd_seg_losses / ucd_seg_losses_ex).
+    ``ce_old_cl`` is None for the call as it always was (one class count K for both losses, unbiased KD, alpha 1)."""
 
     @staticmethod
-    def forward(ctx, sem, sem_old, labels, old_cl, ce_weight, kd_weight, ignore_index):
+    def forward(ctx, sem, sem_old, labels, old_cl, ce_weight, kd_weight, ignore_index, ce_old_cl=None, kd_mode=0, alpha=1.0):
         lib = hip.load()
         B, Ctot, h, w = sem.shape
         H, W = labels.shape[-2:]
@@ -37,9 +39,15 @@ class _FusedSegLosses(torch.autograd.Function):
         nbytes = lib.ucd_seg_losses_workspace_bytes(B, H, W)
         ws = hip.workspace(nbytes, sem.device, "seglosses")
         with hip._timed("ucd_seg_losses", B * H * W * 8 + 2 * B * h * w * (2 * Ctot + K) * 4):
-            hip._check(lib.ucd_seg_losses(hip.ptr(s), Ctot, hip.ptr(t), K, hip.ptr(labels), B, H, W, h, w, Ctot, max(K, 1),
-                                          int(ignore_index), float(ce_weight), float(kd_weight), hip.ptr(out), hip.ptr(d),
-                                          Ctot, hip.ptr(ws), nbytes, hip.stream()), "ucd_seg_losses")
+            if ce_old_cl is None:
+                hip._check(lib.ucd_seg_losses(hip.ptr(s), Ctot, hip.ptr(t), K, hip.ptr(labels), B, H, W, h, w, Ctot, max(K, 1),
+                                              int(ignore_index), float(ce_weight), float(kd_weight), hip.ptr(out), hip.ptr(d),
+                                              Ctot, hip.ptr(ws), nbytes, hip.stream()), "ucd_seg_losses")
+            else:
+                hip._check(lib.ucd_seg_losses_ex(hip.ptr(s), Ctot, hip.ptr(t), K, hip.ptr(labels), B, H, W, h, w, Ctot, max(K, 1),
+                                                 int(ce_old_cl), int(kd_mode), float(alpha), int(ignore_index), float(ce_weight),
+                                                 float(kd_weight), hip.ptr(out), hip.ptr(d), Ctot, hip.ptr(ws), nbytes,
+                                                 hip.stream()), "ucd_seg_losses_ex")
         ctx.save_for_backward(d)
         ctx.meta = (B, Ctot, h, w, sem.dtype)
         ce, kd = out[0], out[1]
@@ -52,16 +60,72 @@ class _FusedSegLosses(torch.autograd.Function):
         (d,) = ctx.saved_tensors
         B, Ctot, h, w, dtype = ctx.meta
         grad = (d * g).view(B, h, w, Ctot).permute(0, 3, 1, 2).to(dtype)
-        return grad, None, None, None, None, None, None
+        return grad, None, None, None, None, None, None, None, None, None
 
 
-def fused_seg_losses(sem, sem_old, labels, old_cl, ce_weight=1.0, kd_weight=0.0, ignore_index=255):
+class _FusedAttnMSE(torch.autograd.Function):
+    """weight * MSE(att(x_s), att(x_t)) from the raw maps (ucd_attn_mse, csrc/featdist.hip); the attention factor of the
+    student is detached, as in the reference (segmentation_module.py:93)."""
+
+    @staticmethod
+    def forward(ctx, x_s, x_t, weight):
+        lib = hip.load()
+        xt = x_t.detach()
+        if xt.dtype != x_s.dtype:
+            xt = xt.to(x_s.dtype)
+        xs, M, C, HW, ld_s = hip.rows_view(x_s.detach())
+        xt, _, _, _, ld_t = hip.rows_view(xt)
+        B = x_s.shape[0]
+        d = hip.empty_like_rows(xs)
+        out = torch.empty(1, dtype=torch.float32, device=x_s.device)
+        nbytes = lib.ucd_attn_mse_workspace_bytes(B, HW)
+        ws = hip.workspace(nbytes, x_s.device, "attn_mse")
+        with hip._timed("ucd_attn_mse", 5 * M * C * xs.element_size()):
+            hip._check(lib.ucd_attn_mse(hip.ptr(xs), ld_s, hip.ptr(xt), ld_t, hip.dtype_code(xs), B, HW, C, float(weight), hip.ptr(out),
+                                        hip.ptr(d), C, hip.ptr(ws), nbytes, hip.stream()), "ucd_attn_mse")
+        ctx.save_for_backward(d)
+        return weight * out[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        (d,) = ctx.saved_tensors
+        return (d * g).to(d.dtype), None, None
+
+
+def fused_attn_mse(x_s_raw, x_t_raw, weight=1.0):
+    """``weight * nn.MSELoss()(att_map(x_s_raw), att_map(x_t_raw))`` (the reference's ``loss_de`` term for one pair of maps,
+    train.py:129) from the RAW [B, C, h, w] maps in one HIP operation; differentiable w.r.t. ``x_s_raw``."""
+    if not x_s_raw.is_cuda:
+        raise RuntimeError("ucd_amd.loss.fused_attn_mse runs on the GPU only (there is no CPU fallback)")
+    if x_s_raw.shape != x_t_raw.shape:
+        raise ValueError(f"student and teacher maps differ in shape: {tuple(x_s_raw.shape)} vs {tuple(x_t_raw.shape)}")
+    return _FusedAttnMSE.apply(x_s_raw, x_t_raw, weight)
+
+
+KD_MODES = {"unbiased": hip.KD_UNBIASED, "plain": hip.KD_PLAIN}
+
+
+def fused_seg_losses(sem, sem_old, labels, old_cl, ce_weight=1.0, kd_weight=0.0, ignore_index=255, *, kd="unbiased", alpha=1.0):
     """Returns (ce_weight*CE + kd_weight*KD [differentiable w.r.t. ``sem``], CE, KD) where CE / KD are the
-    reference's ``UnbiasedCrossEntropy(...)(up(sem), labels).mean()`` and
-    ``UnbiasedKnowledgeDistillationLoss()(up(sem), up(sem_old))`` (``up`` = bilinear to the label size)."""
+    reference's ``UnbiasedCrossEntropy(old_cl)(up(sem), labels).mean()`` (``old_cl`` 1: ``nn.CrossEntropyLoss``) and
+    ``UnbiasedKnowledgeDistillationLoss(alpha=alpha)(up(sem), up(sem_old))`` or, with ``kd="plain"``,
+    ``KnowledgeDistillationLoss(alpha=alpha)(...)`` (``up`` = bilinear to the label size).
+
+    With a teacher of K classes ``old_cl`` is 1 or K (the reference produces no other pair; the kernel refuses one)."""
     if not sem.is_cuda:
         raise RuntimeError("ucd_amd.loss.fused_seg_losses runs on the GPU only (there is no CPU fallback)")
-    return _FusedSegLosses.apply(sem, sem_old, labels, old_cl, ce_weight, kd_weight, ignore_index)
+    if kd not in KD_MODES:
+        raise ValueError(f"kd must be 'unbiased' or 'plain', not {kd!r}")
+    if kd == "unbiased" and float(alpha) == 1.0 and (sem_old is None or int(old_cl) == sem_old.shape[1]):
+        # the pair the kernel was built for: the call, and the bits, of every build so far
+        return _FusedSegLosses.apply(sem, sem_old, labels, old_cl, ce_weight, kd_weight, ignore_index)
+    return _FusedSegLosses.apply(sem, sem_old, labels, old_cl, ce_weight, kd_weight, ignore_index, int(old_cl), KD_MODES[kd],
+                                 float(alpha))
+
+
+def _wide(x):
+    """fp32 arithmetic for half-precision logits; fp32 and fp64 inputs keep their type (the float64 references of the tests)."""
+    return x if x.dtype in (torch.float32, torch.float64) else x.float()
 
 
 class UnbiasedCrossEntropy(nn.Module):
@@ -74,7 +138,7 @@ class UnbiasedCrossEntropy(nn.Module):
 
     def forward(self, inputs, targets):
         old_cl = self.old_cl
-        inputs = inputs.float()
+        inputs = _wide(inputs)
         den = torch.logsumexp(inputs, dim=1)
         log_bkg = torch.logsumexp(inputs[:, :old_cl], dim=1) - den
         # gather instead of materialising the [B, Ctot, H, W] log-probability tensor (loss.py:99-102)
@@ -99,8 +163,8 @@ class KnowledgeDistillationLoss(nn.Module):
         self.reduction, self.alpha = reduction, alpha
 
     def forward(self, inputs, targets, mask=None):
-        inputs = inputs.narrow(1, 0, targets.shape[1]).float()
-        loss = (torch.log_softmax(inputs, dim=1) * torch.softmax(targets.float() * self.alpha, dim=1)).mean(dim=1)
+        inputs = _wide(inputs.narrow(1, 0, targets.shape[1]))
+        loss = (torch.log_softmax(inputs, dim=1) * torch.softmax(_wide(targets) * self.alpha, dim=1)).mean(dim=1)
         if mask is not None:
             loss = loss * mask.float()
         if self.reduction == "mean":
@@ -121,7 +185,7 @@ class UnbiasedKnowledgeDistillationLoss(nn.Module):
 
     def forward(self, inputs, targets, mask=None):
         K = targets.shape[1]
-        inputs, targets = inputs.float(), targets.float() * self.alpha
+        inputs, targets = _wide(inputs), _wide(targets) * self.alpha
         den = torch.logsumexp(inputs, dim=1)
         out_old = inputs[:, 1:K] - den.unsqueeze(1)
         # LSE over {background} U {new classes}: index_select-free

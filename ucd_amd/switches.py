@@ -34,6 +34,8 @@ DEFAULTS = {
     "UCD_CONV3_MIN_ROWS": "0",     # stand-alone 3x3 layers (ASPP) below this many rows stay on the library path (round 6: 0 - the own kernels win at 3 / 6 images too: 9.33 -> 9.03 / 12.46 -> 11.97 ms)
     "UCD_STAT_ATOMIC": "1",        # conv + ABN nodes: statistics / link sums by fp32 atomics into arena slots, finalised by the apply passes (0: per-tile rows + reduction launches, bit-reproducible)
     "UCD_SEG_PK": "1",             # fused logit losses: packed math, fp64 LDS accumulators (0: the round-3 register form; read by the library)
+    "UCD_SEG_KD_EX": "1",          # fused logit losses for every pair of {plain, unbiased} CE x {none, plain, unbiased} KD and any --alpha (ucd_seg_losses_ex); 0: only (any CE) or (unbiased CE + unbiased KD at alpha 1) fused, the rest on the torch modules
+    "UCD_FUSED_LDE": "1",          # ILT's encoder term (--loss_de) as one HIP operation on the raw maps (ucd_attn_mse), ILT inside the teacher / whole-step graphs; 0: attention maps + MSELoss in torch, ILT eager
     "UCD_STEM_EVAL_FUSED": "1",    # frozen-statistics stem (the teacher): conv1 + norm + activation + max pool as one kernel (0: two kernels)
     "UCD_STEM_FOLD": "1",          # stem norm + max-pool as one pass
     "UCD_ABN_NODE": "1",           # C++ autograd nodes

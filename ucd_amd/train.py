@@ -16,11 +16,15 @@ What changed for the hardware: activations are channels-last bf16 (``--opt_level
 the contrastive term is one fused HIP operation with no host round trip; the per-iteration ``.item()``
 reads (train.py:153-157, >= 5 device syncs) are replaced by device-side accumulators read once per
 ``print_int`` iterations; gradient averaging overlaps the backward (ucd_amd.ddp).
+The logit losses - (unbiased or plain) CE with no, the plain or the unbiased KD at any ``--alpha``: FT, LWF, ILT, MiB, UCD -
+come from one fused HIP kernel on the low-resolution logits (``UCD_SEG_KD_EX=0``: only the pairs without ``--alpha`` / plain
+KD); ILT's encoder term is one HIP operation on the raw maps (``UCD_FUSED_LDE=0``: torch), which puts ILT inside the graphs.
 EWC / PI / RW (``--method EWC|PI|RW``) add the weight-space penalty of ucd_amd.regularizer between the gradient
 all-reduce and the optimiser (train.py:139-145).  Out of scope on this path (raise ``NotImplementedError``): BCE/iCaRL.
 """
 from __future__ import annotations
 
+import math
 from functools import reduce
 
 import torch
@@ -30,7 +34,7 @@ import torch.nn as nn
 from . import switches as _switches
 from .contrastive import ucd_contrastive_loss
 from .loss import (KnowledgeDistillationLoss, UnbiasedCrossEntropy, UnbiasedKnowledgeDistillationLoss,
-                   fused_seg_losses)
+                   fused_attn_mse, fused_seg_losses)
 
 
 def _raw(features, name):
@@ -61,6 +65,8 @@ class Trainer:
         self.lde = opts.loss_de
         self.lde_flag = self.lde > 0. and model_old is not None
         self.lde_loss = nn.MSELoss()
+        # the encoder term from the raw maps in one HIP operation (UCD_FUSED_LDE=0: attention maps + MSELoss in torch)
+        self.fused_lde = self.lde_flag and device.type == "cuda" and _switches.get("UCD_FUSED_LDE", "1") != "0"
         self.lkd = opts.loss_kd
         self.lkd_flag = self.lkd > 0. and model_old is not None
         self.lkd_loss = (UnbiasedKnowledgeDistillationLoss if opts.unkd else KnowledgeDistillationLoss)(alpha=opts.alpha)
@@ -77,11 +83,18 @@ class Trainer:
         self._side = torch.cuda.Stream(device) if self.overlap_teacher else None
         self.ret_intermediate = self.lde
         self.unce = bool(opts.unce and self.old_classes != 0)
-        # fused up-sampling + CE + KD kernel whenever the loss pair is one it implements:
-        # (unbiased or plain) CE, optionally with the unbiased KD
-        # (the kernel has no --alpha: utils/loss.py:158 scales the teacher logits by it, so alpha != 1 takes the unfused path)
+        # fused up-sampling + CE + KD kernel: every pair of (unbiased or plain) CE with no, the plain or the
+        # unbiased KD, at any finite non-zero --alpha (LWF, ILT, MiB, UCD).  UCD_SEG_KD_EX=0: only the pairs of the first
+        # kernel - no KD, or unbiased CE + unbiased KD at alpha 1 - and the torch modules on up-sampled logits for the rest
+        self.kd_mode = "unbiased" if opts.unkd else "plain"
+        self.alpha = float(opts.alpha)
+        first_pair = bool(opts.unkd) and self.unce and self.alpha == 1.0
+        any_pair = _switches.get("UCD_SEG_KD_EX", "1") != "0" and math.isfinite(self.alpha) and self.alpha != 0.0
         self.fuse_logit_losses = (getattr(opts, "fused_logit_losses", True) and device.type == "cuda"
-                                  and (not self.lkd_flag or (opts.unkd and self.unce and float(opts.alpha) == 1.0)))
+                                  and (not self.lkd_flag or first_pair or any_pair))
+        # an ILT iteration reads the lazy attention maps of the Features dict unless both of its losses are fused: such a run stays
+        # outside the teacher graph and the whole-step graph
+        self.lde_lazy = self.lde_flag and not (self.fused_lde and self.fuse_logit_losses)
         self.amp = getattr(opts, "opt_level", "O0") != "O0"
         # contrastive arithmetic: exact fp32 MFMA with fp32 activations (O0), fp16 operands otherwise
         self.pixcon_precision = getattr(opts, "pixcon_precision", None) or ("f16" if self.amp else "f32")
@@ -108,7 +121,7 @@ class Trainer:
         sw = _switches.get("UCD_STEP_GRAPH", "auto")
         world = dist.get_world_size() if (dist.is_available() and dist.is_initialized()) else 1
         self.step_graph = (device.type == "cuda" and bool(getattr(opts, "step_graph", True)) and sw != "0"
-                           and (world == 1 or sw == "1") and not self.lde_flag)
+                           and (world == 1 or sw == "1") and not self.lde_lazy)
         self.step_graph_warmup = 3          # eager iterations before the capture (solver search, GEMM tuning, optimiser tables)
         self._sg = None
         self._sg_seen = 0
@@ -121,7 +134,7 @@ class Trainer:
         ucd_amd.comm.direct_comm of the default group; the gradient buckets: GradReducer.enable_direct) and every rank must agree -
         otherwise the run stays eager.  Collective: every rank calls it at the same point.  Returns True when the next iterations
         will be captured."""
-        if self.device.type != "cuda" or _switches.get("UCD_STEP_GRAPH", "auto") == "0" or self.lde_flag:
+        if self.device.type != "cuda" or _switches.get("UCD_STEP_GRAPH", "auto") == "0" or self.lde_lazy:
             return False
         ok = True
         if dist.is_available() and dist.is_initialized():
@@ -148,7 +161,7 @@ class Trainer:
         """(outputs_old, features_old); replayed from a captured graph when enabled and the input shape is stable."""
         if self._teacher_w16 is not None:
             self._teacher_w16.refresh_if_stale()
-        if not self.graph_teacher or self.lde_flag or torch.cuda.is_current_stream_capturing():
+        if not self.graph_teacher or self.lde_lazy or torch.cuda.is_current_stream_capturing():
             return self._teacher_eager(images, up)          # (inside a whole-step capture the teacher is part of that graph)
         tg = self._tg
         if tg is not None and tg["shape"] == tuple(images.shape) and tg["up"] == bool(up):
@@ -293,7 +306,9 @@ class Trainer:
             # one pass over the label map: bilinear up-sampling + CE (+ KD) + gradient w.r.t. the low-res logits
             total, ce, kd = fused_seg_losses(features["sem"], features_old["sem"] if self.lkd_flag else None, labels,
                                              self.old_classes if self.unce else 1, 1.0,
-                                             self.lkd if self.lkd_flag else 0.0)
+                                             self.lkd if self.lkd_flag else 0.0,
+                                             kd=self.kd_mode if self.lkd_flag else "unbiased",
+                                             alpha=self.alpha if self.lkd_flag else 1.0)
         else:
             ce = self.criterion(outputs.float() if outputs.dtype != torch.float32 else outputs, labels).mean()
         con = zero
@@ -303,8 +318,12 @@ class Trainer:
                                        self.pixcon_precision)
         loss = ce + con * self.pixcon_weight                                      # train.py:116 (/100)
         if self.lde_flag:
-            lde = self.lde * (self.lde_loss(features["body"].float(), features_old["body"].float())
-                              + self.lde_loss(features["pre_logits"].float(), features_old["pre_logits"].float()))
+            if self.fused_lde:
+                lde = (fused_attn_mse(_raw(features, "body"), _raw(features_old, "body"), self.lde)
+                       + fused_attn_mse(_raw(features, "pre_logits"), _raw(features_old, "pre_logits"), self.lde))
+            else:
+                lde = self.lde * (self.lde_loss(features["body"].float(), features_old["body"].float())
+                                  + self.lde_loss(features["pre_logits"].float(), features_old["pre_logits"].float()))
         if self.lkd_flag:
             lkd = self.lkd * (kd if fuse else self.lkd_loss(outputs, outputs_old))   # train.py:131-133
         loss_tot = (total + con * self.pixcon_weight + lde) if fuse else (loss + lkd + lde)
