@@ -370,7 +370,34 @@ int ucd_pixcon_gather(const void* f_n, int ld_n, const void* f_o, int ld_o, int 
                       void* p16 /* fp16 [Cpad, 2, K rounded up to 16]: hi | lo split of pcat, or NULL */,
                       float* inv_norm, ucd_stream_t stream);
 
+/* Enough for every path a call of this size can take (any precision, temperature and K): >= the workspace_bytes that
+ * ucd_pixcon_loss_plan reports for it. */
 size_t ucd_pixcon_loss_workspace_bytes(int BHW, int N, int K);
+
+/* Which kernels serve a ucd_pixcon_loss call, and with what launch.  Touches no device (it answers on a machine without a
+ * GPU); ucd_pixcon_loss takes its launch parameters from the same function.  For BHW pixels, K teacher classes, a
+ * precision, use_prob and the temperature it returns the code ucd_pixcon_loss would return for these arguments and, on 0:
+ *   path            enum ucd_pixcon_path
+ *                   F32       K <= 110 (or use_prob == 0): the anchor block's probability rows are staged in LDS;
+ *                   F32_WIDE  110 < K <= 255: they are read from pcat in global memory inside the class loop (same order of
+ *                             the MFMA accumulation), so that the LDS holds two contrast tiles' rows only;
+ *                   F16_PLANNED  UCD_PIXCON_F16 with T >= 0.06, at most 32 classes and fewer than 1024 anchor blocks;
+ *                   F16_SPLIT    every other fp16 call, K <= 255
+ *   class_chunk     classes per staged piece of the probability product; 0: no path chunks the classes
+ *   nsplit1/2       grid.y of the negatives / positives sweep (grid.x = ceil(BHW / 128)); 0 for F16_PLANNED, whose persistent
+ *                   grid is the device's CU count
+ *   lds_sweep1/2    bytes of dynamic LDS of the two sweeps (at most 160 KiB)
+ *   workspace_bytes what the path lays out in the workspace
+ * Output pointers may be NULL.  Errors: UCD_EINVAL (BHW < 1, temperature <= 0, unknown precision, K < 0, K < 1 with use_prob),
+ * UCD_EUNSUPPORTED (K > 255: row labels are bytes and 255 marks padding rows); the message states the bound. */
+enum ucd_pixcon_path {
+  UCD_PIXCON_PATH_F32 = 1,
+  UCD_PIXCON_PATH_F32_WIDE = 2,
+  UCD_PIXCON_PATH_F16_PLANNED = 3,
+  UCD_PIXCON_PATH_F16_SPLIT = 4
+};
+int ucd_pixcon_loss_plan(int BHW, int K, int precision, int use_prob, float temperature, int* path, int* class_chunk,
+                         int* nsplit1, int* nsplit2, size_t* lds_sweep1, size_t* lds_sweep2, size_t* workspace_bytes);
 
 /* Loss and its gradient w.r.t. the normalised anchors in one launch sequence (utils/loss.py:435-466):
  *   S_ij = a_i . c_j / T;  neg_i = sum_j [la_i != lc_j] exp(S_ij)                     (un-shifted)
@@ -385,7 +412,8 @@ size_t ucd_pixcon_loss_workspace_bytes(int BHW, int N, int K);
  * precision = UCD_PIXCON_F32: exact float32 MFMA (v_mfma_f32_32x32x2_f32) on chat / pcat - the parity
  * mode; UCD_PIXCON_F16: fp16 operands ch16 / p16 (from ucd_pixcon_gather), fp32 accumulation
  * (v_mfma_f32_32x32x16_f16, 16x the rate) with an online rescale of the negative sums - the
- * performance mode; loss within ~1e-4, gradients within ~1e-3 of the float32 path. */
+ * performance mode; loss within ~1e-4, gradients within ~1e-3 of the float32 path.
+ * 1 <= K <= 255 with use_prob in every precision (ucd_pixcon_loss_plan names the kernels and their LDS). */
 int ucd_pixcon_loss(const float* chat, int ldc, int N, const uint8_t* row_label,
                     const float* pcat, int ldp, int K, const void* ch16, const void* p16, int precision,
                     const ucd_pixcon_meta* meta, int BHW,

@@ -239,7 +239,9 @@ def pre_contractive_pixel(f_n, l_n, l_po=None, f_o=None, max_label=20, materiali
         pa = pb.pcat[:A, :pb.K]
         pc = torch.cat((pa, pb.pcat[Apad:Apad + Co, :pb.K]), dim=0)
         P = pa @ pc.T
-        gt_a, gt_c = la >= m.min_new, lc >= m.min_new
+        # on the byte labels: the int8 copies returned to the caller wrap 128 .. 254 to negatives
+        lc_u = torch.cat((pb.row_label[:A], pb.row_label[Apad:Apad + Co]))
+        gt_a, gt_c = pb.row_label[:A] >= m.min_new, lc_u >= m.min_new
         P = torch.where(gt_a[:, None] & gt_c[None, :], torch.ones_like(P), P)
     out = PixconTuple((a, c, la, lc, P))
     out.batch = pb
@@ -266,7 +268,7 @@ def _meta_from_labels(A, Co, la, lc):
     tile = hip.PIX_TILE
     Apad = (A + tile - 1) // tile * tile
     Cpad = (Apad + Co + tile - 1) // tile * tile
-    la64, lc64 = la.long(), lc.long()
+    la64, lc64 = la.long() & 0xFF, lc.long() & 0xFF          # int8 labels like the reference's: 128 .. 254 arrive negative
     count_a = torch.bincount(la64, minlength=256)[:256]
     count_c = torch.bincount(lc64, minlength=256)[:256]
     n_valid = (count_c[la64] > 1).sum().reshape(1)

@@ -203,6 +203,10 @@ __global__ __launch_bounds__(kThreads, 1) void pixcon_neg_kernel(const float* __
 }
 
 // ---- sweep 2: positives ----------------------------------------------------------------------------
+// PA_LDS: the anchor block's probability rows are staged in LDS once (K <= kMaxKAnchorLds).  Without it every lane reads
+// its own anchor's row from pcat in global memory inside the class loop (same k order, same MFMA sequence, so the same
+// bits for the same operands); the LDS then holds the two contrast tiles' rows only, which fits every K <= 255.
+template <bool PA_LDS>
 __global__ __launch_bounds__(kThreads, 1) void pixcon_pos_kernel(
     const float* __restrict__ chat, int ldc, const uint8_t* __restrict__ row_label, const float* __restrict__ pcat, int ldp,
     int KP2, const ucd_pixcon_meta* __restrict__ meta, float inv_T, int shift_pos, int use_prob, int nsplit1, int nsplit2,
@@ -215,7 +219,7 @@ __global__ __launch_bounds__(kThreads, 1) void pixcon_pos_kernel(
   float* cs0 = smem;                                             // [2][32][kPitch]
   int* labs0 = reinterpret_cast<int*>(smem + 2 * kTJ * kPitch);  // [2][32]
   float* ps0 = smem + 2 * kTJ * kPitch + 2 * kTJ;                // [2][32][ppitch]  contrast probabilities
-  float* pa0 = ps0 + 2 * kTJ * ppitch;                           // [4][32][ppitch]  anchor probabilities
+  float* pa0 = ps0 + 2 * kTJ * ppitch;                           // [4][32][ppitch]  anchor probabilities (PA_LDS only)
   const int A = meta->A, Apad = meta->Apad, Cpad = meta->Cpad, min_new = meta->min_new;
   const int i_base = blockIdx.x * kBI;
   if (i_base >= A) return;
@@ -253,7 +257,7 @@ __global__ __launch_bounds__(kThreads, 1) void pixcon_pos_kernel(
 
   float areg[128];
   load_anchor_frags(areg, chat, ldc, i_row, row_ok, half);
-  if (use_prob) {
+  if (PA_LDS && use_prob) {
     float* pa = pa0 + (wave * kTI + (lane & 31)) * ppitch;
     for (int k = half; k < KP2; k += 2) pa[k] = row_ok ? pcat[(size_t)i_row * ldp + k] : 0.f;
   }
@@ -297,8 +301,15 @@ __global__ __launch_bounds__(kThreads, 1) void pixcon_pos_kernel(
 #pragma unroll
         for (int r = 0; r < 16; ++r) pm[r] = 0.f;
         const float* pc = ps0 + (cur * kTJ + (lane & 31)) * ppitch + half;
-        const float* pa = pa0 + (wave * kTI + (lane & 31)) * ppitch + half;
-        for (int k = 0; k < KP2; k += 2) pm = __builtin_amdgcn_mfma_f32_32x32x2f32(pc[k], pa[k], pm, 0, 0, 0);
+        if (PA_LDS) {
+          const float* pa = pa0 + (wave * kTI + (lane & 31)) * ppitch + half;
+          for (int k = 0; k < KP2; k += 2) pm = __builtin_amdgcn_mfma_f32_32x32x2f32(pc[k], pa[k], pm, 0, 0, 0);
+        } else {
+          // 32 rows x one 128-byte line per load: the lines stay in the vector cache across 32 class steps
+          const float* pa = pcat + (size_t)(row_ok ? i_row : 0) * ldp + half;
+          for (int k = 0; k < KP2; k += 2)
+            pm = __builtin_amdgcn_mfma_f32_32x32x2f32(pc[k], row_ok ? pa[k] : 0.f, pm, 0, 0, 0);
+        }
       }
 #pragma unroll
       for (int reg = 0; reg < 16; ++reg) {
@@ -412,20 +423,19 @@ __global__ __launch_bounds__(1024) void pixcon_reduce_kernel(const float* __rest
   }
 }
 
-struct Plan {
-  int nt_i, nsplit1, nsplit2, KP2;
+// workspace layout of the fp32 path; the split counts come from here and nowhere else
+struct Layout {
+  int nt_i, nsplit;
   size_t off_negp, off_maxp, off_lossp, off_qsump, off_rowloss, off_Up, off_Vp, total;
 };
 
-Plan make_plan(int BHW, int K) {
-  Plan p;
+Layout make_layout(int BHW) {
+  Layout p;
   p.nt_i = ceil_div(BHW, kBI);
   int ns = ceil_div(1024, p.nt_i);
   if (ns > kMaxSplit) ns = kMaxSplit;
   if (ns < 1) ns = 1;
-  p.nsplit1 = ns;
-  p.nsplit2 = ns;
-  p.KP2 = (K + 1) & ~1;
+  p.nsplit = ns;
   size_t o = 0;
   const size_t rowvec = align_up((size_t)BHW * 4, 256);
   p.off_negp = o; o += rowvec * ns;
@@ -439,10 +449,47 @@ Plan make_plan(int BHW, int K) {
   return p;
 }
 
+// Largest K whose anchor-block probability rows are staged in LDS next to the two contrast tiles (152 064 bytes at 110).
+// Past it the rows of the anchor block stay in global memory: (2 kTJ)(KP2 + 1) floats remain, 132 608 bytes at K = 255.
+constexpr int kMaxKAnchorLds = 110;
+constexpr size_t kLdsLimit = 160 * 1024;
+
+void pixcon32_plan(int BHW, int K, int use_prob, PixconPlan* p) {
+  const Layout L = make_layout(BHW);
+  const bool wide = use_prob && K > kMaxKAnchorLds;
+  p->path = wide ? UCD_PIXCON_PATH_F32_WIDE : UCD_PIXCON_PATH_F32;
+  p->class_chunk = 0;
+  p->kp = use_prob ? (K + 1) & ~1 : 0;
+  p->nt_i = L.nt_i;
+  p->nsplit1 = p->nsplit2 = L.nsplit;
+  p->lds1 = (size_t)(2 * kTJ * kPitch + 2 * kTJ) * 4;
+  p->lds2 = p->lds1 + (size_t)(2 * kTJ + (wide ? 0 : kBI)) * (p->kp + 1) * 4;
+  p->workspace = L.total;
+}
+
 }  // namespace
 
 void pixcon_launch_reduce(const float* row_loss, const ucd_pixcon_meta* meta, float* loss_out, hipStream_t s) {
   pixcon_reduce_kernel<<<1, 1024, 0, s>>>(row_loss, meta, loss_out);
+}
+
+int pixcon_make_plan(const char* fn, int BHW, int K, int precision, int use_prob, float temperature, PixconPlan* p) {
+  UCD_REQUIRE(BHW > 0 && temperature > 0.f, UCD_EINVAL, "%s: bad sizes", fn);
+  UCD_REQUIRE(precision == UCD_PIXCON_F32 || precision == UCD_PIXCON_F16 || precision == UCD_PIXCON_F16_SPLIT, UCD_EINVAL,
+              "%s: unknown precision %d", fn, precision);
+  UCD_REQUIRE(K >= 0 && (!use_prob || K >= 1), UCD_EINVAL, "%s: K = %d: use_prob needs 1 <= K <= 255 teacher classes", fn, K);
+  UCD_REQUIRE(K <= 255, UCD_EUNSUPPORTED, "%s: K = %d teacher classes: labels are bytes with 255 as padding (1 <= K <= 255)", fn,
+              K);
+  if (precision == UCD_PIXCON_F32) {
+    pixcon32_plan(BHW, K, use_prob, p);
+  } else {
+    const int KP16 = use_prob ? (K + 15) / 16 * 16 : 0;
+    if (precision == UCD_PIXCON_F16 && pixcon16p_eligible(BHW, temperature, use_prob, K)) pixcon16p_plan(BHW, KP16, use_prob, p);
+    else pixcon16_plan(BHW, KP16, p);
+  }
+  UCD_REQUIRE(p->lds1 <= kLdsLimit && p->lds2 <= kLdsLimit, UCD_EUNSUPPORTED, "%s: %zu / %zu bytes of LDS for K = %d (limit %zu)",
+              fn, p->lds1, p->lds2, K, kLdsLimit);
+  return 0;
 }
 }  // namespace ucd
 
@@ -450,10 +497,34 @@ using namespace ucd;
 
 extern "C" {
 
+int ucd_pixcon_loss_plan(int BHW, int K, int precision, int use_prob, float temperature, int* path, int* class_chunk,
+                         int* nsplit1, int* nsplit2, size_t* lds_sweep1, size_t* lds_sweep2, size_t* workspace_bytes) {
+  PixconPlan p;
+  const int rc = pixcon_make_plan("ucd_pixcon_loss_plan", BHW, K, precision, use_prob, temperature, &p);
+  if (rc) return rc;
+  if (path) *path = p.path;
+  if (class_chunk) *class_chunk = p.class_chunk;
+  if (nsplit1) *nsplit1 = p.nsplit1;
+  if (nsplit2) *nsplit2 = p.nsplit2;
+  if (lds_sweep1) *lds_sweep1 = p.lds1;
+  if (lds_sweep2) *lds_sweep2 = p.lds2;
+  if (workspace_bytes) *workspace_bytes = p.workspace;
+  return 0;
+}
+
+// the largest layout any path can ask for at this size: one buffer serves every precision and temperature
 size_t ucd_pixcon_loss_workspace_bytes(int BHW, int N, int K) {
   (void)N;
-  const size_t a = make_plan(BHW, K).total, b = pixcon16_workspace_bytes(BHW), c = pixcon16p_workspace_bytes(BHW);
-  return a > b ? (a > c ? a : c) : (b > c ? b : c);
+  (void)K;
+  if (BHW <= 0) return 0;
+  PixconPlan p;
+  size_t best = 0;
+  pixcon32_plan(BHW, 0, 0, &p);
+  best = p.workspace;
+  pixcon16_plan(BHW, 0, &p);
+  if (p.workspace > best) best = p.workspace;
+  if (pixcon16p_workspace_bytes(BHW) > best) best = pixcon16p_workspace_bytes(BHW);
+  return best;
 }
 
 static int pixcon_loss_impl(const char* fn, const float* chat, int ldc, int N, const uint8_t* row_label, const float* pcat,
@@ -467,11 +538,13 @@ static int pixcon_loss_impl(const char* fn, const float* chat, int ldc, int N, c
               "%s: unknown precision %d", fn, precision);
   UCD_REQUIRE(!grad_a || (aligned16(grad_a) && ldg % 4 == 0 && ldg >= N && ldg <= kN), UCD_EALIGN,
               "%s: grad_a must be 16-byte aligned, ldg a multiple of 4 in [N, %d]", fn, kN);
+  PixconPlan p;
   if (precision == UCD_PIXCON_F16 || precision == UCD_PIXCON_F16_SPLIT) {
     UCD_REQUIRE(ch16 && aligned16(ch16) && N <= kN, UCD_EINVAL, "%s: the fp16 path needs ch16 [Cpad, %d]", fn, kN);
-    UCD_REQUIRE(!use_prob || (p16 && aligned16(p16) && K > 0 && K <= 112), UCD_EUNSUPPORTED,
-                "%s: the fp16 path needs p16 and K <= 112", fn);
-    if (precision == UCD_PIXCON_F16 && pixcon16p_eligible(BHW, temperature, use_prob, K))
+    UCD_REQUIRE(!use_prob || (p16 && aligned16(p16)), UCD_EINVAL, "%s: the fp16 path needs p16 with use_prob", fn);
+    const int rc = pixcon_make_plan(fn, BHW, K, precision, use_prob, temperature, &p);
+    if (rc) return rc;
+    if (p.path == UCD_PIXCON_PATH_F16_PLANNED)
       return pixcon16p_launch((const _Float16*)ch16, row_label, (const _Float16*)p16, K, meta, BHW, temperature, shift_pos,
                               use_prob, loss_out, grad_a, ldg, row_stats, workspace, workspace_bytes, (hipStream_t)stream);
     return pixcon16_launch((const _Float16*)ch16, row_label, (const _Float16*)p16, K, meta, BHW, temperature, shift_pos,
@@ -483,34 +556,39 @@ static int pixcon_loss_impl(const char* fn, const float* chat, int ldc, int N, c
               "%s: chat / grad_a must be 16-byte aligned, ldg a multiple of 4", fn);
   UCD_REQUIRE(!use_prob || (pcat && K > 0 && ldp >= ((K + 1) & ~1)), UCD_EINVAL,
               "%s: use_prob needs pcat with ldp >= K rounded up to even", fn);
-  UCD_REQUIRE(K <= 110, UCD_EUNSUPPORTED, "%s: K = %d teacher classes exceed the LDS budget (K <= 110)", fn, K);
-  const Plan p = make_plan(BHW, K);
-  UCD_REQUIRE(workspace_bytes >= p.total, UCD_EWORKSPACE, "%s: workspace too small (%zu < %zu)", fn, workspace_bytes, p.total);
+  int rc = pixcon_make_plan(fn, BHW, K, precision, use_prob, temperature, &p);
+  if (rc) return rc;
+  const Layout L = make_layout(BHW);
+  UCD_REQUIRE(workspace_bytes >= L.total, UCD_EWORKSPACE, "%s: workspace too small (%zu < %zu)", fn, workspace_bytes, L.total);
   hipStream_t s = (hipStream_t)stream;
   char* ws = (char*)workspace;
-  float* negp = (float*)(ws + p.off_negp);
-  float* maxp = (float*)(ws + p.off_maxp);
-  float* lossp = (float*)(ws + p.off_lossp);
-  float* qsump = (float*)(ws + p.off_qsump);
-  float* rowloss = (float*)(ws + p.off_rowloss);
-  float* Up = (float*)(ws + p.off_Up);
-  float* Vp = (float*)(ws + p.off_Vp);
+  float* negp = (float*)(ws + L.off_negp);
+  float* maxp = (float*)(ws + L.off_maxp);
+  float* lossp = (float*)(ws + L.off_lossp);
+  float* qsump = (float*)(ws + L.off_qsump);
+  float* rowloss = (float*)(ws + L.off_rowloss);
+  float* Up = (float*)(ws + L.off_Up);
+  float* Vp = (float*)(ws + L.off_Vp);
   const float inv_T = 1.f / temperature;
   const int maxA = BHW;
 
-  const size_t lds1 = (size_t)(2 * kTJ * kPitch + 2 * kTJ) * 4;
   // opt in to more than 64 KiB of dynamic LDS (gfx950 has 160 KiB per workgroup); per call, no process-wide state
   UCD_TRY_LDS(pixcon_neg_kernel, 160 * 1024);
-  UCD_TRY_LDS(pixcon_pos_kernel, 160 * 1024);
-  pixcon_neg_kernel<<<dim3(p.nt_i, p.nsplit1), kThreads, lds1, s>>>(chat, ldc, row_label, meta, inv_T, p.nsplit1, maxA,
-                                                                    negp, maxp, Up);
-  int rc = check_launch(fn);
+  pixcon_neg_kernel<<<dim3(p.nt_i, p.nsplit1), kThreads, p.lds1, s>>>(chat, ldc, row_label, meta, inv_T, p.nsplit1, maxA,
+                                                                      negp, maxp, Up);
+  rc = check_launch(fn);
   if (rc) return rc;
-  const int KP2 = use_prob ? p.KP2 : 0;
-  const size_t lds2 = lds1 + (size_t)(2 * kTJ + kBI) * (KP2 + 1) * 4;
-  pixcon_pos_kernel<<<dim3(p.nt_i, p.nsplit2), kThreads, lds2, s>>>(chat, ldc, row_label, pcat, ldp, KP2, meta, inv_T,
-                                                                    shift_pos, use_prob, p.nsplit1, p.nsplit2, maxA,
-                                                                    negp, maxp, lossp, qsump, Vp, Pmat, ldP);
+  if (p.path == UCD_PIXCON_PATH_F32_WIDE) {
+    UCD_TRY_LDS(pixcon_pos_kernel<false>, 160 * 1024);
+    pixcon_pos_kernel<false><<<dim3(p.nt_i, p.nsplit2), kThreads, p.lds2, s>>>(chat, ldc, row_label, pcat, ldp, p.kp, meta, inv_T,
+                                                                               shift_pos, use_prob, p.nsplit1, p.nsplit2, maxA,
+                                                                               negp, maxp, lossp, qsump, Vp, Pmat, ldP);
+  } else {
+    UCD_TRY_LDS(pixcon_pos_kernel<true>, 160 * 1024);
+    pixcon_pos_kernel<true><<<dim3(p.nt_i, p.nsplit2), kThreads, p.lds2, s>>>(chat, ldc, row_label, pcat, ldp, p.kp, meta, inv_T,
+                                                                              shift_pos, use_prob, p.nsplit1, p.nsplit2, maxA,
+                                                                              negp, maxp, lossp, qsump, Vp, Pmat, ldP);
+  }
   rc = check_launch(fn);
   if (rc) return rc;
   pixcon_finalize_kernel<<<ceil_div(BHW, kThreads / 64), kThreads, 0, s>>>(row_label, meta, inv_T, p.nsplit1, p.nsplit2,

@@ -469,14 +469,30 @@ __global__ __launch_bounds__(kThreads) void pixcon16_finalize_kernel(
 
 }  // namespace
 
-// Plan shared with the fp32 path (same workspace layout + one extra row vector)
-size_t pixcon16_workspace_bytes(int BHW) {
-  int nt_i = ceil_div(BHW, kBI);
-  int ns = ceil_div(1024, nt_i);
+// Plan shared with the fp32 path (same workspace layout + one extra row vector).
+// LDS of sweep 2: three contrast tiles + labels + three tiles of probability rows (hi | lo | 8 halfs of padding), i.e.
+// 54 144 + 192 (2 KP16 + 8) bytes: 153 984 at KP16 = 256, inside the 160 KiB of a workgroup, so every K <= 255 is served in
+// one piece.  The kernel's class loop (nk = KP16 / 16 steps, anchors' fragments from global memory when nk > 2), the commit
+// copy (16-byte pieces, KP16 / 4 per row) and the p16 row stride 2 KP16 hold for any multiple of 16.
+void pixcon16_plan(int BHW, int KP16, PixconPlan* p) {
+  p->path = UCD_PIXCON_PATH_F16_SPLIT;
+  p->class_chunk = 0;
+  p->kp = KP16;
+  p->nt_i = ceil_div(BHW, kBI);
+  int ns = ceil_div(1024, p->nt_i);
   if (ns > kMaxSplit) ns = kMaxSplit;
   if (ns < 1) ns = 1;
+  p->nsplit1 = p->nsplit2 = ns;
+  p->lds1 = (size_t)3 * kTJ * kPitchH * 2 + 3 * (kTJ + 4) * 4;
+  p->lds2 = (size_t)3 * kTJ * kPitchH * 2 + 3 * kTJ * 4 + (size_t)3 * kTJ * (2 * KP16 + 8) * 2;
   const size_t rowvec = align_up((size_t)BHW * 4, 256);
-  return rowvec * ns * 5 + rowvec + (size_t)2 * ns * BHW * kN * 4;
+  p->workspace = rowvec * ns * 5 + rowvec + (size_t)2 * ns * BHW * kN * 4;
+}
+
+size_t pixcon16_workspace_bytes(int BHW) {
+  PixconPlan p;
+  pixcon16_plan(BHW, 0, &p);
+  return p.workspace;
 }
 
 int pixcon16_launch(const _Float16* ch16, const uint8_t* row_label, const _Float16* p16, int K,
@@ -484,11 +500,11 @@ int pixcon16_launch(const _Float16* ch16, const uint8_t* row_label, const _Float
                     float* loss_out, float* grad_a, int ldg, float* row_stats, void* workspace, size_t workspace_bytes,
                     hipStream_t s) {
   static const char* fn = "ucd_pixcon_loss[f16]";
-  const int nt_i = ceil_div(BHW, kBI);
-  int ns = ceil_div(1024, nt_i);
-  if (ns > kMaxSplit) ns = kMaxSplit;
-  if (ns < 1) ns = 1;
-  UCD_REQUIRE(workspace_bytes >= pixcon16_workspace_bytes(BHW), UCD_EWORKSPACE, "%s: workspace too small", fn);
+  const int KP16 = use_prob ? (K + 15) / 16 * 16 : 0;
+  PixconPlan p;
+  pixcon16_plan(BHW, KP16, &p);
+  const int nt_i = p.nt_i, ns = p.nsplit1;
+  UCD_REQUIRE(workspace_bytes >= p.workspace, UCD_EWORKSPACE, "%s: workspace too small", fn);
   const size_t rowvec = align_up((size_t)BHW * 4, 256);
   char* ws = (char*)workspace;
   float* negp = (float*)ws; ws += rowvec * ns;
@@ -499,23 +515,20 @@ int pixcon16_launch(const _Float16* ch16, const uint8_t* row_label, const _Float
   float* rowloss = (float*)ws; ws += rowvec;
   float* Up = (float*)ws; ws += (size_t)ns * BHW * kN * 4;
   float* Vp = (float*)ws;
-  const int KP16 = use_prob ? (K + 15) / 16 * 16 : 0;
   const float k2 = kLog2e / temperature;
   const int maxA = BHW;
   // opt in to more than 64 KiB of dynamic LDS: per call (the attribute is per device; there is no process-wide state here)
   UCD_TRY_LDS(pixcon16_neg_kernel<true>, 160 * 1024);
   UCD_TRY_LDS(pixcon16_neg_kernel<false>, 160 * 1024);
   UCD_TRY_LDS(pixcon16_pos_kernel, 160 * 1024);
-  const size_t lds1n = (size_t)3 * kTJ * kPitchH * 2 + 3 * (kTJ + 4) * 4;
   if (k2 <= kFixedShiftMaxK2)
-    pixcon16_neg_kernel<true><<<dim3(nt_i, ns), kThreads, lds1n, s>>>(ch16, row_label, meta, k2, ns, maxA, negp, mrunp, maxp, Up);
+    pixcon16_neg_kernel<true><<<dim3(nt_i, ns), kThreads, p.lds1, s>>>(ch16, row_label, meta, k2, ns, maxA, negp, mrunp, maxp, Up);
   else
-    pixcon16_neg_kernel<false><<<dim3(nt_i, ns), kThreads, lds1n, s>>>(ch16, row_label, meta, k2, ns, maxA, negp, mrunp, maxp, Up);
+    pixcon16_neg_kernel<false><<<dim3(nt_i, ns), kThreads, p.lds1, s>>>(ch16, row_label, meta, k2, ns, maxA, negp, mrunp, maxp, Up);
   int rc = check_launch(fn);
   if (rc) return rc;
-  const size_t lds2 = (size_t)3 * kTJ * kPitchH * 2 + 3 * kTJ * 4 + (size_t)3 * kTJ * (2 * KP16 + 8) * 2;
-  pixcon16_pos_kernel<<<dim3(nt_i, ns), kThreads, lds2, s>>>(ch16, row_label, p16, KP16, meta, k2, shift_pos, use_prob, ns,
-                                                            ns, maxA, negp, mrunp, maxp, lossp, qsump, Vp);
+  pixcon16_pos_kernel<<<dim3(nt_i, ns), kThreads, p.lds2, s>>>(ch16, row_label, p16, KP16, meta, k2, shift_pos, use_prob, ns,
+                                                              ns, maxA, negp, mrunp, maxp, lossp, qsump, Vp);
   rc = check_launch(fn);
   if (rc) return rc;
   pixcon16_finalize_kernel<<<ceil_div(BHW, kThreads / 64), kThreads, 0, s>>>(row_label, meta, 1.f / temperature, ns, ns,

@@ -691,6 +691,19 @@ bool pixcon16p_eligible(int BHW, float temperature, int use_prob, int K) {
 
 size_t pixcon16p_workspace_bytes(int BHW) { return ceil_div(BHW, kBI) < kPlanThreads ? make_layout_p(BHW).total : 0; }
 
+// host half of the launch (ucd_pixcon_loss_plan): the persistent grid is the CU count, known only with a device, so the split
+// counts are reported as 0; the sweep with probabilities adds kRing tiles of probability rows to the LDS
+void pixcon16p_plan(int BHW, int KP16, int use_prob, PixconPlan* p) {
+  p->path = UCD_PIXCON_PATH_F16_PLANNED;
+  p->class_chunk = 0;
+  p->kp = KP16;
+  p->nt_i = ceil_div(BHW, kBI);
+  p->nsplit1 = p->nsplit2 = 0;
+  p->lds1 = (size_t)kRing * kBufHalfs * 2 + kRing * 8 * 4 + 16;
+  p->lds2 = use_prob ? p->lds1 + (size_t)kRing * kTJ * (2 * KP16 + 8) * 2 : p->lds1;
+  p->workspace = pixcon16p_workspace_bytes(BHW);
+}
+
 int pixcon16p_launch(const _Float16* ch16, const uint8_t* row_label, const _Float16* p16, int K,
                      const ucd_pixcon_meta* meta, int BHW, float temperature, int shift_pos, int use_prob,
                      float* loss_out, float* grad_a, int ldg, float* row_stats, void* workspace, size_t workspace_bytes,
@@ -716,8 +729,9 @@ int pixcon16p_launch(const _Float16* ch16, const uint8_t* row_label, const _Floa
   pixcon16p_plan_kernel<<<1, kPlanThreads, 0, s>>>(row_label, meta, L.umax, hdr, seg1, seg2, us1, us2, order1, order2);
   int rc = check_launch(fn);
   if (rc) return rc;
-  const size_t lds_base = (size_t)kRing * kBufHalfs * 2 + kRing * 8 * 4 + 16;
-  const size_t lds_prob = lds_base + (size_t)kRing * kTJ * (2 * KP16 + 8) * 2;
+  PixconPlan pl;
+  pixcon16p_plan(BHW, KP16, use_prob, &pl);
+  const size_t lds_base = pl.lds1, lds_prob = pl.lds2;
   // opt in to more than 64 KiB of dynamic LDS, per call (no process-wide state); only what is needed: the block-wide vote of
   // the probability instance keeps a static word of its own
   UCD_TRY_LDS((pixcon16p_sweep_kernel<0, false>), (int)lds_base);

@@ -25,6 +25,8 @@ PIXCON_F32, PIXCON_F16, PIXCON_F16_SPLIT = 0, 1, 2
 KD_UNBIASED, KD_PLAIN = 0, 1              # enum ucd_seg_kd_mode
 # enum ucd_seg_form (include/ucd_hip.h): the kernel ucd_seg_losses_plan names
 SEG_FORMS = {1: "pk<16,8>", 2: "pk<20,4>", 3: "pk<12,12>", 4: "reg<24,16>", 5: "reg<24,24>", 6: "wide/fixed", 7: "wide/f32"}
+# enum ucd_pixcon_path (include/ucd_hip.h): the kernels ucd_pixcon_loss_plan names
+PIXCON_PATHS = {1: "f32", 2: "f32/wide", 3: "f16/planned", 4: "f16/split"}
 PIXCON_PRECISION = {"f32": PIXCON_F32, "fp32": PIXCON_F32, "f16": PIXCON_F16, "fp16": PIXCON_F16,
                     "f16_split": PIXCON_F16_SPLIT}
 
@@ -151,6 +153,7 @@ SIGNATURES = {
     "ucd_pixcon_prep": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _z, _p]),
     "ucd_pixcon_gather": (_i, [_p, _i, _p, _i, _i, _i, _i, _p, _p, _p, _i, _p, _p, _i, _p, _i, _p, _p, _p, _p]),
     "ucd_pixcon_loss_workspace_bytes": (_z, [_i, _i, _i]),
+    "ucd_pixcon_loss_plan": (_i, [_i, _i, _i, _i, _f, _p, _p, _p, _p, _p, _p, _p]),
     "ucd_pixcon_loss": (_i, [_p, _i, _i, _p, _p, _i, _i, _p, _p, _i, _p, _i, _f, _i, _i, _p, _p, _i, _p, _p, _z, _p]),
     "ucd_pixcon_loss_given_p": (_i, [_p, _i, _i, _p, _p, _i, _p, _i, _f, _i, _p, _p, _i, _p, _p, _z, _p]),
     "ucd_pixcon_scatter_grad": (_i, [_p, _p, _i, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
@@ -400,6 +403,21 @@ def abn_backward(x, ld_x, dy, ld_dy, y, ld_y, dx, ld_dx, dz, ld_dz, M, Cc, plane
                               1 if training else 0, 1 if need_sums else 0, act, slope, ws.data_ptr(), nbytes, stream())
     if rc:
         _check(rc, "ucd_abn_backward")
+
+
+def pixcon_loss_plan(BHW, K, precision="f32", use_prob=True, temperature=0.07):
+    """Host-only ``ucd_pixcon_loss_plan``: which kernels serve a contrastive-loss call and with what launch.  Returns a dict
+    (``path`` as a name of :data:`PIXCON_PATHS`, ``class_chunk``, ``nsplit1`` / ``nsplit2``, ``lds_sweep1`` / ``lds_sweep2``,
+    ``workspace_bytes``); raises what the loss call would raise for these arguments.  Needs no GPU."""
+    lib = load()
+    prec = PIXCON_PRECISION[precision] if isinstance(precision, str) else int(precision)
+    path, chunk, n1, n2 = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
+    l1, l2, wsb = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
+    _check(lib.ucd_pixcon_loss_plan(int(BHW), int(K), prec, int(bool(use_prob)), float(temperature), C.addressof(path),
+                                    C.addressof(chunk), C.addressof(n1), C.addressof(n2), C.addressof(l1), C.addressof(l2),
+                                    C.addressof(wsb)), "ucd_pixcon_loss_plan")
+    return {"path": PIXCON_PATHS[path.value], "class_chunk": chunk.value, "nsplit1": n1.value, "nsplit2": n2.value,
+            "lds_sweep1": l1.value, "lds_sweep2": l2.value, "workspace_bytes": wsb.value}
 
 
 _gemm_ready = None
