@@ -43,32 +43,62 @@ __host__ __device__ __forceinline__ void up_src(int dst, int in_size, float scal
   l0 = 1.f - l1;
 }
 
+// the low-resolution cells under the pixels [t0, min(t0 + tile, out)) of one dimension: the first cell and their count (the source
+// index is monotone in the pixel).  The one copy of the footprint arithmetic: the kernels index their LDS with it, the plan sizes it
+__host__ __device__ __forceinline__ void tile_span(int t0, int tile, int out, int in_size, float scale, int& first, int& count) {
+  int last, dummy;
+  float f0, f1;
+  up_src(t0, in_size, scale, first, dummy, f0, f1);
+  up_src((t0 + tile < out ? t0 + tile : out) - 1, in_size, scale, dummy, last, f0, f1);
+  count = last - first + 1;
+}
+
+struct Footprint { int ya, xa, ny, nx, ncell; };     // cells [ya, ya + ny) x [xa, xa + nx) lie under a tile
+__device__ __forceinline__ Footprint tile_footprint(int ty0, int tx0, int tile_y, int H, int W, int h, int w, float scale_h,
+                                                    float scale_w) {
+  Footprint f;
+  tile_span(ty0, tile_y, H, h, scale_h, f.ya, f.ny);
+  tile_span(tx0, kTileX, W, w, scale_w, f.xa, f.nx);
+  f.ncell = f.ny * f.nx;
+  return f;
+}
+
+// a block's two loss sums in a fixed order: lanes, then the four waves through red[2][4]
+__device__ __forceinline__ void store_block_losses(float ce_sum, float kd_sum, float* red, float* __restrict__ loss_part, int tiles_x,
+                                                   int tiles_y) {
+  ce_sum = wave_sum(ce_sum);
+  kd_sum = wave_sum(kd_sum);
+  if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = ce_sum; red[4 + (threadIdx.x >> 6)] = kd_sum; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const int blk = (blockIdx.z * tiles_y + blockIdx.y) * tiles_x + blockIdx.x;
+    loss_part[2 * blk + 0] = red[0] + red[1] + red[2] + red[3];
+    loss_part[2 * blk + 1] = red[4] + red[5] + red[6] + red[7];
+  }
+}
+
 // loss_part: [blocks][2] (ce sum, kd sum) ; d_sem accumulates ce_scale*dCE + kd_scale*dKD
-// CT > 0: Ctot <= CT and the per-class gradient of a thread's pixel column is accumulated in 2*CT registers
-// over consecutive rows that share the same low-res row pair (8x fewer LDS atomics); CT == 0: any Ctot,
-// four LDS atomics per pixel and class.
-// EX (CT > 0 only; see seg_losses_pk_kernel): cross entropy pooled over [0, kce), kce == K or 1; teacher rows staged times alpha;
+// The register form: Ctot <= CT student and K <= KT teacher classes, every class of a pixel in a register.  The per-class gradient
+// of a thread's pixel column is accumulated in 2 * CT registers over the consecutive rows that share a low-res row pair and
+// flushed with four LDS atomics per class and row pair (8x fewer than per pixel).  Serves the few-class geometries the packed
+// form below does not: UCD_SEG_PK=0, a d_sem off the 16-byte grid, accumulator copies that do not fit the LDS.
+// EX (see seg_losses_pk_kernel): cross entropy pooled over [0, kce), kce == K or 1; teacher rows staged times alpha;
 // kd_plain: KD = -sum_{c<K} q_c (z_c - LSE_old) / K.  EX == false keeps the arithmetic the kernel had.
-template <int CT, int KT = CT, bool EX = false>
+template <int CT, int KT, bool EX>
 __global__ __launch_bounds__(kThreads) void seg_losses_kernel(
     const float* __restrict__ sem_s, int ld_s, const float* __restrict__ sem_t, int ld_t, const int64_t* __restrict__ labels,
     int H, int W, int h, int w, int Ctot, int K, int ignore_index, float scale_h, float scale_w, float ce_scale,
     float kd_scale, float* __restrict__ loss_part, float* __restrict__ d_sem, int ld_d, int tiles_x, int tiles_y, int kce,
     int kd_plain, float alpha) {
+  static_assert(CT > 0 && KT > 0 && KT <= CT, "the classes of a pixel live in CT + KT registers");
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int b = blockIdx.z, ty0 = blockIdx.y * kTileY, tx0 = blockIdx.x * kTileX;
-  // low-res footprint of the tile
-  int ya, yb, xa, xb, dummy;
-  float f0, f1;
-  up_src(ty0, h, scale_h, ya, dummy, f0, f1);
-  up_src(min(ty0 + kTileY, H) - 1, h, scale_h, dummy, yb, f0, f1);
-  up_src(tx0, w, scale_w, xa, dummy, f0, f1);
-  up_src(min(tx0 + kTileX, W) - 1, w, scale_w, dummy, xb, f0, f1);
-  const int ny = yb - ya + 1, nx = xb - xa + 1, ncell = ny * nx;
-  // CT > 0: kRep copies of the gradient accumulators, a lane adds into copy (lane & 15): the 15-16 consecutive pixel
-  // columns under one low-resolution cell would otherwise hit the same LDS word with one ds_add each (a 16-way
-  // serialisation per class: 0.98 -> measured below); copies are ncell * Ctot floats apart, an odd count of banks
-  constexpr int kRep = CT > 0 ? 16 : 1;
+  const Footprint fp = tile_footprint(ty0, tx0, kTileY, H, W, h, w, scale_h, scale_w);
+  const int ya = fp.ya, xa = fp.xa, nx = fp.nx, ncell = fp.ncell;
+  // kRep copies of the gradient accumulators, a lane adds into copy (lane & 15): the 15-16 consecutive pixel columns under
+  // one low-resolution cell would otherwise hit the same LDS word with one ds_add each (a 16-way serialisation per
+  // class); copies are ncell * Ctot floats apart, an odd count of banks
+  constexpr int kRep = 16;
   float* s_log = smem;                      // [ncell][Ctot] student logits
   float* t_log = s_log + ncell * Ctot;      // [ncell][K]    teacher logits
   float* g_acc = t_log + ncell * K;         // [kRep][ncell][Ctot] gradient accumulators
@@ -93,24 +123,22 @@ __global__ __launch_bounds__(kThreads) void seg_losses_kernel(
   const int X = tx0 + (threadIdx.x & 63);
   const float invK = K > 0 ? 1.f / (float)K : 0.f;
   const bool plain = EX && kd_plain != 0, pool = !EX || kce == K;
-  constexpr int CTA = CT > 0 ? CT : 1;
-  float acc0[CTA], acc1[CTA];          // sum over rows of ly0*g / ly1*g for the current low-res row pair
+  float acc0[CT], acc1[CT];          // sum over rows of ly0*g / ly1*g for the current low-res row pair
   int cur_y0 = -1, cur_y1 = -1, x0 = 0, x1 = 0;
   float lx0 = 0.f, lx1 = 0.f;
   if (X < W) up_src(X, w, scale_w, x0, x1, lx0, lx1);
   auto flush = [&]() {
-    if (CT > 0 && cur_y0 >= 0) {
-      const int r0 = (cur_y0 - ya) * nx, r1 = (cur_y1 - ya) * nx;
-      float* ga = g_acc + (threadIdx.x & (kRep - 1)) * gstride;
+    if (cur_y0 < 0) return;
+    const int r0 = (cur_y0 - ya) * nx, r1 = (cur_y1 - ya) * nx;
+    float* ga = g_acc + (threadIdx.x & (kRep - 1)) * gstride;
 #pragma unroll
-      for (int c = 0; c < CTA; ++c)
-        if (c < Ctot) {
-          atomicAdd(&ga[(r0 + x0 - xa) * Ctot + c], lx0 * acc0[c]);
-          atomicAdd(&ga[(r0 + x1 - xa) * Ctot + c], lx1 * acc0[c]);
-          atomicAdd(&ga[(r1 + x0 - xa) * Ctot + c], lx0 * acc1[c]);
-          atomicAdd(&ga[(r1 + x1 - xa) * Ctot + c], lx1 * acc1[c]);
-        }
-    }
+    for (int c = 0; c < CT; ++c)
+      if (c < Ctot) {
+        atomicAdd(&ga[(r0 + x0 - xa) * Ctot + c], lx0 * acc0[c]);
+        atomicAdd(&ga[(r0 + x1 - xa) * Ctot + c], lx1 * acc0[c]);
+        atomicAdd(&ga[(r1 + x0 - xa) * Ctot + c], lx0 * acc1[c]);
+        atomicAdd(&ga[(r1 + x1 - xa) * Ctot + c], lx1 * acc1[c]);
+      }
   };
   for (int it = 0; it < kRows; ++it) {
     const int Y = ty0 + (threadIdx.x >> 6) * kRows + it;
@@ -118,11 +146,11 @@ __global__ __launch_bounds__(kThreads) void seg_losses_kernel(
     int y0, y1;
     float ly0, ly1;
     up_src(Y, h, scale_h, y0, y1, ly0, ly1);
-    if (CT > 0 && (y0 != cur_y0 || y1 != cur_y1)) {
+    if (y0 != cur_y0 || y1 != cur_y1) {
       flush();
       cur_y0 = y0; cur_y1 = y1;
 #pragma unroll
-      for (int c = 0; c < CTA; ++c) { acc0[c] = 0.f; acc1[c] = 0.f; }
+      for (int c = 0; c < CT; ++c) { acc0[c] = 0.f; acc1[c] = 0.f; }
     }
     const int c00 = (y0 - ya) * nx + (x0 - xa), c01 = (y0 - ya) * nx + (x1 - xa);
     const int c10 = (y1 - ya) * nx + (x0 - xa), c11 = (y1 - ya) * nx + (x1 - xa);
@@ -135,217 +163,112 @@ __global__ __launch_bounds__(kThreads) void seg_losses_kernel(
     const bool ignored = lab64 == ignore_index;
     int lab = ignored ? 0 : (int)lab64;
     if (lab < (EX ? kce : K)) lab = 0;                       // loss.py:104-105
-    if (CT > 0) {
-      // Register form (Ctot <= CT, K <= KT).  Every interpolated logit is formed once; the class-set tests (c < K,
-      // c == 0 || c >= K, 1 <= c < K) are wave-uniform 0 / 1 multipliers, classes past Ctot / K carry -1e30 (their
-      // exponentials are exact zeros, so no guards inside the unrolled loops); e_c = exp(z_c - max) is computed once and
-      // every later exponential is a ratio of it:  exp(z_c - LSE_S) = e_c / sum_S e.  (The first version re-evaluated
-      // ~120 exponentials and ~1700 vector instructions per pixel and was issue-bound, tools/prof_seglosses.sh: 980 ->
-      // 630 us at B = 24, 513^2.  227 VGPRs = two waves per SIMD; capping at three spills and is slower, 790 us.)
-      constexpr float kL2e = 1.4426950408889634f, kLn2 = 0.6931471805599453f, kNegBig = -1e30f;
-      constexpr int KTA = KT > 0 ? KT : 1;
-      float zc[CTA], ec[CTA];
-      float mz = kNegBig;
+    // Every interpolated logit is formed once; the class-set tests (c < K, c == 0 || c >= K, 1 <= c < K) are wave-uniform
+    // 0 / 1 multipliers, classes past Ctot / K carry -1e30 (their exponentials are exact zeros, so no guards inside the
+    // unrolled loops); e_c = exp(z_c - max) is computed once and every later exponential is a ratio of it:
+    // exp(z_c - LSE_S) = e_c / sum_S e.  (630 us at B = 24, 513^2, tools/prof_seglosses.sh.  227 VGPRs = two waves per SIMD;
+    // capping at three spills and is slower, 790 us.)
+    constexpr float kL2e = 1.4426950408889634f, kLn2 = 0.6931471805599453f, kNegBig = -1e30f;
+    float zc[CT], ec[CT];
+    float mz = kNegBig;
 #pragma unroll
-      for (int c = 0; c < CTA; ++c) {
-        const float z = interp(s_log, Ctot, c);
-        zc[c] = c < Ctot ? z : kNegBig;
-        mz = fmaxf(mz, zc[c]);
-      }
-      const float mzl = mz * kL2e;
-      float s_all = 0.f, s_old = 0.f, s_bn = 0.f, z_lab = 0.f;
-#pragma unroll
-      for (int c = 0; c < CTA; ++c) {
-        const float e = __builtin_amdgcn_exp2f(__builtin_fmaf(zc[c], kL2e, -mzl));
-        ec[c] = e;
-        s_all += e;
-        s_old = __builtin_fmaf(e, c < K ? 1.f : 0.f, s_old);
-        s_bn = __builtin_fmaf(e, (c == 0 || c >= K) ? 1.f : 0.f, s_bn);
-        z_lab = c == lab ? zc[c] : z_lab;
-      }
-      const float den = mz + kLn2 * __builtin_amdgcn_logf(s_all);
-      float lse_old = mz + kLn2 * __builtin_amdgcn_logf(s_old), lse_bn = mz + kLn2 * __builtin_amdgcn_logf(s_bn);
-      float inv_old = 1.f / s_old, inv_bn = 1.f / s_bn;
-      const bool rescue = s_old < kSubsetTiny || s_bn < kSubsetTiny;
-      float m_o = 0.f, m_b = 0.f, r_o = 0.f, r_b = 0.f;
-      if (rescue) {
-        m_o = kNegBig; m_b = zc[0];
-#pragma unroll
-        for (int c = 0; c < CTA; ++c) {
-          m_o = c < K ? fmaxf(m_o, zc[c]) : m_o;
-          m_b = c >= K ? fmaxf(m_b, zc[c]) : m_b;
-        }
-        float so = 0.f, sb = 0.f;
-#pragma unroll
-        for (int c = 0; c < CTA; ++c) {
-          so += c < K ? __builtin_amdgcn_exp2f((zc[c] - m_o) * kL2e) : 0.f;
-          sb += (c == 0 || c >= K) ? __builtin_amdgcn_exp2f((zc[c] - m_b) * kL2e) : 0.f;
-        }
-        lse_old = m_o + kLn2 * __builtin_amdgcn_logf(so);
-        lse_bn = m_b + kLn2 * __builtin_amdgcn_logf(sb);
-        r_o = 1.f / so; r_b = 1.f / sb;
-        inv_old = 0.f; inv_bn = 0.f;                 // the subset terms of the gradient come from r_o / r_b below
-      }
-      const bool lab0 = EX ? pool && lab == 0 : lab == 0;     // the label is the pooled background (plain CE: a one-hot like any)
-      const float logp = lab0 ? lse_old - den : z_lab - den;
-      if (!ignored) ce_sum += -logp;
-      const float inv_all = 1.f / s_all;
-      // teacher soft-max
-      float te[KTA];
-      float inv_st = 0.f, q0 = 0.f, kd_pix = 0.f;
-      if (sem_t) {
-        float tcv[KTA];
-        float mt = kNegBig, st = 0.f;
-#pragma unroll
-        for (int c = 0; c < KTA; ++c) {
-          const float t = interp(t_log, K, c);
-          tcv[c] = c < K ? t : kNegBig;
-          mt = fmaxf(mt, tcv[c]);
-        }
-        const float mtl = mt * kL2e;
-#pragma unroll
-        for (int c = 0; c < KTA; ++c) {
-          te[c] = __builtin_amdgcn_exp2f(__builtin_fmaf(tcv[c], kL2e, -mtl));
-          st += te[c];
-        }
-        inv_st = 1.f / st;
-        q0 = te[0] * inv_st;
-        kd_pix = plain ? q0 * (zc[0] - lse_old) : q0 * (lse_bn - den);
-      }
-      const float ce_w = ignored ? 0.f : ce_scale;
-      const float kdw = kd_scale * invK;
-      const float q0bn = q0 * inv_bn;
-      const float kd_ref = plain ? lse_old : den;      // what the old classes' log-probabilities are taken against
-#pragma unroll
-      for (int c = 0; c < CTA; ++c) {
-        const float p = ec[c] * inv_all;
-        const float t_old = ec[c] * (c < K ? inv_old : 0.f);
-        const float t_hot = c == lab ? 1.f : 0.f;
-        float g = ce_w * (p - (lab0 ? t_old : t_hot));
-        if (sem_t) {
-          float qc = 0.f;
-          if (c >= 1 && c < KTA) {                      // compile-time; the 1 <= c < K test is the uniform multiplier
-            qc = te[c] * (c < K ? inv_st : 0.f);
-            kd_pix = __builtin_fmaf(qc, zc[c] - kd_ref, kd_pix);
-          }
-          if (EX && plain) {                            // soft-max over the old classes against q, the background included
-            if (c == 0) qc = q0;
-            g = __builtin_fmaf(kdw, t_old - qc, g);
-          } else {
-            const float bn = ec[c] * ((c == 0 || c >= K) ? q0bn : 0.f);
-            g = __builtin_fmaf(kdw, p - bn - qc, g);
-          }
-        }
-        if (rescue) {
-          if (lab0 && c < K) g -= ce_w * r_o * __builtin_amdgcn_exp2f((zc[c] - m_o) * kL2e);
-          if (EX && plain) {
-            if (c < K) g += kdw * r_o * __builtin_amdgcn_exp2f((zc[c] - m_o) * kL2e);
-          } else if (sem_t && (c == 0 || c >= K)) g -= kdw * q0 * r_b * __builtin_amdgcn_exp2f((zc[c] - m_b) * kL2e);
-        }
-        acc0[c] = __builtin_fmaf(ly0, g, acc0[c]);
-        acc1[c] = __builtin_fmaf(ly1, g, acc1[c]);
-      }
-      kd_sum += -kd_pix * invK;
-      continue;
+    for (int c = 0; c < CT; ++c) {
+      const float z = interp(s_log, Ctot, c);
+      zc[c] = c < Ctot ? z : kNegBig;
+      mz = fmaxf(mz, zc[c]);
     }
-    // CT > 0: every interpolated logit is formed ONCE and kept in a register (the three passes below would otherwise
-    // redo the 4 LDS reads + 6 flops of the interpolation three times per class: ~450 LDS reads per pixel)
-    float zc[CTA], tc[CTA];
-    if (CT > 0) {
-#pragma unroll
-      for (int c = 0; c < CTA; ++c) {
-        zc[c] = c < Ctot ? interp(s_log, Ctot, c) : -INFINITY;
-        tc[c] = (sem_t && c < K) ? interp(t_log, K, c) : -INFINITY;
-      }
-    }
-    // pass A: maxima
-    float mz = -INFINITY;
-    if (CT > 0) {
-#pragma unroll
-      for (int c = 0; c < CTA; ++c) mz = fmaxf(mz, zc[c]);
-    } else {
-      for (int c = 0; c < Ctot; ++c) mz = fmaxf(mz, interp(s_log, Ctot, c));
-    }
-    // pass B: the three sums, the labelled logit
+    const float mzl = mz * kL2e;
     float s_all = 0.f, s_old = 0.f, s_bn = 0.f, z_lab = 0.f;
-    if (CT > 0) {
 #pragma unroll
-      for (int c = 0; c < CTA; ++c)
-        if (c < Ctot) {
-          const float z = zc[c];
-          const float e = __expf(z - mz);
-          s_all += e;
-          if (c < K) s_old += e;
-          if (c == 0 || c >= K) s_bn += e;
-          if (c == lab) z_lab = z;
-        }
-    } else {
-      for (int c = 0; c < Ctot; ++c) {
-        const float z = interp(s_log, Ctot, c);
-        const float e = __expf(z - mz);
-        s_all += e;
-        if (c < K) s_old += e;
-        if (c == 0 || c >= K) s_bn += e;
-        if (c == lab) z_lab = z;
-      }
+    for (int c = 0; c < CT; ++c) {
+      const float e = __builtin_amdgcn_exp2f(__builtin_fmaf(zc[c], kL2e, -mzl));
+      ec[c] = e;
+      s_all += e;
+      s_old = __builtin_fmaf(e, c < K ? 1.f : 0.f, s_old);
+      s_bn = __builtin_fmaf(e, (c == 0 || c >= K) ? 1.f : 0.f, s_bn);
+      z_lab = c == lab ? zc[c] : z_lab;
     }
-    const float den = mz + __logf(s_all);
-    const float lse_old = mz + __logf(s_old), lse_bn = mz + __logf(s_bn);
-    const float logp = lab == 0 ? lse_old - den : z_lab - den;
+    const float den = mz + kLn2 * __builtin_amdgcn_logf(s_all);
+    float lse_old = mz + kLn2 * __builtin_amdgcn_logf(s_old), lse_bn = mz + kLn2 * __builtin_amdgcn_logf(s_bn);
+    float inv_old = 1.f / s_old, inv_bn = 1.f / s_bn;
+    const bool rescue = s_old < kSubsetTiny || s_bn < kSubsetTiny;
+    float m_o = 0.f, m_b = 0.f, r_o = 0.f, r_b = 0.f;
+    if (rescue) {
+      m_o = kNegBig; m_b = zc[0];
+#pragma unroll
+      for (int c = 0; c < CT; ++c) {
+        m_o = c < K ? fmaxf(m_o, zc[c]) : m_o;
+        m_b = c >= K ? fmaxf(m_b, zc[c]) : m_b;
+      }
+      float so = 0.f, sb = 0.f;
+#pragma unroll
+      for (int c = 0; c < CT; ++c) {
+        so += c < K ? __builtin_amdgcn_exp2f((zc[c] - m_o) * kL2e) : 0.f;
+        sb += (c == 0 || c >= K) ? __builtin_amdgcn_exp2f((zc[c] - m_b) * kL2e) : 0.f;
+      }
+      lse_old = m_o + kLn2 * __builtin_amdgcn_logf(so);
+      lse_bn = m_b + kLn2 * __builtin_amdgcn_logf(sb);
+      r_o = 1.f / so; r_b = 1.f / sb;
+      inv_old = 0.f; inv_bn = 0.f;                 // the subset terms of the gradient come from r_o / r_b below
+    }
+    const bool lab0 = pool && lab == 0;    // the label is the pooled background (plain CE: a one-hot like any)
+    const float logp = lab0 ? lse_old - den : z_lab - den;
     if (!ignored) ce_sum += -logp;
+    const float inv_all = 1.f / s_all;
     // teacher soft-max
-    float mt = -INFINITY, st = 0.f, q0 = 0.f, kd_pix = 0.f;
+    float te[KT];
+    float inv_st = 0.f, q0 = 0.f, kd_pix = 0.f;
     if (sem_t) {
-      if (CT > 0) {
+      float tcv[KT];
+      float mt = kNegBig, st = 0.f;
 #pragma unroll
-        for (int c = 0; c < CTA; ++c) mt = fmaxf(mt, tc[c]);
-#pragma unroll
-        for (int c = 0; c < CTA; ++c) {
-          tc[c] = c < K ? __expf(tc[c] - mt) : 0.f;      // from here on: un-normalised teacher probabilities
-          st += tc[c];
-        }
-        q0 = tc[0] / st;
-      } else {
-        for (int c = 0; c < K; ++c) mt = fmaxf(mt, interp(t_log, K, c));
-        for (int c = 0; c < K; ++c) st += __expf(interp(t_log, K, c) - mt);
-        q0 = __expf(interp(t_log, K, 0) - mt) / st;
+      for (int c = 0; c < KT; ++c) {
+        const float t = interp(t_log, K, c);
+        tcv[c] = c < K ? t : kNegBig;
+        mt = fmaxf(mt, tcv[c]);
       }
-      kd_pix = q0 * (lse_bn - den);
+      const float mtl = mt * kL2e;
+#pragma unroll
+      for (int c = 0; c < KT; ++c) {
+        te[c] = __builtin_amdgcn_exp2f(__builtin_fmaf(tcv[c], kL2e, -mtl));
+        st += te[c];
+      }
+      inv_st = 1.f / st;
+      q0 = te[0] * inv_st;
+      kd_pix = plain ? q0 * (zc[0] - lse_old) : q0 * (lse_bn - den);
     }
-    // pass C: gradients (and the old-class part of the KD loss)
     const float ce_w = ignored ? 0.f : ce_scale;
-    const float inv_st = sem_t ? 1.f / st : 0.f;
-    auto grad_c = [&](int c, float z, float te) {   // te: exp(teacher_c - mt) (CT > 0) or unused
-      const float p = __expf(z - den);
-      float g = ce_w * (p - (lab == 0 ? (c < K ? __expf(z - lse_old) : 0.f) : (c == lab ? 1.f : 0.f)));
+    const float kdw = kd_scale * invK;
+    const float q0bn = q0 * inv_bn;
+    const float kd_ref = plain ? lse_old : den;      // what the old classes' log-probabilities are taken against
+#pragma unroll
+    for (int c = 0; c < CT; ++c) {
+      const float p = ec[c] * inv_all;
+      const float t_old = ec[c] * (c < K ? inv_old : 0.f);
+      const float t_hot = c == lab ? 1.f : 0.f;
+      float g = ce_w * (p - (lab0 ? t_old : t_hot));
       if (sem_t) {
         float qc = 0.f;
-        if (c >= 1 && c < K) {
-          qc = CT > 0 ? te * inv_st : __expf(interp(t_log, K, c) - mt) / st;
-          kd_pix += qc * (z - den);
+        if (c >= 1 && c < KT) {                      // compile-time; the 1 <= c < K test is the uniform multiplier
+          qc = te[c] * (c < K ? inv_st : 0.f);
+          kd_pix = __builtin_fmaf(qc, zc[c] - kd_ref, kd_pix);
         }
-        const float bn = (c == 0 || c >= K) ? q0 * __expf(z - lse_bn) : 0.f;
-        g += kd_scale * invK * (p - bn - qc);
-      }
-      return g;
-    };
-    if (CT > 0) {
-#pragma unroll
-      for (int c = 0; c < CTA; ++c)
-        if (c < Ctot) {
-          const float g = grad_c(c, zc[c], tc[c]);
-          acc0[c] += ly0 * g;
-          acc1[c] += ly1 * g;
+        if (plain) {                            // soft-max over the old classes against q, the background included
+          if (c == 0) qc = q0;
+          g = __builtin_fmaf(kdw, t_old - qc, g);
+        } else {
+          const float bn = ec[c] * ((c == 0 || c >= K) ? q0bn : 0.f);
+          g = __builtin_fmaf(kdw, p - bn - qc, g);
         }
-    } else {
-      const float w00 = ly0 * lx0, w01 = ly0 * lx1, w10 = ly1 * lx0, w11 = ly1 * lx1;
-      for (int c = 0; c < Ctot; ++c) {
-        const float g = grad_c(c, interp(s_log, Ctot, c), 0.f);
-        atomicAdd(&g_acc[c00 * Ctot + c], w00 * g);
-        atomicAdd(&g_acc[c01 * Ctot + c], w01 * g);
-        atomicAdd(&g_acc[c10 * Ctot + c], w10 * g);
-        atomicAdd(&g_acc[c11 * Ctot + c], w11 * g);
       }
+      if (rescue) {
+        if (lab0 && c < K) g -= ce_w * r_o * __builtin_amdgcn_exp2f((zc[c] - m_o) * kL2e);
+        if (plain) {
+          if (c < K) g += kdw * r_o * __builtin_amdgcn_exp2f((zc[c] - m_o) * kL2e);
+        } else if (sem_t && (c == 0 || c >= K)) g -= kdw * q0 * r_b * __builtin_amdgcn_exp2f((zc[c] - m_b) * kL2e);
+      }
+      acc0[c] = __builtin_fmaf(ly0, g, acc0[c]);
+      acc1[c] = __builtin_fmaf(ly1, g, acc1[c]);
     }
     kd_sum += -kd_pix * invK;
   }
@@ -361,16 +284,7 @@ __global__ __launch_bounds__(kThreads) void seg_losses_kernel(
       atomicAdd(&d_sem[((size_t)(b * h + cy) * w + cx) * ld_d + c], v);
     }
   }
-  // block loss sums (fixed order)
-  ce_sum = wave_sum(ce_sum);
-  kd_sum = wave_sum(kd_sum);
-  if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = ce_sum; red[4 + (threadIdx.x >> 6)] = kd_sum; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const int blk = (blockIdx.z * tiles_y + blockIdx.y) * tiles_x + blockIdx.x;
-    loss_part[2 * blk + 0] = red[0] + red[1] + red[2] + red[3];
-    loss_part[2 * blk + 1] = red[4] + red[5] + red[6] + red[7];
-  }
+  store_block_losses(ce_sum, kd_sum, red, loss_part, tiles_x, tiles_y);
 }
 
 // ---- round 5: the few-class form on packed fp32 math, old and new classes in separate register groups ------------------------------
@@ -397,7 +311,7 @@ __device__ __forceinline__ f32x2 exp2_2(f32x2 a) { return f32x2{__builtin_amdgcn
 //   KD = -sum_{c<K} q_c (z_c - LSE_old) / K,   dKD/dz_c = [c < K] (e_c / sum_old - q_c) / K.
 // All three are block-uniform; the sums it needs (old slots, all slots) are the ones the unbiased pair takes already.  EX == false
 // keeps the arithmetic the kernel had (the same operations in the same order: the same bits).
-template <int KT, int NT, bool EX = false>
+template <int KT, int NT, bool EX>
 __global__ __launch_bounds__(kThreads) void seg_losses_pk_kernel(
     const float* __restrict__ sem_s, int ld_s, const float* __restrict__ sem_t, int ld_t, const int64_t* __restrict__ labels,
     int H, int W, int h, int w, int Ctot, int K, int ignore_index, float scale_h, float scale_w, float ce_scale,
@@ -412,13 +326,8 @@ __global__ __launch_bounds__(kThreads) void seg_losses_pk_kernel(
   static_assert(KT % 4 == 0 && NT % 4 == 0, "slot groups are read four at a time");
   constexpr float kL2e = 1.4426950408889634f, kLn2 = 0.6931471805599453f, kNegBig = -1e30f;
   const int b = blockIdx.z, ty0 = blockIdx.y * kTileY, tx0 = blockIdx.x * kTileX;
-  int ya, yb, xa, xb, dummy;
-  float f0, f1;
-  up_src(ty0, h, scale_h, ya, dummy, f0, f1);
-  up_src(min(ty0 + kTileY, H) - 1, h, scale_h, dummy, yb, f0, f1);
-  up_src(tx0, w, scale_w, xa, dummy, f0, f1);
-  up_src(min(tx0 + kTileX, W) - 1, w, scale_w, dummy, xb, f0, f1);
-  const int ny = yb - ya + 1, nx = xb - xa + 1, ncell = ny * nx;
+  const Footprint fp = tile_footprint(ty0, tx0, kTileY, H, W, h, w, scale_h, scale_w);
+  const int ya = fp.ya, xa = fp.xa, nx = fp.nx, ncell = fp.ncell;
   // the host sized the LDS for the exact footprint it computed with the same arithmetic; a disagreement must not become a silent
   // overrun of the accumulators
   if (ncell > cell_cap) __builtin_trap();
@@ -442,7 +351,7 @@ __global__ __launch_bounds__(kThreads) void seg_losses_pk_kernel(
 #pragma unroll
     for (int it = 0; it < kRows; ++it) lv[it] = (Xl < W && Yl + it < H) ? labels[((size_t)b * H + Yl + it) * W + Xl] : 0;
 #pragma unroll
-    for (int it = 0; it < kRows; ++it)      // as the generic form reads them: negative -> background, above the classes -> no class
+    for (int it = 0; it < kRows; ++it)      // a byte per label that reads as the int64 does in the other kernels: negative -> background, above the classes -> no class
       lab_s[it * kThreads + threadIdx.x] = lv[it] == ignore_index ? 0xFF : (unsigned char)(lv[it] < 0 ? 0 : lv[it] > 254 ? 254 : lv[it]);
   }
   for (int i = threadIdx.x; i < ncell * CT; i += kThreads) {
@@ -528,7 +437,7 @@ __global__ __launch_bounds__(kThreads) void seg_losses_pk_kernel(
     const bool ignored = code == 0xFF;
     int lab = ignored ? 0 : code;
     if (lab < (EX ? kce : K)) lab = 0;                       // loss.py:104-105
-    const bool lab0 = EX ? pool && lab == 0 : lab == 0;      // the label is the pooled background (EX, plain CE: never - a one-hot)
+    const bool lab0 = pool && lab == 0;     // the label is the pooled background (EX, plain CE: never - a one-hot)
     // the label's new-class slot (negative: background / old / ignored); EX: its slot among ALL slots, -1 when pooled
     const int jlab = EX ? (lab0 ? -1 : lab < K ? lab : KT + lab - K) : lab - K;
 
@@ -628,20 +537,20 @@ __global__ __launch_bounds__(kThreads) void seg_losses_pk_kernel(
     //       - ce_w [label new][c == label] - kdw q_c [1 <= c < K]
     // EX: plain KD moves kdw from the sum over all slots to the sum over the old ones, drops the background + new term and gives
     // slot 0 its q_0 like any old class; a one-hot label may sit in an old slot
-    const float A = EX ? (ce_w + (plain ? 0.f : kdw)) * inv_all : (ce_w + kdw) * inv_all;
-    const float Bo = EX ? (lab0 ? ce_w * inv_old : 0.f) - (plain ? kdw * inv_old : 0.f) : (lab0 ? ce_w * inv_old : 0.f);
-    const float Bb = (EX && plain) ? 0.f : kdw * q0 * inv_bn;
+    const float A = (ce_w + (plain ? 0.f : kdw)) * inv_all;
+    const float Bo = (lab0 ? ce_w * inv_old : 0.f) - (plain ? kdw * inv_old : 0.f);
+    const float Bb = plain ? 0.f : kdw * q0 * inv_bn;
     const float coef_old = A - Bo, coef_new = A - Bb, nkq = -kdw * inv_st;
     const f32x2 COLD = bc2(coef_old), CNEW = bc2(coef_new), NKQ = bc2(nkq);
     const float hot_w = (EX && lab0) ? 0.f : ce_w;           // (EX == false: the tests on jlab alone decide)
-    const float rc_old = EX ? (lab0 ? ce_w * r_o : 0.f) - (plain ? kdw * r_o : 0.f) : (lab0 ? ce_w * r_o : 0.f);
-    const float rc_bn = (EX && plain) ? 0.f : kdw * q0 * r_b;
+    const float rc_old = (lab0 ? ce_w * r_o : 0.f) - (plain ? kdw * r_o : 0.f);
+    const float rc_bn = plain ? 0.f : kdw * q0 * r_b;
 #pragma unroll
     for (int p = 0; p < NP; ++p) {
       f32x2 g;
       if (p == 0) {
         g = e[0] * f32x2{coef_old - Bb, coef_old};
-        g = fma2(te[0], f32x2{(EX && plain) ? nkq : 0.f, nkq}, g);
+        g = fma2(te[0], f32x2{plain ? nkq : 0.f, nkq}, g);
         if (EX) g -= f32x2{jlab == 0 ? hot_w : 0.f, jlab == 1 ? hot_w : 0.f};
       } else if (p < KP) {
         g = fma2(te[p], NKQ, e[p] * COLD);
@@ -683,22 +592,11 @@ __global__ __launch_bounds__(kThreads) void seg_losses_pk_kernel(
       atomicAdd(reinterpret_cast<int*>(d_sem) + ((size_t)(b * h + cy) * w + cx) * ld_d + c, __double2int_rn(vd * (double)fx_scale));
     }
   }
-  // block loss sums (fixed order)
-  ce_sum = wave_sum(ce_sum);
-  kd_sum = wave_sum(kd_sum);
-  if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = ce_sum; red[4 + (threadIdx.x >> 6)] = kd_sum; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const int blk = (blockIdx.z * tiles_y + blockIdx.y) * tiles_x + blockIdx.x;
-    loss_part[2 * blk + 0] = red[0] + red[1] + red[2] + red[3];
-    loss_part[2 * blk + 1] = red[4] + red[5] + red[6] + red[7];
-  }
+  store_block_losses(ce_sum, kd_sum, red, loss_part, tiles_x, tiles_y);
 }
 
 // ---- the same losses for MANY classes (ADE20K: 151 student / 101 teacher classes; any Ctot the LDS holds) ----------------------
-// The generic form above (CT == 0) re-interpolates every logit in each of its passes and adds every pixel's gradient to LDS with
-// four float atomics per class - 604 contended LDS atomics and ~900 exponentials per pixel at 151 classes: 4.8 ms for ONE rank's
-// 3 x 512^2 batch (26 % of that step; bench.py --dataset ade --task 100-50 --global_batch 3).  Here:
+// Ctot > 24: the classes of a pixel no longer fit in registers, so a row's classes are walked from LDS (history: DESIGN.md 3.5):
 //   * a thread owns one pixel column of RW rows; phase A walks all classes of a row twice (maxima, then sums: student e_c and -
 //     for the old classes - teacher te_c in the same pass; exp(z_c - LSE_S) is e_c / sum_S e, so no exponential is evaluated
 //     for a ratio) and keeps 8 constants per row in registers; the loss values need nothing else:
@@ -733,13 +631,8 @@ __global__ __launch_bounds__(kThreads) void seg_losses_wide_kernel(
   constexpr float kL2e = 1.4426950408889634f, kLn2 = 0.6931471805599453f, kNegBig = -1e30f;
   const int CS = (Ctot + 3) & ~3, KS = sem_t ? ((K + 3) & ~3) : 0;
   const int b = blockIdx.z, ty0 = blockIdx.y * kTY, tx0 = blockIdx.x * kTileX;
-  int ya, yb, xa, xb, dummy;
-  float f0, f1;
-  up_src(ty0, h, scale_h, ya, dummy, f0, f1);
-  up_src(min(ty0 + kTY, H) - 1, h, scale_h, dummy, yb, f0, f1);
-  up_src(tx0, w, scale_w, xa, dummy, f0, f1);
-  up_src(min(tx0 + kTileX, W) - 1, w, scale_w, dummy, xb, f0, f1);
-  const int ny = yb - ya + 1, nx = xb - xa + 1, ncell = ny * nx;
+  const Footprint fp = tile_footprint(ty0, tx0, kTY, H, W, h, w, scale_h, scale_w);
+  const int ya = fp.ya, xa = fp.xa, nx = fp.nx, ncell = fp.ncell;
   float* s_log = smem;                         // [ncell][CS]
   float* t_log = s_log + ncell * CS;           // [ncell][KS]
   // fp64 accumulators, two copies in the bytes of four fp32 ones: ds_add_f64 is 20x the rate of ds_add_f32 on gfx950 (section 3.5 of
@@ -822,7 +715,7 @@ __global__ __launch_bounds__(kThreads) void seg_losses_wide_kernel(
           const float te = __builtin_amdgcn_exp2f(__builtin_fmaf(tv[j], kL2e, -mtl));   // 0 for the padding classes
           st += te;
           te0 = cc == 0 ? te : te0;
-          const float tq = (cc >= (EX ? q_lo : 1) && cc < K) ? te : 0.f;
+          const float tq = (cc >= q_lo && cc < K) ? te : 0.f;
           T0 += tq;
           T1 = __builtin_fmaf(tq, v[j], T1);
         }
@@ -859,7 +752,7 @@ __global__ __launch_bounds__(kThreads) void seg_losses_wide_kernel(
       inv_old = 0.f; inv_bn = 0.f;                   // the subset terms of the gradient come from rco / rcb in phase B
       rescue_rows |= 1 << it;
     }
-    const bool lab0 = EX ? pool && lab == 0 : lab == 0;      // the label is the pooled background (plain CE: a one-hot like any)
+    const bool lab0 = pool && lab == 0;     // the label is the pooled background (plain CE: a one-hot like any)
     const float logp = lab0 ? lse_old - den : z_lab - den;
     if (!ignored) ce_sum += -logp;
     const float ce_w = ignored ? 0.f : ce_scale;
@@ -873,12 +766,12 @@ __global__ __launch_bounds__(kThreads) void seg_losses_wide_kernel(
     }
     rmzl[it] = mzl;
     ra_all[it] = (ce_w + (plain ? 0.f : kdw)) / s_all;
-    ra_old[it] = EX ? (lab0 ? ce_w * inv_old : 0.f) - (plain ? kdw * inv_old : 0.f) : (lab0 ? ce_w * inv_old : 0.f);
+    ra_old[it] = (lab0 ? ce_w * inv_old : 0.f) - (plain ? kdw * inv_old : 0.f);
     rhot[it] = lab0 ? 0.f : ce_w;
     rlab[it] = lab;
     rbbn[it] = plain ? 0.f : kdw * q0 * inv_bn;
     rmo[it] = m_o; rmb[it] = m_b;
-    rco[it] = EX ? (lab0 ? ce_w * r_o : 0.f) - (plain ? kdw * r_o : 0.f) : (lab0 ? ce_w * r_o : 0.f);
+    rco[it] = (lab0 ? ce_w * r_o : 0.f) - (plain ? kdw * r_o : 0.f);
     rcb[it] = plain ? 0.f : kdw * q0 * r_b;
     rmtl[it] = mtl;
     rbq[it] = kdw * inv_st;
@@ -937,7 +830,7 @@ __global__ __launch_bounds__(kThreads) void seg_losses_wide_kernel(
           float g = e * coef - (cc == rlab[it] ? rhot[it] : 0.f);
           if (c < KS) {
             const float te = __builtin_amdgcn_exp2f(__builtin_fmaf(tv[j], kL2e, -rmtl[it]));
-            g = __builtin_fmaf(-rbq[it], (cc >= (EX ? q_lo : 1) && cc < K) ? te : 0.f, g);
+            g = __builtin_fmaf(-rbq[it], (cc >= q_lo && cc < K) ? te : 0.f, g);
           }
           if ((rescue_rows >> it) & 1) {
             if (cc < K) g -= rco[it] * __builtin_amdgcn_exp2f((v[j] - rmo[it]) * kL2e);
@@ -964,15 +857,7 @@ __global__ __launch_bounds__(kThreads) void seg_losses_wide_kernel(
       else atomicAdd(dst, (float)vd);
     }
   }
-  ce_sum = wave_sum(ce_sum);
-  kd_sum = wave_sum(kd_sum);
-  if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = ce_sum; red[4 + (threadIdx.x >> 6)] = kd_sum; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const int blk = (blockIdx.z * tiles_y + blockIdx.y) * tiles_x + blockIdx.x;
-    loss_part[2 * blk + 0] = red[0] + red[1] + red[2] + red[3];
-    loss_part[2 * blk + 1] = red[4] + red[5] + red[6] + red[7];
-  }
+  store_block_losses(ce_sum, kd_sum, red, loss_part, tiles_x, tiles_y);
 }
 
 // ---- validation: up-sampling + arg-max + confusion matrix ---------------------------------------
@@ -989,13 +874,8 @@ __global__ __launch_bounds__(kThreads) void seg_confusion_kernel(const float* __
                                                                 int64_t* __restrict__ pred) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int b = blockIdx.z, ty0 = blockIdx.y * kTileY, tx0 = blockIdx.x * kTileX;
-  int ya, yb, xa, xb, dummy;
-  float f0, f1;
-  up_src(ty0, h, scale_h, ya, dummy, f0, f1);
-  up_src(min(ty0 + kTileY, H) - 1, h, scale_h, dummy, yb, f0, f1);
-  up_src(tx0, w, scale_w, xa, dummy, f0, f1);
-  up_src(min(tx0 + kTileX, W) - 1, w, scale_w, dummy, xb, f0, f1);
-  const int ny = yb - ya + 1, nx = xb - xa + 1, ncell = ny * nx;
+  const Footprint fp = tile_footprint(ty0, tx0, kTileY, H, W, h, w, scale_h, scale_w);
+  const int ya = fp.ya, xa = fp.xa, nx = fp.nx, ncell = fp.ncell;
   float* s_log = smem;                                          // [ncell][Ctot]
   unsigned int* l_hist = reinterpret_cast<unsigned int*>(s_log + ncell * Ctot);   // [n][n] when use_lds_hist
   for (int i = threadIdx.x; i < ncell * Ctot; i += kThreads) {
@@ -1100,16 +980,13 @@ int ucd_seg_losses_plan(int H, int W, int h, int w, int Ctot, int K, int has_tea
   // worst-case footprint: (tile/scale + 3) cells per dimension
   int ny = (int)(tile_y * (float)h / H) + 3, nx = (int)(kTileX * (float)w / W) + 3;
   {
-    // the exact footprint instead of the bound: the kernels' own source-index function over the first and the last pixel of every
-    // tile (it is monotone in the pixel) - 6 x 6 cells instead of 7 x 7 at 513 / 33, which is what lets two workgroups share a
-    // CU's LDS
+    // the exact footprint instead of the bound: the kernels' own tile_span over every tile - 6 x 6 cells instead of 7 x 7 at
+    // 513 / 33, which is what lets two workgroups share a CU's LDS
     auto span = [](int out, int in_size, float scale, int tile) {
-      int m = 1, a, bnd, dummy;
-      float f0, f1;
+      int m = 1, first, count;
       for (int t0 = 0; t0 < out; t0 += tile) {
-        up_src(t0, in_size, scale, a, dummy, f0, f1);
-        up_src((t0 + tile < out ? t0 + tile : out) - 1, in_size, scale, dummy, bnd, f0, f1);
-        if (bnd - a + 1 > m) m = bnd - a + 1;
+        tile_span(t0, tile, out, in_size, scale, first, count);
+        if (count > m) m = count;
       }
       return m;
     };
