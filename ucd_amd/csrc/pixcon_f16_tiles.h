@@ -1,39 +1,23 @@
 // Tile helpers shared by the fp16-operand contrastive kernels (pixcon_loss_f16.hip: fixed-split sweeps;
 // pixcon_loss_f16p.hip: planned, software-pipelined sweeps): MFMA fragment loads from the padded LDS tile, the
-// global -> register -> LDS staging of a 32 x 256 contrast tile, accumulator stores.
+// global -> register -> LDS staging of a 32 x 256 contrast tile.
+// The geometry and everything that does not depend on the operand precision is in pixcon_tiles.h.
 #pragma once
 #include <type_traits>
 
-#include "common.h"
-#include "pixcon.h"
+#include "pixcon_tiles.h"
 
 namespace ucd {
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef __fp16 h4 __attribute__((ext_vector_type(4)));
 
-constexpr int kThreads = 256;
-constexpr int kWaves = 4;
-constexpr int kTI = 32;
-constexpr int kBI = kWaves * kTI;
-constexpr int kTJ = 32;
-constexpr int kN = 256;
 constexpr int kPitchH = kN + 24;   // halfs; 560 B = 140 dwords = 12 (mod 64): ds_read_b128 rows conflict-free
-constexpr int kMaxSplit = 16;
 constexpr float kRescaleTh = 8.f;  // log2 units
 constexpr float kFixedShiftMaxK2 = 24.f;   // log2(e)/T <= 24  <=>  T >= 0.0601: the constant-shift form of sweep 1
 constexpr float kLog2e = 1.4426950408889634f;
 constexpr float kLn2 = 0.6931471805599453f;
-
-__device__ __forceinline__ int tile_row(int reg, int half) { return (reg & 3) + 8 * (reg >> 2) + 4 * half; }
-
-struct TileList {
-  int t1a, n1, t2a, n2;
-  __device__ __forceinline__ int count() const { return n1 + n2; }
-  __device__ __forceinline__ int at(int v) const { return v < n1 ? t1a + v : t2a + (v - n1); }
-};
 
 __device__ __forceinline__ void load_anchor_frags(f16x8 (&a16)[16], const _Float16* __restrict__ ch16, int row, bool ok, int half) {
   if (ok) {
@@ -54,7 +38,8 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 struct Stage {
   u32x4 a, b, c, d;
   u32x4 side;          // sweep 2: this thread's 16-byte chunk of the tile's teacher-probability rows
-  unsigned lab;        // label byte of contrast row (threadIdx.x & 31) of the tile
+  unsigned lab;        // fixed split: label byte of contrast row (threadIdx.x & 31) of the tile; planned: label bytes of
+                       // rows 4 (threadIdx.x & 7) + 0..3 as one dword
 };
 // The values fetched here are not needed before the commit at the end of the iteration, and the compiler sinks loads
 // down to their first use (load ; wait ; write - the whole HBM/L2 round trip exposed once per tile).  A memory-clobbering
@@ -62,14 +47,18 @@ struct Stage {
 // ch16 / row_label / p16 without __restrict__.  (Inline-asm loads would hide the pending register writes from the
 // compiler - any copy the register allocator inserts before a hand-written s_waitcnt reads stale data; volatile
 // loads become system-scope FLAT loads that bypass the L2.)
-__device__ __forceinline__ void tile_fetch(Stage& st, const _Float16* ch16, const uint8_t* row_label, int j0) {
-  st.lab = row_label[j0 + (threadIdx.x & 31)];
+// The label byte (here) or dword (tile_fetch_p of the planned form) is fetched first, then the four pieces.
+__device__ __forceinline__ void tile_fetch_rows(Stage& st, const _Float16* ch16, int j0) {
   const int row = threadIdx.x >> 5, c = threadIdx.x & 31;   // piece q covers rows 8q + row
   const _Float16* p0 = ch16 + (size_t)(j0 + row) * kN + c * 8;
   st.a = *reinterpret_cast<const u32x4*>(p0);
   st.b = *reinterpret_cast<const u32x4*>(p0 + 8 * kN);
   st.c = *reinterpret_cast<const u32x4*>(p0 + 16 * kN);
   st.d = *reinterpret_cast<const u32x4*>(p0 + 24 * kN);
+}
+__device__ __forceinline__ void tile_fetch(Stage& st, const _Float16* ch16, const uint8_t* row_label, int j0) {
+  st.lab = row_label[j0 + (threadIdx.x & 31)];
+  tile_fetch_rows(st, ch16, j0);
 }
 __device__ __forceinline__ void side_fetch(Stage& st, const _Float16* src) {
   st.side = *reinterpret_cast<const u32x4*>(src);
@@ -156,16 +145,6 @@ __device__ __forceinline__ void gemm_values(f32x16 (&acc)[8], const _Float16* __
   load_value_frags(f, cs, lane);
   __builtin_amdgcn_sched_barrier(0);
   mfma_values(acc, f, w);
-}
-
-__device__ __forceinline__ void store_values(const f32x16 (&acc)[8], float* __restrict__ dst, int half) {
-#pragma unroll
-  for (int nt = 0; nt < 8; ++nt)
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      float4 v = {acc[nt][4 * g + 0], acc[nt][4 * g + 1], acc[nt][4 * g + 2], acc[nt][4 * g + 3]};
-      *reinterpret_cast<float4*>(dst + 32 * nt + 8 * g + 4 * half) = v;
-    }
 }
 
 }  // namespace

@@ -26,30 +26,15 @@
 // movement (register r covers contrast rows (r&3)+8(r>>2) and +4 on the upper half-wave, which is the
 // k-pair of one 32x32x2 step).  Contrast tiles (32 rows x 256) are staged through LDS once per
 // workgroup, double buffered, row pitch 260 floats (conflict-free ds_read_b128 / ds_read_b32).
-#include "common.h"
-#include "pixcon.h"
+//
+// The geometry, the split count, the workspace layout (SplitLayout) and the combine kernel (no slot scale here) are shared
+// with the fp16 units: pixcon_tiles.h.
+#include "pixcon_tiles.h"
 
 namespace ucd {
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int kThreads = 256;
-constexpr int kWaves = 4;
-constexpr int kTI = 32;             // anchors per wave
-constexpr int kBI = kWaves * kTI;   // anchors per workgroup
-constexpr int kTJ = 32;             // contrast rows per tile
-constexpr int kN = 256;             // padded feature dimension
 constexpr int kPitch = kN + 4;      // LDS row pitch (floats)
-constexpr int kMaxSplit = 16;
-
-__device__ __forceinline__ int tile_row(int reg, int half) { return (reg & 3) + 8 * (reg >> 2) + 4 * half; }
-
-struct TileList {  // two ranges of contrast tiles, addressed as one virtual list
-  int t1a, n1, t2a, n2;
-  __device__ __forceinline__ int count() const { return n1 + n2; }
-  __device__ __forceinline__ int at(int v) const { return v < n1 ? t1a + v : t2a + (v - n1); }
-};
 
 // Registers <- 32 anchors of this wave: lane (i = lane&31, h = lane>>5) holds a_i[h*128 .. h*128+127].
 __device__ __forceinline__ void load_anchor_frags(float (&areg)[128], const float* __restrict__ chat, int ldc, int row,
@@ -111,17 +96,6 @@ __device__ __forceinline__ void gemm_values(f32x16 (&acc)[8], const float* __res
       acc[nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(c, w[reg], acc[nt], 0, 0, 0);
     }
   }
-}
-
-// store the lane's 128 accumulator values of anchor row `dst` (n = 32 nt + 8 g + 4 half + 0..3)
-__device__ __forceinline__ void store_values(const f32x16 (&acc)[8], float* __restrict__ dst, int half) {
-#pragma unroll
-  for (int nt = 0; nt < 8; ++nt)
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      float4 v = {acc[nt][4 * g + 0], acc[nt][4 * g + 1], acc[nt][4 * g + 2], acc[nt][4 * g + 3]};
-      *reinterpret_cast<float4*>(dst + 32 * nt + 8 * g + 4 * half) = v;
-    }
 }
 
 // ---- sweep 1: negatives ----------------------------------------------------------------------------
@@ -353,56 +327,6 @@ __global__ __launch_bounds__(kThreads, 1) void pixcon_pos_kernel(
   }
 }
 
-// ---- combine: per-row loss and gradient ---------------------------------------------------------------
-// one wave per anchor row
-__global__ __launch_bounds__(kThreads) void pixcon_finalize_kernel(
-    const uint8_t* __restrict__ row_label, const ucd_pixcon_meta* __restrict__ meta, float inv_T, int nsplit1, int nsplit2,
-    int maxA, const float* __restrict__ negp, const float* __restrict__ lossp, const float* __restrict__ qsump,
-    const float* __restrict__ Up, const float* __restrict__ Vp, float* __restrict__ grad_a, int ldg, int N,
-    float* __restrict__ row_stats, float* __restrict__ row_loss) {
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int i = blockIdx.x * (kThreads / 64) + wave;
-  const int A = meta->A;
-  if (i >= A) return;
-  const int num = meta->label_count_c[row_label[i]] - 1;
-  const float R = (float)meta->n_valid;
-  float neg = 0.f, la = 0.f, qs = 0.f;
-  for (int s = 0; s < nsplit1; ++s) neg += negp[(size_t)s * maxA + i];
-  for (int s = 0; s < nsplit2; ++s) {
-    la += lossp[(size_t)s * maxA + i];
-    qs += qsump[(size_t)s * maxA + i];
-  }
-  const float coef = num > 0 ? inv_T / ((float)num * R) : 0.f;
-  const float ratio = neg > 0.f ? qs / neg : 0.f;
-  const float rl = num > 0 ? -la / (float)num : 0.f;
-  if (grad_a) {
-    for (int c = lane * 4; c < ldg; c += 256) {
-      float4 u = {0.f, 0.f, 0.f, 0.f}, vv = {0.f, 0.f, 0.f, 0.f};
-      if (c < kN) {
-        for (int s = 0; s < nsplit1; ++s) {
-          const float4 t = *reinterpret_cast<const float4*>(Up + ((size_t)s * maxA + i) * kN + c);
-          u.x += t.x; u.y += t.y; u.z += t.z; u.w += t.w;
-        }
-        for (int s = 0; s < nsplit2; ++s) {
-          const float4 t = *reinterpret_cast<const float4*>(Vp + ((size_t)s * maxA + i) * kN + c);
-          vv.x += t.x; vv.y += t.y; vv.z += t.z; vv.w += t.w;
-        }
-      }
-      float4 g = {coef * (ratio * u.x - vv.x), coef * (ratio * u.y - vv.y), coef * (ratio * u.z - vv.z),
-                  coef * (ratio * u.w - vv.w)};
-      *reinterpret_cast<float4*>(grad_a + (size_t)i * ldg + c) = g;
-    }
-  }
-  if (lane == 0) {
-    row_loss[i] = rl;
-    if (row_stats) {
-      row_stats[i] = neg;
-      row_stats[(size_t)maxA + i] = (float)num;
-      row_stats[(size_t)2 * maxA + i] = rl;
-    }
-  }
-}
-
 // loss = sum_i row_loss_i / R  (fixed summation order: deterministic)
 __global__ __launch_bounds__(1024) void pixcon_reduce_kernel(const float* __restrict__ row_loss,
                                                             const ucd_pixcon_meta* __restrict__ meta,
@@ -423,39 +347,13 @@ __global__ __launch_bounds__(1024) void pixcon_reduce_kernel(const float* __rest
   }
 }
 
-// workspace layout of the fp32 path; the split counts come from here and nowhere else
-struct Layout {
-  int nt_i, nsplit;
-  size_t off_negp, off_maxp, off_lossp, off_qsump, off_rowloss, off_Up, off_Vp, total;
-};
-
-Layout make_layout(int BHW) {
-  Layout p;
-  p.nt_i = ceil_div(BHW, kBI);
-  int ns = ceil_div(1024, p.nt_i);
-  if (ns > kMaxSplit) ns = kMaxSplit;
-  if (ns < 1) ns = 1;
-  p.nsplit = ns;
-  size_t o = 0;
-  const size_t rowvec = align_up((size_t)BHW * 4, 256);
-  p.off_negp = o; o += rowvec * ns;
-  p.off_maxp = o; o += rowvec * ns;
-  p.off_lossp = o; o += rowvec * ns;
-  p.off_qsump = o; o += rowvec * ns;
-  p.off_rowloss = o; o += rowvec;
-  p.off_Up = o; o += (size_t)ns * BHW * kN * 4;
-  p.off_Vp = o; o += (size_t)ns * BHW * kN * 4;
-  p.total = o;
-  return p;
-}
-
 // Largest K whose anchor-block probability rows are staged in LDS next to the two contrast tiles (152 064 bytes at 110).
 // Past it the rows of the anchor block stay in global memory: (2 kTJ)(KP2 + 1) floats remain, 132 608 bytes at K = 255.
 constexpr int kMaxKAnchorLds = 110;
 constexpr size_t kLdsLimit = 160 * 1024;
 
 void pixcon32_plan(int BHW, int K, int use_prob, PixconPlan* p) {
-  const Layout L = make_layout(BHW);
+  const SplitLayout L(BHW, false);
   const bool wide = use_prob && K > kMaxKAnchorLds;
   p->path = wide ? UCD_PIXCON_PATH_F32_WIDE : UCD_PIXCON_PATH_F32;
   p->class_chunk = 0;
@@ -465,6 +363,45 @@ void pixcon32_plan(int BHW, int K, int use_prob, PixconPlan* p) {
   p->lds1 = (size_t)(2 * kTJ * kPitch + 2 * kTJ) * 4;
   p->lds2 = p->lds1 + (size_t)(2 * kTJ + (wide ? 0 : kBI)) * (p->kp + 1) * 4;
   p->workspace = L.total;
+}
+
+// the fp32 launch: every number comes from the plan, every offset from the layout the plan was sized by
+int pixcon32_launch(const char* fn, const float* chat, int ldc, const uint8_t* row_label, const float* pcat, int ldp,
+                    const float* Pmat, int ldP, const ucd_pixcon_meta* meta, int BHW, float temperature, int shift_pos,
+                    int use_prob, float* loss_out, float* grad_a, int ldg, float* row_stats, void* workspace,
+                    const PixconPlan& p, hipStream_t s) {
+  const SplitLayout L(BHW, false);
+  char* ws = (char*)workspace;
+  float* negp = (float*)(ws + L.off_negp);
+  float* maxp = (float*)(ws + L.off_maxp);
+  float* lossp = (float*)(ws + L.off_lossp);
+  float* qsump = (float*)(ws + L.off_qsump);
+  float* rowloss = (float*)(ws + L.off_rowloss);
+  float* Up = (float*)(ws + L.off_Up);
+  float* Vp = (float*)(ws + L.off_Vp);
+  const float inv_T = 1.f / temperature;
+  const int maxA = BHW;
+
+  // opt in to more than 64 KiB of dynamic LDS (gfx950 has 160 KiB per workgroup); per call, no process-wide state
+  UCD_TRY_LDS(pixcon_neg_kernel, 160 * 1024);
+  pixcon_neg_kernel<<<dim3(p.nt_i, p.nsplit1), kThreads, p.lds1, s>>>(chat, ldc, row_label, meta, inv_T, p.nsplit1, maxA,
+                                                                      negp, maxp, Up);
+  int rc = check_launch(fn);
+  if (rc) return rc;
+  const auto pos_kernel = p.path == UCD_PIXCON_PATH_F32_WIDE ? pixcon_pos_kernel<false> : pixcon_pos_kernel<true>;
+  UCD_TRY_LDS(pos_kernel, 160 * 1024);
+  pos_kernel<<<dim3(p.nt_i, p.nsplit2), kThreads, p.lds2, s>>>(chat, ldc, row_label, pcat, ldp, p.kp, meta, inv_T, shift_pos,
+                                                               use_prob, p.nsplit1, p.nsplit2, maxA, negp, maxp, lossp, qsump,
+                                                               Vp, Pmat, ldP);
+  rc = check_launch(fn);
+  if (rc) return rc;
+  const SplitSlots<kScaleNone> slots = {p.nsplit1, p.nsplit2, maxA, nullptr};
+  pixcon_combine_kernel<<<ceil_div(BHW, kThreads / 64), kThreads, 0, s>>>(slots, row_label, meta, inv_T, negp, lossp, qsump, Up,
+                                                                          Vp, grad_a, ldg, row_stats, maxA, rowloss);
+  rc = check_launch(fn);
+  if (rc) return rc;
+  pixcon_reduce_kernel<<<1, 1024, 0, s>>>(rowloss, meta, loss_out);
+  return check_launch(fn);
 }
 
 }  // namespace
@@ -534,70 +471,29 @@ static int pixcon_loss_impl(const char* fn, const float* chat, int ldc, int N, c
                             size_t workspace_bytes, ucd_stream_t stream) {
   UCD_REQUIRE(row_label && meta && loss_out && workspace, UCD_EINVAL, "%s: NULL argument", fn);
   UCD_REQUIRE(BHW > 0 && N > 0 && temperature > 0.f, UCD_EINVAL, "%s: bad sizes", fn);
-  UCD_REQUIRE(precision == UCD_PIXCON_F32 || precision == UCD_PIXCON_F16 || precision == UCD_PIXCON_F16_SPLIT, UCD_EINVAL,
-              "%s: unknown precision %d", fn, precision);
+  PixconPlan p;
+  const int rc = pixcon_make_plan(fn, BHW, K, precision, use_prob, temperature, &p);   // precision, K and the LDS bound
+  if (rc) return rc;
   UCD_REQUIRE(!grad_a || (aligned16(grad_a) && ldg % 4 == 0 && ldg >= N && ldg <= kN), UCD_EALIGN,
               "%s: grad_a must be 16-byte aligned, ldg a multiple of 4 in [N, %d]", fn, kN);
-  PixconPlan p;
-  if (precision == UCD_PIXCON_F16 || precision == UCD_PIXCON_F16_SPLIT) {
+  if (precision == UCD_PIXCON_F32) {
+    UCD_REQUIRE(chat, UCD_EINVAL, "%s: chat is NULL", fn);
+    UCD_REQUIRE(ldc == kN && N <= kN, UCD_EUNSUPPORTED, "%s: the contrast matrix must be padded to ldc == %d columns (N <= %d)", fn, kN, kN);
+    UCD_REQUIRE(aligned16(chat), UCD_EALIGN, "%s: chat / grad_a must be 16-byte aligned, ldg a multiple of 4", fn);
+    UCD_REQUIRE(!use_prob || (pcat && ldp >= p.kp), UCD_EINVAL, "%s: use_prob needs pcat with ldp >= K rounded up to even", fn);
+  } else {
     UCD_REQUIRE(ch16 && aligned16(ch16) && N <= kN, UCD_EINVAL, "%s: the fp16 path needs ch16 [Cpad, %d]", fn, kN);
     UCD_REQUIRE(!use_prob || (p16 && aligned16(p16)), UCD_EINVAL, "%s: the fp16 path needs p16 with use_prob", fn);
-    const int rc = pixcon_make_plan(fn, BHW, K, precision, use_prob, temperature, &p);
-    if (rc) return rc;
-    if (p.path == UCD_PIXCON_PATH_F16_PLANNED)
-      return pixcon16p_launch((const _Float16*)ch16, row_label, (const _Float16*)p16, K, meta, BHW, temperature, shift_pos,
-                              use_prob, loss_out, grad_a, ldg, row_stats, workspace, workspace_bytes, (hipStream_t)stream);
-    return pixcon16_launch((const _Float16*)ch16, row_label, (const _Float16*)p16, K, meta, BHW, temperature, shift_pos,
-                           use_prob, loss_out, grad_a, ldg, row_stats, workspace, workspace_bytes, (hipStream_t)stream);
   }
-  UCD_REQUIRE(chat, UCD_EINVAL, "%s: chat is NULL", fn);
-  UCD_REQUIRE(ldc == kN && N <= kN, UCD_EUNSUPPORTED, "%s: the contrast matrix must be padded to ldc == %d columns (N <= %d)", fn, kN, kN);
-  UCD_REQUIRE(aligned16(chat) && (!grad_a || (aligned16(grad_a) && ldg % 4 == 0 && ldg >= N)), UCD_EALIGN,
-              "%s: chat / grad_a must be 16-byte aligned, ldg a multiple of 4", fn);
-  UCD_REQUIRE(!use_prob || (pcat && K > 0 && ldp >= ((K + 1) & ~1)), UCD_EINVAL,
-              "%s: use_prob needs pcat with ldp >= K rounded up to even", fn);
-  int rc = pixcon_make_plan(fn, BHW, K, precision, use_prob, temperature, &p);
-  if (rc) return rc;
-  const Layout L = make_layout(BHW);
-  UCD_REQUIRE(workspace_bytes >= L.total, UCD_EWORKSPACE, "%s: workspace too small (%zu < %zu)", fn, workspace_bytes, L.total);
-  hipStream_t s = (hipStream_t)stream;
-  char* ws = (char*)workspace;
-  float* negp = (float*)(ws + L.off_negp);
-  float* maxp = (float*)(ws + L.off_maxp);
-  float* lossp = (float*)(ws + L.off_lossp);
-  float* qsump = (float*)(ws + L.off_qsump);
-  float* rowloss = (float*)(ws + L.off_rowloss);
-  float* Up = (float*)(ws + L.off_Up);
-  float* Vp = (float*)(ws + L.off_Vp);
-  const float inv_T = 1.f / temperature;
-  const int maxA = BHW;
-
-  // opt in to more than 64 KiB of dynamic LDS (gfx950 has 160 KiB per workgroup); per call, no process-wide state
-  UCD_TRY_LDS(pixcon_neg_kernel, 160 * 1024);
-  pixcon_neg_kernel<<<dim3(p.nt_i, p.nsplit1), kThreads, p.lds1, s>>>(chat, ldc, row_label, meta, inv_T, p.nsplit1, maxA,
-                                                                      negp, maxp, Up);
-  rc = check_launch(fn);
-  if (rc) return rc;
-  if (p.path == UCD_PIXCON_PATH_F32_WIDE) {
-    UCD_TRY_LDS(pixcon_pos_kernel<false>, 160 * 1024);
-    pixcon_pos_kernel<false><<<dim3(p.nt_i, p.nsplit2), kThreads, p.lds2, s>>>(chat, ldc, row_label, pcat, ldp, p.kp, meta, inv_T,
-                                                                               shift_pos, use_prob, p.nsplit1, p.nsplit2, maxA,
-                                                                               negp, maxp, lossp, qsump, Vp, Pmat, ldP);
-  } else {
-    UCD_TRY_LDS(pixcon_pos_kernel<true>, 160 * 1024);
-    pixcon_pos_kernel<true><<<dim3(p.nt_i, p.nsplit2), kThreads, p.lds2, s>>>(chat, ldc, row_label, pcat, ldp, p.kp, meta, inv_T,
-                                                                              shift_pos, use_prob, p.nsplit1, p.nsplit2, maxA,
-                                                                              negp, maxp, lossp, qsump, Vp, Pmat, ldP);
-  }
-  rc = check_launch(fn);
-  if (rc) return rc;
-  pixcon_finalize_kernel<<<ceil_div(BHW, kThreads / 64), kThreads, 0, s>>>(row_label, meta, inv_T, p.nsplit1, p.nsplit2,
-                                                                           maxA, negp, lossp, qsump, Up, Vp, grad_a,
-                                                                           ldg, N, row_stats, rowloss);
-  rc = check_launch(fn);
-  if (rc) return rc;
-  pixcon_reduce_kernel<<<1, 1024, 0, s>>>(rowloss, meta, loss_out);
-  return check_launch(fn);
+  UCD_REQUIRE(workspace_bytes >= p.workspace, UCD_EWORKSPACE, "%s: workspace too small (%zu < %zu)", fn, workspace_bytes,
+              p.workspace);
+  const hipStream_t s = (hipStream_t)stream;
+  if (precision == UCD_PIXCON_F32)
+    return pixcon32_launch(fn, chat, ldc, row_label, pcat, ldp, Pmat, ldP, meta, BHW, temperature, shift_pos, use_prob, loss_out,
+                           grad_a, ldg, row_stats, workspace, p, s);
+  const auto launch16 = p.path == UCD_PIXCON_PATH_F16_PLANNED ? pixcon16p_launch : pixcon16_launch;
+  return launch16((const _Float16*)ch16, row_label, (const _Float16*)p16, meta, BHW, temperature, shift_pos, use_prob, loss_out,
+                  grad_a, ldg, row_stats, workspace, p, s);
 }
 
 int ucd_pixcon_loss(const float* chat, int ldc, int N, const uint8_t* row_label, const float* pcat, int ldp, int K,

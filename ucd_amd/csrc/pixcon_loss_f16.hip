@@ -22,6 +22,9 @@
 //   fetched with ds_read_b64_tr_b16 from the row-major LDS tile (hardware transpose, 4 rows x 16 columns
 //   per 16-lane group).
 //   Teacher joint probabilities P = p_i . p_j use a hi/lo fp16 split (3 MFMAs per 16 classes, ~2^-21).
+//
+// Shared: geometry, split count, workspace layout (SplitLayout with mrun) and the combine kernel (per-slot mrun scale) in
+// pixcon_tiles.h; the tile staging and the MFMA fragment helpers in pixcon_f16_tiles.h.
 #include "pixcon_f16_tiles.h"
 
 namespace ucd {
@@ -415,106 +418,40 @@ __global__ __launch_bounds__(kThreads, 1) void pixcon16_pos_kernel(
   }
 }
 
-// ---- combine ----------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kThreads) void pixcon16_finalize_kernel(
-    const uint8_t* __restrict__ row_label, const ucd_pixcon_meta* __restrict__ meta, float inv_T, int nsplit1, int nsplit2,
-    int maxA, const float* __restrict__ negp, const float* __restrict__ mrunp, const float* __restrict__ lossp,
-    const float* __restrict__ qsump, const float* __restrict__ Up, const float* __restrict__ Vp,
-    float* __restrict__ grad_a, int ldg, float* __restrict__ row_stats, float* __restrict__ row_loss) {
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int i = blockIdx.x * (kThreads / 64) + wave;
-  const int A = meta->A;
-  if (i >= A) return;
-  const int num = meta->label_count_c[row_label[i]] - 1;
-  const float R = (float)meta->n_valid;
-  float M = -1e30f;
-  for (int s = 0; s < nsplit1; ++s) M = fmaxf(M, mrunp[(size_t)s * maxA + i]);
-  float negs = 0.f, la = 0.f, qs = 0.f;   // negs in units of 2^M
-  for (int s = 0; s < nsplit1; ++s) negs += negp[(size_t)s * maxA + i] * exp2f(mrunp[(size_t)s * maxA + i] - M);
-  for (int s = 0; s < nsplit2; ++s) {
-    la += lossp[(size_t)s * maxA + i];
-    qs += qsump[(size_t)s * maxA + i];
-  }
-  const float coef = num > 0 ? inv_T / ((float)num * R) : 0.f;
-  const float ratio = negs > 0.f ? qs / negs : 0.f;   // U is in the same 2^M units: the scale cancels
-  const float rl = num > 0 ? -la / (float)num : 0.f;
-  if (grad_a) {
-    for (int c = lane * 4; c < ldg; c += 256) {
-      float4 u = {0.f, 0.f, 0.f, 0.f}, vv = {0.f, 0.f, 0.f, 0.f};
-      if (c < kN) {
-        for (int s = 0; s < nsplit1; ++s) {
-          const float w = exp2f(mrunp[(size_t)s * maxA + i] - M);
-          const float4 t = *reinterpret_cast<const float4*>(Up + ((size_t)s * maxA + i) * kN + c);
-          u.x += w * t.x; u.y += w * t.y; u.z += w * t.z; u.w += w * t.w;
-        }
-        for (int s = 0; s < nsplit2; ++s) {
-          const float4 t = *reinterpret_cast<const float4*>(Vp + ((size_t)s * maxA + i) * kN + c);
-          vv.x += t.x; vv.y += t.y; vv.z += t.z; vv.w += t.w;
-        }
-      }
-      float4 g = {coef * (ratio * u.x - vv.x), coef * (ratio * u.y - vv.y), coef * (ratio * u.z - vv.z),
-                  coef * (ratio * u.w - vv.w)};
-      *reinterpret_cast<float4*>(grad_a + (size_t)i * ldg + c) = g;
-    }
-  }
-  if (lane == 0) {
-    row_loss[i] = rl;
-    if (row_stats) {
-      row_stats[i] = negs > 0.f ? negs * exp2f(M) : 0.f;
-      row_stats[(size_t)maxA + i] = (float)num;
-      row_stats[(size_t)2 * maxA + i] = rl;
-    }
-  }
-}
-
 }  // namespace
 
-// Plan shared with the fp32 path (same workspace layout + one extra row vector).
+// Plan: the split count and the workspace are the fp32 path's (SplitLayout, pixcon_tiles.h) with the mrun row vector.
 // LDS of sweep 2: three contrast tiles + labels + three tiles of probability rows (hi | lo | 8 halfs of padding), i.e.
 // 54 144 + 192 (2 KP16 + 8) bytes: 153 984 at KP16 = 256, inside the 160 KiB of a workgroup, so every K <= 255 is served in
 // one piece.  The kernel's class loop (nk = KP16 / 16 steps, anchors' fragments from global memory when nk > 2), the commit
 // copy (16-byte pieces, KP16 / 4 per row) and the p16 row stride 2 KP16 hold for any multiple of 16.
 void pixcon16_plan(int BHW, int KP16, PixconPlan* p) {
+  const SplitLayout L(BHW, true);
   p->path = UCD_PIXCON_PATH_F16_SPLIT;
   p->class_chunk = 0;
   p->kp = KP16;
-  p->nt_i = ceil_div(BHW, kBI);
-  int ns = ceil_div(1024, p->nt_i);
-  if (ns > kMaxSplit) ns = kMaxSplit;
-  if (ns < 1) ns = 1;
-  p->nsplit1 = p->nsplit2 = ns;
+  p->nt_i = L.nt_i;
+  p->nsplit1 = p->nsplit2 = L.nsplit;
   p->lds1 = (size_t)3 * kTJ * kPitchH * 2 + 3 * (kTJ + 4) * 4;
   p->lds2 = (size_t)3 * kTJ * kPitchH * 2 + 3 * kTJ * 4 + (size_t)3 * kTJ * (2 * KP16 + 8) * 2;
-  const size_t rowvec = align_up((size_t)BHW * 4, 256);
-  p->workspace = rowvec * ns * 5 + rowvec + (size_t)2 * ns * BHW * kN * 4;
+  p->workspace = L.total;
 }
 
-size_t pixcon16_workspace_bytes(int BHW) {
-  PixconPlan p;
-  pixcon16_plan(BHW, 0, &p);
-  return p.workspace;
-}
-
-int pixcon16_launch(const _Float16* ch16, const uint8_t* row_label, const _Float16* p16, int K,
-                    const ucd_pixcon_meta* meta, int BHW, float temperature, int shift_pos, int use_prob,
-                    float* loss_out, float* grad_a, int ldg, float* row_stats, void* workspace, size_t workspace_bytes,
-                    hipStream_t s) {
+int pixcon16_launch(const _Float16* ch16, const uint8_t* row_label, const _Float16* p16, const ucd_pixcon_meta* meta, int BHW,
+                    float temperature, int shift_pos, int use_prob, float* loss_out, float* grad_a, int ldg, float* row_stats,
+                    void* workspace, const PixconPlan& p, hipStream_t s) {
   static const char* fn = "ucd_pixcon_loss[f16]";
-  const int KP16 = use_prob ? (K + 15) / 16 * 16 : 0;
-  PixconPlan p;
-  pixcon16_plan(BHW, KP16, &p);
+  const SplitLayout L(BHW, true);
   const int nt_i = p.nt_i, ns = p.nsplit1;
-  UCD_REQUIRE(workspace_bytes >= p.workspace, UCD_EWORKSPACE, "%s: workspace too small", fn);
-  const size_t rowvec = align_up((size_t)BHW * 4, 256);
   char* ws = (char*)workspace;
-  float* negp = (float*)ws; ws += rowvec * ns;
-  float* mrunp = (float*)ws; ws += rowvec * ns;
-  float* maxp = (float*)ws; ws += rowvec * ns;
-  float* lossp = (float*)ws; ws += rowvec * ns;
-  float* qsump = (float*)ws; ws += rowvec * ns;
-  float* rowloss = (float*)ws; ws += rowvec;
-  float* Up = (float*)ws; ws += (size_t)ns * BHW * kN * 4;
-  float* Vp = (float*)ws;
+  float* negp = (float*)(ws + L.off_negp);
+  float* mrunp = (float*)(ws + L.off_mrunp);
+  float* maxp = (float*)(ws + L.off_maxp);
+  float* lossp = (float*)(ws + L.off_lossp);
+  float* qsump = (float*)(ws + L.off_qsump);
+  float* rowloss = (float*)(ws + L.off_rowloss);
+  float* Up = (float*)(ws + L.off_Up);
+  float* Vp = (float*)(ws + L.off_Vp);
   const float k2 = kLog2e / temperature;
   const int maxA = BHW;
   // opt in to more than 64 KiB of dynamic LDS: per call (the attribute is per device; there is no process-wide state here)
@@ -527,13 +464,13 @@ int pixcon16_launch(const _Float16* ch16, const uint8_t* row_label, const _Float
     pixcon16_neg_kernel<false><<<dim3(nt_i, ns), kThreads, p.lds1, s>>>(ch16, row_label, meta, k2, ns, maxA, negp, mrunp, maxp, Up);
   int rc = check_launch(fn);
   if (rc) return rc;
-  pixcon16_pos_kernel<<<dim3(nt_i, ns), kThreads, p.lds2, s>>>(ch16, row_label, p16, KP16, meta, k2, shift_pos, use_prob, ns,
-                                                              ns, maxA, negp, mrunp, maxp, lossp, qsump, Vp);
+  pixcon16_pos_kernel<<<dim3(nt_i, ns), kThreads, p.lds2, s>>>(ch16, row_label, p16, p.kp, meta, k2, shift_pos, use_prob, ns, ns,
+                                                              maxA, negp, mrunp, maxp, lossp, qsump, Vp);
   rc = check_launch(fn);
   if (rc) return rc;
-  pixcon16_finalize_kernel<<<ceil_div(BHW, kThreads / 64), kThreads, 0, s>>>(row_label, meta, 1.f / temperature, ns, ns,
-                                                                             maxA, negp, mrunp, lossp, qsump, Up, Vp,
-                                                                             grad_a, ldg, row_stats, rowloss);
+  const SplitSlots<kScaleSlot> slots = {ns, ns, maxA, mrunp};
+  pixcon_combine_kernel<<<ceil_div(BHW, kThreads / 64), kThreads, 0, s>>>(slots, row_label, meta, 1.f / temperature, negp, lossp,
+                                                                          qsump, Up, Vp, grad_a, ldg, row_stats, maxA, rowloss);
   rc = check_launch(fn);
   if (rc) return rc;
   pixcon_launch_reduce(rowloss, meta, loss_out, s);

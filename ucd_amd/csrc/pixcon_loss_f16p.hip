@@ -30,6 +30,8 @@
 //     barrier; no longer needed.
 // Kept from pixcon_loss_f16.hip (and used for what this file does not cover: T < 0.06, more than 32 teacher classes,
 // more than 1024 anchor blocks): the fixed-split kernels there.
+// Shared: geometry and the combine kernel (UnitSlots policy below: unit slots, one constant scale) in pixcon_tiles.h; the
+// four-piece row fetch / commit of a tile and the MFMA fragment helpers in pixcon_f16_tiles.h.
 #include "pixcon_f16_tiles.h"
 
 namespace ucd {
@@ -203,30 +205,16 @@ __device__ __forceinline__ f16x8 join(const h4& lo, const h4& hi) {
 }
 __device__ __forceinline__ u32 label_byte(const u32x4& lw, int e) { return (lw[e >> 2] >> (8 * (e & 3))) & 0xffu; }
 
-struct StageP {
-  u32x4 a, b, c, d;
-  u32x4 side;
-  u32 lab4;
-};
-__device__ __forceinline__ void tile_fetch_p(StageP& st, const _Float16* ch16, const uint8_t* row_label, int j0) {
-  st.lab4 = *reinterpret_cast<const u32*>(row_label + j0 + 4 * (threadIdx.x & 7));
-  const int row = threadIdx.x >> 5, c = threadIdx.x & 31;
-  const _Float16* p0 = ch16 + (size_t)(j0 + row) * kN + c * 8;
-  st.a = *reinterpret_cast<const u32x4*>(p0);
-  st.b = *reinterpret_cast<const u32x4*>(p0 + 8 * kN);
-  st.c = *reinterpret_cast<const u32x4*>(p0 + 16 * kN);
-  st.d = *reinterpret_cast<const u32x4*>(p0 + 24 * kN);
-}
+// The stage's `lab` is a dword here: the label bytes of rows 4 (threadIdx.x & 7) + 0..3.
 // labels of a tile in LDS: 8 dwords, dword (4 half + g) = label bytes of rows 8 g + 4 half + 0..3, so a lane's 16 rows
 // (tile_row(reg, half), reg = 4 g + r) are the 16 bytes at 16 half
-__device__ __forceinline__ void tile_commit_p(const StageP& st, _Float16* __restrict__ cs, u32* __restrict__ labs) {
-  const int row = threadIdx.x >> 5, c = threadIdx.x & 31;
-  _Float16* p = cs + row * kPitchH + c * 8;
-  *reinterpret_cast<u32x4*>(p) = st.a;
-  *reinterpret_cast<u32x4*>(p + 8 * kPitchH) = st.b;
-  *reinterpret_cast<u32x4*>(p + 16 * kPitchH) = st.c;
-  *reinterpret_cast<u32x4*>(p + 24 * kPitchH) = st.d;
-  if (threadIdx.x < 8) labs[(threadIdx.x & 1) * 4 + (threadIdx.x >> 1)] = st.lab4;
+__device__ __forceinline__ void tile_fetch_p(Stage& st, const _Float16* ch16, const uint8_t* row_label, int j0) {
+  st.lab = *reinterpret_cast<const u32*>(row_label + j0 + 4 * (threadIdx.x & 7));
+  tile_fetch_rows(st, ch16, j0);
+}
+__device__ __forceinline__ void tile_commit_p(const Stage& st, _Float16* __restrict__ cs, u32* __restrict__ labs) {
+  tile_commit(st, cs);
+  if (threadIdx.x < 8) labs[(threadIdx.x & 1) * 4 + (threadIdx.x >> 1)] = st.lab;
 }
 
 struct Frags {
@@ -264,7 +252,7 @@ struct TileSrc {   // what a fetch needs
   int KP16, s_row, s_c, chunks, ppitch;
 };
 template <bool PROB>
-__device__ __forceinline__ void fetch_tile(StageP& st, const TileSrc& src, int j0) {
+__device__ __forceinline__ void fetch_tile(Stage& st, const TileSrc& src, int j0) {
   tile_fetch_p(st, src.ch16, src.row_label, j0);
   if (PROB) st.side = *reinterpret_cast<const u32x4*>(src.p16 + (size_t)(j0 + src.s_row) * 2 * src.KP16 + src.s_c * 8);
   fetch_fence();
@@ -282,7 +270,7 @@ __device__ __forceinline__ void tile_step(f32x16 (&acc)[8], const f16x8 (&a16)[1
                                           f32x16& x_next, const f16x8 (&w_prev)[2], f16x8 (&w_new)[2], const u32x4& lw_in,
                                           u32x4& lw_next, RowState& rs, const f32x16& pm, _Float16* cs0, u32* labs0,
                                           _Float16* ps0, int sbase, int vbase, int half, bool self_tile, const u32x4& self_patch,
-                                          StageP& stage, const TileSrc& src, int j0_fetch) {
+                                          Stage& stage, const TileSrc& src, int j0_fetch) {
   constexpr int b_cur = BUF, b_nxt = (BUF + 1) % kRing, b_new = (BUF + 2) % kRing;
   const _Float16* cs_cur = cs0 + b_cur * kBufHalfs;
   const _Float16* cs_nxt = cs0 + b_nxt * kBufHalfs;
@@ -318,7 +306,7 @@ __device__ __forceinline__ void tile_step(f32x16 (&acc)[8], const f16x8 (&a16)[1
       if (g == 13) *reinterpret_cast<u32x4*>(cdst + 16 * kPitchH) = stage.c;
       if (g == 14) *reinterpret_cast<u32x4*>(cdst + 24 * kPitchH) = stage.d;
       if (g == 15) {
-        if (threadIdx.x < 8) labs0[b_new * 8 + (threadIdx.x & 1) * 4 + (threadIdx.x >> 1)] = stage.lab4;
+        if (threadIdx.x < 8) labs0[b_new * 8 + (threadIdx.x & 1) * 4 + (threadIdx.x >> 1)] = stage.lab;
         if (PROB && (int)threadIdx.x < kTJ * src.chunks)
           *reinterpret_cast<u32x4*>(ps0 + (b_new * kTJ + src.s_row) * src.ppitch + src.s_c * 8) = stage.side;
       }
@@ -508,7 +496,7 @@ __global__ __launch_bounds__(kThreads, 1) void pixcon16p_sweep_kernel(
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[q][r] = 0.f;
 
-    StageP stage;
+    Stage stage;
     TileSrc src;
     src.ch16 = ch16; src.row_label = row_label; src.p16 = p16; src.KP16 = KP16; src.s_row = s_row; src.s_c = s_c;
     src.chunks = chunks; src.ppitch = ppitch;
@@ -601,55 +589,17 @@ __global__ __launch_bounds__(kThreads, 1) void pixcon16p_sweep_kernel(
   }
 }
 
-__global__ __launch_bounds__(kThreads) void pixcon16p_finalize_kernel(
-    const uint8_t* __restrict__ row_label, const ucd_pixcon_meta* __restrict__ meta, float inv_T, float m_run,
-    const int* __restrict__ us1, const int* __restrict__ us2, const float* __restrict__ negp, const float* __restrict__ lossp,
-    const float* __restrict__ qsump, const float* __restrict__ Up, const float* __restrict__ Vp, float* __restrict__ grad_a,
-    int ldg, float* __restrict__ row_stats, int maxA, float* __restrict__ row_loss) {
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int i = blockIdx.x * (kThreads / 64) + wave;
-  const int A = meta->A;
-  if (i >= A) return;
-  const int b = i / kBI, il = i - b * kBI;
-  const int u1a = us1[b], u1b = us1[b + 1], u2a = us2[b], u2b = us2[b + 1];
-  const int num = meta->label_count_c[row_label[i]] - 1;
-  const float R = (float)meta->n_valid;
-  float negs = 0.f, la = 0.f, qs = 0.f;   // negs in units of 2^m_run
-  for (int s = u1a; s < u1b; ++s) negs += negp[(size_t)s * kBI + il];
-  for (int s = u2a; s < u2b; ++s) {
-    la += lossp[(size_t)s * kBI + il];
-    qs += qsump[(size_t)s * kBI + il];
+// combine policy (pixcon_tiles.h): row i of block b sums the block's unit slots us[b] .. us[b + 1] - 1, [slot][128] each,
+// all in units of 2^m_run
+struct UnitSlots {
+  static constexpr CombineScale kScale = kScaleConst;
+  const int *us1, *us2;
+  float m_run;
+  __device__ __forceinline__ SlotRange row(int i) const {
+    const int b = i / kBI;
+    return {i - b * kBI, kBI, us1[b], us1[b + 1], us2[b], us2[b + 1]};
   }
-  const float coef = num > 0 ? inv_T / ((float)num * R) : 0.f;
-  const float ratio = negs > 0.f ? qs / negs : 0.f;   // U is in the same 2^m_run units: the scale cancels
-  const float rl = num > 0 ? -la / (float)num : 0.f;
-  if (grad_a) {
-    for (int c = lane * 4; c < ldg; c += 256) {
-      float4 uu = {0.f, 0.f, 0.f, 0.f}, vv = {0.f, 0.f, 0.f, 0.f};
-      if (c < kN) {
-        for (int s = u1a; s < u1b; ++s) {
-          const float4 t = *reinterpret_cast<const float4*>(Up + ((size_t)s * kBI + il) * kN + c);
-          uu.x += t.x; uu.y += t.y; uu.z += t.z; uu.w += t.w;
-        }
-        for (int s = u2a; s < u2b; ++s) {
-          const float4 t = *reinterpret_cast<const float4*>(Vp + ((size_t)s * kBI + il) * kN + c);
-          vv.x += t.x; vv.y += t.y; vv.z += t.z; vv.w += t.w;
-        }
-      }
-      float4 g = {coef * (ratio * uu.x - vv.x), coef * (ratio * uu.y - vv.y), coef * (ratio * uu.z - vv.z),
-                  coef * (ratio * uu.w - vv.w)};
-      *reinterpret_cast<float4*>(grad_a + (size_t)i * ldg + c) = g;
-    }
-  }
-  if (lane == 0) {
-    row_loss[i] = rl;
-    if (row_stats) {
-      row_stats[i] = negs > 0.f ? negs * exp2f(m_run) : 0.f;
-      row_stats[(size_t)maxA + i] = (float)num;
-      row_stats[(size_t)2 * maxA + i] = rl;
-    }
-  }
-}
+};
 
 struct LayoutP {
   int nbmax, umax;
@@ -704,13 +654,11 @@ void pixcon16p_plan(int BHW, int KP16, int use_prob, PixconPlan* p) {
   p->workspace = pixcon16p_workspace_bytes(BHW);
 }
 
-int pixcon16p_launch(const _Float16* ch16, const uint8_t* row_label, const _Float16* p16, int K,
-                     const ucd_pixcon_meta* meta, int BHW, float temperature, int shift_pos, int use_prob,
-                     float* loss_out, float* grad_a, int ldg, float* row_stats, void* workspace, size_t workspace_bytes,
-                     hipStream_t s) {
+int pixcon16p_launch(const _Float16* ch16, const uint8_t* row_label, const _Float16* p16, const ucd_pixcon_meta* meta, int BHW,
+                     float temperature, int shift_pos, int use_prob, float* loss_out, float* grad_a, int ldg, float* row_stats,
+                     void* workspace, const PixconPlan& p, hipStream_t s) {
   static const char* fn = "ucd_pixcon_loss[f16]";
   const LayoutP L = make_layout_p(BHW);
-  UCD_REQUIRE(workspace_bytes >= L.total, UCD_EWORKSPACE, "%s: workspace too small (%zu < %zu)", fn, workspace_bytes, L.total);
   char* ws = (char*)workspace;
   PlanHdr* hdr = (PlanHdr*)(ws + L.off_hdr);
   int* seg1 = (int*)(ws + L.off_seg1); int* seg2 = (int*)(ws + L.off_seg2);
@@ -720,7 +668,6 @@ int pixcon16p_launch(const _Float16* ch16, const uint8_t* row_label, const _Floa
   float* lossp = (float*)(ws + L.off_lossp); float* qsump = (float*)(ws + L.off_qsump);
   float* rowloss = (float*)(ws + L.off_rowloss);
   float* Up = (float*)(ws + L.off_Up); float* Vp = (float*)(ws + L.off_Vp);
-  const int KP16 = use_prob ? (K + 15) / 16 * 16 : 0;
   const float k2 = kLog2e / temperature;
   int dev = 0, cus = 0;
   UCD_REQUIRE(hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0,
@@ -729,29 +676,26 @@ int pixcon16p_launch(const _Float16* ch16, const uint8_t* row_label, const _Floa
   pixcon16p_plan_kernel<<<1, kPlanThreads, 0, s>>>(row_label, meta, L.umax, hdr, seg1, seg2, us1, us2, order1, order2);
   int rc = check_launch(fn);
   if (rc) return rc;
-  PixconPlan pl;
-  pixcon16p_plan(BHW, KP16, use_prob, &pl);
-  const size_t lds_base = pl.lds1, lds_prob = pl.lds2;
   // opt in to more than 64 KiB of dynamic LDS, per call (no process-wide state); only what is needed: the block-wide vote of
   // the probability instance keeps a static word of its own
-  UCD_TRY_LDS((pixcon16p_sweep_kernel<0, false>), (int)lds_base);
-  UCD_TRY_LDS((pixcon16p_sweep_kernel<1, false>), (int)lds_base);
-  UCD_TRY_LDS((pixcon16p_sweep_kernel<1, true>), (int)lds_prob);
-  pixcon16p_sweep_kernel<0, false><<<grid, kThreads, lds_base, s>>>(ch16, row_label, nullptr, 0, meta, hdr, seg1, us1, order1, us1,
-                                                                    k2, shift_pos, nullptr, nullptr, negp, mxp, Up);
+  UCD_TRY_LDS((pixcon16p_sweep_kernel<0, false>), (int)p.lds1);
+  UCD_TRY_LDS((pixcon16p_sweep_kernel<1, false>), (int)p.lds1);
+  UCD_TRY_LDS((pixcon16p_sweep_kernel<1, true>), (int)p.lds2);
+  pixcon16p_sweep_kernel<0, false><<<grid, kThreads, p.lds1, s>>>(ch16, row_label, nullptr, 0, meta, hdr, seg1, us1, order1, us1, k2,
+                                                                  shift_pos, nullptr, nullptr, negp, mxp, Up);
   rc = check_launch(fn);
   if (rc) return rc;
   if (use_prob)
-    pixcon16p_sweep_kernel<1, true><<<grid, kThreads, lds_prob, s>>>(ch16, row_label, p16, KP16, meta, hdr, seg2, us2, order2, us1,
-                                                                    k2, shift_pos, negp, mxp, lossp, qsump, Vp);
+    pixcon16p_sweep_kernel<1, true><<<grid, kThreads, p.lds2, s>>>(ch16, row_label, p16, p.kp, meta, hdr, seg2, us2, order2, us1, k2,
+                                                                   shift_pos, negp, mxp, lossp, qsump, Vp);
   else
-    pixcon16p_sweep_kernel<1, false><<<grid, kThreads, lds_base, s>>>(ch16, row_label, nullptr, 0, meta, hdr, seg2, us2, order2,
-                                                                      us1, k2, shift_pos, negp, mxp, lossp, qsump, Vp);
+    pixcon16p_sweep_kernel<1, false><<<grid, kThreads, p.lds1, s>>>(ch16, row_label, nullptr, 0, meta, hdr, seg2, us2, order2, us1,
+                                                                    k2, shift_pos, negp, mxp, lossp, qsump, Vp);
   rc = check_launch(fn);
   if (rc) return rc;
-  pixcon16p_finalize_kernel<<<ceil_div(BHW, kThreads / 64), kThreads, 0, s>>>(row_label, meta, 1.f / temperature, k2 - 14.5f,
-                                                                              us1, us2, negp, lossp, qsump, Up, Vp, grad_a,
-                                                                              ldg, row_stats, BHW, rowloss);
+  const UnitSlots slots = {us1, us2, k2 - 14.5f};
+  pixcon_combine_kernel<<<ceil_div(BHW, kThreads / 64), kThreads, 0, s>>>(slots, row_label, meta, 1.f / temperature, negp, lossp,
+                                                                          qsump, Up, Vp, grad_a, ldg, row_stats, BHW, rowloss);
   rc = check_launch(fn);
   if (rc) return rc;
   pixcon_launch_reduce(rowloss, meta, loss_out, s);
