@@ -525,6 +525,39 @@ int ucd_seg_losses_ex(const float* sem_s, int ld_s, const float* sem_t, int ld_t
                       int ignore_index, float ce_weight, float kd_weight, float* loss_out, float* d_sem, int ld_d,
                       void* workspace, size_t workspace_bytes, ucd_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Fused full-resolution BINARY cross entropy losses: --bce, --icarl, --method LWF-MC (csrc/seg_bce.hip).
+ * Rows as for ucd_seg_losses: sem_s [B*h*w, ld_s >= Ctot] / sem_t [B*h*w, ld_t >= K] float32 (sem_t may be NULL), labels int64
+ * [B, H, W].  With z = up(sem_s) [B, Ctot, H, W], zt = up(sem_t) [B, K, H, W] (up: bilinear, align_corners=False, as
+ * F.interpolate computes it), y the labels, s() the logistic function and
+ *   bce(z, t) = max(z, 0) - t z + log1p(exp(-|z|))                      (finite at any z; logits of +-90 are served)
+ *   loss_out[0] = 1 / (B H W) sum_p [y_p valid] sum_c bce(z_pc, [c == y_p])
+ *                 - BCEWithLogitsLossWithIgnoreIndex(reduction='none')(z, y).mean() (utils/loss.py:31-54, train.py:112/116);
+ *                 an all-ignored batch gives exactly 0
+ *   loss_out[1] = 1 / (B H W) sum_p sum_{c<K} bce(z_pc, s(zt_pc))
+ *                 - K * nn.BCEWithLogitsLoss()(z[:, :K], sigmoid(zt)) (train.py:119-124; no ignore mask; the sigmoid is applied
+ *                 AFTER the up-sampling); 0 with sem_t == NULL
+ *   d_sem[b, i, j, c] = d(hard_weight loss_out[0] + soft_weight loss_out[1]) / d sem_s[b, i, j, c]
+ *                 = 1 / (B H W) sum_p w_p(i, j) (hard_weight [y_p valid] (s(z_pc) - [c == y_p]) + soft_weight [c < K] (s(z_pc) - s(zt_pc)))
+ *                 with w_p(i, j) the bilinear weight of cell (i, j) in pixel p.
+ * d_sem may be NULL (losses only: the same loss_out bits).  Otherwise the call writes every row, columns < Ctot, each element
+ * ONCE - it does not accumulate, needs no memset and does not touch columns Ctot .. ld_d - 1.
+ * A label is valid when it is in [0, Ctot) and not ignore_index: any other value counts as ignored (the reference's F.one_hot
+ * raises for a label in [Ctot, ...) other than 255).
+ * Gather form: one wave per low-resolution cell re-evaluates the pixels under the cell's bilinear footprint and sums in
+ * registers; a pixel's loss is counted by the cell of its (y0, x0) corner; a second launch adds the per-cell pairs in index
+ * order.  No atomics, no fixed point: the same inputs give the same bits.  Any up-sampling factor >= 1 is served.
+ * workspace: ucd_seg_bce_workspace_bytes(B, h, w) bytes (one pair of floats per cell).
+ * Checked on the host before any device call: UCD_EINVAL (NULL sem_s / labels / loss_out / workspace; a size < 1; K < 1 or K >
+ * Ctot; ld_s < Ctot; ld_t < K with a teacher; ld_d < Ctot with d_sem; H < h or W < w), UCD_EWORKSPACE (a short workspace),
+ * UCD_EUNSUPPORTED (9 (Ctot + K) floats over 64 KB of LDS); else the hipError_t of a failed launch. */
+size_t ucd_seg_bce_workspace_bytes(int B, int h, int w);
+int ucd_seg_bce(const float* sem_s, int ld_s, const float* sem_t, int ld_t, const int64_t* labels,
+                int B, int H, int W, int h, int w, int Ctot, int K, int ignore_index,
+                float hard_weight, float soft_weight, float* loss_out /*[2]*/,
+                float* d_sem /* NULL: losses only */, int ld_d,
+                void* workspace, size_t workspace_bytes, ucd_stream_t stream);
+
 /* Validation on the device: bilinear up-sampling of the low-resolution logits
  * (segmentation_module.py:133), arg-max over the classes (train.py:242 `outputs.max(dim=1)`) and the confusion matrix of
  * metrics/stream_metrics.py:65-71 (`bincount(n * label + pred)` over the pixels with 0 <= label < n_classes) in one pass;

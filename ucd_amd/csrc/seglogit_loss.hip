@@ -17,6 +17,7 @@
 // addition has no order: the same bits on every run), fp32 atomics in the register form and for a d_sem that
 // is not 16-byte aligned (last bits run-dependent).  The loss sums use a fixed order in every form.
 #include "common.h"
+#include "upsample_index.h"
 
 #include <cmath>
 
@@ -32,26 +33,7 @@ constexpr int kRows = kTileY / 4;
 // training (a class set 70 below the leader), so a branch: the common path keeps its arithmetic.
 constexpr float kSubsetTiny = 1e-30f;
 
-// torch's align_corners=False source index.  Host and device: ucd_seg_losses_plan sizes the LDS with the very function the
-// kernels index it with (-ffp-contract=off on both sides: the same roundings)
-__host__ __device__ __forceinline__ void up_src(int dst, int in_size, float scale, int& i0, int& i1, float& l0, float& l1) {
-  float src = scale * ((float)dst + 0.5f) - 0.5f;
-  src = src < 0.f ? 0.f : src;
-  i0 = (int)src < in_size - 1 ? (int)src : in_size - 1;
-  i1 = i0 + (i0 < in_size - 1 ? 1 : 0);
-  l1 = src - (float)i0;
-  l0 = 1.f - l1;
-}
-
-// the low-resolution cells under the pixels [t0, min(t0 + tile, out)) of one dimension: the first cell and their count (the source
-// index is monotone in the pixel).  The one copy of the footprint arithmetic: the kernels index their LDS with it, the plan sizes it
-__host__ __device__ __forceinline__ void tile_span(int t0, int tile, int out, int in_size, float scale, int& first, int& count) {
-  int last, dummy;
-  float f0, f1;
-  up_src(t0, in_size, scale, first, dummy, f0, f1);
-  up_src((t0 + tile < out ? t0 + tile : out) - 1, in_size, scale, dummy, last, f0, f1);
-  count = last - first + 1;
-}
+// up_src (torch's align_corners=False source index) and tile_span (the cells under a run of pixels): upsample_index.h
 
 struct Footprint { int ya, xa, ny, nx, ncell; };     // cells [ya, ya + ny) x [xa, xa + nx) lie under a tile
 __device__ __forceinline__ Footprint tile_footprint(int ty0, int tx0, int tile_y, int H, int W, int h, int w, float scale_h,

@@ -1,0 +1,30 @@
+// The source-index arithmetic of the bilinear up-sampling (F.interpolate, align_corners=False), shared by the kernels that
+// rebuild full-resolution logits from the low-resolution ones (seglogit_loss.hip, seg_bce.hip).  One copy: host and device,
+// under -ffp-contract=off on both sides, so a plan computed on the host rounds exactly as the kernel it sizes.
+#pragma once
+#include <hip/hip_runtime.h>
+
+namespace ucd {
+
+// torch's align_corners=False source index.  Host and device: ucd_seg_losses_plan sizes the LDS with the very function the
+// kernels index it with (-ffp-contract=off on both sides: the same roundings)
+__host__ __device__ __forceinline__ void up_src(int dst, int in_size, float scale, int& i0, int& i1, float& l0, float& l1) {
+  float src = scale * ((float)dst + 0.5f) - 0.5f;
+  src = src < 0.f ? 0.f : src;
+  i0 = (int)src < in_size - 1 ? (int)src : in_size - 1;
+  i1 = i0 + (i0 < in_size - 1 ? 1 : 0);
+  l1 = src - (float)i0;
+  l0 = 1.f - l1;
+}
+
+// the low-resolution cells under the pixels [t0, min(t0 + tile, out)) of one dimension: the first cell and their count (the source
+// index is monotone in the pixel).  The one copy of the footprint arithmetic: the kernels index their LDS with it, the plan sizes it
+__host__ __device__ __forceinline__ void tile_span(int t0, int tile, int out, int in_size, float scale, int& first, int& count) {
+  int last, dummy;
+  float f0, f1;
+  up_src(t0, in_size, scale, first, dummy, f0, f1);
+  up_src((t0 + tile < out ? t0 + tile : out) - 1, in_size, scale, dummy, last, f0, f1);
+  count = last - first + 1;
+}
+
+}  // namespace ucd

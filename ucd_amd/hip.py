@@ -161,6 +161,8 @@ SIGNATURES = {
     "ucd_seg_losses_workspace_bytes": (_z, [_i, _i, _i]),
     "ucd_seg_losses_plan": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p]),
     "ucd_seg_losses": (_i, [_p, _i, _p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _p, _p, _i, _p, _z, _p]),
+    "ucd_seg_bce_workspace_bytes": (_z, [_i, _i, _i]),
+    "ucd_seg_bce": (_i, [_p, _i, _p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _p, _p, _i, _p, _z, _p]),
     "ucd_seg_losses_plan_ex": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p]),
     "ucd_seg_losses_ex": (_i, [_p, _i, _p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _f, _f, _p, _p, _i, _p, _z, _p]),
 }

@@ -63,6 +63,61 @@ class _FusedSegLosses(torch.autograd.Function):
         return grad, None, None, None, None, None, None, None, None, None
 
 
+class _FusedSegBCE(torch.autograd.Function):
+    """total = hard_weight * BCE + soft_weight * soft from the LOW-resolution logits (ucd_seg_bce, csrc/seg_bce.hip): BCE is the
+    reference's ``BCEWithLogitsLossWithIgnoreIndex(reduction='none')(up(sem), labels).mean()``, soft its combined iCaRL term
+    ``K * BCEWithLogitsLoss()(up(sem)[:, :K], sigmoid(up(sem_old)))``.  Without a gradient to form, the kernel gets no ``d_sem``."""
+
+    @staticmethod
+    def forward(ctx, sem, sem_old, labels, hard_weight, soft_weight, ignore_index):
+        lib = hip.load()
+        B, Ctot, h, w = sem.shape
+        H, W = labels.shape[-2:]
+        s = sem.detach().permute(0, 2, 3, 1).reshape(B * h * w, Ctot).float().contiguous()
+        t, K = None, 1
+        if sem_old is not None:
+            K = sem_old.shape[1]
+            t = sem_old.detach().permute(0, 2, 3, 1).reshape(B * h * w, K).float().contiguous()
+        labels = labels.contiguous()
+        out = torch.empty(2, dtype=torch.float32, device=sem.device)
+        need_grad = ctx.needs_input_grad[0]
+        d = torch.empty(B * h * w, Ctot, dtype=torch.float32, device=sem.device) if need_grad else None
+        nbytes = lib.ucd_seg_bce_workspace_bytes(B, h, w)
+        ws = hip.workspace(nbytes, sem.device, "seg_bce")
+        with hip._timed("ucd_seg_bce", B * H * W * 8 + B * h * w * (2 * Ctot + K) * 4):
+            hip._check(lib.ucd_seg_bce(hip.ptr(s), Ctot, hip.ptr(t), K, hip.ptr(labels), B, H, W, h, w, Ctot, K, int(ignore_index),
+                                       float(hard_weight), float(soft_weight), hip.ptr(out), hip.ptr(d), Ctot, hip.ptr(ws), nbytes,
+                                       hip.stream()), "ucd_seg_bce")
+        if need_grad:
+            ctx.save_for_backward(d)
+        ctx.meta = (B, Ctot, h, w, sem.dtype)
+        bce, soft = out[0], out[1]
+        total = hard_weight * bce + soft_weight * soft
+        ctx.mark_non_differentiable(bce, soft)
+        return total, bce, soft
+
+    @staticmethod
+    def backward(ctx, g, _gbce, _gsoft):
+        (d,) = ctx.saved_tensors
+        B, Ctot, h, w, dtype = ctx.meta
+        grad = (d * g).view(B, h, w, Ctot).permute(0, 3, 1, 2).to(dtype)
+        return grad, None, None, None, None, None
+
+
+def fused_seg_bce(sem, sem_old, labels, hard_weight=1.0, soft_weight=0.0, ignore_index=255):
+    """Returns (hard_weight*BCE + soft_weight*soft [differentiable w.r.t. ``sem``], BCE, soft) from the LOW-resolution logits:
+    BCE is the reference's ``BCEWithLogitsLossWithIgnoreIndex(reduction='none')(up(sem), labels).mean()`` (utils/loss.py:31-54,
+    train.py:112/116) and soft, with a teacher of K classes, ``K * nn.BCEWithLogitsLoss()(up(sem)[:, :K], sigmoid(up(sem_old)))``
+    (the combined iCaRL term of train.py:119-124 before ``icarl_importance``; 0 without ``sem_old``); ``up`` = bilinear to the label
+    size.  A label outside ``[0, Ctot)`` counts as ignored.  Under ``torch.no_grad()`` or with a ``sem`` that requires no gradient
+    only the losses are computed."""
+    if not sem.is_cuda:
+        raise RuntimeError("ucd_amd.loss.fused_seg_bce runs on the GPU only (there is no CPU fallback)")
+    if sem_old is not None and (sem_old.shape[0] != sem.shape[0] or sem_old.shape[2:] != sem.shape[2:] or sem_old.shape[1] > sem.shape[1]):
+        raise ValueError(f"student and teacher logits do not match: {tuple(sem.shape)} vs {tuple(sem_old.shape)}")
+    return _FusedSegBCE.apply(sem, sem_old, labels, hard_weight, soft_weight, ignore_index)
+
+
 class _FusedAttnMSE(torch.autograd.Function):
     """weight * MSE(att(x_s), att(x_t)) from the raw maps (ucd_attn_mse, csrc/featdist.hip); the attention factor of the
     student is detached, as in the reference (segmentation_module.py:93)."""

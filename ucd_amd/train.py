@@ -20,7 +20,10 @@ The logit losses - (unbiased or plain) CE with no, the plain or the unbiased KD 
 come from one fused HIP kernel on the low-resolution logits (``UCD_SEG_KD_EX=0``: only the pairs without ``--alpha`` / plain
 KD); ILT's encoder term is one HIP operation on the raw maps (``UCD_FUSED_LDE=0``: torch), which puts ILT inside the graphs.
 EWC / PI / RW (``--method EWC|PI|RW``) add the weight-space penalty of ucd_amd.regularizer between the gradient
-all-reduce and the optimiser (train.py:139-145).  Out of scope on this path (raise ``NotImplementedError``): BCE/iCaRL.
+all-reduce and the optimiser (train.py:139-145).  ``--bce``, ``--icarl`` and ``--method LWF-MC`` take the per-class binary cross
+entropy and the combined iCaRL term (train.py:119-124) from their own fused HIP kernel (``fused_seg_bce``, csrc/seg_bce.hip),
+inside the graphs like the others.  Out of scope (raise ``NotImplementedError``): ``--icarl_disjoint`` with a teacher, and any BCE
+run on a CPU device.
 """
 from __future__ import annotations
 
@@ -34,7 +37,7 @@ import torch.nn as nn
 from . import switches as _switches
 from .contrastive import ucd_contrastive_loss
 from .loss import (KnowledgeDistillationLoss, UnbiasedCrossEntropy, UnbiasedKnowledgeDistillationLoss,
-                   fused_attn_mse, fused_seg_losses)
+                   fused_attn_mse, fused_seg_bce, fused_seg_losses)
 
 
 def _raw(features, name):
@@ -50,9 +53,17 @@ class Trainer:
             self.tot_classes = tot_classes
         else:
             self.old_classes, self.tot_classes = 0, getattr(opts, "num_classes", None) or 21
-        if opts.bce or opts.icarl:
-            raise NotImplementedError("BCE / iCaRL (--bce, --icarl, --method LWF-MC) are other baselines, "
-                                      "outside the UCD hot path")
+        # BCE family (train.py:34-36, :55-66): the criterion is the binary cross entropy of every class, --icarl adds the combined
+        # distillation term next to a teacher.  Both come from one fused HIP kernel on the low-resolution logits (fused_seg_bce)
+        self.bce = bool(opts.bce or opts.icarl)
+        self.icarl_combined = bool(opts.icarl and not getattr(opts, "icarl_disjoint", False) and model_old is not None)
+        self.icarl = float(getattr(opts, "icarl_importance", 1.0))
+        if self.bce and device.type != "cuda":
+            raise NotImplementedError("BCE / iCaRL (--bce, --icarl, --method LWF-MC) exist on the GPU only: the losses are one fused "
+                                      "HIP kernel (ucd_amd.loss.fused_seg_bce), there is no CPU path")
+        if opts.icarl and getattr(opts, "icarl_disjoint", False) and model_old is not None:
+            raise NotImplementedError("BCE / iCaRL: --icarl_disjoint with a teacher is not supported - the reference's loop never assigns "
+                                      "its loss on that branch (train.py:110-116 has no else), so there is nothing to be at parity with")
         self.temperature = opts.temperature
         self.pixcon_weight = getattr(opts, "pixcon_weight", 0.01)      # the reference hard-codes /100 (train.py:116)
         # the reference clamps down-sampled labels at the VOC bound 20 (utils/utils.py:267-268); datasets
@@ -92,6 +103,14 @@ class Trainer:
         any_pair = _switches.get("UCD_SEG_KD_EX", "1") != "0" and math.isfinite(self.alpha) and self.alpha != 0.0
         self.fuse_logit_losses = (getattr(opts, "fused_logit_losses", True) and device.type == "cuda"
                                   and (not self.lkd_flag or first_pair or any_pair))
+        if self.bce:
+            # the student never up-samples under BCE: a --loss_kd term next to it (--method LWF --bce) comes from the fused kernel
+            # too (its CE value discarded, old_cl 1 next to a teacher), which only the any-pair form of that kernel serves
+            if self.lkd_flag and not any_pair:
+                raise NotImplementedError("BCE / iCaRL with --loss_kd needs the fused logit-loss kernel for the KD term (UCD_SEG_KD_EX=0 "
+                                          "or an --alpha of 0 / inf would send it to the torch modules): BCE runs have no up-sampled "
+                                          "logits")
+            self.fuse_logit_losses = True
         # an ILT iteration reads the lazy attention maps of the Features dict unless both of its losses are fused: such a run stays
         # outside the teacher graph and the whole-step graph
         self.lde_lazy = self.lde_flag and not (self.fused_lde and self.fuse_logit_losses)
@@ -302,7 +321,18 @@ class Trainer:
                                           ret_intermediate=self.ret_intermediate, **up)
         if model_old is not None and self._side is not None:
             torch.cuda.current_stream(self.device).wait_stream(self._side)     # teacher outputs are needed from here on
-        if fuse:
+        soft = None
+        if self.bce:
+            # train.py:112/116 with the BCE criterion, and :119-124: up-sampling + per-class BCE (+ the combined iCaRL term against
+            # sigmoid(up(teacher))) + the gradient w.r.t. the low-res logits in one kernel; --unce is ignored (train.py:35-38)
+            total, ce, soft = fused_seg_bce(features["sem"], features_old["sem"] if self.icarl_combined else None, labels, 1.0,
+                                            self.icarl if self.icarl_combined else 0.0)
+            if self.lkd_flag:
+                # --loss_kd next to BCE: the KD term of the softmax kernel, its CE discarded; the two gradients add in autograd
+                kd_total, _, kd = fused_seg_losses(features["sem"], features_old["sem"], labels, 1, 0.0, self.lkd,
+                                                   kd=self.kd_mode, alpha=self.alpha)
+                total = total + kd_total
+        elif fuse:
             # one pass over the label map: bilinear up-sampling + CE (+ KD) + gradient w.r.t. the low-res logits
             total, ce, kd = fused_seg_losses(features["sem"], features_old["sem"] if self.lkd_flag else None, labels,
                                              self.old_classes if self.unce else 1, 1.0,
@@ -340,6 +370,8 @@ class Trainer:
                      "con": con.detach()}
         if self.regularizer_flag:
             self.last["reg"] = l_reg.detach()
+        if self.icarl_combined:
+            self.last["icarl"] = (self.icarl * soft).detach()       # l_icarl of train.py:123; its gradient is part of `total`
         return self.last
 
     def train(self, cur_epoch, optim, train_loader, scheduler=None, print_int=10, logger=None):
@@ -362,6 +394,9 @@ class Trainer:
             if "reg" in r:                                      # train.py:154-157: l_reg counts as regularisation loss
                 reg_loss += r["reg"]
                 interval += r["reg"]
+            if "icarl" in r:                                    # train.py:155-156: l_icarl counts as regularisation loss
+                reg_loss += r["icarl"]
+                interval += r["icarl"]
             n += 1
             if (cur_step + 1) % print_int == 0:
                 value = (interval / print_int).item()           # the only host sync of the interval
@@ -396,7 +431,9 @@ class Trainer:
             check_mailbox(None)
 
     def validate(self, loader, metrics, ret_samples_ids=None, logger=None):
-        """Evaluation loop (train.py:185-270): class loss + confusion matrix, accumulated on the device."""
+        """Evaluation loop (train.py:185-270): class loss + confusion matrix, accumulated on the device.  Under BCE the class loss is
+        the fused BCE on the low-resolution logits.  Validation runs no teacher, so the teacher-side terms (KD, encoder, iCaRL) are
+        not evaluated and its "Reg Loss" stays 0, for every method."""
         metrics.reset()
         model = self.model
         dev = self.device
@@ -414,8 +451,17 @@ class Trainer:
                     with self._autocast():
                         _, feats = model(images, ret_intermediate=False, upsample=False)
                     sem = feats["sem"]
-                    class_loss += fused_seg_losses(sem, None, labels, self.old_classes if self.unce else 1, 1.0, 0.0)[1]
+                    if self.bce:
+                        class_loss += fused_seg_bce(sem, None, labels)[1]
+                    else:
+                        class_loss += fused_seg_losses(sem, None, labels, self.old_classes if self.unce else 1, 1.0, 0.0)[1]
                     metrics.update_from_logits(labels, sem)
+                elif self.bce:
+                    # metrics without update_from_logits: the up-sampled logits only feed the arg-max, the loss stays on the kernel
+                    with self._autocast():
+                        outputs, feats = model(images, ret_intermediate=False)
+                    class_loss += fused_seg_bce(feats["sem"], None, labels)[1]
+                    metrics.update(labels, outputs.argmax(dim=1))
                 else:
                     with self._autocast():
                         outputs, _ = model(images, ret_intermediate=False)
