@@ -22,6 +22,7 @@ from __future__ import annotations
 
 import os
 from collections import OrderedDict
+from typing import NamedTuple
 
 import torch
 import torch.nn as nn
@@ -518,6 +519,31 @@ def _own_conv3x3(M, K, N):
     return tiles >= int(_env("UCD_OWN3X3_MIN_TILES", "1"))
 
 
+LINK_CHAIN, LINK_BLOCK = 1, 3     # csrc/abn_node.cpp Link::Kind
+
+
+class Link(NamedTuple):
+    """The backward link a conv + ABN node offers on its output (csrc/abn_node.cpp: offer / serve / claim): the producer's ``z``,
+    statistics buffer, bias, ``partial`` and flag, its activation code and slope.  ``LINK_CHAIN`` hangs on the output as
+    ``_ucd_link`` (the one consumer is the next conv + ABN node), ``LINK_BLOCK`` as ``_ucd_blink`` (the producer is the last node of a
+    residual block, the consumer the first convolution + shortcut of the next; ``bias`` None, ``act`` 0: the block activation)."""
+    z: torch.Tensor
+    buf: torch.Tensor
+    bias: object
+    partial: torch.Tensor
+    flag: object
+    act: int
+    slope: float
+    kind: int
+
+
+def _offer_link(y, z, buf, bias, partial, flag, act, slope, block):
+    if block:
+        y._ucd_blink = Link(z, buf, None, partial, flag, 0, float(slope), LINK_BLOCK)
+    else:
+        y._ucd_link = Link(z, buf, bias, partial, flag, int(act), float(slope), LINK_CHAIN)
+
+
 class _ConvABNFunction(torch.autograd.Function):
     """Python twin of csrc/abn_node.cpp::ConvABNTrainNode (single process; the node adds the SyncBN exchange and the
     shortcut fold): z = x . w^T with the statistics in the GEMM epilogue -> finalize -> y = act(norm(z) [+ residual]).
@@ -525,7 +551,7 @@ class _ConvABNFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w4, weight, bias, residual, running_mean, running_var, momentum, eps, act, slope, fused, dilation=0,
-                wflip=None, own_dgrad=False, wgrad_conv=False, make_link=False, link=None, with_skip=False, blink=None):
+                wflip=None, own_dgrad=False, wgrad_conv=False, make_link=False, link=None, with_skip=False):
         from . import hip
         B, K, H, W = x.shape
         N = w4.shape[0]
@@ -537,10 +563,7 @@ class _ConvABNFunction(torch.autograd.Function):
         conv3 = dilation > 0
         w2 = w4.permute(0, 2, 3, 1).reshape(N, 9 * K) if conv3 else w4.reshape(N, K)
         ctx.conv3 = (dilation, wflip, own_dgrad, wgrad_conv)
-        # backward link (see ConvABNTrainNode): link = the producer's (z, buf, bias, partial, flag, act, slope)
-        ctx.link = link
-        ctx.blink = blink if with_skip else None        # block link (kind 3): (z, buf, partial, flag, slope) of the block in front
-        ctx.with_skip = with_skip
+        ctx.link = link                                 # the Link consumed (see ConvABNTrainNode), or None
         ctx.my_link = None
         if conv3 and not fused:
             z = F.conv2d(x, w4, None, 1, dilation, dilation).contiguous(memory_format=torch.channels_last)
@@ -561,11 +584,8 @@ class _ConvABNFunction(torch.autograd.Function):
         ctx.cfg = (act, slope, residual is not None)
         if make_link and bias is not None and (act & hip.ACT_MASK) != hip.ACT_ELU and (residual is None or needs_y):
             partial = torch.empty(hip.conv1x1_row_tiles(M), 2, N, dtype=torch.float32, device=x.device)
-            ctx.my_link = (partial, [0, 0, 0])   # {served, address of the consumer's dx, its version} (see ConvABNTrainNode::backward)
-            if residual is None:
-                y._ucd_link = (z, buf, bias, partial, ctx.my_link[1], act, slope)
-            else:                                # the block's last node: the NEXT block's conv1 + shortcut node may serve it
-                y._ucd_blink = (z, buf, partial, ctx.my_link[1], slope)
+            ctx.my_link = (partial, [0, 0, 0])   # {served, address of the consumer's dx, its version} (see LinkFlag in csrc/abn_node.cpp)
+            _offer_link(y, z, buf, bias, partial, ctx.my_link[1], act, slope, block=residual is not None)
         if with_skip:
             return y, x.view_as(x)
         return y
@@ -607,14 +627,15 @@ class _ConvABNFunction(torch.autograd.Function):
         dilation, wflip, own_dgrad, wgrad_conv = ctx.conv3
         link = ctx.link
 
-        def link_args(dx):     # out_mode 3 against the producer's statistics; marks the link as served (for THIS dx)
-            lz, lbuf, lbias, lpart, lflag, lact, lslope = link
-            C = lz.shape[1]
-            lflag[0] = 1
-            lflag[1] = dx.data_ptr()
-            lflag[2] = dx._version
-            return dict(out_mode=3, out_norm=(lbuf[3 * C:4 * C], lbuf[5 * C:], lbias, lbuf[4 * C:5 * C], lact & hip.ACT_MASK, lslope),
-                        residual=rows(lz), partial=lpart)
+        def serve(dx):     # the producer's backward reduction as the epilogue of the product that writes dx; marks the link served
+            C = link.z.shape[1]
+            link.flag[:3] = 1, dx.data_ptr(), dx._version
+            mean, invstd = link.buf[3 * C:4 * C], link.buf[4 * C:5 * C]
+            if link.kind == LINK_BLOCK:        # out_mode 4 against the block in front
+                return dict(out_mode=4, out_norm=(mean, None, None, invstd, hip.ACT_LEAKY_RELU, link.slope), residual=rows(x),
+                            side2=rows(link.z), partial=link.partial)
+            return dict(out_mode=3, out_norm=(mean, link.buf[5 * C:], link.bias, invstd, link.act & hip.ACT_MASK, link.slope),
+                        residual=rows(link.z), partial=link.partial)
         dx = None
         if dilation > 0:
             if ctx.needs_input_grad[0]:
@@ -623,7 +644,7 @@ class _ConvABNFunction(torch.autograd.Function):
                 if own_dgrad:
                     dx = torch.empty_like(x)
                     hip.conv1x1(rows(dz), wflip.permute(0, 2, 3, 1).reshape(K, 9 * N), rows(dx), conv3=(H, W, dilation),
-                                **(link_args(dx) if link is not None else {}))
+                                **(serve(dx) if link is not None else {}))
                 else:
                     dx = F.conv2d(dz, wflip, None, 1, dilation, dilation)
         elif ctx.needs_input_grad[0]:
@@ -631,42 +652,43 @@ class _ConvABNFunction(torch.autograd.Function):
                     and dskip.is_contiguous(memory_format=torch.channels_last) and own_dgrad and wflip is not None)
             dx = dskip if fold else torch.empty_like(x)
             if own_dgrad and wflip is not None:
-                extra = {}
-                if ctx.blink is not None and (fold or dskip is None):
-                    bz, bbuf, bpart, bflag, bslope = ctx.blink            # block link: out_mode 4 against the block in front
-                    bflag[0], bflag[1], bflag[2] = 1, dx.data_ptr(), dx._version
-                    extra = dict(out_mode=4, out_norm=(bbuf[3 * K:4 * K], None, None, bbuf[4 * K:5 * K], hip.ACT_LEAKY_RELU, bslope),
-                                 residual=rows(x), side2=rows(bz), partial=bpart)
-                elif link is not None and dskip is None:
-                    extra = link_args(dx)
-                hip.conv1x1(rows(dz), wflip.reshape(K, N), rows(dx), accumulate=fold, **extra)
+                # a chain link needs dx to be the whole gradient; a block link also takes the shortcut's folded in
+                served = link is not None and (dskip is None or (fold and link.kind == LINK_BLOCK))
+                hip.conv1x1(rows(dz), wflip.reshape(K, N), rows(dx), accumulate=fold, **(serve(dx) if served else {}))
             else:
                 hip.gemm_bf16(1, rows(dz), w4.reshape(N, K), rows(dx))
             if dskip is not None and not fold:
                 dx = dx + dskip
         # the own kernel's fallback is MIOpen here, where the C++ node falls back to the split products on a 1x1 layer
         dw = _conv_wgrad(dz, x, w4, dilation or 1, wgrad_conv, WGRAD_LIBRARY) if ctx.needs_input_grad[1] else None
-        return dx, dw, sums[N:], sums[:N], dres, None, None, None, None, None, None, None, None, None, None, None, None, None, None, None
+        return (dx, dw, sums[N:], sums[:N], dres) + (None,) * 14
 
 
-def _conv_abn_train(conv, bn, x, residual=None, activation=None, activation_param=None, with_skip=False, make_link=False):
-    """``bn(conv(x) [, residual])`` of a wide 1x1 convolution and a training-mode HIP ABN as ONE autograd node
-    (csrc/abn_node.cpp::ConvABNTrainNode): the ABN's batch statistics come out of the GEMM's epilogue.  Returns None when the
-    pair is not eligible (the caller then runs the modules one after the other), else ``y`` or ``(y, shortcut alias of x)``.
-    ``make_link``: the caller promises that ``y`` feeds exactly one further ``_conv_abn_train`` call and nothing else; ``y`` then
-    carries the link (``y._ucd_link``) through which that consumer's input-gradient product does this ABN's backward reduction
-    in its epilogue (csrc/abn_node.cpp; under SyncBN the producer all-reduces the combined sums; ``UCD_BWD_LINK=0`` switches it
-    off)."""
+class _Route(NamedTuple):
+    """What ``_conv_abn_route`` decided for one conv + ABN pair (the arguments of the node of the same names)."""
+    is3: bool
+    stride: int          # 0: not one of the own strided layers
+    fused: bool
+    dilation: int
+    own_dgrad: bool
+    wflip: object        # the cached flipped / transposed bf16 weight, where there is one
+    wgrad_conv: int
+    link: object         # the Link this node may serve, or None
+    make_link: bool
+
+
+def _conv_abn_route(conv, bn, x, residual, with_skip, make_link):
+    """Is the pair eligible for the one-node path, and on which kernels does it run?  None: the module path."""
     if _env("UCD_FUSED_CONV1X1", "1") == "0":
         return None
-    link = getattr(x, "_ucd_link", None) if _env("UCD_BWD_LINK", "1") != "0" else None
-    # block link (csrc/abn_node.cpp: block_link_epilogue): x is the output of a residual block whose last node offers its
-    # backward reduction to the first convolution of THIS identity-shortcut block (UCD_BLOCK_LINK=0 switches only this kind off)
-    blink = (getattr(x, "_ucd_blink", None) if (with_skip and _env("UCD_BWD_LINK", "1") != "0"
-                                                and _env("UCD_BLOCK_LINK", "1") != "0") else None)
-    make_link = make_link and _env("UCD_BWD_LINK", "1") != "0"
-    if residual is not None and _env("UCD_BLOCK_LINK", "1") == "0":
-        make_link = False
+    links = _env("UCD_BWD_LINK", "1") != "0"
+    block_links = links and _env("UCD_BLOCK_LINK", "1") != "0"      # UCD_BLOCK_LINK=0 switches only this kind off
+    # x is the output of a conv + ABN node (chain link) or, for the first convolution of an identity-shortcut block, of the residual
+    # block in front (block link), which offers its backward reduction to this node's input-gradient product (csrc/abn_node.cpp)
+    link = getattr(x, "_ucd_blink", None) if (with_skip and block_links) else None
+    if link is None and links:
+        link = getattr(x, "_ucd_link", None)
+    make_link = bool(make_link and (links if residual is None else block_links))
     is3 = isinstance(conv, Conv3x3)
     stride = _own_stride(conv) if not (with_skip or residual is not None) else 0
     if stride:
@@ -675,13 +697,13 @@ def _conv_abn_train(conv, bn, x, residual=None, activation=None, activation_para
             and _is_fused_abn(bn) and bn.training and bn.weight is not None and torch.is_grad_enabled() and x.is_cuda
             and x.dim() == 4 and x.dtype == torch.bfloat16 and conv.in_channels % 64 == 0 and conv.out_channels % 64 == 0):
         return None
-    dilation, wflip, fused, own_dgrad, wgrad_conv = 0, None, None, False, WGRAD_LIBRARY
+    dilation, wflip, own_dgrad, wgrad_conv = 0, None, False, WGRAD_LIBRARY
     if stride:
         # the strided layers of a stage's first block: forward (+ statistics) and weight gradient on the own kernels, the input
         # gradient stays with the library's backward-data solver; no link consumed (the producer falls back to its own reduction)
         if is3 and not conv.weight.is_contiguous(memory_format=torch.channels_last):
             return None
-        dilation, fused, link, blink = (conv.dilation[0] if is3 else 0), True, None, None
+        dilation, fused, link = (conv.dilation[0] if is3 else 0), True, None
     elif is3:
         if not (conv.stride == (1, 1) and conv.padding == conv.dilation and conv.dilation[0] == conv.dilation[1]
                 and conv.groups == 1 and not with_skip and conv.weight.is_contiguous(memory_format=torch.channels_last)):
@@ -695,71 +717,72 @@ def _conv_abn_train(conv, bn, x, residual=None, activation=None, activation_para
         wflip = conv._w16_flip if conv.working_weight() is not None else None
     else:
         fused = _own_gemm_with_stats(conv.in_channels, conv.out_channels)
-        own_dgrad = conv.own_dgrad or (link is not None and conv.link_dgrad and not with_skip) or (blink is not None and conv.link_dgrad)
-        # the transposed weight: cached with the bf16 working copies, else made per call below (same kernels either way)
+        own_dgrad = conv.own_dgrad or (link is not None and conv.link_dgrad and (link.kind == LINK_BLOCK or not with_skip))
+        # the transposed weight: cached with the bf16 working copies, else made per call (same kernels either way)
         wflip = conv._w16_flip if (own_dgrad and conv.working_weight() is not None) else None
         # narrow layers (<= 512 channels at 65^2 / 129^2): MIOpen's weight-gradient solver beats the split-M products
         wgrad_conv = WGRAD_SPLIT if conv.wide else WGRAD_LIBRARY
     if _own_wgrad():
         wgrad_conv = WGRAD_OWN
-    if link is not None and (not own_dgrad or with_skip):
-        link = None                              # the consumer's input gradient does not run on the own kernel: no link
-    if blink is not None and (not own_dgrad or is3):
-        blink = None
+    # the consumer's input gradient must run on the own kernel; a chain link wants no shortcut next to it, a block link a 1x1 layer
+    if link is not None and (not own_dgrad or (is3 if link.kind == LINK_BLOCK else with_skip)):
+        link = None
+    return _Route(is3, stride, bool(fused), dilation, bool(own_dgrad), wflip, int(wgrad_conv), link, make_link)
+
+
+def _conv_abn_train(conv, bn, x, residual=None, activation=None, activation_param=None, with_skip=False, make_link=False):
+    """``bn(conv(x) [, residual])`` of a wide 1x1 convolution and a training-mode HIP ABN as ONE autograd node
+    (csrc/abn_node.cpp::ConvABNTrainNode): the ABN's batch statistics come out of the GEMM's epilogue.  Returns None when the
+    pair is not eligible (the caller then runs the modules one after the other), else ``y`` or ``(y, shortcut alias of x)``.
+    ``make_link``: the caller promises that ``y`` feeds exactly one further ``_conv_abn_train`` call and nothing else; ``y`` then
+    carries the link (``y._ucd_link``) through which that consumer's input-gradient product does this ABN's backward reduction
+    in its epilogue (csrc/abn_node.cpp; under SyncBN the producer all-reduces the combined sums; ``UCD_BWD_LINK=0`` switches it
+    off)."""
+    r = _conv_abn_route(conv, bn, x, residual, with_skip, make_link)
+    if r is None:
+        return None
     from . import abn as _abn
     from . import hip
     node = _gemm_node()
     if node is None or not hasattr(node, "conv_abn_train"):
-        # no C++ node (not built, or switched off by bench.py's instrumented pass): the Python twin, single process only
-        if stride:
-            return None                          # the twin has no strided form: the module path
+        # no C++ node (not built, or switched off by bench.py's instrumented pass): the Python twin, single process only and
+        # without a strided form (the module path)
+        node = None
         dense = lambda t: t.dim() == 4 and t.is_contiguous(memory_format=torch.channels_last) and t.shape[2] > 1 and t.shape[3] > 1
-        if (_lib_gemm() is None or _abn._group_size(bn._group()) > 1 or not dense(x)
+        if (r.stride or _lib_gemm() is None or _abn._group_size(bn._group()) > 1 or not dense(x)
                 or (residual is not None and not (dense(residual) and residual.dtype == x.dtype))):
             return None
-        w16 = conv.working_weight()
-        if w16 is None:
-            w16 = conv.weight.to(x.dtype)
-        if own_dgrad and not is3 and wflip is None:
-            wflip = w16.reshape(conv.out_channels, conv.in_channels).t().contiguous().view(conv.in_channels, conv.out_channels, 1, 1)
-        act = _abn._act_code(bn.activation if activation is None else activation) | (hip.NORM_ABS_GAMMA if bn._abs_gamma else 0)
-        slope = bn.activation_param if activation_param is None else activation_param
-        bn.__dict__.pop("_eval_cache", None)
-        return _ConvABNFunction.apply(x, w16, bn.weight, bn.bias, residual, bn.running_mean, bn.running_var, bn.momentum, bn.eps,
-                                      act, slope, fused, dilation, wflip, own_dgrad, wgrad_conv, bool(make_link), link,
-                                      bool(with_skip), blink)
-    if not node.dense_channels_last(x):
-        return None
-    if residual is not None and not (residual.dtype == x.dtype and node.dense_channels_last(residual)):
-        return None
-    group = bn._group()
-    world = _abn._group_size(group)
-    sync = group is not False and (world > 1 or (_abn._FORCE_SYNC and torch.distributed.is_initialized()))
-    comm = _abn.direct_comm(group) if sync else None
-    if sync and comm is None:
-        return None
+    else:
+        if not node.dense_channels_last(x):
+            return None
+        if residual is not None and not (residual.dtype == x.dtype and node.dense_channels_last(residual)):
+            return None
+        group = bn._group()
+        world = _abn._group_size(group)
+        sync = group is not False and (world > 1 or (_abn._FORCE_SYNC and torch.distributed.is_initialized()))
+        comm = _abn.direct_comm(group) if sync else None
+        if sync and comm is None:
+            return None
     w16 = conv.working_weight()
     if w16 is None:
         w16 = conv.weight.to(x.dtype)
-    if own_dgrad and not is3 and wflip is None:
+    wflip = r.wflip
+    if r.own_dgrad and not r.is3 and wflip is None:
         wflip = w16.reshape(conv.out_channels, conv.in_channels).t().contiguous().view(conv.in_channels, conv.out_channels, 1, 1)
     act = _abn._act_code(bn.activation if activation is None else activation) | (hip.NORM_ABS_GAMMA if bn._abs_gamma else 0)
     slope = bn.activation_param if activation_param is None else activation_param
     bn.__dict__.pop("_eval_cache", None)
+    if node is None:
+        return _ConvABNFunction.apply(x, w16, bn.weight, bn.bias, residual, bn.running_mean, bn.running_var, bn.momentum, bn.eps,
+                                      act, slope, r.fused, r.dilation, wflip, r.own_dgrad, r.wgrad_conv, r.make_link, r.link,
+                                      bool(with_skip))
     out = node.conv_abn_train(x, w16, bn.weight, bn.bias, residual, bn.running_mean, bn.running_var, bn.momentum, bn.eps, act,
                               slope, comm.handle if comm is not None else 0, world, _hip_stream(), bn._direct_grad_ptr(),
-                              bool(with_skip), bool(fused), dilation, wflip, bool(own_dgrad), int(wgrad_conv),
-                              bool(make_link),
-                              *((blink[0], blink[1], None, blink[2], blink[3], 0, float(blink[4]), 3) if blink is not None else
-                                (link[0], link[1], link[2], link[3], link[4], int(link[5]), float(link[6]), 1) if link is not None
-                                else (None, None, None, None, None, 0, 0.0, 0)), int(stride) if stride else 1,
-                              _env("UCD_STAT_ATOMIC", "1") != "0")
+                              bool(with_skip), r.fused, r.dilation, wflip, r.own_dgrad, r.wgrad_conv, r.make_link, r.link,
+                              r.stride or 1, _env("UCD_STAT_ATOMIC", "1") != "0")
     k = 2 if with_skip else 1
     if len(out) > k:                             # the node made a link: (z, buf, partial, flag) follow the regular outputs
-        if residual is None:
-            out[0]._ucd_link = (out[k], out[k + 1], bn.bias, out[k + 2], out[k + 3], act, slope)
-        else:
-            out[0]._ucd_blink = (out[k], out[k + 1], out[k + 2], out[k + 3], slope)
+        _offer_link(out[0], out[k], out[k + 1], bn.bias, out[k + 2], out[k + 3], act, slope, block=residual is not None)
     return (out[0], out[1]) if with_skip else out[0]
 
 

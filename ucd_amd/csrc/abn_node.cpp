@@ -14,10 +14,12 @@
 #include <torch/csrc/autograd/graph_task.h>
 #include <torch/csrc/autograd/utils/grad_layout_contract.h>
 
+#include <array>
 #include <cstring>
 #include <map>
 #include <mutex>
 #include <set>
+#include <tuple>
 
 #include "../../include/ucd_hip.h"
 
@@ -344,7 +346,143 @@ at::Tensor conv_wgrad(const at::Tensor& dz, const at::Tensor& x, const at::Tenso
                                               {0, 0}, 1, {false, true, false}));
 }
 
+// ---- what the nodes share ----------------------------------------------------------------------------------------------------------
+// The state a node keeps for its backward is ONE struct S: tensors() points at its tensor members in the order they are saved,
+// scalars() ties the rest.  forward hands it to keep(), backward gets it back from kept() - no index and no key is written twice.
+template <class... A> std::tuple<A...> values(const std::tuple<A&...>& refs) { return refs; }
+
+template <class S> void keep(AutogradContext* ctx, S& s) {
+  variable_list v;
+  for (at::Tensor* t : s.tensors()) v.push_back(*t);
+  ctx->save_for_backward(std::move(v));
+  ctx->saved_data["scalars"] = values(s.scalars());
+}
+
+template <class S> S kept(AutogradContext* ctx) {
+  S s;
+  const variable_list saved = ctx->get_saved_variables();
+  size_t i = 0;
+  for (at::Tensor* t : s.tensors()) *t = saved[i++];
+  auto refs = s.scalars();
+  refs = ctx->saved_data["scalars"].to<decltype(values(refs))>();
+  return s;
+}
+
+// what a backward returns: one gradient per argument of the node's forward, undefined until set
+template <class R, class... A> variable_list no_grads(R (*)(AutogradContext*, A...)) { return variable_list(sizeof...(A)); }
+
+at::Tensor or_undefined(const c10::optional<at::Tensor>& t) { return t.has_value() ? *t : at::Tensor(); }
+
+// Training-mode ABN forward, y = act(BN_batch(in) [+ residual]) with the statistics left in buf (comm != 0: SyncBN through the
+// library's communicator): ABNTrainNode, and the unfused arm of ConvABNTrainNode on the convolution's output.
+void abn_batch_forward(int64_t comm, int64_t world, const at::Tensor& in, const at::Tensor& y, const at::Tensor& residual, int64_t M,
+                       int64_t C, int64_t HW, const at::Tensor& weight, const at::Tensor& bias, const at::Tensor& running_mean,
+                       const at::Tensor& running_var, double momentum, double eps, float* buf, int64_t act, double slope, void* ws,
+                       size_t ws_bytes, int64_t stream) {
+  const void* res = residual.defined() ? residual.data_ptr() : nullptr;
+  const int ldr = res ? (int)C : 0, dt = dtype_code(in);
+  if (comm != 0) {
+    check(ucd_abn_sync_forward_comm((ucd_comm_t)comm, (int)world, in.data_ptr(), (int)C, y.data_ptr(), (int)C, res, ldr, dt, (int)M,
+                                    (int)C, nullptr, (int)HW, fptr(weight), fptr(bias), running_mean.data_ptr<float>(),
+                                    running_var.data_ptr<float>(), (float)momentum, (float)eps, buf, (int)act, (float)slope, ws,
+                                    ws_bytes, (ucd_stream_t)stream),
+          "ucd_abn_sync_forward_comm");
+  } else {
+    check(ucd_abn_forward(in.data_ptr(), (int)C, y.data_ptr(), (int)C, res, ldr, dt, (int)M, (int)C, nullptr, (int)HW, fptr(weight),
+                          fptr(bias), running_mean.data_ptr<float>(), running_var.data_ptr<float>(), (float)momentum, (float)eps, 1,
+                          buf, nullptr, (int)act, (float)slope, ws, ws_bytes, (ucd_stream_t)stream),
+          "ucd_abn_forward");
+  }
+}
+
+// Where the two backward sums of an ABN layer live.  `local` receives this rank's [d bias | d weight]: the layer's slice of the
+// gradient bucket when the caller gave one (param_grad; the node then reports no parameter gradients), else a fresh tensor whose
+// halves are dbias / dweight.  `global` is what the apply pass reads: the same place in a single process; under SyncBN the sums
+// over all ranks, in front of the local ones ([global 2 N | local 2 N], or [global 2 N] alone with param_grad).
+struct Sums {
+  at::Tensor store, dbias, dweight;
+  float *global = nullptr, *local = nullptr;
+  Sums(bool sync, float* param_grad, int64_t N, const at::Tensor& like) {
+    if (sync || !param_grad) store = at::empty({(sync && !param_grad ? 4 : 2) * N}, like.options().dtype(at::kFloat));
+    const int64_t off = sync ? 2 * N : 0;
+    local = param_grad ? param_grad : store.data_ptr<float>() + off;
+    global = sync ? store.data_ptr<float>() : local;
+    if (!param_grad) {
+      dbias = store.narrow(0, off, N);
+      dweight = store.narrow(0, off + N, N);
+    }
+  }
+};
+
+// Training-mode ABN backward (reduction + apply; comm != 0: SyncBN): din = d in, dres = d residual where the layer has one (else
+// undefined), y the saved output where the activation's sign needs it (else undefined), b the forward's statistics buffer.
+void abn_batch_backward(int64_t comm, int64_t world, const at::Tensor& in, const at::Tensor& dy, const at::Tensor& y,
+                        const at::Tensor& din, const at::Tensor& dres, int64_t M, int64_t C, int64_t HW, const float* b,
+                        const at::Tensor& weight, const at::Tensor& bias, const Sums& sums, int64_t act, double slope, void* ws,
+                        size_t ws_bytes, int64_t stream) {
+  const float *mean = b + 3 * C, *invstd = b + 4 * C, *scale = b + 5 * C;
+  const void* yp = y.defined() ? y.data_ptr() : nullptr;
+  void* dresp = dres.defined() ? dres.data_ptr() : nullptr;
+  const int ldy = yp ? (int)C : 0, ldres = dresp ? (int)C : 0, dt = dtype_code(in);
+  if (comm != 0) {
+    check(ucd_abn_sync_backward_comm((ucd_comm_t)comm, (int)world, in.data_ptr(), (int)C, dy.data_ptr(), (int)C, yp, ldy, din.data_ptr(),
+                                     (int)C, dresp, ldres, dt, (int)M, (int)C, nullptr, (int)HW, mean, invstd, scale, fptr(bias),
+                                     fptr(weight), sums.global, sums.local, (int)act, (float)slope, ws, ws_bytes, (ucd_stream_t)stream),
+          "ucd_abn_sync_backward_comm");
+  } else {
+    check(ucd_abn_backward(in.data_ptr(), (int)C, dy.data_ptr(), (int)C, yp, ldy, din.data_ptr(), (int)C, dresp, ldres, dt, (int)M,
+                           (int)C, nullptr, (int)HW, mean, invstd, scale, fptr(bias), fptr(weight), sums.local, (float)M, 1, 1, (int)act,
+                           (float)slope, ws, ws_bytes, (ucd_stream_t)stream),
+          "ucd_abn_backward");
+  }
+}
+
+// d x = dy . w through the tuned library product (x: rows [M, Ci], or a dense channels-last map of M rows; w4 [Co, Ci, 1, 1]) with
+// the gradient of a shortcut that left x next to the convolution: folded into the product where it is bf16 (beta = 1, in place on
+// dskip), else added afterwards.  dy or dskip may be undefined.
+at::Tensor library_dgrad(const at::Tensor& dy, const at::Tensor& w4, const at::Tensor& x, at::Tensor dskip, int64_t M, void* ws,
+                         size_t wsb, int64_t stream) {
+  const int Ci = (int)w4.size(1), Co = (int)w4.size(0);
+  auto product = [&](const at::Tensor& out) {
+    check(ucd_gemm_bf16(1, (int)M, Ci, Co, dy.data_ptr(), Co, w4.data_ptr(), Ci, out.data_ptr(), Ci, ws, wsb, 1, (ucd_stream_t)stream),
+          "ucd_gemm_bf16");
+  };
+  if (dskip.defined() && dy.defined() && dskip.scalar_type() == at::kBFloat16) {
+    if (x.dim() != 4) dskip = dskip.contiguous();
+    else if (!dense_channels_last(dskip)) dskip = dskip.contiguous(at::MemoryFormat::ChannelsLast);
+    if (!ucd_gemm_has_plan(1, (int)M, Ci, Co, Co, Ci, Ci)) product(at::empty_like(x));   // tune once, into scratch
+    check(ucd_gemm_bf16_acc(1, (int)M, Ci, Co, dy.data_ptr(), Co, w4.data_ptr(), Ci, dskip.data_ptr(), Ci, ws, wsb, (ucd_stream_t)stream),
+          "ucd_gemm_bf16_acc");
+    return dskip;
+  }
+  if (!dy.defined()) return dskip;
+  at::Tensor dx = at::empty_like(x);
+  product(dx);
+  return dskip.defined() ? dx + dskip : dx;
+}
+
+// The plain fields of a product of the own kernel, y[M, N] = a[M, K] . w[N, taps K]^T, all dense: a 1x1 layer, or with dilation > 0
+// the 3x3 layer (padding = dilation) over H x W maps as an implicit GEMM.  The callers add their epilogue.
+ucd_conv1x1_desc conv_desc(const at::Tensor& a, const at::Tensor& w, const at::Tensor& y, int64_t M, int64_t N, int64_t K,
+                           int64_t H = 0, int64_t W = 0, int64_t dilation = 0) {
+  ucd_conv1x1_desc d;
+  memset(&d, 0, sizeof(d));
+  d.a = a.data_ptr(); d.lda = (int)K; d.w = w.data_ptr(); d.ldw = (int)(dilation > 0 ? 9 * K : K); d.y = y.data_ptr(); d.ldy = (int)N;
+  d.M = (int)M; d.N = (int)N; d.K = (int)K; d.out_mode = 0;
+  if (dilation > 0) { d.taps = 9; d.H = (int)H; d.W = (int)W; d.dilation = (int)dilation; }
+  return d;
+}
+
 class ABNTrainNode : public torch::autograd::Function<ABNTrainNode> {
+  struct Kept {
+    at::Tensor x, y, weight, bias, buf;
+    int64_t act = 0, comm = 0, world = 0, stream = 0, param_grad = 0;
+    double slope = 0;
+    bool has_res = false;
+    std::array<at::Tensor*, 5> tensors() { return {&x, &y, &weight, &bias, &buf}; }
+    auto scalars() { return std::tie(act, comm, world, stream, param_grad, slope, has_res); }
+  };
+
  public:
   static at::Tensor forward(AutogradContext* ctx, at::Tensor x, at::Tensor weight, at::Tensor bias,
                             c10::optional<at::Tensor> residual_, at::Tensor running_mean, at::Tensor running_var,
@@ -354,135 +492,84 @@ class ABNTrainNode : public torch::autograd::Function<ABNTrainNode> {
     // out back to back by ucd_amd.ddp); the backward kernels then write the parameter gradients there themselves and the
     // node reports none - no gradient tensors, no AccumulateGrad adds (212 tiny launches per step)
     TORCH_CHECK(dense_channels_last(x), "ucd abn node: input must be a dense channels-last tensor");
-    at::Tensor residual = residual_.has_value() ? *residual_ : at::Tensor();
+    at::Tensor residual = or_undefined(residual_);
     const bool has_res = residual.defined();
     if (has_res) TORCH_CHECK(dense_channels_last(residual) && residual.sizes() == x.sizes() && residual.scalar_type() == x.scalar_type(),
                              "ucd abn node: residual must match the input");
     const int64_t C = x.size(1), HW = x.size(2) * x.size(3), M = x.size(0) * HW;
-    const bool sync = comm != 0;
     at::Tensor y = at::empty_like(x);   // preserves channels-last
-    at::Tensor buf = at::empty({(sync ? 8 + 2 * world : 6) * C}, x.options().dtype(at::kFloat));
+    at::Tensor buf = at::empty({(comm != 0 ? 8 + 2 * world : 6) * C}, x.options().dtype(at::kFloat));
     const size_t ws_bytes = ucd_abn_workspace_bytes((int)M, (int)C);
-    void* ws = workspace(x, ws_bytes, stream);
-    const int dt = dtype_code(x);
-    if (sync) {
-      check(ucd_abn_sync_forward_comm((ucd_comm_t)comm, (int)world, x.data_ptr(), (int)C, y.data_ptr(), (int)C,
-                                      has_res ? residual.data_ptr() : nullptr, has_res ? (int)C : 0, dt, (int)M, (int)C, nullptr,
-                                      (int)HW, fptr(weight), fptr(bias), running_mean.data_ptr<float>(),
-                                      running_var.data_ptr<float>(), (float)momentum, (float)eps, buf.data_ptr<float>(), (int)act,
-                                      (float)slope, ws, ws_bytes, (ucd_stream_t)stream),
-            "ucd_abn_sync_forward_comm");
-    } else {
-      check(ucd_abn_forward(x.data_ptr(), (int)C, y.data_ptr(), (int)C, has_res ? residual.data_ptr() : nullptr,
-                            has_res ? (int)C : 0, dt, (int)M, (int)C, nullptr, (int)HW, fptr(weight), fptr(bias),
-                            running_mean.data_ptr<float>(), running_var.data_ptr<float>(), (float)momentum, (float)eps, 1,
-                            buf.data_ptr<float>(), nullptr, (int)act, (float)slope, ws, ws_bytes, (ucd_stream_t)stream),
-            "ucd_abn_forward");
-    }
+    abn_batch_forward(comm, world, x, y, residual, M, C, HW, weight, bias, running_mean, running_var, momentum, eps,
+                      buf.data_ptr<float>(), act, slope, workspace(x, ws_bytes, stream), ws_bytes, stream);
     const bool needs_y = has_res && (act & UCD_ACT_MASK) != UCD_ACT_IDENTITY;  // the sign of z is not recoverable from x alone
-    ctx->save_for_backward({x, needs_y ? y : at::Tensor(), weight, bias, buf});
-    ctx->saved_data["act"] = act;
-    ctx->saved_data["slope"] = slope;
-    ctx->saved_data["comm"] = comm;
-    ctx->saved_data["world"] = world;
-    ctx->saved_data["stream"] = stream;
-    ctx->saved_data["has_res"] = has_res;
-    ctx->saved_data["param_grad"] = param_grad;
+    Kept k{x, needs_y ? y : at::Tensor(), weight, bias, buf, act, comm, world, stream, param_grad, slope, has_res};
+    keep(ctx, k);
     return y;
   }
 
   static variable_list backward(AutogradContext* ctx, variable_list grads) {
-    auto saved = ctx->get_saved_variables();
-    at::Tensor x = saved[0], y = saved[1], weight = saved[2], bias = saved[3], buf = saved[4];
-    const int64_t act = ctx->saved_data["act"].toInt(), comm = ctx->saved_data["comm"].toInt();
-    const int64_t world = ctx->saved_data["world"].toInt(), stream = ctx->saved_data["stream"].toInt();
-    const double slope = ctx->saved_data["slope"].toDouble();
-    const bool has_res = ctx->saved_data["has_res"].toBool();
-    float* param_grad = reinterpret_cast<float*>(ctx->saved_data["param_grad"].toInt());
+    Kept k = kept<Kept>(ctx);
+    const at::Tensor& x = k.x;
     const int64_t C = x.size(1), HW = x.size(2) * x.size(3), M = x.size(0) * HW;
     at::Tensor dy = grads[0];
     if (dy.scalar_type() != x.scalar_type()) dy = dy.to(x.scalar_type());
     if (!dense_channels_last(dy)) dy = dy.contiguous(at::MemoryFormat::ChannelsLast);
     at::Tensor dx = at::empty_like(x);
-    at::Tensor dz = has_res ? at::empty_like(x) : at::Tensor();
-    const bool sync = comm != 0;
-    at::Tensor sums;
-    if (sync || !param_grad) sums = at::empty({(sync && !param_grad ? 4 : 2) * C}, x.options().dtype(at::kFloat));
-    float* b = buf.data_ptr<float>();
-    const float *mean = b + 3 * C, *invstd = b + 4 * C, *scale = b + 5 * C;
+    at::Tensor dres = k.has_res ? at::empty_like(x) : at::Tensor();
+    const Sums sums(k.comm != 0, reinterpret_cast<float*>(k.param_grad), C, x);
     const size_t ws_bytes = ucd_abn_workspace_bytes((int)M, (int)C);
-    void* ws = workspace(x, ws_bytes, stream);
-    const int dt = dtype_code(x);
-    const void* yp = y.defined() ? y.data_ptr() : nullptr;
-    at::Tensor dbias, dweight;
-    if (sync) {
-      check(ucd_abn_sync_backward_comm((ucd_comm_t)comm, (int)world, x.data_ptr(), (int)C, dy.data_ptr(), (int)C, yp, yp ? (int)C : 0,
-                                       dx.data_ptr(), (int)C, has_res ? dz.data_ptr() : nullptr, has_res ? (int)C : 0, dt, (int)M,
-                                       (int)C, nullptr, (int)HW, mean, invstd, scale, fptr(bias), fptr(weight), sums.data_ptr<float>(),
-                                       param_grad ? param_grad : sums.data_ptr<float>() + 2 * C, (int)act, (float)slope, ws,
-                                       ws_bytes, (ucd_stream_t)stream),
-            "ucd_abn_sync_backward_comm");
-      if (!param_grad) {
-        dbias = sums.narrow(0, 2 * C, C);
-        dweight = sums.narrow(0, 3 * C, C);
-      }
-    } else {
-      check(ucd_abn_backward(x.data_ptr(), (int)C, dy.data_ptr(), (int)C, yp, yp ? (int)C : 0, dx.data_ptr(), (int)C,
-                             has_res ? dz.data_ptr() : nullptr, has_res ? (int)C : 0, dt, (int)M, (int)C, nullptr, (int)HW, mean,
-                             invstd, scale, fptr(bias), fptr(weight), param_grad ? param_grad : sums.data_ptr<float>(), (float)M,
-                             1, 1, (int)act, (float)slope, ws, ws_bytes, (ucd_stream_t)stream),
-            "ucd_abn_backward");
-      if (!param_grad) {
-        dbias = sums.narrow(0, 0, C);
-        dweight = sums.narrow(0, C, C);
-      }
-    }
-    at::Tensor none;
-    return {dx, dweight, dbias, has_res ? dz : none, none, none, none, none, none, none, none, none, none, none};
+    abn_batch_backward(k.comm, k.world, x, dy, k.y, dx, dres, M, C, HW, k.buf.data_ptr<float>(), k.weight, k.bias, sums, k.act, k.slope,
+                       workspace(x, ws_bytes, k.stream), ws_bytes, k.stream);
+    variable_list out = no_grads(&forward);
+    out[0] = dx; out[1] = sums.dweight; out[2] = sums.dbias; out[3] = dres;
+    return out;
   }
 };
 
 // ---- wide 1x1 convolution as a row-matrix GEMM (ucd_amd/blocks.py::_Gemm1x1 is the Python twin) ------------------
 // y[M, Co] = rows[M, Ci] . w[Co, Ci]^T through ucd_gemm_bf16 (hipBLASLt, tuned once per shape)
+at::Tensor gemm1x1_forward(AutogradContext* ctx, const at::Tensor& rows, const at::Tensor& w4, int64_t stream, bool own_wg,
+                           const char* who) {
+  TORCH_CHECK(rows.dim() == 2 && rows.is_contiguous() && rows.scalar_type() == at::kBFloat16 && w4.dim() == 4 &&
+                  w4.scalar_type() == at::kBFloat16 && w4.size(1) == rows.size(1) && w4.size(2) == 1 && w4.size(3) == 1,
+              "ucd ", who, ": rows [M, Ci] bf16 contiguous and weight [Co, Ci, 1, 1] bf16 expected");
+  ctx->saved_data["own_wgrad"] = own_wg;
+  const int64_t M = rows.size(0), Ci = rows.size(1), Co = w4.size(0);
+  at::Tensor y = at::empty({M, Co}, rows.options());
+  const size_t wsb = ucd_gemm_workspace_bytes();
+  check(ucd_gemm_bf16(0, (int)M, (int)Co, (int)Ci, rows.data_ptr(), (int)Ci, w4.data_ptr(), (int)Ci, y.data_ptr(), (int)Co,
+                      workspace(rows, wsb, stream, 1), wsb, 1, (ucd_stream_t)stream),
+        "ucd_gemm_bf16");
+  ctx->save_for_backward({rows, w4});
+  ctx->saved_data["stream"] = stream;
+  return y;
+}
+
+// (d rows, d w, none, none); dskip: the gradient of the shortcut that Gemm1x1SkipNode hands out, undefined for Gemm1x1Node
+variable_list gemm1x1_backward(AutogradContext* ctx, at::Tensor dy, const at::Tensor& dskip) {
+  const auto saved = ctx->get_saved_variables();
+  const at::Tensor &rows = saved[0], &w4 = saved[1];
+  const int64_t stream = ctx->saved_data["stream"].toInt();
+  const size_t wsb = ucd_gemm_workspace_bytes();
+  void* ws = workspace(rows, wsb, stream, 1);
+  at::Tensor dx, dw;
+  if (dy.defined()) {
+    dy = dy.contiguous();
+    if (dy.scalar_type() != at::kBFloat16) dy = dy.to(at::kBFloat16);
+  }
+  if (ctx->needs_input_grad(0)) dx = library_dgrad(dy, w4, rows, dskip, rows.size(0), ws, wsb, stream);
+  if (ctx->needs_input_grad(1) && dy.defined())
+    dw = conv_wgrad(dy, rows, w4, 1, 1, ctx->saved_data["own_wgrad"].toBool() ? kWgradOwn : kWgradSplit, kWgradSplit, stream);
+  return {dx, dw, at::Tensor(), at::Tensor()};
+}
 
 class Gemm1x1Node : public torch::autograd::Function<Gemm1x1Node> {
  public:
   static at::Tensor forward(AutogradContext* ctx, at::Tensor rows, at::Tensor w4, int64_t stream, bool own_wg) {
-    TORCH_CHECK(rows.dim() == 2 && rows.is_contiguous() && rows.scalar_type() == at::kBFloat16 && w4.dim() == 4 &&
-                    w4.scalar_type() == at::kBFloat16 && w4.size(1) == rows.size(1) && w4.size(2) == 1 && w4.size(3) == 1,
-                "ucd gemm1x1 node: rows [M, Ci] bf16 contiguous and weight [Co, Ci, 1, 1] bf16 expected");
-    ctx->saved_data["own_wgrad"] = own_wg;
-    const int64_t M = rows.size(0), Ci = rows.size(1), Co = w4.size(0);
-    at::Tensor y = at::empty({M, Co}, rows.options());
-    const size_t wsb = ucd_gemm_workspace_bytes();
-    check(ucd_gemm_bf16(0, (int)M, (int)Co, (int)Ci, rows.data_ptr(), (int)Ci, w4.data_ptr(), (int)Ci, y.data_ptr(), (int)Co,
-                        workspace(rows, wsb, stream, 1), wsb, 1, (ucd_stream_t)stream),
-          "ucd_gemm_bf16");
-    ctx->save_for_backward({rows, w4});
-    ctx->saved_data["stream"] = stream;
-    return y;
+    return gemm1x1_forward(ctx, rows, w4, stream, own_wg, "gemm1x1 node");
   }
-
-  static variable_list backward(AutogradContext* ctx, variable_list grads) {
-    auto saved = ctx->get_saved_variables();
-    at::Tensor rows = saved[0], w4 = saved[1];
-    const int64_t stream = ctx->saved_data["stream"].toInt();
-    const int64_t M = rows.size(0), Ci = rows.size(1), Co = w4.size(0);
-    at::Tensor dy = grads[0].contiguous();
-    if (dy.scalar_type() != at::kBFloat16) dy = dy.to(at::kBFloat16);
-    const size_t wsb = ucd_gemm_workspace_bytes();
-    void* ws = workspace(rows, wsb, stream, 1);
-    at::Tensor dx, dw;
-    if (ctx->needs_input_grad(0)) {
-      dx = at::empty_like(rows);
-      check(ucd_gemm_bf16(1, (int)M, (int)Ci, (int)Co, dy.data_ptr(), (int)Co, w4.data_ptr(), (int)Ci, dx.data_ptr(), (int)Ci, ws,
-                          wsb, 1, (ucd_stream_t)stream),
-            "ucd_gemm_bf16");
-    }
-    if (ctx->needs_input_grad(1))
-      dw = conv_wgrad(dy, rows, w4, 1, 1, ctx->saved_data["own_wgrad"].toBool() ? kWgradOwn : kWgradSplit, kWgradSplit, stream);
-    return {dx, dw, at::Tensor(), at::Tensor()};
-  }
+  static variable_list backward(AutogradContext* ctx, variable_list grads) { return gemm1x1_backward(ctx, grads[0], at::Tensor()); }
 };
 
 at::Tensor gemm1x1(at::Tensor rows, at::Tensor w4, int64_t stream, bool own_wg) { return Gemm1x1Node::apply(rows, w4, stream, own_wg); }
@@ -494,60 +581,10 @@ at::Tensor gemm1x1(at::Tensor rows, at::Tensor w4, int64_t stream, bool own_wg) 
 class Gemm1x1SkipNode : public torch::autograd::Function<Gemm1x1SkipNode> {
  public:
   static variable_list forward(AutogradContext* ctx, at::Tensor rows, at::Tensor w4, int64_t stream, bool own_wg) {
-    TORCH_CHECK(rows.dim() == 2 && rows.is_contiguous() && rows.scalar_type() == at::kBFloat16 && w4.dim() == 4 &&
-                    w4.scalar_type() == at::kBFloat16 && w4.size(1) == rows.size(1) && w4.size(2) == 1 && w4.size(3) == 1,
-                "ucd gemm1x1 skip node: rows [M, Ci] bf16 contiguous and weight [Co, Ci, 1, 1] bf16 expected");
-    ctx->saved_data["own_wgrad"] = own_wg;
-    const int64_t M = rows.size(0), Ci = rows.size(1), Co = w4.size(0);
-    at::Tensor y = at::empty({M, Co}, rows.options());
-    const size_t wsb = ucd_gemm_workspace_bytes();
-    check(ucd_gemm_bf16(0, (int)M, (int)Co, (int)Ci, rows.data_ptr(), (int)Ci, w4.data_ptr(), (int)Ci, y.data_ptr(), (int)Co,
-                        workspace(rows, wsb, stream, 1), wsb, 1, (ucd_stream_t)stream),
-          "ucd_gemm_bf16");
-    ctx->save_for_backward({rows, w4});
-    ctx->saved_data["stream"] = stream;
+    at::Tensor y = gemm1x1_forward(ctx, rows, w4, stream, own_wg, "gemm1x1 skip node");
     return {y, rows};          // an input returned as an output: autograd hands out an alias with this node as grad_fn
   }
-
-  static variable_list backward(AutogradContext* ctx, variable_list grads) {
-    auto saved = ctx->get_saved_variables();
-    at::Tensor rows = saved[0], w4 = saved[1];
-    const int64_t stream = ctx->saved_data["stream"].toInt();
-    const int64_t M = rows.size(0), Ci = rows.size(1), Co = w4.size(0);
-    const size_t wsb = ucd_gemm_workspace_bytes();
-    void* ws = workspace(rows, wsb, stream, 1);
-    at::Tensor dy = grads[0], dskip = grads[1], dx, dw;
-    if (dy.defined()) {
-      dy = dy.contiguous();
-      if (dy.scalar_type() != at::kBFloat16) dy = dy.to(at::kBFloat16);
-    }
-    if (ctx->needs_input_grad(0)) {
-      if (dskip.defined() && dy.defined() && dskip.scalar_type() == at::kBFloat16) {
-        dskip = dskip.contiguous();
-        if (!ucd_gemm_has_plan(1, (int)M, (int)Ci, (int)Co, (int)Co, (int)Ci, (int)Ci)) {   // tune once, into scratch
-          at::Tensor scratch = at::empty_like(rows);
-          check(ucd_gemm_bf16(1, (int)M, (int)Ci, (int)Co, dy.data_ptr(), (int)Co, w4.data_ptr(), (int)Ci, scratch.data_ptr(),
-                              (int)Ci, ws, wsb, 1, (ucd_stream_t)stream),
-                "ucd_gemm_bf16");
-        }
-        check(ucd_gemm_bf16_acc(1, (int)M, (int)Ci, (int)Co, dy.data_ptr(), (int)Co, w4.data_ptr(), (int)Ci, dskip.data_ptr(),
-                                (int)Ci, ws, wsb, (ucd_stream_t)stream),
-              "ucd_gemm_bf16_acc");
-        dx = dskip;
-      } else if (dy.defined()) {
-        dx = at::empty_like(rows);
-        check(ucd_gemm_bf16(1, (int)M, (int)Ci, (int)Co, dy.data_ptr(), (int)Co, w4.data_ptr(), (int)Ci, dx.data_ptr(), (int)Ci, ws,
-                            wsb, 1, (ucd_stream_t)stream),
-              "ucd_gemm_bf16");
-        if (dskip.defined()) dx = dx + dskip;
-      } else {
-        dx = dskip;
-      }
-    }
-    if (ctx->needs_input_grad(1) && dy.defined())
-      dw = conv_wgrad(dy, rows, w4, 1, 1, ctx->saved_data["own_wgrad"].toBool() ? kWgradOwn : kWgradSplit, kWgradSplit, stream);
-    return {dx, dw, at::Tensor(), at::Tensor()};
-  }
+  static variable_list backward(AutogradContext* ctx, variable_list grads) { return gemm1x1_backward(ctx, grads[0], grads[1]); }
 };
 
 std::vector<at::Tensor> gemm1x1_skip(at::Tensor rows, at::Tensor w4, int64_t stream, bool own_wg) {
@@ -625,75 +662,165 @@ at::Tensor conv_stride1(at::Tensor x, at::Tensor w, int64_t d, c10::optional<at:
 // with_skip: x is also the block's identity shortcut; the node returns (y, alias of x) so that x has one consumer and the
 // shortcut's gradient is folded into the input-gradient product (Gemm1x1SkipNode's trick).
 // Reference: conv1 -> bn1, conv3 -> bn3 (+ shortcut, activation), proj_conv -> proj_bn of modules/residual.py:57-97.
-// Atomic link (round 5): the producer's `partial` is a zeroed arena slot [2 C] (SyncBN: [4 C] = to-be-reduced | local) instead of
-// per-tile rows; flag = {served, address of the consumer's dx, its version, arena generation of the slot (0: tile rows), state, replicas}
-// with state 0 empty -> 1 filled by the consumer's product -> 2 read by the producer's backward.
-static bool link_is_atomic(const at::Tensor& flag) { return flag.defined() && flag.numel() >= 6 && flag.data_ptr<int64_t>()[3] != 0; }
-// may this consumer serve the link?  (tile-row links: always; atomic links: the slot must be of the current generation and empty)
-static bool link_servable(const at::Tensor& flag, const at::Tensor& like) {
-  if (!link_is_atomic(flag)) return true;
-  const int64_t* f = flag.data_ptr<int64_t>();
-  TORCH_CHECK(f[4] != 1, "ucd conv+abn node: a backward link's accumulator was filled twice (retain_graph replay of the consumer) - "
-                         "run with UCD_STAT_ATOMIC=0");
-  return f[4] == 0 && f[3] == arena_gen((int)like.get_device());
-}
-static void link_atomic(ucd_conv1x1_desc& d, const at::Tensor& lk_partial, const at::Tensor& lk_flag, int64_t C) {
-  if (!link_is_atomic(lk_flag)) return;
-  const int64_t R = lk_flag.data_ptr<int64_t>()[5];            // replicas (the producer sized the slot: [R][2 C], SyncBN twice)
-  d.stat_acc = lk_partial.data_ptr<float>();
-  d.stat_rep = (int)R;
-  d.stat_acc2 = lk_partial.numel() >= 2 * R * 2 * C ? d.stat_acc + R * 2 * C : nullptr;
-  lk_flag.data_ptr<int64_t>()[4] = 1;
-}
+//
+// Backward link between two nodes  A (producer) -> B (consumer)  where A's output feeds B only: B's input-gradient product applies
+// A's activation derivative and accumulates A's two backward sums in its epilogue, so A's backward skips its reduction pass
+// (ucd_abn_bwd_reduce: two reads of the map).  The protocol is three operations on the link's flag, a 6-word int64 CPU tensor that
+// A's forward returns and B receives with the rest of the link:
+//   offer (A forward)   a fresh flag and the `partial` the sums will go to: per-tile rows [row tiles][2][N], or - atomic link, round
+//                       5 - a zeroed arena slot [replicas][2 N] (SyncBN: twice that, to-be-reduced | local) with its generation;
+//   serve (B backward)  B's product takes the epilogue; the flag gets served, the address and version of the dx it writes, and an
+//                       atomic slot goes empty -> filled;
+//   claim (A backward)  dy must be that very dx, untouched; served is cleared, an atomic slot goes filled -> read.
+class LinkFlag {
+ public:
+  enum State : int64_t { kEmpty = 0, kFilled = 1, kRead = 2 };      // of an atomic link's arena slot
+  enum Claim { kNotLinked, kTileRows, kAtomic };
 
-// B side of the backward link: turn the input-gradient product into out_mode 3 against the producer's statistics
-static void link_epilogue(ucd_conv1x1_desc& d, const at::Tensor& lk_z, const at::Tensor& lk_buf, const at::Tensor& lk_bias,
-                          const at::Tensor& lk_partial, const at::Tensor& lk_flag, int64_t C, AutogradContext* ctx) {
-  const float* b = lk_buf.data_ptr<float>();
-  d.out_mode = 3;
-  d.out_mean = b + 3 * C; d.out_invstd = b + 4 * C; d.out_scale = b + 5 * C;
-  d.out_shift = lk_bias.data_ptr<float>();
-  d.residual = lk_z.data_ptr(); d.ldr = (int)C;
-  d.out_act = (int)(ctx->saved_data["lk_act"].toInt() & UCD_ACT_MASK);
-  d.out_slope = (float)ctx->saved_data["lk_slope"].toDouble();
-  d.partial = lk_partial.data_ptr<float>();
-  link_atomic(d, lk_partial, lk_flag, C);
-  // served: the producer's backward may skip its reduction pass - but ONLY for the gradient this product writes.  The address
-  // of that tensor is recorded so the producer can tell "dy is exactly the consumer's dx" from "autograd summed several
-  // contributions" (a second consumer of the producer's output: the derivative would be applied to a part of dy only).
-  lk_flag.data_ptr<int64_t>()[0] = 1;
-  lk_flag.data_ptr<int64_t>()[1] = (int64_t)reinterpret_cast<intptr_t>(d.y);
-}
+  explicit LinkFlag(const at::Tensor& t) : f_(t.defined() ? t.data_ptr<int64_t>() : nullptr) {
+    TORCH_CHECK(!f_ || t.numel() == kWords, "ucd conv+abn node: a backward link's flag has ", (int)kWords, " words");
+  }
+  explicit operator bool() const { return f_ != nullptr; }
+  bool atomic() const { return f_ && f_[kGeneration] != 0; }
+  int64_t replicas() const { return f_[kReplicas]; }      // the producer sized the slot: [R][2 C], SyncBN twice
 
-// Block link (kind 3): the producer is the LAST node of a residual block, out = act(norm(z) + shortcut), and this product is
-// the input gradient of the next block's first convolution with the identity shortcut's gradient folded in (accumulate): what
-// it computes is d out, so its epilogue (out_mode 4) applies the block activation's derivative (sign of out = this node's own
-// input x) and accumulates the two backward sums of the producer's norm against x-hat(z).  The producer then runs
-// reduce-partials + apply on d pre and hands d pre on as the shortcut's gradient (no second tensor).
-static void block_link_epilogue(ucd_conv1x1_desc& d, const at::Tensor& out, const at::Tensor& lk_z, const at::Tensor& lk_buf,
-                                const at::Tensor& lk_partial, const at::Tensor& lk_flag, int64_t C, AutogradContext* ctx) {
-  const float* b = lk_buf.data_ptr<float>();
-  d.out_mode = 4;
-  d.out_mean = b + 3 * C; d.out_invstd = b + 4 * C;
-  d.residual = out.data_ptr(); d.ldr = (int)C;
-  d.side2 = lk_z.data_ptr(); d.ld2 = (int)C;
-  d.out_act = UCD_ACT_LEAKY_RELU;
-  d.out_slope = (float)ctx->saved_data["lk_slope"].toDouble();
-  d.partial = lk_partial.data_ptr<float>();
-  link_atomic(d, lk_partial, lk_flag, C);
-  lk_flag.data_ptr<int64_t>()[0] = 1;
-  lk_flag.data_ptr<int64_t>()[1] = (int64_t)reinterpret_cast<intptr_t>(d.y);
-}
+  // (partial, flag) for the output [M, N] of a producer on `stream`
+  static std::pair<at::Tensor, at::Tensor> offer(const at::Tensor& x, int64_t M, int64_t N, bool sync, bool stat_atomic, int64_t stream) {
+    at::Tensor flag = at::zeros({(int64_t)kWords}, at::TensorOptions().dtype(at::kLong)), partial;
+    int64_t gen = 0;
+    const int64_t R = ucd_conv1x1_stat_replicas((int)M), floats = (sync ? 2 : 1) * R * 2 * N;
+    if (stat_atomic && N % 8 == 0) partial = arena_alloc(x, floats, &gen, stream);
+    if (partial.defined()) {
+      partial = partial.narrow(0, 0, floats);
+      int64_t* f = flag.data_ptr<int64_t>();
+      f[kGeneration] = gen;
+      f[kReplicas] = R;
+    } else {
+      partial = at::empty({(int64_t)ucd_conv1x1_row_tiles((int)M), 2, N}, x.options().dtype(at::kFloat));
+    }
+    return {partial, flag};
+  }
 
-// the version counter of the gradient tensor a served link's product wrote: the engine's input buffer may later add a
-// second consumer's gradient INTO that tensor in place - same address, so the address check alone would pass - which bumps it
-static void link_record_version(const at::Tensor& lk_flag, const at::Tensor& dx) {
-  if (lk_flag.defined() && lk_flag.numel() >= 3 && lk_flag.data_ptr<int64_t>()[0] == 1 &&
-      lk_flag.data_ptr<int64_t>()[1] == (int64_t)reinterpret_cast<intptr_t>(dx.data_ptr()))
-    lk_flag.data_ptr<int64_t>()[2] = (int64_t)dx._version();
-}
+  // may a consumer on device `dev` serve the link?  (tile rows: always; atomic: the slot must be of the current generation and empty)
+  bool servable(int dev) const {
+    if (!atomic()) return true;
+    TORCH_CHECK(f_[kState] != kFilled, "ucd conv+abn node: a backward link's accumulator was filled twice (retain_graph replay of the consumer) - "
+                                       "run with UCD_STAT_ATOMIC=0");
+    return f_[kState] == kEmpty && f_[kGeneration] == arena_gen(dev);
+  }
+
+  // The product d, which writes dx [M, C], leaves the two sums in `partial`.  served: the producer's backward may skip its reduction
+  // pass - but ONLY for the gradient this product writes.  The address of that tensor is recorded so the producer can tell "dy is
+  // exactly the consumer's dx" from "autograd summed several contributions" (a second consumer of the producer's output: the
+  // derivative would be applied to a part of dy only), and its version counter because the engine's input buffer may
+  // later add a second consumer's gradient INTO that tensor in place - same address - which bumps it.
+  void serve(ucd_conv1x1_desc& d, const at::Tensor& partial, const at::Tensor& dx) {
+    const int64_t C = d.N;
+    d.partial = partial.data_ptr<float>();
+    if (atomic()) {
+      const int64_t R = replicas();
+      d.stat_acc = partial.data_ptr<float>();
+      d.stat_rep = (int)R;
+      d.stat_acc2 = partial.numel() >= 2 * R * 2 * C ? d.stat_acc + R * 2 * C : nullptr;
+      f_[kState] = kFilled;
+    }
+    f_[kServed] = 1;
+    f_[kAddress] = address(dx);
+    f_[kVersion] = (int64_t)dx._version();
+  }
+
+  // The link's promise (one consumer of y) is checked, not trusted: the incoming gradient must be the very tensor the consumer's
+  // input-gradient product wrote.  Anything else (a sum made by the engine, a hook's copy, a stale flag from a backward pass that
+  // stopped short of this node) carries a derivative on part of dy only - wrong gradients, silently.
+  Claim claim(const at::Tensor& dy, int dev) {
+    if (!f_ || f_[kServed] != 1) return kNotLinked;
+    const bool same = dy.defined() && address(dy) == f_[kAddress] && (int64_t)dy._version() == f_[kVersion];
+    f_[kServed] = 0;
+    TORCH_CHECK(same, "ucd conv+abn node: the backward link was served but the gradient that arrived is not the consumer's "
+                      "input gradient, or was added to in place since - the linked map has a second consumer (hook, "
+                      "ret_intermediate tap, retain_graph replay).  Run with UCD_BWD_LINK=0.");
+    if (!atomic()) return kTileRows;
+    TORCH_CHECK(f_[kState] == kFilled && f_[kGeneration] == arena_gen(dev),
+                "ucd conv+abn node: the statistics arena was reset between a link's consumer and its producer (a training forward "
+                "inside a backward pass?) - run with UCD_STAT_ATOMIC=0");
+    f_[kState] = kRead;
+    return kAtomic;
+  }
+
+ private:
+  enum Field { kServed, kAddress, kVersion, kGeneration /* of the arena slot; 0: tile rows */, kState, kReplicas, kWords };
+  static int64_t address(const at::Tensor& t) { return (int64_t)reinterpret_cast<intptr_t>(t.data_ptr()); }
+  int64_t* f_;
+};
+
+// The link a node consumes: its producer's z, statistics buffer, bias, partial, flag, activation.
+// kChain: A (conv + ABN) -> B (conv + ABN); B's product runs out_mode 3 against A's statistics.
+// kBlock: A is the LAST node of a residual block, out = act(norm(z) + shortcut), and B the first convolution of the next,
+// identity-shortcut block (with_skip), whose input-gradient product has the shortcut's gradient folded in (accumulate): what it
+// computes is d out, so its epilogue (out_mode 4) applies the block activation's derivative (sign of out = B's own input x) and
+// accumulates the two sums against x-hat(z).  A then runs reduce-partials + apply on d pre and hands d pre on as the shortcut's
+// gradient (no second tensor).  bias and act are unused.
+struct Link {
+  enum Kind : int64_t { kNone = 0, kChain = 1, kBlock = 3 };
+  at::Tensor z, buf, bias, partial, flag;
+  int64_t act = 0;
+  double slope = 0;
+  int64_t kind = kNone;
+
+  // complete, and of a form this consumer (K input channels) can serve?
+  bool consumable(bool with_skip, int64_t K) const {
+    return z.defined() && buf.defined() && (bias.defined() || kind == kBlock) && partial.defined() && flag.defined() &&
+           (kind != kBlock || with_skip) && (!LinkFlag(flag).atomic() || K % 8 == 0);
+  }
+
+  // serve: give the input-gradient product d, which writes dx (d out of the producer = the gradient of this node's input `out`),
+  // the producer's backward reduction as its epilogue.  alone: no shortcut gradient arrives next to dx; fold: one does and is this
+  // product's accumulate operand - a chain link needs the first, a block link either.  False: not served, the producer reduces for
+  // itself (also an atomic link whose arena slot is stale).
+  bool serve(ucd_conv1x1_desc& d, const at::Tensor& dx, const at::Tensor& out, bool alone, bool fold) const {
+    LinkFlag f(flag);
+    if (!f || !f.servable((int)out.get_device())) return false;
+    if (!(alone || (kind == kBlock && fold))) return false;
+    const int64_t C = d.N;
+    const float* b = buf.data_ptr<float>();
+    d.out_mean = b + 3 * C; d.out_invstd = b + 4 * C;
+    d.ldr = (int)C;
+    d.out_slope = (float)slope;
+    if (kind == kBlock) {
+      d.out_mode = 4;
+      d.residual = out.data_ptr();
+      d.side2 = z.data_ptr(); d.ld2 = (int)C;
+      d.out_act = UCD_ACT_LEAKY_RELU;
+    } else {
+      d.out_mode = 3;
+      d.out_scale = b + 5 * C;
+      d.out_shift = bias.data_ptr<float>();
+      d.residual = z.data_ptr();
+      d.out_act = (int)(act & UCD_ACT_MASK);
+    }
+    f.serve(d, partial, dx);
+    return true;
+  }
+};
 
 class ConvABNTrainNode : public torch::autograd::Function<ConvABNTrainNode> {
+  struct Kept {
+    at::Tensor x, w4, z, y, weight, bias, buf, wflip;
+    Link link;                                // the link consumed (undefined tensors: none)
+    at::Tensor my_partial, my_flag;           // the link offered
+    int64_t act = 0, comm = 0, world = 0, stream = 0, param_grad = 0, dilation = 0, stride = 1, wgrad_conv = 0;
+    double slope = 0;
+    bool has_res = false, with_skip = false, own_dgrad = false;
+    std::array<at::Tensor*, 15> tensors() {
+      return {&x, &w4, &z, &y, &weight, &bias, &buf, &wflip, &link.z, &link.buf, &link.bias, &link.partial, &link.flag, &my_partial,
+              &my_flag};
+    }
+    auto scalars() {
+      return std::tie(link.act, link.slope, link.kind, act, comm, world, stream, param_grad, dilation, stride, wgrad_conv, slope, has_res,
+                      with_skip, own_dgrad);
+    }
+  };
+
  public:
   static variable_list forward(AutogradContext* ctx, at::Tensor x, at::Tensor w4, at::Tensor weight, at::Tensor bias,
                                c10::optional<at::Tensor> residual_, at::Tensor running_mean, at::Tensor running_var,
@@ -709,17 +836,14 @@ class ConvABNTrainNode : public torch::autograd::Function<ConvABNTrainNode> {
     // stride > 1: the strided layers of the first block of a stage (conv2 3x3 stride 2 with padding = dilation, proj_conv 1x1
     // stride 2): forward and weight gradient on the own kernels (the strided row gather / implicit GEMM, ucd_conv_wgrad_strided),
     // input gradient through the library's backward-data solver; no shortcut fold, no link consumed (it may still MAKE one).
-    // Backward link between two nodes of a chain  A (conv + ABN) -> B (conv + ABN)  where A's output feeds B only:
-    // B's input-gradient product applies A's activation derivative and accumulates A's two backward sums in its epilogue
-    // (ucd_conv1x1 out_mode 3), so A's backward skips its reduction pass (ucd_abn_bwd_reduce: two reads of the map).
-    // make_link (A): also return (z, buf, partial, flag) - partial [row tiles][2][N] on the device, flag a CPU word B sets.
-    // lk_* (B): A's z, statistics buffer, bias, partial, flag, activation.  Under SyncBN the producer all-reduces the sums.
-    // lk_kind 3 (block link, block_link_epilogue above): A is the previous block's conv3 + bn3 + shortcut + activation node
-    // (make_link with a residual), B the first convolution of an identity-shortcut block (with_skip); lk_bias is unused.
+    // make_link: offer a backward link (LinkFlag above) - also return (z, buf, partial, flag).  lk_*: the Link consumed; under
+    // SyncBN its producer all-reduces the sums.
     // dilation = 0: 1x1 convolution; dilation >= 1: 3x3, stride 1, padding = dilation (implicit GEMM, taps = 9), weight in
     // channels-last memory order; wflip = w.flip(2, 3).transpose(0, 1) (channels-last; for a 1x1 layer the transposed
     // weight [Ci, Co]) for the input gradient through the own kernel (own_dgrad); wgrad_conv: the WgradRoute of the weight gradient
     // (conv_wgrad; a layer the own kernel does not take falls back to the split products, which a 3x3 / strided layer takes on MIOpen)
+    Link link{or_undefined(lk_z_), or_undefined(lk_buf_), or_undefined(lk_bias_), or_undefined(lk_partial_), or_undefined(lk_flag_),
+              lk_act, lk_slope, lk_kind};
     TORCH_CHECK(dense_channels_last(x) && x.scalar_type() == at::kBFloat16, "ucd conv+abn node: x must be dense channels-last bf16");
     const bool conv3 = dilation > 0;
     TORCH_CHECK(w4.dim() == 4 && w4.scalar_type() == at::kBFloat16 && w4.size(1) == x.size(1) &&
@@ -727,8 +851,7 @@ class ConvABNTrainNode : public torch::autograd::Function<ConvABNTrainNode> {
                            : (w4.size(2) == 1 && w4.size(3) == 1 && w4.is_contiguous())),
                 "ucd conv+abn node: weight [Co, Ci, 1, 1] (contiguous) or [Co, Ci, 3, 3] (channels-last) bf16 expected");
     TORCH_CHECK(!(conv3 && with_skip), "ucd conv+abn node: the shortcut fold belongs to the 1x1 layers");
-    at::Tensor wflip = wflip_.has_value() ? *wflip_ : at::Tensor();
-    at::Tensor residual = residual_.has_value() ? *residual_ : at::Tensor();
+    at::Tensor residual = or_undefined(residual_);
     const bool has_res = residual.defined();
     const int64_t B = x.size(0), K = x.size(1), H = x.size(2), W = x.size(3), N = w4.size(0);
     if (stride < 1) stride = 1;
@@ -749,11 +872,8 @@ class ConvABNTrainNode : public torch::autograd::Function<ConvABNTrainNode> {
     if (fused) {
       size_t need = ucd_conv1x1_stats_partial_bytes((int)M, (int)N);
       float* partial = (float*)workspace(x, need > ws_bytes ? need : ws_bytes, stream);
-      ucd_conv1x1_desc d;
-      memset(&d, 0, sizeof(d));
-      d.a = x.data_ptr(); d.lda = (int)K; d.w = w4.data_ptr(); d.ldw = (int)(conv3 ? 9 * K : K); d.y = z.data_ptr(); d.ldy = (int)N;
-      d.M = (int)M; d.N = (int)N; d.K = (int)K; d.out_mode = 2; d.partial = partial;
-      if (conv3) { d.taps = 9; d.H = (int)H; d.W = (int)W; d.dilation = (int)dilation; }
+      ucd_conv1x1_desc d = conv_desc(x, w4, z, M, N, K, H, W, dilation);
+      d.out_mode = 2; d.partial = partial;
       if (stride > 1) { d.H = (int)H; d.W = (int)W; d.stride = (int)stride; }
       int64_t gen = 0;
       const int64_t R = ucd_conv1x1_stat_replicas((int)M);
@@ -773,27 +893,27 @@ class ConvABNTrainNode : public torch::autograd::Function<ConvABNTrainNode> {
                                   b + 4 * N, b + 5 * N, (int)act, (float)slope, (ucd_stream_t)stream),
               "ucd_abn_apply_stats");
       } else {
-      check(ucd_conv1x1(&d, (ucd_stream_t)stream), "ucd_conv1x1");
-      if (!sync) {
-        check(ucd_conv1x1_stats_finalize(partial, (int)M, (int)N, fptr(weight), running_mean.data_ptr<float>(),
-                                         running_var.data_ptr<float>(), (float)momentum, (float)eps, b, nullptr, (int)act,
-                                         (ucd_stream_t)stream),
-              "ucd_conv1x1_stats_finalize");
-        check(ucd_abn_apply(z.data_ptr(), (int)N, y.data_ptr(), (int)N, resp, has_res ? (int)N : 0, UCD_BF16, (int)M, (int)N, nullptr,
-                            (int)HW, b + 3 * N, b + 5 * N, fptr(bias), (int)act, (float)slope, (ucd_stream_t)stream),
-              "ucd_abn_apply");
-      } else {
-        float *pack = b + 6 * N, *gathered = b + 8 * N;
-        check(ucd_conv1x1_stats_finalize(partial, (int)M, (int)N, nullptr, nullptr, nullptr, (float)momentum, (float)eps, b, pack, 0,
-                                         (ucd_stream_t)stream),
-              "ucd_conv1x1_stats_finalize");
-        check(ucd_comm_all_gather((ucd_comm_t)comm, pack, gathered, (size_t)2 * N, (ucd_stream_t)stream), "ucd_comm_all_gather");
-        check(ucd_abn_sync_forward(z.data_ptr(), (int)N, y.data_ptr(), (int)N, resp, has_res ? (int)N : 0, UCD_BF16, (int)M, (int)N,
-                                   nullptr, (int)HW, gathered, (int)world, fptr(weight), fptr(bias), running_mean.data_ptr<float>(),
-                                   running_var.data_ptr<float>(), (float)momentum, (float)eps, b, (int)act, (float)slope,
-                                   (ucd_stream_t)stream),
-              "ucd_abn_sync_forward");
-      }
+        check(ucd_conv1x1(&d, (ucd_stream_t)stream), "ucd_conv1x1");
+        if (!sync) {
+          check(ucd_conv1x1_stats_finalize(partial, (int)M, (int)N, fptr(weight), running_mean.data_ptr<float>(),
+                                           running_var.data_ptr<float>(), (float)momentum, (float)eps, b, nullptr, (int)act,
+                                           (ucd_stream_t)stream),
+                "ucd_conv1x1_stats_finalize");
+          check(ucd_abn_apply(z.data_ptr(), (int)N, y.data_ptr(), (int)N, resp, has_res ? (int)N : 0, UCD_BF16, (int)M, (int)N, nullptr,
+                              (int)HW, b + 3 * N, b + 5 * N, fptr(bias), (int)act, (float)slope, (ucd_stream_t)stream),
+                "ucd_abn_apply");
+        } else {
+          float *pack = b + 6 * N, *gathered = b + 8 * N;
+          check(ucd_conv1x1_stats_finalize(partial, (int)M, (int)N, nullptr, nullptr, nullptr, (float)momentum, (float)eps, b, pack, 0,
+                                           (ucd_stream_t)stream),
+                "ucd_conv1x1_stats_finalize");
+          check(ucd_comm_all_gather((ucd_comm_t)comm, pack, gathered, (size_t)2 * N, (ucd_stream_t)stream), "ucd_comm_all_gather");
+          check(ucd_abn_sync_forward(z.data_ptr(), (int)N, y.data_ptr(), (int)N, resp, has_res ? (int)N : 0, UCD_BF16, (int)M, (int)N,
+                                     nullptr, (int)HW, gathered, (int)world, fptr(weight), fptr(bias), running_mean.data_ptr<float>(),
+                                     running_var.data_ptr<float>(), (float)momentum, (float)eps, b, (int)act, (float)slope,
+                                     (ucd_stream_t)stream),
+                "ucd_abn_sync_forward");
+        }
       }
     } else {
       if (conv3 || stride > 1) {
@@ -806,187 +926,89 @@ class ConvABNTrainNode : public torch::autograd::Function<ConvABNTrainNode> {
                             workspace(x, wsb, stream, 1), wsb, 1, (ucd_stream_t)stream),
               "ucd_gemm_bf16");
       }
-      void* ws = workspace(x, ws_bytes, stream);
-      if (sync)
-        check(ucd_abn_sync_forward_comm((ucd_comm_t)comm, (int)world, z.data_ptr(), (int)N, y.data_ptr(), (int)N, resp,
-                                        has_res ? (int)N : 0, UCD_BF16, (int)M, (int)N, nullptr, (int)HW, fptr(weight), fptr(bias),
-                                        running_mean.data_ptr<float>(), running_var.data_ptr<float>(), (float)momentum, (float)eps, b,
-                                        (int)act, (float)slope, ws, ws_bytes, (ucd_stream_t)stream),
-              "ucd_abn_sync_forward_comm");
-      else
-        check(ucd_abn_forward(z.data_ptr(), (int)N, y.data_ptr(), (int)N, resp, has_res ? (int)N : 0, UCD_BF16, (int)M, (int)N, nullptr,
-                              (int)HW, fptr(weight), fptr(bias), running_mean.data_ptr<float>(), running_var.data_ptr<float>(),
-                              (float)momentum, (float)eps, 1, b, nullptr, (int)act, (float)slope, ws, ws_bytes, (ucd_stream_t)stream),
-              "ucd_abn_forward");
+      abn_batch_forward(comm, world, z, y, residual, M, N, HW, weight, bias, running_mean, running_var, momentum, eps, b, act, slope,
+                        workspace(x, ws_bytes, stream), ws_bytes, stream);
     }
     const bool needs_y = has_res && (act & UCD_ACT_MASK) != UCD_ACT_IDENTITY;
-    at::Tensor lk_z = lk_z_.has_value() ? *lk_z_ : at::Tensor(), lk_buf = lk_buf_.has_value() ? *lk_buf_ : at::Tensor();
-    at::Tensor lk_bias = lk_bias_.has_value() ? *lk_bias_ : at::Tensor();
-    at::Tensor lk_partial = lk_partial_.has_value() ? *lk_partial_ : at::Tensor();
-    at::Tensor lk_flag = lk_flag_.has_value() ? *lk_flag_ : at::Tensor();
-    const bool consume_link = lk_z.defined() && lk_buf.defined() && (lk_bias.defined() || lk_kind == 3) && lk_partial.defined() &&
-                              lk_flag.defined() && (lk_kind != 3 || with_skip) && (!link_is_atomic(lk_flag) || (K % 8 == 0));
-    at::Tensor my_partial, my_flag;
+    if (!link.consumable(with_skip, K)) link = Link();
     // a link needs leaky_relu / identity (the fused epilogues' activations); with a residual it is the block link, whose
     // consumer reads the sign from y - so y must be among the saved tensors (needs_y: leaky_relu with a residual)
     make_link = make_link && bias.defined() && (act & UCD_ACT_MASK) != UCD_ACT_ELU && (!has_res || needs_y);
-    if (make_link) {
-      my_flag = at::zeros({6}, at::TensorOptions().dtype(at::kLong));   // {served, address of the consumer's dx, its version, generation, state, replicas}
-      int64_t gen = 0;
-      const int64_t R = ucd_conv1x1_stat_replicas((int)M);
-      if (stat_atomic && N % 8 == 0) my_partial = arena_alloc(x, (sync ? 2 : 1) * R * 2 * N, &gen, stream);
-      if (my_partial.defined()) {
-        my_partial = my_partial.narrow(0, 0, (sync ? 2 : 1) * R * 2 * N);
-        my_flag.data_ptr<int64_t>()[3] = gen;
-        my_flag.data_ptr<int64_t>()[5] = R;
-      } else {
-        my_partial = at::empty({(int64_t)ucd_conv1x1_row_tiles((int)M), 2, N}, x.options().dtype(at::kFloat));
-      }
-    }
-    ctx->save_for_backward({x, w4, z, needs_y ? y : at::Tensor(), weight, bias, buf, wflip,
-                            consume_link ? lk_z : at::Tensor(), consume_link ? lk_buf : at::Tensor(),
-                            consume_link ? lk_bias : at::Tensor(), consume_link ? lk_partial : at::Tensor(),
-                            consume_link ? lk_flag : at::Tensor(), my_partial, my_flag});
-    ctx->saved_data["lk_act"] = lk_act;
-    ctx->saved_data["lk_slope"] = lk_slope;
-    ctx->saved_data["lk_kind"] = lk_kind;
-    ctx->saved_data["act"] = act;
-    ctx->saved_data["slope"] = slope;
-    ctx->saved_data["comm"] = comm;
-    ctx->saved_data["world"] = world;
-    ctx->saved_data["stream"] = stream;
-    ctx->saved_data["has_res"] = has_res;
-    ctx->saved_data["param_grad"] = param_grad;
-    ctx->saved_data["with_skip"] = with_skip;
-    ctx->saved_data["dilation"] = dilation;
-    ctx->saved_data["stride"] = stride;
-    ctx->saved_data["own_dgrad"] = own_dgrad;
-    ctx->saved_data["wgrad_conv"] = wgrad_conv;
+    at::Tensor my_partial, my_flag;
+    if (make_link) std::tie(my_partial, my_flag) = LinkFlag::offer(x, M, N, sync, stat_atomic, stream);
+    Kept k{x, w4, z, needs_y ? y : at::Tensor(), weight, bias, buf, or_undefined(wflip_), link, my_partial, my_flag, act, comm, world,
+           stream, param_grad, dilation, stride, wgrad_conv, slope, has_res, with_skip, own_dgrad};
+    keep(ctx, k);
+    variable_list out = {y};
+    if (with_skip) out.push_back(x);
     if (make_link) {   // outputs: y, [x], z, buf, partial, flag
       // no zero-filled stand-ins for the gradients of the link tensors (the engine would launch a fill per output and step)
       ctx->set_materialize_grads(false);
       ctx->mark_non_differentiable({z, buf, my_partial, my_flag});
-      if (with_skip) return {y, x, z, buf, my_partial, my_flag};
-      return {y, z, buf, my_partial, my_flag};
+      out.insert(out.end(), {z, buf, my_partial, my_flag});
     }
-    if (with_skip) return {y, x};
-    return {y};
+    return out;
   }
 
   static variable_list backward(AutogradContext* ctx, variable_list grads) {
-    auto saved = ctx->get_saved_variables();
-    at::Tensor x = saved[0], w4 = saved[1], z = saved[2], y = saved[3], weight = saved[4], bias = saved[5], buf = saved[6];
-    at::Tensor wflip = saved[7];
-    at::Tensor lk_z = saved[8], lk_buf = saved[9], lk_bias = saved[10], lk_partial = saved[11], lk_flag = saved[12];
-    at::Tensor my_partial = saved[13], my_flag = saved[14];
-    const int64_t dilation = ctx->saved_data["dilation"].toInt();
-    const bool conv3 = dilation > 0, own_dgrad = ctx->saved_data["own_dgrad"].toBool();
-    const int64_t act = ctx->saved_data["act"].toInt(), comm = ctx->saved_data["comm"].toInt();
-    const int64_t world = ctx->saved_data["world"].toInt(), stream = ctx->saved_data["stream"].toInt();
-    const double slope = ctx->saved_data["slope"].toDouble();
-    const bool has_res = ctx->saved_data["has_res"].toBool(), with_skip = ctx->saved_data["with_skip"].toBool();
-    float* param_grad = reinterpret_cast<float*>(ctx->saved_data["param_grad"].toInt());
-    const int64_t stride = ctx->saved_data["stride"].toInt();
+    Kept k = kept<Kept>(ctx);
+    const at::Tensor &x = k.x, &w4 = k.w4, &z = k.z;
+    const int64_t dilation = k.dilation, stride = k.stride, stream = k.stream;
+    const bool conv3 = dilation > 0, sync = k.comm != 0;
+    float* param_grad = reinterpret_cast<float*>(k.param_grad);
     const int64_t B = x.size(0), K = x.size(1), H = x.size(2), W = x.size(3), N = w4.size(0);
     const int64_t HW = z.size(2) * z.size(3), M = B * HW;       // rows of the output map (smaller than x's when strided)
     at::Tensor dy = grads[0];
-    at::Tensor dskip = with_skip ? grads[1] : at::Tensor();
-    at::Tensor none;
+    at::Tensor dskip = k.with_skip ? grads[1] : at::Tensor();
     at::Tensor dx, dw, dweight, dbias, dres;
     at::Tensor dz;   // gradient w.r.t. the convolution output z
-    if (my_flag.defined() && my_flag.data_ptr<int64_t>()[0] == 1) {
-      // the link's promise (one consumer of y) is checked, not trusted: the incoming gradient must be the very tensor the
-      // consumer's input-gradient product wrote.  Anything else (a sum made by the engine, a hook's copy, a stale flag from
-      // a backward pass that stopped short of this node) carries a derivative on part of dy only - wrong gradients, silently.
-      const int64_t want = my_flag.data_ptr<int64_t>()[1];
-      const bool same = dy.defined() && (int64_t)reinterpret_cast<intptr_t>(dy.data_ptr()) == want &&
-                        (my_flag.numel() < 3 || (int64_t)dy._version() == my_flag.data_ptr<int64_t>()[2]);
-      if (!same) {
-        my_flag.data_ptr<int64_t>()[0] = 0;
-        TORCH_CHECK(false, "ucd conv+abn node: the backward link was served but the gradient that arrived is not the consumer's "
-                           "input gradient, or was added to in place since - the linked map has a second consumer (hook, "
-                           "ret_intermediate tap, retain_graph replay).  Run with UCD_BWD_LINK=0.");
-      }
-    }
+    LinkFlag my_flag(k.my_flag);
+    const LinkFlag::Claim claim = my_flag.claim(dy, (int)x.get_device());
     if (dy.defined()) {
       if (dy.scalar_type() != at::kBFloat16) dy = dy.to(at::kBFloat16);
       if (!dense_channels_last(dy)) dy = dy.contiguous(at::MemoryFormat::ChannelsLast);
       dz = at::empty_like(z);
-      const bool linked_now = my_flag.defined() && my_flag.data_ptr<int64_t>()[0] == 1;
-      if (has_res && !linked_now) dres = at::empty_like(z);
-      const bool sync = comm != 0;
-      at::Tensor sums;
-      if (sync || !param_grad) sums = at::empty({(sync && !param_grad ? 4 : 2) * N}, x.options().dtype(at::kFloat));
-      float* b = buf.data_ptr<float>();
+      if (k.has_res && claim == LinkFlag::kNotLinked) dres = at::empty_like(z);
+      Sums sums(sync, param_grad, N, x);
+      const float* b = k.buf.data_ptr<float>();
       const float *mean = b + 3 * N, *invstd = b + 4 * N, *scale = b + 5 * N;
       const size_t ws_bytes = ucd_abn_workspace_bytes((int)M, (int)N);
       void* ws = workspace(x, ws_bytes, stream);
-      const void* yp = y.defined() ? y.data_ptr() : nullptr;
-      const bool linked = my_flag.defined() && my_flag.data_ptr<int64_t>()[0] == 1;
-      if (linked && link_is_atomic(my_flag)) {
+      const float count = (float)M * (sync ? (float)k.world : 1.f);
+      const int norm_only = (int)(UCD_ACT_IDENTITY | (k.act & UCD_NORM_ABS_GAMMA));   // a served link: the activation is done
+      if (claim == LinkFlag::kAtomic) {
         // atomic link: the consumer's product added the two sums into this layer's arena slot; the apply pass finalises them in its
         // prologue and writes the parameter gradients (SyncBN: the first half is all-reduced, the second stays this rank's)
-        int64_t* fl = my_flag.data_ptr<int64_t>();
-        fl[0] = 0;
-        TORCH_CHECK(fl[4] == 1 && fl[3] == arena_gen((int)x.get_device()),
-                    "ucd conv+abn node: the statistics arena was reset between a link's consumer and its producer (a training forward "
-                    "inside a backward pass?) - run with UCD_STAT_ATOMIC=0");
-        fl[4] = 2;
-        const int64_t R = fl[5];
-        float* global = my_partial.data_ptr<float>();
+        const int64_t R = my_flag.replicas();
+        float* global = k.my_partial.data_ptr<float>();
         float* local = sync ? global + R * 2 * N : global;
-        if (sync) check(ucd_comm_all_reduce_sum((ucd_comm_t)comm, global, (size_t)(R * 2 * N), (ucd_stream_t)stream), "ucd_comm_all_reduce_sum");
-        if (!param_grad) sums = at::empty({2 * N}, x.options().dtype(at::kFloat));
+        if (sync) check(ucd_comm_all_reduce_sum((ucd_comm_t)k.comm, global, (size_t)(R * 2 * N), (ucd_stream_t)stream), "ucd_comm_all_reduce_sum");
+        sums = Sums(false, param_grad, N, x);      // only the parameter gradients need a home
         check(ucd_abn_bwd_apply_raw(z.data_ptr(), (int)N, dy.data_ptr(), (int)N, nullptr, 0, dz.data_ptr(), (int)N, nullptr, 0, (int)M,
-                                    (int)N, mean, invstd, scale, fptr(bias), fptr(weight), global, local, (int)R,
-                                    param_grad ? param_grad : sums.data_ptr<float>(), (float)M * (sync ? (float)world : 1.f),
-                                    (int)(UCD_ACT_IDENTITY | (act & UCD_NORM_ABS_GAMMA)), 0.f, (ucd_stream_t)stream),
+                                    (int)N, mean, invstd, scale, fptr(k.bias), fptr(k.weight), global, local, (int)R, sums.local, count,
+                                    norm_only, 0.f, (ucd_stream_t)stream),
               "ucd_abn_bwd_apply_raw");
-        if (has_res) dres = dy;
-        if (!param_grad) {
-          dbias = sums.narrow(0, 0, N);
-          dweight = sums.narrow(0, N, N);
-        }
-      } else if (linked) {
+      } else if (claim == LinkFlag::kTileRows) {
         // the consumer's input-gradient product already applied this layer's activation derivative and left the two sums
         // as per-tile partials: combine them (fixed order) and go straight to the apply pass
-        my_flag.data_ptr<int64_t>()[0] = 0;
         // single process: the sums are the parameter gradients and the constants of the apply pass.  SyncBN: the apply
         // pass needs the sums over all ranks (all-reduce, like ucd_abn_sync_backward_comm), the parameter gradients stay
         // this rank's (the DDP wrapper averages them).
-        float* local = param_grad ? param_grad : sums.data_ptr<float>() + (sync ? 2 * N : 0);
-        float* global = sync ? sums.data_ptr<float>() : local;
-        check(ucd_abn_reduce_partials(my_partial.data_ptr<float>(), ucd_conv1x1_row_tiles((int)M), (int)N, global,
-                                      sync ? local : nullptr, fptr(weight), (int)(act & UCD_NORM_ABS_GAMMA), (ucd_stream_t)stream),
+        check(ucd_abn_reduce_partials(k.my_partial.data_ptr<float>(), ucd_conv1x1_row_tiles((int)M), (int)N, sums.global,
+                                      sync ? sums.local : nullptr, fptr(k.weight), (int)(k.act & UCD_NORM_ABS_GAMMA), (ucd_stream_t)stream),
               "ucd_abn_reduce_partials");
-        if (sync) check(ucd_comm_all_reduce_sum((ucd_comm_t)comm, global, (size_t)2 * N, (ucd_stream_t)stream), "ucd_comm_all_reduce_sum");
+        if (sync) check(ucd_comm_all_reduce_sum((ucd_comm_t)k.comm, sums.global, (size_t)2 * N, (ucd_stream_t)stream), "ucd_comm_all_reduce_sum");
         check(ucd_abn_bwd_apply(z.data_ptr(), (int)N, dy.data_ptr(), (int)N, nullptr, 0, dz.data_ptr(), (int)N, nullptr, 0, UCD_BF16,
-                                (int)M, (int)N, nullptr, (int)HW, mean, invstd, scale, fptr(bias), fptr(weight), global,
-                                (float)M * (sync ? (float)world : 1.f), 0, (int)(UCD_ACT_IDENTITY | (act & UCD_NORM_ABS_GAMMA)), 0.f,
-                                (ucd_stream_t)stream),
+                                (int)M, (int)N, nullptr, (int)HW, mean, invstd, scale, fptr(k.bias), fptr(k.weight), sums.global, count, 0,
+                                norm_only, 0.f, (ucd_stream_t)stream),
               "ucd_abn_bwd_apply");
-        // block link: dy already IS d pre = d out * act'(out); the shortcut's gradient is that same tensor (no copy, no write)
-        if (has_res) dres = dy;
-        if (!param_grad) {
-          dbias = sums.narrow(0, sync ? 2 * N : 0, N);
-          dweight = sums.narrow(0, sync ? 3 * N : N, N);
-        }
-      } else if (sync) {
-        check(ucd_abn_sync_backward_comm((ucd_comm_t)comm, (int)world, z.data_ptr(), (int)N, dy.data_ptr(), (int)N, yp, yp ? (int)N : 0,
-                                         dz.data_ptr(), (int)N, has_res ? dres.data_ptr() : nullptr, has_res ? (int)N : 0, UCD_BF16,
-                                         (int)M, (int)N, nullptr, (int)HW, mean, invstd, scale, fptr(bias), fptr(weight),
-                                         sums.data_ptr<float>(), param_grad ? param_grad : sums.data_ptr<float>() + 2 * N, (int)act,
-                                         (float)slope, ws, ws_bytes, (ucd_stream_t)stream),
-              "ucd_abn_sync_backward_comm");
-        if (!param_grad) { dbias = sums.narrow(0, 2 * N, N); dweight = sums.narrow(0, 3 * N, N); }
       } else {
-        check(ucd_abn_backward(z.data_ptr(), (int)N, dy.data_ptr(), (int)N, yp, yp ? (int)N : 0, dz.data_ptr(), (int)N,
-                               has_res ? dres.data_ptr() : nullptr, has_res ? (int)N : 0, UCD_BF16, (int)M, (int)N, nullptr, (int)HW,
-                               mean, invstd, scale, fptr(bias), fptr(weight), param_grad ? param_grad : sums.data_ptr<float>(),
-                               (float)M, 1, 1, (int)act, (float)slope, ws, ws_bytes, (ucd_stream_t)stream),
-              "ucd_abn_backward");
-        if (!param_grad) { dbias = sums.narrow(0, 0, N); dweight = sums.narrow(0, N, N); }
+        abn_batch_backward(k.comm, k.world, z, dy, k.y, dz, dres, M, N, HW, b, k.weight, k.bias, sums, k.act, k.slope, ws, ws_bytes, stream);
       }
+      // block link: dy already IS d pre = d out * act'(out); the shortcut's gradient is that same tensor (no copy, no write)
+      if (k.has_res && claim != LinkFlag::kNotLinked) dres = dy;
+      dbias = sums.dbias;
+      dweight = sums.dweight;
     }
     if (stride > 1) {
       const int64_t pad = conv3 ? dilation : 0, dil = conv3 ? dilation : 1;
@@ -997,18 +1019,11 @@ class ConvABNTrainNode : public torch::autograd::Function<ConvABNTrainNode> {
       // 3x3: input gradient = the same convolution on the flipped + transposed weight (own implicit GEMM, or MIOpen's
       // FORWARD solver when the cached weight is missing / the map is too small to fill the chip)
       if (ctx->needs_input_grad(0) && dz.defined()) {
-        if (!wflip.defined()) wflip = w4.flip({2, 3}).transpose(0, 1).contiguous(at::MemoryFormat::ChannelsLast);
-        if (own_dgrad) {
+        at::Tensor wflip = k.wflip.defined() ? k.wflip : w4.flip({2, 3}).transpose(0, 1).contiguous(at::MemoryFormat::ChannelsLast);
+        if (k.own_dgrad) {
           dx = at::empty_like(x);
-          ucd_conv1x1_desc d;
-          memset(&d, 0, sizeof(d));
-          d.a = dz.data_ptr(); d.lda = (int)N; d.w = wflip.data_ptr(); d.ldw = (int)(9 * N); d.y = dx.data_ptr(); d.ldy = (int)K;
-          d.M = (int)M; d.N = (int)K; d.K = (int)N; d.out_mode = 0;
-          d.taps = 9; d.H = (int)H; d.W = (int)W; d.dilation = (int)dilation;
-          if (lk_flag.defined() && ctx->saved_data["lk_kind"].toInt() != 3 && link_servable(lk_flag, x)) {
-            link_epilogue(d, lk_z, lk_buf, lk_bias, lk_partial, lk_flag, K, ctx);
-            link_record_version(lk_flag, dx);
-          }
+          ucd_conv1x1_desc d = conv_desc(dz, wflip, dx, M, K, N, H, W, dilation);
+          k.link.serve(d, dx, x, true, false);
           check(ucd_conv1x1(&d, (ucd_stream_t)stream), "ucd_conv1x1");
         } else {
           dx = at::conv2d(dz, wflip, {}, {1, 1}, {dilation, dilation}, {dilation, dilation}, 1);
@@ -1017,65 +1032,43 @@ class ConvABNTrainNode : public torch::autograd::Function<ConvABNTrainNode> {
     } else if (ctx->needs_input_grad(0)) {
       const size_t wsb = ucd_gemm_workspace_bytes();
       void* gws = workspace(x, wsb, stream, 1);
-      const bool fold = dskip.defined() && dz.defined() && dskip.scalar_type() == at::kBFloat16;
-      if (own_dgrad && dz.defined() && wflip.defined()) {
+      if (k.own_dgrad && dz.defined() && k.wflip.defined()) {
         // narrow / short-K layers: d x = d z . w through the own kernel on the cached transposed weight [Ci, Co]; the
         // shortcut's gradient is the accumulate operand (no separate add)
+        const bool fold = dskip.defined() && dskip.scalar_type() == at::kBFloat16;
         if (fold && !dense_channels_last(dskip)) dskip = dskip.contiguous(at::MemoryFormat::ChannelsLast);
         dx = fold ? dskip : at::empty_like(x);
-        ucd_conv1x1_desc d;
-        memset(&d, 0, sizeof(d));
-        d.a = dz.data_ptr(); d.lda = (int)N; d.w = wflip.data_ptr(); d.ldw = (int)N; d.y = dx.data_ptr(); d.ldy = (int)K;
-        d.M = (int)M; d.N = (int)K; d.K = (int)N; d.out_mode = 0; d.accumulate = fold ? 1 : 0;
-        const bool block_link = lk_flag.defined() && ctx->saved_data["lk_kind"].toInt() == 3;
-        if (lk_flag.defined() && !link_servable(lk_flag, x)) {
-          // an atomic link whose arena slot is stale: not served - the producer runs its own reduction pass
-        } else if (block_link) {
-          if (with_skip && (fold || !dskip.defined())) block_link_epilogue(d, x, lk_z, lk_buf, lk_partial, lk_flag, K, ctx);
-        } else if (lk_flag.defined() && !fold && !dskip.defined()) {
-          link_epilogue(d, lk_z, lk_buf, lk_bias, lk_partial, lk_flag, K, ctx);
-        }
-        link_record_version(lk_flag, dx);
+        ucd_conv1x1_desc d = conv_desc(dz, k.wflip, dx, M, K, N);
+        d.accumulate = fold ? 1 : 0;
+        k.link.serve(d, dx, x, !dskip.defined(), fold);
         check(ucd_conv1x1(&d, (ucd_stream_t)stream), "ucd_conv1x1");
         if (!fold && dskip.defined()) dx = dx + dskip;
-      } else if (fold) {
-        if (!dense_channels_last(dskip)) dskip = dskip.contiguous(at::MemoryFormat::ChannelsLast);
-        if (!ucd_gemm_has_plan(1, (int)M, (int)K, (int)N, (int)N, (int)K, (int)K)) {   // tune once, into scratch
-          at::Tensor scratch = at::empty_like(x);
-          check(ucd_gemm_bf16(1, (int)M, (int)K, (int)N, dz.data_ptr(), (int)N, w4.data_ptr(), (int)K, scratch.data_ptr(), (int)K,
-                              gws, wsb, 1, (ucd_stream_t)stream),
-                "ucd_gemm_bf16");
-        }
-        check(ucd_gemm_bf16_acc(1, (int)M, (int)K, (int)N, dz.data_ptr(), (int)N, w4.data_ptr(), (int)K, dskip.data_ptr(), (int)K, gws,
-                                wsb, (ucd_stream_t)stream),
-              "ucd_gemm_bf16_acc");
-        dx = dskip;
-      } else if (dz.defined()) {
-        dx = at::empty_like(x);
-        check(ucd_gemm_bf16(1, (int)M, (int)K, (int)N, dz.data_ptr(), (int)N, w4.data_ptr(), (int)K, dx.data_ptr(), (int)K, gws, wsb, 1,
-                            (ucd_stream_t)stream),
-              "ucd_gemm_bf16");
-        if (dskip.defined()) dx = dx + dskip;
       } else {
-        dx = dskip;
+        dx = library_dgrad(dz, w4, x, dskip, M, gws, wsb, stream);
       }
     }
     if (ctx->needs_input_grad(1) && dz.defined())
-      dw = conv_wgrad(dz, x, w4, conv3 ? dilation : 1, stride, ctx->saved_data["wgrad_conv"].toInt(), kWgradSplit, stream);
-    return {dx, dw, dweight, dbias, has_res ? dres : none, none, none, none, none, none, none, none, none, none, none, none, none,
-            none, none, none, none, none, none, none, none, none, none, none, none, none, none, none};
+      dw = conv_wgrad(dz, x, w4, conv3 ? dilation : 1, stride, k.wgrad_conv, kWgradSplit, stream);
+    variable_list out = no_grads(&forward);
+    out[0] = dx; out[1] = dw; out[2] = dweight; out[3] = dbias; out[4] = dres;
+    return out;
   }
 };
+
+// the link as Python hands it over (ucd_amd/blocks.py Link): the fields of Link above in their order, bias None on a block link
+using PyLink = std::tuple<at::Tensor, at::Tensor, c10::optional<at::Tensor>, at::Tensor, at::Tensor, int64_t, double, int64_t>;
 
 std::vector<at::Tensor> conv_abn_train(at::Tensor x, at::Tensor w4, at::Tensor weight, at::Tensor bias,
                                        c10::optional<at::Tensor> residual, at::Tensor running_mean, at::Tensor running_var,
                                        double momentum, double eps, int64_t act, double slope, int64_t comm, int64_t world,
                                        int64_t stream, int64_t param_grad, bool with_skip, bool fused, int64_t dilation,
                                        c10::optional<at::Tensor> wflip, bool own_dgrad, int64_t wgrad_conv, bool make_link,
-                                       c10::optional<at::Tensor> lk_z, c10::optional<at::Tensor> lk_buf,
-                                       c10::optional<at::Tensor> lk_bias, c10::optional<at::Tensor> lk_partial,
-                                       c10::optional<at::Tensor> lk_flag, int64_t lk_act, double lk_slope, int64_t lk_kind,
-                                       int64_t stride, bool stat_atomic) {
+                                       c10::optional<PyLink> link, int64_t stride, bool stat_atomic) {
+  // the link's tensors stay arguments of the node (they keep their edges in the graph, the producer's bias among them)
+  c10::optional<at::Tensor> lk_z, lk_buf, lk_bias, lk_partial, lk_flag;
+  int64_t lk_act = 0, lk_kind = Link::kNone;
+  double lk_slope = 0.0;
+  if (link) std::tie(lk_z, lk_buf, lk_bias, lk_partial, lk_flag, lk_act, lk_slope, lk_kind) = *link;
   return ConvABNTrainNode::apply(x, w4, weight, bias, residual, running_mean, running_var, momentum, eps, act, slope, comm, world,
                                  stream, param_grad, with_skip, fused, dilation, wflip, own_dgrad, wgrad_conv, make_link, lk_z,
                                  lk_buf, lk_bias, lk_partial, lk_flag, lk_act, lk_slope, lk_kind, stride, stat_atomic);
