@@ -1,6 +1,6 @@
 """GPU probe: the element-wise ABN passes against torch's plain element-wise kernels moving the same bytes (copy_ = one read + one
 write like abn_apply; add(out=) = two reads + one write like abn_bwd_apply), every call timed inside a replayed hipGraph of 20 launches
-(no host in the loop).  UCD_ABN_GENERIC=1 selects the per-element kernels (the A/B of the packed-math forms of round 4).
+(no host in the loop).
 usage: python tools/abn_stream_probe.py [images]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

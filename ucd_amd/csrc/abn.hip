@@ -72,6 +72,38 @@ __device__ __forceinline__ void block_reduce_rows(float (&v)[NV], int tx, int ty
   }
 }
 
+// ---- the band walk ------------------------------------------------------------------------------
+// A lane's rows r, r + TY, ... below r_end: four rows (4-12 independent 16-byte loads) in flight, then one row at a time.  With
+// <= 512 row bands (2 blocks per CU) the loop is latency-bound otherwise, and the small stride-16 layers are a handful of rows
+// per thread: a one-row-at-a-time loop is a chain of exposed HBM round trips.  first(row, r) and second(row, r) request the
+// operands of row r; a batch issues its four `first` requests before its four `second` ones (the order make_geom was measured with).
+template <typename Row, typename First, typename Second>
+__device__ __forceinline__ void request4(Row (&q)[4], int r, int TY, First first, Second second) {
+#pragma unroll
+  for (int u = 0; u < 4; ++u) first(q[u], r + u * TY);
+#pragma unroll
+  for (int u = 0; u < 4; ++u) second(q[u], r + u * TY);
+}
+template <typename Row, typename Use>
+__device__ __forceinline__ void use4(const Row (&q)[4], int r, int TY, Use use) {
+#pragma unroll
+  for (int u = 0; u < 4; ++u) use(q[u], r + u * TY);
+}
+template <typename Row, typename First, typename Second, typename Use>
+__device__ __forceinline__ void walk_band(int r, int r_end, int TY, First first, Second second, Use use) {
+  for (; r + 3 * TY < r_end; r += 4 * TY) {
+    Row q[4];
+    request4(q, r, TY, first, second);
+    use4(q, r, TY, use);
+  }
+  for (; r < r_end; r += TY) {
+    Row q;
+    first(q, r);
+    second(q, r);
+    use(q, r);
+  }
+}
+
 // ---- forward statistics -------------------------------------------------------------------------
 template <typename T>
 __global__ __launch_bounds__(kBlock) void abn_stats_kernel(const T* __restrict__ x, int ld_x, int M, int C,
@@ -121,25 +153,8 @@ __global__ __launch_bounds__(kBlock) void abn_stats_kernel(const T* __restrict__
         }
       }
     };
-    int r = r_begin + ty;
-    // four independent 16-byte loads in flight per lane: with <= 512 row bands (2 blocks per CU) the loop
-    // is latency-bound otherwise
-    for (; r + 3 * TY < r_end; r += 4 * TY) {
-      Vec<T> v0, v1, v2, v3;
-      v0.load(xp + (size_t)r * ld_x);
-      v1.load(xp + (size_t)(r + TY) * ld_x);
-      v2.load(xp + (size_t)(r + 2 * TY) * ld_x);
-      v3.load(xp + (size_t)(r + 3 * TY) * ld_x);
-      accumulate(v0, r);
-      accumulate(v1, r + TY);
-      accumulate(v2, r + 2 * TY);
-      accumulate(v3, r + 3 * TY);
-    }
-    for (; r < r_end; r += TY) {
-      Vec<T> v;
-      v.load(xp + (size_t)r * ld_x);
-      accumulate(v, r);
-    }
+    walk_band<Vec<T>>(r_begin + ty, r_end, TY, [&](Vec<T>& v, int r) { v.load(xp + (size_t)r * ld_x); }, [](Vec<T>&, int) {},
+                      accumulate);
   }
   // idle tail threads (TX does not divide 256) carry zeros through the reduction: ty*TX+tx == threadIdx.x
   block_reduce_rows<2 * VEC>(acc, tx, ty, TX, TY, lds);
@@ -264,75 +279,7 @@ __global__ void abn_eval_params_kernel(const float* __restrict__ weight, const f
   scale[c] = (weight ? gamma_eff(weight[c], eps, abs_gamma) : 1.f) * is;
 }
 
-// ---- forward apply ------------------------------------------------------------------------------
-template <typename T, int ACT>
-__global__ __launch_bounds__(kBlock) void abn_apply_kernel(const T* x, int ld_x, T* y, int ld_y,
-                                                          const T* __restrict__ res, int ld_r, int M, int C,
-                                                          const float* __restrict__ plane_bias, int HW,
-                                                          const float* __restrict__ mean, const float* __restrict__ scale,
-                                                          const float* __restrict__ beta,
-                                                          float slope, int TX, int TY, int rows_per_band) {
-  constexpr int VEC = Vec<T>::N;
-  const int tx = threadIdx.x % TX, ty = threadIdx.x / TX;
-  const int cg = blockIdx.x * TX + tx;
-  if (ty >= TY || cg * VEC >= C) return;
-  float mu[VEC], sc[VEC], sh[VEC];
-#pragma unroll
-  for (int i = 0; i < VEC; ++i) {
-    mu[i] = mean[cg * VEC + i];
-    sc[i] = scale[cg * VEC + i];
-    sh[i] = beta ? beta[cg * VEC + i] : 0.f;
-  }
-  const int r_begin = blockIdx.y * rows_per_band;
-  const int r_end = min(M, r_begin + rows_per_band);
-  const size_t coff = (size_t)cg * VEC;
-  auto emit = [&](const Vec<T>& v, const Vec<T>& rv, int r) {
-    Vec<T> o;
-    const float* pb = plane_bias ? plane_bias + (size_t)(r / HW) * C + coff : nullptr;
-#pragma unroll
-    for (int i = 0; i < VEC; ++i) {
-      float f = v.get(i);
-      if (pb) f += pb[i];
-      float z = (f - mu[i]) * sc[i] + sh[i];     // subtract first: exact when x is close to the mean
-      if (res) z += rv.get(i);
-      o.set(i, act_fwd<ACT>(z, slope));
-    }
-    o.store(y + (size_t)r * ld_y + coff);
-  };
-  int r = r_begin + ty;
-  // four rows (4-8 independent 16-byte loads) in flight per lane: the small stride-16 layers are a handful
-  // of rows per thread, so a one-row-at-a-time loop is a chain of exposed HBM round trips
-  for (; r + 3 * TY < r_end; r += 4 * TY) {
-    Vec<T> v0, v1, v2, v3, q0, q1, q2, q3;
-    v0.load(x + (size_t)r * ld_x + coff);
-    v1.load(x + (size_t)(r + TY) * ld_x + coff);
-    v2.load(x + (size_t)(r + 2 * TY) * ld_x + coff);
-    v3.load(x + (size_t)(r + 3 * TY) * ld_x + coff);
-    if (res) {
-      q0.load(res + (size_t)r * ld_r + coff);
-      q1.load(res + (size_t)(r + TY) * ld_r + coff);
-      q2.load(res + (size_t)(r + 2 * TY) * ld_r + coff);
-      q3.load(res + (size_t)(r + 3 * TY) * ld_r + coff);
-    }
-    emit(v0, q0, r);
-    emit(v1, q1, r + TY);
-    emit(v2, q2, r + 2 * TY);
-    emit(v3, q3, r + 3 * TY);
-  }
-  for (; r < r_end; r += TY) {
-    Vec<T> v, q;
-    v.load(x + (size_t)r * ld_x + coff);
-    if (res) q.load(res + (size_t)r * ld_r + coff);
-    emit(v, q, r);
-  }
-}
-
-// bf16, no plane bias, leaky_relu / identity (slope = 1): the layers of the train step.  Same arithmetic as abn_apply_kernel
-// ((x - mean) * scale + shift, + residual, select; no contraction) on float pairs.
-// FIN (round 5): the statistics arrive as RAW sums about a shift (fin.acc = [sum (x - k) | sum (x - k)^2], fin.kshift = k: the
-// atomic accumulator of the producing GEMM's epilogue) and every thread finalises its eight channels itself - the arithmetic of
-// finalize_channel_pre; the first row band also stores mean / invstd / scale for the backward and updates the running statistics
-// (what tile_stats_reduce_kernel<1> did in a launch of its own, 103 times per step).
+// ---- statistics finalised by the consumer (FIN / RAW forms) ------------------------------------
 // Sum of the `reps` replicas of a [2 C] accumulator for this thread's eight channels, valid in EVERY thread on return.  The replicas
 // were filled by atomics (executed at the memory side: their lines come from memory, ~1-2 us per dependent round trip), so the TY
 // row threads of a channel group split them - thread ty takes replicas ty, ty + TY, ... with up to four (16 loads) in flight - and
@@ -428,42 +375,83 @@ __device__ __forceinline__ void apply_fin_channels(const ApplyFin& f, const Pack
   }
 }
 
-template <bool RES, bool FIN = false>
-__global__ __launch_bounds__(kBlock) void abn_apply_fast_kernel(const __hip_bfloat16* x, int ld_x, __hip_bfloat16* y, int ld_y,
-                                                               const __hip_bfloat16* __restrict__ res, int ld_r, int M, int C,
-                                                               const float* __restrict__ mean, const float* __restrict__ scale,
-                                                               const float* __restrict__ beta, float slope, int TX, int TY,
-                                                               int rows_per_band, ApplyFin fin = ApplyFin{}) {
+// ---- the element-wise passes --------------------------------------------------------------------
+// Each pass is one kernel template on float pairs (common.h: Lane<T>, Pack<NP> - packed-fp32 instructions, one v_cvt_pk_bf16_f32 per
+// bf16 pair; the library is built without fp contraction, so a pair computes what two scalars would).  T: the element type,
+// ELU: elu (a per-half select of expm1f / __expf) instead of leaky_relu (identity = slope 1), PB: plane bias (one more pair add).
+// The train step's form - bf16, leaky_relu / identity, no plane bias - takes its nullable operands (RES, YOUT, DZOUT) as
+// template flags; every other form is instantiated with the flags false and reads an operand's presence from its pointer
+// (block-uniform branches), which keeps the family at 35 kernels.  Per-channel vectors need no 16-byte alignment (load_pairs).
+template <typename T, bool ELU, bool PB>
+constexpr bool kStepForm = std::is_same<T, __hip_bfloat16>::value && !ELU && !PB;
+
+template <bool ELU>
+__device__ __forceinline__ f32x2 act2(f32x2 z, float slope) {
+  if (ELU) return f32x2{act_fwd<UCD_ACT_ELU>(z.x, slope), act_fwd<UCD_ACT_ELU>(z.y, slope)};
+  return leaky2(z, slope);
+}
+
+// One lane of the backward: dz = dy * act'(z) - the sign of z from the stored output (from_y) or recomputed as (x - mean) * scale
+// + shift - and xhat = (x - mean) * invstd
+template <bool ELU, int NP>
+__device__ __forceinline__ void bwd_lane(const Pack<NP>& v, const Pack<NP>& g, const Pack<NP>& yo, bool from_y, const Pack<NP>& mu,
+                                         const Pack<NP>& is, const Pack<NP>& sc, const Pack<NP>& sh, float slope, Pack<NP>& dz,
+                                         Pack<NP>& xh) {
+#pragma unroll
+  for (int j = 0; j < NP; ++j) {
+    const f32x2 d = v.p[j] - mu.p[j];
+    const f32x2 sgn = from_y ? yo.p[j] : d * sc.p[j] + sh.p[j];
+    if (ELU) dz.p[j] = f32x2{g.p[j].x * act_grad<UCD_ACT_ELU>(sgn.x, slope, from_y), g.p[j].y * act_grad<UCD_ACT_ELU>(sgn.y, slope, from_y)};
+    else dz.p[j] = leaky_grad2(g.p[j], sgn, slope);
+    xh.p[j] = d * is.p[j];
+  }
+}
+
+template <typename T>
+__device__ __forceinline__ uint4 load_lane(const T* p) { return *reinterpret_cast<const uint4*>(p); }
+template <typename T>
+__device__ __forceinline__ void store_lane(T* p, const Pack<Lane<T>::NP>& f) { *reinterpret_cast<uint4*>(p) = Lane<T>::pack(f); }
+
+// ---- forward apply ------------------------------------------------------------------------------
+// y = act((x + pb - mean) * scale + shift + residual): subtract first - exact when x is close to the mean.
+// FIN (bf16 only): the statistics arrive as RAW sums about a shift (ApplyFin) and every thread finalises its channels itself.
+struct ApplyRow { uint4 x, r; };   // r is set and read only when there is a residual
+template <typename T, bool ELU, bool PB, bool RES, bool FIN>
+__global__ __launch_bounds__(kBlock) void abn_apply_kernel(const T* x, int ld_x, T* y, int ld_y, const T* __restrict__ res, int ld_r,
+                                                          int M, int C, const float* __restrict__ plane_bias, int HW,
+                                                          const float* __restrict__ mean, const float* __restrict__ scale,
+                                                          const float* __restrict__ beta, float slope, int TX, int TY,
+                                                          int rows_per_band, ApplyFin fin) {
+  constexpr int NP = Lane<T>::NP, VEC = 2 * NP;
+  typedef Pack<NP> P;
   extern __shared__ __attribute__((aligned(16))) float fin_lds[];   // FIN with replicas: [256][16] reduction scratch
   const int tx = threadIdx.x % TX, ty = threadIdx.x / TX;
   const int cg = blockIdx.x * TX + tx;
-  const bool live = ty < TY && cg * 8 < C;
+  const bool live = ty < TY && cg * VEC < C;
   if (!FIN && !live) return;
-  const size_t coff = (size_t)cg * 8;
-  Pack8 mu, sc;
+  const bool has_res = kStepForm<T, ELU, PB> ? RES : res != nullptr;
+  const size_t coff = (size_t)cg * VEC;
+  P mu, sc;
   const int r_begin = blockIdx.y * rows_per_band;
   const int r_end = min(M, r_begin + rows_per_band);
-  auto ld = [&](const __hip_bfloat16* p, int ldp, int r) {
-    const uint4* q = reinterpret_cast<const uint4*>(p + (size_t)r * ldp + coff);
-    if (p == x || p == res) {      // round 6: z is not read again before the backward - a non-temporal load keeps it from displacing what the next
-                       // GEMM wants in L2 / the Infinity Cache (same-box A/B 29.77 -> 29.62 ms at 24 images; the residual, read here for the last time in the forward, the same way: 30.30 -> 30.23; profiles/r06_kernel_ab_during.txt)
-      typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-      const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(q));
-      return make_uint4(v[0], v[1], v[2], v[3]);
-    }
-    return *q;
+  // z is not read again before the backward, the residual is read here for the last time in the forward: non-temporal loads keep
+  // them from displacing what the next GEMM wants in L2 / the Infinity Cache (same-box A/B 29.77 -> 29.62 and 30.30 -> 30.23 ms
+  // at 24 images; profiles/r06_kernel_ab_during.txt).  Measured for the train step's form only: the other forms load plainly
+  auto ld = [&](const T* p, int ldp, int r) {
+    if (!kStepForm<T, ELU, PB>) return load_lane(p + (size_t)r * ldp + coff);
+    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+    const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p + (size_t)r * ldp + coff));
+    return make_uint4(v[0], v[1], v[2], v[3]);
   };
+  auto req_x = [&](ApplyRow& q, int r) { q.x = ld(x, ld_x, r); };
+  auto req_r = [&](ApplyRow& q, int r) { if (has_res) q.r = ld(res, ld_r, r); };
   int r = r_begin + ty;
   // FIN: the first batch of rows is requested BEFORE the statistics (vector memory returns in order: rows first, then the accumulator
   // - both round trips overlap, and the accumulator's lines come from memory: atomics leave nothing in L2)
   const bool pre = FIN && live && r + 3 * TY < r_end;
-  uint4 pv0, pv1, pv2, pv3, pq0, pq1, pq2, pq3;
-  if (pre) {
-    pv0 = ld(x, ld_x, r); pv1 = ld(x, ld_x, r + TY); pv2 = ld(x, ld_x, r + 2 * TY); pv3 = ld(x, ld_x, r + 3 * TY);
-    pq0 = pv0; pq1 = pv0; pq2 = pv0; pq3 = pv0;
-    if (RES) { pq0 = ld(res, ld_r, r); pq1 = ld(res, ld_r, r + TY); pq2 = ld(res, ld_r, r + 2 * TY); pq3 = ld(res, ld_r, r + 3 * TY); }
-  }
-  if (FIN) {
+  ApplyRow pq[4];
+  if (pre) request4(pq, r, TY, req_x, req_r);
+  if constexpr (FIN) {
     Pack8 s1, s2, kk, ww;
     if (live) {                                         // requested with the rows, ahead of the accumulator's round trip
       kk = load_f8(fin.kshift + coff);
@@ -473,124 +461,86 @@ __global__ __launch_bounds__(kBlock) void abn_apply_fast_kernel(const __hip_bflo
     if (!live) return;
     apply_fin_channels(fin, s1, s2, kk, ww, coff, blockIdx.y == 0 && ty == 0, mu, sc);
   } else {
-    mu = load_f8(mean + coff);
-    sc = load_f8(scale + coff);
+    mu = load_pairs<NP>(mean + coff);
+    sc = load_pairs<NP>(scale + coff);
   }
-  Pack8 sh;
-  if (beta) sh = load_f8(beta + coff);
-  else {
+  const P sh = beta ? load_pairs<NP>(beta + coff) : zero_pairs<NP>();
+  auto emit = [&](const ApplyRow& q, int r) {
+    P v = Lane<T>::unpack(q.x), o;
+    if (PB) {
+      const P pb = load_pairs<NP>(plane_bias + (size_t)(r / HW) * C + coff);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) sh.p[j] = f32x2{0.f, 0.f};
-  }
-  auto emit = [&](const uint4& xv, const uint4& rv, int r) {
-    const Pack8 v = unpack8(xv);
-    Pack8 o;
-    if (RES) {
-      const Pack8 q = unpack8(rv);
+      for (int j = 0; j < NP; ++j) v.p[j] = v.p[j] + pb.p[j];
+    }
+    if (has_res) {
+      const P qr = Lane<T>::unpack(q.r);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) o.p[j] = leaky2((v.p[j] - mu.p[j]) * sc.p[j] + sh.p[j] + q.p[j], slope);
+      for (int j = 0; j < NP; ++j) o.p[j] = act2<ELU>((v.p[j] - mu.p[j]) * sc.p[j] + sh.p[j] + qr.p[j], slope);
     } else {
 #pragma unroll
-      for (int j = 0; j < 4; ++j) o.p[j] = leaky2((v.p[j] - mu.p[j]) * sc.p[j] + sh.p[j], slope);
+      for (int j = 0; j < NP; ++j) o.p[j] = act2<ELU>((v.p[j] - mu.p[j]) * sc.p[j] + sh.p[j], slope);
     }
-    *reinterpret_cast<uint4*>(y + (size_t)r * ld_y + coff) = pack8(o);
+    store_lane(y + (size_t)r * ld_y + coff, o);
   };
   if (pre) {
-    emit(pv0, pq0, r);
-    emit(pv1, pq1, r + TY);
-    emit(pv2, pq2, r + 2 * TY);
-    emit(pv3, pq3, r + 3 * TY);
+    use4(pq, r, TY, emit);
     r += 4 * TY;
   }
-  for (; r + 3 * TY < r_end; r += 4 * TY) {
-    uint4 v0 = ld(x, ld_x, r), v1 = ld(x, ld_x, r + TY), v2 = ld(x, ld_x, r + 2 * TY), v3 = ld(x, ld_x, r + 3 * TY);
-    uint4 q0 = v0, q1 = v0, q2 = v0, q3 = v0;
-    if (RES) {
-      q0 = ld(res, ld_r, r); q1 = ld(res, ld_r, r + TY); q2 = ld(res, ld_r, r + 2 * TY); q3 = ld(res, ld_r, r + 3 * TY);
-    }
-    emit(v0, q0, r);
-    emit(v1, q1, r + TY);
-    emit(v2, q2, r + 2 * TY);
-    emit(v3, q3, r + 3 * TY);
-  }
-  for (; r < r_end; r += TY) {
-    const uint4 v = ld(x, ld_x, r);
-    uint4 q = v;
-    if (RES) q = ld(res, ld_r, r);
-    emit(v, q, r);
-  }
+  walk_band<ApplyRow>(r, r_end, TY, req_x, req_r, emit);
 }
 
-// ---- backward reduce ----------------------------------------------------------------------------
-template <typename T, int ACT>
+// ---- backward -----------------------------------------------------------------------------------
+// A row's operands: x and dy are requested row by row, then the stored outputs (y - and the `yo` unpacked from it - is set
+// and read only when the sign comes from the output)
+struct BwdRow { uint4 x, dy, y; };
+
+// sums: [sum dz | sum dz * xhat] per channel and row band
+template <typename T, bool ELU, bool PB, bool YOUT>
 __global__ __launch_bounds__(kBlock) void abn_bwd_reduce_kernel(
-    const T* __restrict__ x, int ld_x, const T* __restrict__ dy, int ld_dy, const T* __restrict__ yout, int ld_y,
-    int M, int C, const float* __restrict__ plane_bias, int HW, const float* __restrict__ mean,
-    const float* __restrict__ invstd, const float* __restrict__ scale, const float* __restrict__ shift, float slope,
-    int TX, int TY, int rows_per_band, float* __restrict__ partial) {
-  constexpr int VEC = Vec<T>::N;
+    const T* __restrict__ x, int ld_x, const T* __restrict__ dy, int ld_dy, const T* __restrict__ yout, int ld_y, int M, int C,
+    const float* __restrict__ plane_bias, int HW, const float* __restrict__ mean, const float* __restrict__ invstd,
+    const float* __restrict__ scale, const float* __restrict__ shift, float slope, int TX, int TY, int rows_per_band,
+    float* __restrict__ partial) {
+  constexpr int NP = Lane<T>::NP, VEC = 2 * NP;
+  typedef Pack<NP> P;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int tx = threadIdx.x % TX, ty = threadIdx.x / TX;
   const int cg = blockIdx.x * TX + tx;
   const bool live = ty < TY && cg * VEC < C;
-  float acc[2 * VEC];
+  const bool from_y = kStepForm<T, ELU, PB> ? YOUT : yout != nullptr;
+  f32x2 s1[NP], s2[NP];
 #pragma unroll
-  for (int i = 0; i < 2 * VEC; ++i) acc[i] = 0.f;
+  for (int j = 0; j < NP; ++j) { s1[j] = f32x2{0.f, 0.f}; s2[j] = f32x2{0.f, 0.f}; }
   if (live) {
-    float mu[VEC], is[VEC], sc[VEC], sh[VEC];
-#pragma unroll
-    for (int i = 0; i < VEC; ++i) {
-      mu[i] = mean[cg * VEC + i];
-      is[i] = invstd[cg * VEC + i];
-      sc[i] = scale[cg * VEC + i];
-      sh[i] = shift ? shift[cg * VEC + i] : 0.f;
-    }
+    const size_t coff = (size_t)cg * VEC;
+    const P mu = load_pairs<NP>(mean + coff), is = load_pairs<NP>(invstd + coff), sc = load_pairs<NP>(scale + coff);
+    const P sh = shift ? load_pairs<NP>(shift + coff) : zero_pairs<NP>();
     const int r_begin = blockIdx.y * rows_per_band;
     const int r_end = min(M, r_begin + rows_per_band);
-    const size_t coff = (size_t)cg * VEC;
-    auto accumulate = [&](const Vec<T>& v, const Vec<T>& g, const Vec<T>& yo, int r) {
-      const float* pb = plane_bias ? plane_bias + (size_t)(r / HW) * C + coff : nullptr;
+    auto accumulate = [&](const BwdRow& q, int r) {
+      P v = Lane<T>::unpack(q.x), yo, dz, xh;
+      const P g = Lane<T>::unpack(q.dy);
+      if (from_y) yo = Lane<T>::unpack(q.y);
+      if (PB) {
+        const P pb = load_pairs<NP>(plane_bias + (size_t)(r / HW) * C + coff);
 #pragma unroll
-      for (int i = 0; i < VEC; ++i) {
-        float f = v.get(i);
-        if (pb) f += pb[i];
-        float sgn = yout ? yo.get(i) : (f - mu[i]) * sc[i] + sh[i];
-        float dz = g.get(i) * act_grad<ACT>(sgn, slope, yout != nullptr);
-        float xh = (f - mu[i]) * is[i];
-        acc[i] += dz;
-        acc[VEC + i] += dz * xh;
+        for (int j = 0; j < NP; ++j) v.p[j] = v.p[j] + pb.p[j];
+      }
+      bwd_lane<ELU>(v, g, yo, from_y, mu, is, sc, sh, slope, dz, xh);
+#pragma unroll
+      for (int j = 0; j < NP; ++j) {
+        s1[j] += dz.p[j];
+        s2[j] += dz.p[j] * xh.p[j];
       }
     };
-    int r = r_begin + ty;
-    for (; r + 3 * TY < r_end; r += 4 * TY) {   // four rows (8-12 independent loads) in flight per lane
-      Vec<T> v0, g0, y0, v1, g1, y1, v2, g2, y2, v3, g3, y3;
-      v0.load(x + (size_t)r * ld_x + coff);
-      g0.load(dy + (size_t)r * ld_dy + coff);
-      v1.load(x + (size_t)(r + TY) * ld_x + coff);
-      g1.load(dy + (size_t)(r + TY) * ld_dy + coff);
-      v2.load(x + (size_t)(r + 2 * TY) * ld_x + coff);
-      g2.load(dy + (size_t)(r + 2 * TY) * ld_dy + coff);
-      v3.load(x + (size_t)(r + 3 * TY) * ld_x + coff);
-      g3.load(dy + (size_t)(r + 3 * TY) * ld_dy + coff);
-      if (yout) {
-        y0.load(yout + (size_t)r * ld_y + coff);
-        y1.load(yout + (size_t)(r + TY) * ld_y + coff);
-        y2.load(yout + (size_t)(r + 2 * TY) * ld_y + coff);
-        y3.load(yout + (size_t)(r + 3 * TY) * ld_y + coff);
-      }
-      accumulate(v0, g0, y0, r);
-      accumulate(v1, g1, y1, r + TY);
-      accumulate(v2, g2, y2, r + 2 * TY);
-      accumulate(v3, g3, y3, r + 3 * TY);
-    }
-    for (; r < r_end; r += TY) {
-      Vec<T> v, g, yo;
-      v.load(x + (size_t)r * ld_x + coff);
-      g.load(dy + (size_t)r * ld_dy + coff);
-      if (yout) yo.load(yout + (size_t)r * ld_y + coff);
-      accumulate(v, g, yo, r);
-    }
+    walk_band<BwdRow>(
+        r_begin + ty, r_end, TY,
+        [&](BwdRow& q, int r) { q.x = load_lane(x + (size_t)r * ld_x + coff); q.dy = load_lane(dy + (size_t)r * ld_dy + coff); },
+        [&](BwdRow& q, int r) { if (from_y) q.y = load_lane(yout + (size_t)r * ld_y + coff); }, accumulate);
   }
+  float acc[2 * VEC];
+#pragma unroll
+  for (int j = 0; j < NP; ++j) { acc[2 * j] = s1[j].x; acc[2 * j + 1] = s1[j].y; acc[VEC + 2 * j] = s2[j].x; acc[VEC + 2 * j + 1] = s2[j].y; }
   block_reduce_rows<2 * VEC>(acc, tx, ty, TX, TY, lds);
   if (ty == 0 && cg * VEC < C) {
     float* p = partial + (size_t)blockIdx.y * 2 * C + cg * VEC;
@@ -602,182 +552,28 @@ __global__ __launch_bounds__(kBlock) void abn_bwd_reduce_kernel(
   }
 }
 
-// ---- backward apply -----------------------------------------------------------------------------
-template <typename T, int ACT>
+// dx = ((dz - mean(dz)) - xhat * mean(dz xhat)) * gamma invstd (no fma anywhere).  frozen: k0 = k1 = invstd = 0, gw = scale.
+// RAW (bf16 only): sums are the atomic accumulator of a link epilogue - [sum dz | sum dz * xhat] with no sign applied; the first row
+// band writes the layer's parameter gradients [d bias | d weight] to grad_out from grad_sums (what reduce_bands_kernel did)
+template <typename T, bool ELU, bool PB, bool YOUT, bool DZOUT, bool RAW>
 __global__ __launch_bounds__(kBlock) void abn_bwd_apply_kernel(
-    const T* x, int ld_x, const T* dy, int ld_dy, const T* yout, int ld_y,
-    T* dx, int ld_dx, T* dz_out, int ld_dz, int M, int C,
+    const T* x, int ld_x, const T* dy, int ld_dy, const T* yout, int ld_y, T* dx, int ld_dx, T* dz_out, int ld_dz, int M, int C,
     const float* __restrict__ plane_bias, int HW, const float* __restrict__ mean, const float* __restrict__ invstd,
     const float* __restrict__ scale, const float* __restrict__ shift, const float* __restrict__ weight,
-    const float* __restrict__ sums, float inv_count, int frozen, int abs_gamma, float slope, int TX, int TY,
-    int rows_per_band) {
-  constexpr int VEC = Vec<T>::N;
-  const int tx = threadIdx.x % TX, ty = threadIdx.x / TX;
-  const int cg = blockIdx.x * TX + tx;
-  if (ty >= TY || cg * VEC >= C) return;
-  float mu[VEC], is[VEC], sc[VEC], sh[VEC], k0[VEC], k1[VEC], gw[VEC];
-#pragma unroll
-  for (int i = 0; i < VEC; ++i) {
-    const int c = cg * VEC + i;
-    sc[i] = scale[c];
-    sh[i] = shift ? shift[c] : 0.f;
-    mu[i] = mean[c];
-    if (frozen) {
-      is[i] = 0.f; k0[i] = 0.f; k1[i] = 0.f;
-      gw[i] = sc[i];
-    } else {
-      is[i] = invstd[c];
-      k0[i] = sums[c] * inv_count;       // mean(dz)
-      k1[i] = sums[C + c] * inv_count;   // mean(dz * xhat)
-      if (abs_gamma) {                   // sums[C + c] is d weight = sign(weight) * sum dz*xhat; scale = (|w| + eps) * invstd
-        if (weight && weight[c] < 0.f) k1[i] = -k1[i];
-        gw[i] = sc[i];
-      } else {
-        gw[i] = (weight ? weight[c] : 1.f) * is[i];
-      }
-    }
-  }
-  const int r_begin = blockIdx.y * rows_per_band;
-  const int r_end = min(M, r_begin + rows_per_band);
-  const size_t coff = (size_t)cg * VEC;
-  auto emit = [&](const Vec<T>& v, const Vec<T>& g, const Vec<T>& yo, int r) {
-    Vec<T> o, oz;
-    const float* pb = plane_bias ? plane_bias + (size_t)(r / HW) * C + coff : nullptr;
-#pragma unroll
-    for (int i = 0; i < VEC; ++i) {
-      float f = v.get(i);
-      if (pb) f += pb[i];
-      float sgn = yout ? yo.get(i) : (f - mu[i]) * sc[i] + sh[i];
-      float dz = g.get(i) * act_grad<ACT>(sgn, slope, yout != nullptr);
-      float xh = (f - mu[i]) * is[i];
-      o.set(i, (dz - k0[i] - xh * k1[i]) * gw[i]);
-      oz.set(i, dz);
-    }
-    o.store(dx + (size_t)r * ld_dx + coff);
-    if (dz_out) oz.store(dz_out + (size_t)r * ld_dz + coff);
-  };
-  int r = r_begin + ty;
-  for (; r + 3 * TY < r_end; r += 4 * TY) {   // four rows (8-12 independent loads) in flight per lane
-    Vec<T> v0, v1, v2, v3, g0, g1, g2, g3, y0, y1, y2, y3;
-    v0.load(x + (size_t)r * ld_x + coff);
-    g0.load(dy + (size_t)r * ld_dy + coff);
-    v1.load(x + (size_t)(r + TY) * ld_x + coff);
-    g1.load(dy + (size_t)(r + TY) * ld_dy + coff);
-    v2.load(x + (size_t)(r + 2 * TY) * ld_x + coff);
-    g2.load(dy + (size_t)(r + 2 * TY) * ld_dy + coff);
-    v3.load(x + (size_t)(r + 3 * TY) * ld_x + coff);
-    g3.load(dy + (size_t)(r + 3 * TY) * ld_dy + coff);
-    if (yout) {
-      y0.load(yout + (size_t)r * ld_y + coff);
-      y1.load(yout + (size_t)(r + TY) * ld_y + coff);
-      y2.load(yout + (size_t)(r + 2 * TY) * ld_y + coff);
-      y3.load(yout + (size_t)(r + 3 * TY) * ld_y + coff);
-    }
-    emit(v0, g0, y0, r);
-    emit(v1, g1, y1, r + TY);
-    emit(v2, g2, y2, r + 2 * TY);
-    emit(v3, g3, y3, r + 3 * TY);
-  }
-  for (; r < r_end; r += TY) {
-    Vec<T> v, g, yo;
-    v.load(x + (size_t)r * ld_x + coff);
-    g.load(dy + (size_t)r * ld_dy + coff);
-    if (yout) yo.load(yout + (size_t)r * ld_y + coff);
-    emit(v, g, yo, r);
-  }
-}
-
-// ---- backward, bf16 fast path (no plane bias, leaky_relu / identity): packed-fp32 math, nullable operands as flags --------
-template <bool YOUT>
-__global__ __launch_bounds__(kBlock) void abn_bwd_reduce_fast_kernel(
-    const __hip_bfloat16* __restrict__ x, int ld_x, const __hip_bfloat16* __restrict__ dy, int ld_dy,
-    const __hip_bfloat16* __restrict__ yout, int ld_y, int M, int C, const float* __restrict__ mean,
-    const float* __restrict__ invstd, const float* __restrict__ scale, const float* __restrict__ shift, float slope, int TX, int TY,
-    int rows_per_band, float* __restrict__ partial) {
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  const int tx = threadIdx.x % TX, ty = threadIdx.x / TX;
-  const int cg = blockIdx.x * TX + tx;
-  const bool live = ty < TY && cg * 8 < C;
-  f32x2 s1[4], s2[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) { s1[j] = f32x2{0.f, 0.f}; s2[j] = f32x2{0.f, 0.f}; }
-  if (live) {
-    const size_t coff = (size_t)cg * 8;
-    const Pack8 mu = load_f8(mean + coff), is = load_f8(invstd + coff), sc = load_f8(scale + coff);
-    Pack8 sh;
-    if (shift) sh = load_f8(shift + coff);
-    else {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) sh.p[j] = f32x2{0.f, 0.f};
-    }
-    const int r_begin = blockIdx.y * rows_per_band;
-    const int r_end = min(M, r_begin + rows_per_band);
-    auto accumulate = [&](const uint4& xv, const uint4& gv, const uint4& yv) {
-      const Pack8 v = unpack8(xv), g = unpack8(gv);
-      Pack8 yo;
-      if (YOUT) yo = unpack8(yv);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const f32x2 d = v.p[j] - mu.p[j];
-        const f32x2 sgn = YOUT ? yo.p[j] : d * sc.p[j] + sh.p[j];
-        const f32x2 dz = leaky_grad2(g.p[j], sgn, slope);
-        s1[j] += dz;
-        s2[j] += dz * (d * is.p[j]);
-      }
-    };
-    auto ld = [&](const __hip_bfloat16* p, int ldp, int r) { return *reinterpret_cast<const uint4*>(p + (size_t)r * ldp + coff); };
-    int r = r_begin + ty;
-    for (; r + 3 * TY < r_end; r += 4 * TY) {
-      const uint4 v0 = ld(x, ld_x, r), g0 = ld(dy, ld_dy, r), v1 = ld(x, ld_x, r + TY), g1 = ld(dy, ld_dy, r + TY);
-      const uint4 v2 = ld(x, ld_x, r + 2 * TY), g2 = ld(dy, ld_dy, r + 2 * TY), v3 = ld(x, ld_x, r + 3 * TY), g3 = ld(dy, ld_dy, r + 3 * TY);
-      uint4 y0 = v0, y1 = v0, y2 = v0, y3 = v0;
-      if (YOUT) { y0 = ld(yout, ld_y, r); y1 = ld(yout, ld_y, r + TY); y2 = ld(yout, ld_y, r + 2 * TY); y3 = ld(yout, ld_y, r + 3 * TY); }
-      accumulate(v0, g0, y0);
-      accumulate(v1, g1, y1);
-      accumulate(v2, g2, y2);
-      accumulate(v3, g3, y3);
-    }
-    for (; r < r_end; r += TY) {
-      const uint4 v = ld(x, ld_x, r), g = ld(dy, ld_dy, r);
-      uint4 yo = v;
-      if (YOUT) yo = ld(yout, ld_y, r);
-      accumulate(v, g, yo);
-    }
-  }
-  float acc[16];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) { acc[2 * j] = s1[j].x; acc[2 * j + 1] = s1[j].y; acc[8 + 2 * j] = s2[j].x; acc[8 + 2 * j + 1] = s2[j].y; }
-  block_reduce_rows<16>(acc, tx, ty, TX, TY, lds);
-  if (ty == 0 && cg * 8 < C) {
-    float* p = partial + (size_t)blockIdx.y * 2 * C + cg * 8;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      p[i] = acc[i];
-      p[C + i] = acc[8 + i];
-    }
-  }
-}
-
-// dx = (dz - mean(dz) - xhat * mean(dz xhat)) * gamma invstd with the same operation order as abn_bwd_apply_kernel:
-// ((dz - k0) - xhat k1) gw (the library is built with -ffp-contract=off: no fma anywhere).  frozen: k0 = k1 = invstd = 0, gw = scale.
-// RAW (round 5): sums are the atomic accumulator of a link epilogue - [sum dz | sum dz * xhat] with no sign applied; the first row
-// band writes the layer's parameter gradients [d bias | d weight] to grad_out from grad_sums (what reduce_bands_kernel did)
-template <bool YOUT, bool DZOUT, bool RAW = false>
-__global__ __launch_bounds__(kBlock) void abn_bwd_apply_fast_kernel(
-    const __hip_bfloat16* x, int ld_x, const __hip_bfloat16* dy, int ld_dy, const __hip_bfloat16* yout, int ld_y,
-    __hip_bfloat16* dx, int ld_dx, __hip_bfloat16* dz_out, int ld_dz, int M, int C, const float* __restrict__ mean,
-    const float* __restrict__ invstd, const float* __restrict__ scale, const float* __restrict__ shift,
-    const float* __restrict__ weight, const float* __restrict__ sums, float inv_count, int frozen, int abs_gamma, float slope,
-    int TX, int TY, int rows_per_band, const float* __restrict__ grad_sums = nullptr, float* __restrict__ grad_out = nullptr,
-    int reps = 1) {
+    const float* __restrict__ sums, float inv_count, int frozen, int abs_gamma, float slope, int TX, int TY, int rows_per_band,
+    const float* __restrict__ grad_sums, float* __restrict__ grad_out, int reps) {
+  constexpr int NP = Lane<T>::NP, VEC = 2 * NP;
+  typedef Pack<NP> P;
   extern __shared__ __attribute__((aligned(16))) float raw_lds[];   // RAW with replicas: [256][16] reduction scratch
   const int tx = threadIdx.x % TX, ty = threadIdx.x / TX;
   const int cg = blockIdx.x * TX + tx;
-  const bool live = ty < TY && cg * 8 < C;
+  const bool live = ty < TY && cg * VEC < C;
   if (!RAW && !live) return;
-  const size_t coff = (size_t)cg * 8;
-  Pack8 rs0, rs1, rg0, rg1;                             // RAW: the replica-summed sums (and this rank's, for the parameter gradients)
-  if (RAW) {
+  const bool from_y = kStepForm<T, ELU, PB> ? YOUT : yout != nullptr;
+  const bool want_dz = kStepForm<T, ELU, PB> ? DZOUT : dz_out != nullptr;
+  const size_t coff = (size_t)cg * VEC;
+  P rs0, rs1, rg0, rg1;                                 // RAW: the replica-summed sums (and this rank's, for the parameter gradients)
+  if constexpr (RAW) {
     replica_sum(sums, reps, C, coff, tx, ty, TX, TY, live, raw_lds, rs0, rs1);
     const bool want_g = grad_out != nullptr && blockIdx.y == 0;       // block-uniform
     if (want_g && grad_sums != sums) {
@@ -788,29 +584,25 @@ __global__ __launch_bounds__(kBlock) void abn_bwd_apply_fast_kernel(
     }
     if (!live) return;
   }
-  const Pack8 mu = load_f8(mean + coff), sc = load_f8(scale + coff);
-  Pack8 sh, is, k0, k1, gw;
-  if (shift) sh = load_f8(shift + coff);
-  else {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) sh.p[j] = f32x2{0.f, 0.f};
-  }
+  // the per-channel constants
+  const P mu = load_pairs<NP>(mean + coff), sc = load_pairs<NP>(scale + coff);
+  const P sh = shift ? load_pairs<NP>(shift + coff) : zero_pairs<NP>();
+  P is, k0, k1, gw;
   if (frozen) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { is.p[j] = f32x2{0.f, 0.f}; k0.p[j] = f32x2{0.f, 0.f}; k1.p[j] = f32x2{0.f, 0.f}; gw.p[j] = sc.p[j]; }
+    is = zero_pairs<NP>(); k0 = zero_pairs<NP>(); k1 = zero_pairs<NP>(); gw = sc;
   } else {
-    is = load_f8(invstd + coff);
-    Pack8 a0, a1;
+    is = load_pairs<NP>(invstd + coff);
+    P a0, a1, w;
     if (RAW) { a0 = rs0; a1 = rs1; }
-    else { a0 = load_f8(sums + coff); a1 = load_f8(sums + C + coff); }
-    Pack8 w;
-    if (weight) w = load_f8(weight + coff);
+    else { a0 = load_pairs<NP>(sums + coff); a1 = load_pairs<NP>(sums + C + coff); }
+    if (weight) w = load_pairs<NP>(weight + coff);
+    auto signed_by_weight = [&](f32x2 v, int j) { return f32x2{w.p[j].x < 0.f ? -v.x : v.x, w.p[j].y < 0.f ? -v.y : v.y}; };
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
+    for (int j = 0; j < NP; ++j) {
       k0.p[j] = a0.p[j] * inv_count;                    // mean(dz)
       f32x2 kk = a1.p[j] * inv_count;                   // mean(dz * xhat)
       if (abs_gamma) {                                  // sums[C + c] is d weight = sign(weight) * sum dz*xhat; scale = (|w| + eps) * invstd
-        if (weight && !RAW) kk = f32x2{w.p[j].x < 0.f ? -kk.x : kk.x, w.p[j].y < 0.f ? -kk.y : kk.y};
+        if (weight && !RAW) kk = signed_by_weight(kk, j);
         gw.p[j] = sc.p[j];
       } else {
         gw.p[j] = weight ? w.p[j] * is.p[j] : is.p[j];
@@ -818,53 +610,35 @@ __global__ __launch_bounds__(kBlock) void abn_bwd_apply_fast_kernel(
       k1.p[j] = kk;
     }
     if (RAW && grad_out && blockIdx.y == 0 && ty == 0) {
-      const Pack8 g0 = rg0, g1 = rg1;
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        f32x2 dwt = g1.p[j];
-        if (abs_gamma && weight) dwt = f32x2{w.p[j].x < 0.f ? -dwt.x : dwt.x, w.p[j].y < 0.f ? -dwt.y : dwt.y};
-        *reinterpret_cast<f32x2*>(grad_out + coff + 2 * j) = g0.p[j];
-        *reinterpret_cast<f32x2*>(grad_out + C + coff + 2 * j) = dwt;
+      for (int j = 0; j < NP; ++j) {
+        *reinterpret_cast<f32x2*>(grad_out + coff + 2 * j) = rg0.p[j];
+        *reinterpret_cast<f32x2*>(grad_out + C + coff + 2 * j) = abs_gamma && weight ? signed_by_weight(rg1.p[j], j) : rg1.p[j];
       }
     }
   }
   const int r_begin = blockIdx.y * rows_per_band;
   const int r_end = min(M, r_begin + rows_per_band);
-  auto emit = [&](const uint4& xv, const uint4& gv, const uint4& yv, int r) {
-    const Pack8 v = unpack8(xv), g = unpack8(gv);
-    Pack8 yo, o, oz;
-    if (YOUT) yo = unpack8(yv);
+  auto emit = [&](const BwdRow& q, int r) {
+    P v = Lane<T>::unpack(q.x), yo, dz, xh, o;
+    const P g = Lane<T>::unpack(q.dy);
+    if (from_y) yo = Lane<T>::unpack(q.y);
+    if (PB) {
+      const P pb = load_pairs<NP>(plane_bias + (size_t)(r / HW) * C + coff);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const f32x2 d = v.p[j] - mu.p[j];
-      const f32x2 sgn = YOUT ? yo.p[j] : d * sc.p[j] + sh.p[j];
-      const f32x2 dz = leaky_grad2(g.p[j], sgn, slope);
-      const f32x2 xh = d * is.p[j];
-      o.p[j] = (dz - k0.p[j] - xh * k1.p[j]) * gw.p[j];
-      oz.p[j] = dz;
+      for (int j = 0; j < NP; ++j) v.p[j] = v.p[j] + pb.p[j];
     }
-    *reinterpret_cast<uint4*>(dx + (size_t)r * ld_dx + coff) = pack8(o);
-    if (DZOUT) *reinterpret_cast<uint4*>(dz_out + (size_t)r * ld_dz + coff) = pack8(oz);
+    bwd_lane<ELU>(v, g, yo, from_y, mu, is, sc, sh, slope, dz, xh);
+#pragma unroll
+    for (int j = 0; j < NP; ++j) o.p[j] = (dz.p[j] - k0.p[j] - xh.p[j] * k1.p[j]) * gw.p[j];
+    store_lane(dx + (size_t)r * ld_dx + coff, o);
+    if (want_dz) store_lane(dz_out + (size_t)r * ld_dz + coff, dz);
   };
   // (non-temporal loads of z and dy - both read here for the last time - measured level: 30.38 vs 30.35 ms; the forward apply keeps its)
-  auto ld = [&](const __hip_bfloat16* p, int ldp, int r) { return *reinterpret_cast<const uint4*>(p + (size_t)r * ldp + coff); };
-  int r = r_begin + ty;
-  for (; r + 3 * TY < r_end; r += 4 * TY) {
-    const uint4 v0 = ld(x, ld_x, r), g0 = ld(dy, ld_dy, r), v1 = ld(x, ld_x, r + TY), g1 = ld(dy, ld_dy, r + TY);
-    const uint4 v2 = ld(x, ld_x, r + 2 * TY), g2 = ld(dy, ld_dy, r + 2 * TY), v3 = ld(x, ld_x, r + 3 * TY), g3 = ld(dy, ld_dy, r + 3 * TY);
-    uint4 y0 = v0, y1 = v0, y2 = v0, y3 = v0;
-    if (YOUT) { y0 = ld(yout, ld_y, r); y1 = ld(yout, ld_y, r + TY); y2 = ld(yout, ld_y, r + 2 * TY); y3 = ld(yout, ld_y, r + 3 * TY); }
-    emit(v0, g0, y0, r);
-    emit(v1, g1, y1, r + TY);
-    emit(v2, g2, y2, r + 2 * TY);
-    emit(v3, g3, y3, r + 3 * TY);
-  }
-  for (; r < r_end; r += TY) {
-    const uint4 v = ld(x, ld_x, r), g = ld(dy, ld_dy, r);
-    uint4 yo = v;
-    if (YOUT) yo = ld(yout, ld_y, r);
-    emit(v, g, yo, r);
-  }
+  walk_band<BwdRow>(
+      r_begin + ty, r_end, TY,
+      [&](BwdRow& q, int r) { q.x = load_lane(x + (size_t)r * ld_x + coff); q.dy = load_lane(dy + (size_t)r * ld_dy + coff); },
+      [&](BwdRow& q, int r) { if (from_y) q.y = load_lane(yout + (size_t)r * ld_y + coff); }, emit);
 }
 
 // ---- per-(image, channel) plane sums ------------------------------------------------------------
@@ -1050,11 +824,34 @@ int check_common(const char* fn, int dtype, int M, int C, int act) {
   return 0;
 }
 
-// bf16 tensors without a plane bias under leaky_relu / identity take the packed-math kernels (UCD_ABN_GENERIC=1: the per-element
-// kernels everywhere - the A/B switch of tools/abn_bench.py)
-inline bool fast_path(int dtype, const float* plane_bias, int act_kind) {
-  static const bool generic = getenv("UCD_ABN_GENERIC") != nullptr && getenv("UCD_ABN_GENERIC")[0] == '1';
-  return !generic && dtype == UCD_BF16 && !plane_bias && act_kind != UCD_ACT_ELU;
+// ---- dispatch -----------------------------------------------------------------------------------
+// f(std::true_type / std::false_type ...): run-time booleans as compile-time ones
+template <typename F>
+void with_flags(F&& f) { f(); }
+template <typename F, typename... Rest>
+void with_flags(F&& f, bool b, Rest... rest) {
+  if (b) with_flags([&](auto... r) { f(std::true_type{}, r...); }, rest...);
+  else with_flags([&](auto... r) { f(std::false_type{}, r...); }, rest...);
+}
+#define UCD_FLAG(x) decltype(x)::value
+
+// f(T{}, ELU, PB, operand flags...) for an element-wise pass.  Outside the train step's form (kStepForm) the operand flags arrive
+// false: those kernels read an operand's presence from its pointer.
+template <typename F, typename... Operands>
+void dispatch_form(int dtype, int act_kind, const float* plane_bias, F&& f, Operands... operands) {
+  with_flags(
+      [&](auto BF, auto ELU, auto PB, auto... OP) {
+        typedef std::conditional_t<UCD_FLAG(BF), __hip_bfloat16, float> T;
+        f(T{}, ELU, PB, std::integral_constant<bool, kStepForm<T, UCD_FLAG(ELU), UCD_FLAG(PB)> && UCD_FLAG(OP)>{}...);
+      },
+      dtype == UCD_BF16, act_kind == UCD_ACT_ELU, plane_bias != nullptr, operands...);
+}
+
+// identity is leaky_relu with slope 1; elu's slope is its alpha
+inline float kernel_slope(int act_kind, float slope) { return act_kind == UCD_ACT_IDENTITY ? 1.f : slope; }
+
+inline Geom geom_for(int dtype, int M, int C, int min_iters, int max_bands = 4096) {
+  return dtype == UCD_BF16 ? make_geom<8>(M, C, 512, min_iters, max_bands) : make_geom<4>(M, C, 512, min_iters, max_bands);
 }
 
 #define UCD_TRY(expr)          \
@@ -1085,18 +882,15 @@ static int abn_stats_impl(const void* x, int ld_x, int dtype, int M, int C, cons
   UCD_REQUIRE(!plane_bias || HW > 0, UCD_EINVAL, "%s: plane_bias needs HW > 0", fn);
   hipStream_t s = (hipStream_t)stream;
   float* partial = (float*)workspace;
-  Geom g;
-  if (dtype == UCD_BF16) {
-    g = make_geom<8>(M, C, 512, 8, kMaxBands);
-    UCD_REQUIRE(workspace_bytes >= (size_t)g.gy * 2 * C * 4, UCD_EWORKSPACE, "%s: workspace too small", fn);
-    abn_stats_kernel<__hip_bfloat16><<<dim3(g.gx, g.gy), kBlock, kBlock * 16 * 4, s>>>(
-        (const __hip_bfloat16*)x, ld_x, M, C, plane_bias, HW, g.TX, g.TY, g.rows_per_band, partial, kshift);
-  } else {
-    g = make_geom<4>(M, C, 512, 8, kMaxBands);
-    UCD_REQUIRE(workspace_bytes >= (size_t)g.gy * 2 * C * 4, UCD_EWORKSPACE, "%s: workspace too small", fn);
-    abn_stats_kernel<float><<<dim3(g.gx, g.gy), kBlock, kBlock * 8 * 4, s>>>(
-        (const float*)x, ld_x, M, C, plane_bias, HW, g.TX, g.TY, g.rows_per_band, partial, kshift);
-  }
+  const Geom g = geom_for(dtype, M, C, 8, kMaxBands);
+  UCD_REQUIRE(workspace_bytes >= (size_t)g.gy * 2 * C * 4, UCD_EWORKSPACE, "%s: workspace too small", fn);
+  with_flags(
+      [&](auto BF) {
+        typedef std::conditional_t<UCD_FLAG(BF), __hip_bfloat16, float> T;
+        abn_stats_kernel<T><<<dim3(g.gx, g.gy), kBlock, kBlock * 2 * Vec<T>::N * 4, s>>>(
+            (const T*)x, ld_x, M, C, plane_bias, HW, g.TX, g.TY, g.rows_per_band, partial, kshift);
+      },
+      dtype == UCD_BF16);
   UCD_TRY(check_launch(fn));
   if (fin && fin->pack)
     UCD_REDUCE_BANDS(2, g.gy, partial, g.gy, C, sums, *fin);
@@ -1153,37 +947,17 @@ int ucd_abn_apply(const void* x, int ld_x, void* y, int ld_y, const void* residu
   UCD_REQUIRE(mean && scale, UCD_EINVAL, "%s: mean/scale is NULL", fn);
   UCD_REQUIRE(!plane_bias || HW > 0, UCD_EINVAL, "%s: plane_bias needs HW > 0", fn);
   hipStream_t s = (hipStream_t)stream;
-#define LAUNCH_APPLY(T, VECN, ACT)                                                                             \
-  {                                                                                                            \
-    Geom g = make_geom<VECN>(M, C, 512, 4);                                                                 \
-    abn_apply_kernel<T, ACT><<<dim3(g.gx, g.gy), kBlock, 0, s>>>((const T*)x, ld_x, (T*)y, ld_y,               \
-                                                                 (const T*)residual, ld_r, M, C, plane_bias,   \
-                                                                 HW, mean, scale, shift, slope, g.TX, g.TY,    \
-                                                                 g.rows_per_band);                             \
-  }
   const int a = act & UCD_ACT_MASK;
-  if (fast_path(dtype, plane_bias, a) && aligned16(mean) && aligned16(scale) && (!shift || aligned16(shift))) {
-    const Geom g = make_geom<8>(M, C, 512, 4);
-    const float sl = a == UCD_ACT_LEAKY_RELU ? slope : 1.f;
-    typedef __hip_bfloat16 B;
-    if (residual)
-      abn_apply_fast_kernel<true><<<dim3(g.gx, g.gy), kBlock, 0, s>>>((const B*)x, ld_x, (B*)y, ld_y, (const B*)residual, ld_r, M, C,
-                                                                      mean, scale, shift, sl, g.TX, g.TY, g.rows_per_band);
-    else
-      abn_apply_fast_kernel<false><<<dim3(g.gx, g.gy), kBlock, 0, s>>>((const B*)x, ld_x, (B*)y, ld_y, nullptr, 0, M, C, mean, scale,
-                                                                       shift, sl, g.TX, g.TY, g.rows_per_band);
-    return check_launch(fn);
-  }
-  if (dtype == UCD_BF16) {
-    if (a == UCD_ACT_LEAKY_RELU) LAUNCH_APPLY(__hip_bfloat16, 8, UCD_ACT_LEAKY_RELU)
-    else if (a == UCD_ACT_ELU) LAUNCH_APPLY(__hip_bfloat16, 8, UCD_ACT_ELU)
-    else LAUNCH_APPLY(__hip_bfloat16, 8, UCD_ACT_IDENTITY)
-  } else {
-    if (a == UCD_ACT_LEAKY_RELU) LAUNCH_APPLY(float, 4, UCD_ACT_LEAKY_RELU)
-    else if (a == UCD_ACT_ELU) LAUNCH_APPLY(float, 4, UCD_ACT_ELU)
-    else LAUNCH_APPLY(float, 4, UCD_ACT_IDENTITY)
-  }
-#undef LAUNCH_APPLY
+  const Geom g = geom_for(dtype, M, C, 4);
+  dispatch_form(
+      dtype, a, plane_bias,
+      [&](auto t, auto ELU, auto PB, auto RES) {
+        typedef decltype(t) T;
+        abn_apply_kernel<T, UCD_FLAG(ELU), UCD_FLAG(PB), UCD_FLAG(RES), false><<<dim3(g.gx, g.gy), kBlock, 0, s>>>(
+            (const T*)x, ld_x, (T*)y, ld_y, (const T*)residual, ld_r, M, C, plane_bias, HW, mean, scale, shift, kernel_slope(a, slope),
+            g.TX, g.TY, g.rows_per_band, ApplyFin{});
+      },
+      residual != nullptr);
   return check_launch(fn);
 }
 
@@ -1208,12 +982,13 @@ int ucd_abn_apply_stats(const void* x, int ld_x, void* y, int ld_y, const void* 
                      (act & UCD_NORM_ABS_GAMMA) != 0};
   typedef __hip_bfloat16 B;
   hipStream_t s = (hipStream_t)stream;
-  if (residual)
-    abn_apply_fast_kernel<true, true><<<dim3(g.gx, g.gy), kBlock, kBlock * 16 * 4, s>>>((const B*)x, ld_x, (B*)y, ld_y, (const B*)residual, ld_r, M, C,
-                                                                          nullptr, nullptr, bias, sl, g.TX, g.TY, g.rows_per_band, fin);
-  else
-    abn_apply_fast_kernel<false, true><<<dim3(g.gx, g.gy), kBlock, kBlock * 16 * 4, s>>>((const B*)x, ld_x, (B*)y, ld_y, nullptr, 0, M, C, nullptr,
-                                                                           nullptr, bias, sl, g.TX, g.TY, g.rows_per_band, fin);
+  with_flags(
+      [&](auto RES) {
+        abn_apply_kernel<B, false, false, UCD_FLAG(RES), true><<<dim3(g.gx, g.gy), kBlock, kBlock * 16 * 4, s>>>(
+            (const B*)x, ld_x, (B*)y, ld_y, (const B*)residual, ld_r, M, C, nullptr, 0, nullptr, nullptr, bias, sl, g.TX, g.TY,
+            g.rows_per_band, fin);
+      },
+      residual != nullptr);
   return check_launch(fn);
 }
 
@@ -1241,14 +1016,13 @@ int ucd_abn_bwd_apply_raw(const void* x, int ld_x, const void* dy, int ld_dy, co
   const int ag = (act & UCD_NORM_ABS_GAMMA) != 0;
   const float* gs = grad_sums ? grad_sums : sums;
   hipStream_t s = (hipStream_t)stream;
-#define UCD_BWD_RAW(YO, DZ)                                                                                                        \
-  abn_bwd_apply_fast_kernel<YO, DZ, true><<<dim3(g.gx, g.gy), kBlock, kBlock * 16 * 4, s>>>((const B*)x, ld_x, (const B*)dy, ld_dy, (const B*)y, ld_y, \
-                                                                              (B*)dx, ld_dx, (B*)dz_out, ld_dz, M, C, mean, invstd, scale, \
-                                                                              shift, weight, sums, 1.f / count, 0, ag, sl, g.TX, g.TY, \
-                                                                              g.rows_per_band, gs, grad_out, reps)
-  if (y) { if (dz_out) UCD_BWD_RAW(true, true); else UCD_BWD_RAW(true, false); }
-  else { if (dz_out) UCD_BWD_RAW(false, true); else UCD_BWD_RAW(false, false); }
-#undef UCD_BWD_RAW
+  with_flags(
+      [&](auto YO, auto DZ) {
+        abn_bwd_apply_kernel<B, false, false, UCD_FLAG(YO), UCD_FLAG(DZ), true><<<dim3(g.gx, g.gy), kBlock, kBlock * 16 * 4, s>>>(
+            (const B*)x, ld_x, (const B*)dy, ld_dy, (const B*)y, ld_y, (B*)dx, ld_dx, (B*)dz_out, ld_dz, M, C, nullptr, 0, mean, invstd,
+            scale, shift, weight, sums, 1.f / count, 0, ag, sl, g.TX, g.TY, g.rows_per_band, gs, grad_out, reps);
+      },
+      y != nullptr, dz_out != nullptr);
   return check_launch(fn);
 }
 
@@ -1265,37 +1039,18 @@ static int bwd_reduce_impl(const char* fn, const void* x, int ld_x, const void* 
   UCD_REQUIRE(!plane_bias || HW > 0, UCD_EINVAL, "%s: plane_bias needs HW > 0", fn);
   hipStream_t s = (hipStream_t)stream;
   float* partial = (float*)workspace;
-  Geom g;
-#define LAUNCH_RED(T, VECN, ACT)                                                                                   \
-  {                                                                                                                \
-    g = make_geom<VECN>(M, C, 512, 8, kMaxBands);                                                                \
-    UCD_REQUIRE(workspace_bytes >= (size_t)g.gy * 2 * C * 4, UCD_EWORKSPACE, "%s: workspace too small", fn);       \
-    abn_bwd_reduce_kernel<T, ACT><<<dim3(g.gx, g.gy), kBlock, kBlock * 2 * VECN * 4, s>>>(                         \
-        (const T*)x, ld_x, (const T*)dy, ld_dy, (const T*)y, ld_y, M, C, plane_bias, HW, mean, invstd, scale,     \
-        shift, slope, g.TX, g.TY, g.rows_per_band, partial);                                                       \
-  }
   const int a = act & UCD_ACT_MASK;
-  if (fast_path(dtype, plane_bias, a) && aligned16(mean) && aligned16(invstd) && aligned16(scale) && (!shift || aligned16(shift))) {
-    typedef __hip_bfloat16 B;
-    g = make_geom<8>(M, C, 512, 8, kMaxBands);
-    UCD_REQUIRE(workspace_bytes >= (size_t)g.gy * 2 * C * 4, UCD_EWORKSPACE, "%s: workspace too small", fn);
-    const float sl = a == UCD_ACT_LEAKY_RELU ? slope : 1.f;
-    if (y)
-      abn_bwd_reduce_fast_kernel<true><<<dim3(g.gx, g.gy), kBlock, kBlock * 16 * 4, s>>>(
-          (const B*)x, ld_x, (const B*)dy, ld_dy, (const B*)y, ld_y, M, C, mean, invstd, scale, shift, sl, g.TX, g.TY, g.rows_per_band, partial);
-    else
-      abn_bwd_reduce_fast_kernel<false><<<dim3(g.gx, g.gy), kBlock, kBlock * 16 * 4, s>>>(
-          (const B*)x, ld_x, (const B*)dy, ld_dy, nullptr, 0, M, C, mean, invstd, scale, shift, sl, g.TX, g.TY, g.rows_per_band, partial);
-  } else if (dtype == UCD_BF16) {
-    if (a == UCD_ACT_LEAKY_RELU) LAUNCH_RED(__hip_bfloat16, 8, UCD_ACT_LEAKY_RELU)
-    else if (a == UCD_ACT_ELU) LAUNCH_RED(__hip_bfloat16, 8, UCD_ACT_ELU)
-    else LAUNCH_RED(__hip_bfloat16, 8, UCD_ACT_IDENTITY)
-  } else {
-    if (a == UCD_ACT_LEAKY_RELU) LAUNCH_RED(float, 4, UCD_ACT_LEAKY_RELU)
-    else if (a == UCD_ACT_ELU) LAUNCH_RED(float, 4, UCD_ACT_ELU)
-    else LAUNCH_RED(float, 4, UCD_ACT_IDENTITY)
-  }
-#undef LAUNCH_RED
+  const Geom g = geom_for(dtype, M, C, 8, kMaxBands);
+  UCD_REQUIRE(workspace_bytes >= (size_t)g.gy * 2 * C * 4, UCD_EWORKSPACE, "%s: workspace too small", fn);
+  dispatch_form(
+      dtype, a, plane_bias,
+      [&](auto t, auto ELU, auto PB, auto YO) {
+        typedef decltype(t) T;
+        abn_bwd_reduce_kernel<T, UCD_FLAG(ELU), UCD_FLAG(PB), UCD_FLAG(YO)><<<dim3(g.gx, g.gy), kBlock, kBlock * 4 * Lane<T>::NP * 4, s>>>(
+            (const T*)x, ld_x, (const T*)dy, ld_dy, (const T*)y, ld_y, M, C, plane_bias, HW, mean, invstd, scale, shift,
+            kernel_slope(a, slope), g.TX, g.TY, g.rows_per_band, partial);
+      },
+      y != nullptr);
   UCD_TRY(check_launch(fn));
   UCD_REDUCE_BANDS(0, g.gy, partial, g.gy, C, sums, FinalizeArgs{}, sums_copy, (act & UCD_NORM_ABS_GAMMA) ? weight : nullptr);
   return check_launch(fn);
@@ -1334,12 +1089,8 @@ int ucd_abn_sync_forward(const void* x, int ld_x, void* y, int ld_y, const void*
                          int act, float slope, ucd_stream_t stream) {
   static const char* fn = "ucd_abn_sync_forward";
   UCD_REQUIRE(gathered && buf && world >= 1 && C > 0 && M > 0, UCD_EINVAL, "%s: bad arguments", fn);
-  float *mean = buf + 3 * C, *invstd = buf + 4 * C, *scale = buf + 5 * C;
-  FinalizeArgs fin{nullptr, weight, running_mean, running_var, mean, invstd, scale, (float)M * (float)world, momentum, eps,
-                   nullptr, (act & UCD_NORM_ABS_GAMMA) != 0};
-  abn_combine_finalize_kernel<<<ceil_div(C, 256), 256, 0, (hipStream_t)stream>>>(gathered, world, C, (float)M, fin);
-  UCD_TRY(check_launch(fn));
-  return ucd_abn_apply(x, ld_x, y, ld_y, residual, ld_r, dtype, M, C, plane_bias, HW, mean, scale, bias, act, slope, stream);
+  UCD_TRY(ucd_abn_sync_finalize(gathered, world, M, C, weight, running_mean, running_var, momentum, eps, buf, act & UCD_NORM_ABS_GAMMA, stream));
+  return ucd_abn_apply(x, ld_x, y, ld_y, residual, ld_r, dtype, M, C, plane_bias, HW, buf + 3 * C, buf + 5 * C, bias, act, slope, stream);
 }
 
 int ucd_abn_sync_finalize(const float* gathered, int world, int M, int C, const float* weight, float* running_mean,
@@ -1404,41 +1155,18 @@ int ucd_abn_bwd_apply(const void* x, int ld_x, const void* dy, int ld_dy, const 
   UCD_REQUIRE(!plane_bias || HW > 0, UCD_EINVAL, "%s: plane_bias needs HW > 0", fn);
   hipStream_t s = (hipStream_t)stream;
   const float inv_count = frozen ? 0.f : 1.f / count;
-#define LAUNCH_BWD(T, VECN, ACT)                                                                                   \
-  {                                                                                                                \
-    Geom g = make_geom<VECN>(M, C, 512, 4);                                                                    \
-    abn_bwd_apply_kernel<T, ACT><<<dim3(g.gx, g.gy), kBlock, 0, s>>>(                                              \
-        (const T*)x, ld_x, (const T*)dy, ld_dy, (const T*)y, ld_y, (T*)dx, ld_dx, (T*)dz_out, ld_dz, M, C,        \
-        plane_bias, HW, mean, invstd, scale, shift, weight, sums, inv_count, frozen,                              \
-        (act & UCD_NORM_ABS_GAMMA) != 0, slope, g.TX, g.TY, g.rows_per_band);                                                                                          \
-  }
   const int a = act & UCD_ACT_MASK;
-  if (fast_path(dtype, plane_bias, a) && aligned16(mean) && aligned16(scale) && (!shift || aligned16(shift)) &&
-      (frozen || (aligned16(invstd) && aligned16(sums) && C % 4 == 0 && (!weight || aligned16(weight))))) {
-    typedef __hip_bfloat16 B;
-    const Geom g = make_geom<8>(M, C, 512, 4);
-    const float sl = a == UCD_ACT_LEAKY_RELU ? slope : 1.f;
-    const int ag = (act & UCD_NORM_ABS_GAMMA) != 0;
-#define UCD_BWD_FAST(YO, DZ)                                                                                                      \
-  abn_bwd_apply_fast_kernel<YO, DZ><<<dim3(g.gx, g.gy), kBlock, 0, s>>>((const B*)x, ld_x, (const B*)dy, ld_dy, (const B*)y, ld_y, \
-                                                                        (B*)dx, ld_dx, (B*)dz_out, ld_dz, M, C, mean, invstd, scale, \
-                                                                        shift, weight, sums, inv_count, frozen, ag, sl, g.TX, g.TY, \
-                                                                        g.rows_per_band)
-    if (y) { if (dz_out) UCD_BWD_FAST(true, true); else UCD_BWD_FAST(true, false); }
-    else { if (dz_out) UCD_BWD_FAST(false, true); else UCD_BWD_FAST(false, false); }
-#undef UCD_BWD_FAST
-    return check_launch(fn);
-  }
-  if (dtype == UCD_BF16) {
-    if (a == UCD_ACT_LEAKY_RELU) LAUNCH_BWD(__hip_bfloat16, 8, UCD_ACT_LEAKY_RELU)
-    else if (a == UCD_ACT_ELU) LAUNCH_BWD(__hip_bfloat16, 8, UCD_ACT_ELU)
-    else LAUNCH_BWD(__hip_bfloat16, 8, UCD_ACT_IDENTITY)
-  } else {
-    if (a == UCD_ACT_LEAKY_RELU) LAUNCH_BWD(float, 4, UCD_ACT_LEAKY_RELU)
-    else if (a == UCD_ACT_ELU) LAUNCH_BWD(float, 4, UCD_ACT_ELU)
-    else LAUNCH_BWD(float, 4, UCD_ACT_IDENTITY)
-  }
-#undef LAUNCH_BWD
+  const Geom g = geom_for(dtype, M, C, 4);
+  dispatch_form(
+      dtype, a, plane_bias,
+      [&](auto t, auto ELU, auto PB, auto YO, auto DZ) {
+        typedef decltype(t) T;
+        abn_bwd_apply_kernel<T, UCD_FLAG(ELU), UCD_FLAG(PB), UCD_FLAG(YO), UCD_FLAG(DZ), false><<<dim3(g.gx, g.gy), kBlock, 0, s>>>(
+            (const T*)x, ld_x, (const T*)dy, ld_dy, (const T*)y, ld_y, (T*)dx, ld_dx, (T*)dz_out, ld_dz, M, C, plane_bias, HW, mean,
+            invstd, scale, shift, weight, sums, inv_count, frozen, (act & UCD_NORM_ABS_GAMMA) != 0, kernel_slope(a, slope), g.TX, g.TY,
+            g.rows_per_band, nullptr, nullptr, 1);
+      },
+      y != nullptr, dz_out != nullptr);
   return check_launch(fn);
 }
 

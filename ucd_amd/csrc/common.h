@@ -6,6 +6,7 @@
 #include <stdio.h>
 #include <stdarg.h>
 #include <string.h>
+#include <type_traits>
 
 #include "../../include/ucd_hip.h"
 
@@ -75,16 +76,18 @@ template <> struct Vec<__hip_bfloat16> {
   }
 };
 
-// ---- eight bf16 activations as four float pairs ---------------------------------------------------
-// The element-wise passes (ABN apply / backward) are VALU-issue-bound when written per element: ~17 instructions per value
+// ---- a lane's 16 bytes as float pairs: four pairs of bf16, two of f32 ------------------------------
+// The element-wise passes (ABN apply / backward) are VALU-issue-bound when written per element: ~17 instructions per bf16 value
 // (the unpack / select / re-insert of Vec<bf16>::get/set, one exec-masked branch per nullable operand) against ~5 with
 // packed-fp32 math (v_pk_add_f32 / v_pk_mul_f32; the library is built without fp contraction), one v_cvt_pk_bf16_f32 per PAIR and the nullable operands
 // as template flags (round 4: abn_apply on a 13 MB layer 11.7 -> see profiles/r04_abn_fast.txt).
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x2v __attribute__((ext_vector_type(2)));
-struct Pack8 {
-  f32x2 p[4];          // p[j] = elements (2j, 2j + 1)
+template <int NP>
+struct Pack {
+  f32x2 p[NP];         // p[j] = elements (2j, 2j + 1)
 };
+typedef Pack<4> Pack8;
 __device__ __forceinline__ Pack8 unpack8(const uint4& raw) {
   Pack8 o;
   const uint32_t w[4] = {raw.x, raw.y, raw.z, raw.w};
@@ -101,10 +104,44 @@ __device__ __forceinline__ uint4 pack8(const Pack8& f) {   // round-to-nearest-e
   }
   return make_uint4(w[0], w[1], w[2], w[3]);
 }
+template <typename T> struct Lane;
+template <> struct Lane<__hip_bfloat16> {
+  static constexpr int NP = 4;
+  static __device__ __forceinline__ Pack<4> unpack(const uint4& raw) { return unpack8(raw); }
+  static __device__ __forceinline__ uint4 pack(const Pack<4>& f) { return pack8(f); }
+};
+template <> struct Lane<float> {
+  static constexpr int NP = 2;
+  static __device__ __forceinline__ Pack<2> unpack(const uint4& raw) {
+    Pack<2> o;
+    o.p[0] = f32x2{__uint_as_float(raw.x), __uint_as_float(raw.y)};
+    o.p[1] = f32x2{__uint_as_float(raw.z), __uint_as_float(raw.w)};
+    return o;
+  }
+  static __device__ __forceinline__ uint4 pack(const Pack<2>& f) {
+    return make_uint4(__float_as_uint(f.p[0].x), __float_as_uint(f.p[0].y), __float_as_uint(f.p[1].x), __float_as_uint(f.p[1].y));
+  }
+};
 __device__ __forceinline__ Pack8 load_f8(const float* p) {  // eight per-channel constants (32-byte aligned: channel groups of 8)
   const float4 a = *reinterpret_cast<const float4*>(p), b = *reinterpret_cast<const float4*>(p + 4);
   Pack8 o;
   o.p[0] = f32x2{a.x, a.y}; o.p[1] = f32x2{a.z, a.w}; o.p[2] = f32x2{b.x, b.y}; o.p[3] = f32x2{b.z, b.w};
+  return o;
+}
+// The 2 NP per-channel constants of a lane's channel group, read as floats: the vector needs no 16-byte alignment, and the
+// compiler still merges the reads into 16-byte loads (global memory takes those at any dword address)
+template <int NP>
+__device__ __forceinline__ Pack<NP> load_pairs(const float* p) {
+  Pack<NP> o;
+#pragma unroll
+  for (int j = 0; j < NP; ++j) o.p[j] = f32x2{p[2 * j], p[2 * j + 1]};
+  return o;
+}
+template <int NP>
+__device__ __forceinline__ Pack<NP> zero_pairs() {
+  Pack<NP> o;
+#pragma unroll
+  for (int j = 0; j < NP; ++j) o.p[j] = f32x2{0.f, 0.f};
   return o;
 }
 // leaky_relu on a pair: z > 0 ? z : z * slope (slope = 1: identity)
