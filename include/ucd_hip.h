@@ -673,6 +673,29 @@ int ucd_conv1x1_stat_replicas(int M);   /* replicas of an atomic statistics accu
 size_t ucd_conv1x1_stats_partial_bytes(int M, int C);
 int ucd_conv1x1(const ucd_conv1x1_desc* desc, ucd_stream_t stream);
 
+/* Class-ordered rows of the stand-alone dilated 3x3 products (taps = 9, stride 1, dilation > 1, out_mode 0: the ASPP branches,
+ * forward and input gradient).  A pixel is classed by which of its four axis neighbours at distance `dilation` lie inside the map;
+ * the kernels then take GEMM row r to be pixel perm[r] - class-major over the whole batch, the classes by falling number of live
+ * taps, raster order inside a class - and every row tile walks only the taps of its 9-bit mask (bit kh * 3 + kw), the union of the
+ * live taps of its rows.  Skipped steps would have added exact zeros and the live steps keep their order: the outputs are bit-identical
+ * to those of the raster order.  The library builds the plan of a (device, B, H, W, dilation, tile rows) at the first ucd_conv1x1
+ * call that needs it and keeps it in device memory; that takes blocking calls, so it happens only outside a stream capture - a call
+ * that arrives under capture without its plan runs in raster order (run one eager step before capturing).
+ * ucd_conv3_tap_plan: the host half - fills perm[B * H * W] and masks[ceil(B * H * W / tile_rows)] (tile_rows 64, 128 or 256) and
+ *   reports the number of classes that occur (<= 16); no GPU needed.
+ * ucd_conv3_tap_classes: mode = 0 / 1 / 2 sets the switch inside the process, mode < 0 only reads it; returns the value in force.
+ *   The first use reads the environment variable UCD_CONV3_TAP_CLASSES (default 1; 0: exactly the launches without the plans).
+ *   Mode 1 leaves one kind of launch in raster order: at most one 64-row workgroup per CU whose heaviest tile keeps its tap count
+ *   in class order (such a launch lasts as long as that tile; measured 4 - 5 % slower with the row table).  Mode 2 takes the
+ *   class order there too (tests, probes).
+ * ucd_conv3_tap_plans_resident: number of plans in device memory (at most 64; further shapes run in raster order).
+ * ucd_conv3_tap_stats: launches that took the class-ordered kernels so far, and for the latest stand-alone dilated 3x3 product
+ *   the rows of its workgroup tile and whether it took them (any pointer may be NULL). */
+int ucd_conv3_tap_plan(int B, int H, int W, int dilation, int tile_rows, int* perm, int* masks, int* n_classes);
+int ucd_conv3_tap_classes(int mode);
+int ucd_conv3_tap_plans_resident(void);
+int ucd_conv3_tap_stats(long long* launches, int* last_tile_rows, int* last_class_ordered);
+
 /* out_mode 2 partials -> batch statistics of the [M, C] product -> buf = [sums(2C) | kshift(C) | mean | invstd | scale]
  * (the layout ucd_abn_forward leaves for the backward) and the running statistics, like ucd_abn_stats_finalize; with
  * pack != NULL it writes this rank's [mean_r | M2_r] instead (SyncBN: all-gather, then ucd_abn_sync_forward). */

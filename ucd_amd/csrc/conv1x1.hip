@@ -38,6 +38,10 @@
 // column tiles of one row strip sit on the same XCD (ids congruent mod 8 share an L2), so a strip of A leaves HBM once.
 #include "common.h"
 #include "abn_finalize.h"
+#include "conv3_taps.h"
+#include <algorithm>
+#include <mutex>
+#include <vector>
 
 namespace ucd {
 namespace {
@@ -75,7 +79,12 @@ struct Args {
   const float* stat_shift;   // OUT 2 with stat_acc: the common shift of the sums (the layer's running mean)
   float* stat_acc2;  // optional second accumulator (the same adds)
   int stat_rep;      // replicas of the accumulator (power of two): row tile t adds into replica t & (stat_rep - 1)
+  const int* perm;   // RT kernels (class-ordered rows, conv3_taps.h): GEMM row r is pixel perm[r] of the map, for A and for Y
+  const int* masks;  // RT kernels: the 9-bit set of live taps of every row tile of the launch's tile height
 };
+
+// output row of GEMM row r (conv1x1_epilogue.inc): the row itself, or its pixel in the class-ordered kernels (RT)
+#define UCD_EPI_ROW(r) (RT ? p.perm[min((r), p.M - 1)] : (r))
 
 // The fused transforms take leaky_relu(slope) only; identity arrives as slope = 1 (elu layers keep the separate ABN
 // kernels: a per-element expm1 makes every fused loop a chain of exec-masked branches, measured 2x on the epilogue).
@@ -132,9 +141,12 @@ __device__ __forceinline__ void live_taps(int m0, int m1, int ohw, int oW, int i
   if (ymin >= iH - dil) ntap -= 3;                         // dy = +d
 }
 
-template <int BN, bool PRO, int OUT, bool CONV3 = false, bool DB = false>
+// RT (class-ordered rows of the stand-alone dilated 3x3 products, conv3_taps.h): row r of the tile is pixel p.perm[m0 + r], and the
+// K loop walks the set bits of p.masks[tile] in rising tap order instead of the contiguous range of live_taps.
+template <int BN, bool PRO, int OUT, bool CONV3 = false, bool DB = false, bool RT = false>
 __global__ __launch_bounds__(kThreads, DB ? 2 : ((PRO || OUT >= 3) && BN == 128 ? 3 : 4)) void conv1x1_kernel(Args p) {
   static_assert(!DB || !PRO, "the double-buffered form has no input transform");
+  static_assert(!RT || (CONV3 && OUT == 0 && !PRO), "class-ordered rows: the plain 3x3 product");
   constexpr int kStage = (kBM + BN) * kBK * 2;  // bytes of one LDS stage (A tile + W tile)
   constexpr int WN = BN / 2;           // columns per wave
   constexpr int TN = WN / 32;          // 32-wide accumulator tiles per wave along N
@@ -177,7 +189,8 @@ __global__ __launch_bounds__(kThreads, DB ? 2 : ((PRO || OUT >= 3) && BN == 128 
     if (CONV3 || p.stride > 1) {
       const int m = m0 + row;
       const int mm = min(m, p.M - 1);
-      const int b = mm / p.ohw, rem = mm - b * p.ohw;
+      const int pix = RT ? p.perm[mm] : mm;
+      const int b = pix / p.ohw, rem = pix - b * p.ohw;
       const int oy = rem / p.oW, ox = rem - oy * p.oW;
       py[i] = m < p.M ? oy * p.stride : -(1 << 20);        // rows past M: never inside the map -> zeros
       px[i] = ox * p.stride;
@@ -209,8 +222,20 @@ __global__ __launch_bounds__(kThreads, DB ? 2 : ((PRO || OUT >= 3) && BN == 128 
   const int fr = lane & 31, fh = lane >> 5;
   const int kpt = p.K / kBK;                           // K steps per tap
   int tap0 = 0, ntap = 9;
-  if (CONV3 && p.stride == 1) live_taps(m0, min(m0 + kBM, p.M), p.ohw, p.oW, p.iH, p.dil, tap0, ntap);
+  unsigned trem = 0;                                   // RT: the live taps not walked yet
+  if constexpr (RT) { trem = (unsigned)p.masks[tm]; ntap = __builtin_popcount(trem); }
+  else if (CONV3 && p.stride == 1) live_taps(m0, min(m0 + kBM, p.M), p.ohw, p.oW, p.iH, p.dil, tap0, ntap);
   const int nk = CONV3 ? ntap * kpt : kpt;             // K steps of the live taps; step kb belongs to tap tap0 + kb / kpt
+  // tap of the kt-th live tap; RT: the steps arrive in rising order, each new kt takes the lowest bit left (scalar arithmetic)
+  int akt = -1, ctap = 0;
+  auto tap_of = [&](int kt) {
+    if constexpr (RT) {
+      if (kt != akt) { ctap = __builtin_ctz(trem); trem &= trem - 1; akt = kt; }
+      return ctap;
+    } else {
+      return tap0 + kt;
+    }
+  };
   uint4 ra[4];
   if (PRO) {
 #pragma unroll
@@ -244,7 +269,7 @@ __global__ __launch_bounds__(kThreads, DB ? 2 : ((PRO || OUT >= 3) && BN == 128 
     atap = tap;
   };
   auto fill3 = [&](int kb, unsigned char* Ad, unsigned char* Bd) {   // LDS-DMA fill of step kb (double-buffered form)
-    const int kt = CONV3 ? kb / kpt : 0, tap = tap0 + kt;
+    const int kt = CONV3 ? kb / kpt : 0, tap = tap_of(kt);
     const int k0 = (kb - kt * kpt) * kBK;
     if (CONV3) {
       if (tap != atap) set_tap(tap);
@@ -266,7 +291,7 @@ __global__ __launch_bounds__(kThreads, DB ? 2 : ((PRO || OUT >= 3) && BN == 128 
       if (st < nk) fill3(st, As + st * kStage, Bs + st * kStage);
   }
   for (int kb = 0; kb < nk; ++kb) {
-    const int kt = CONV3 ? kb / kpt : 0, tap = tap0 + kt;
+    const int kt = CONV3 ? kb / kpt : 0, tap = DB ? 0 : tap_of(kt);   // (DB: fill3 walks the taps)
     const int k0 = (kb - kt * kpt) * kBK;
     const int wk0 = CONV3 ? tap * p.K + k0 : k0;       // column offset inside a weight row (pitch 9 K)
     if (kb) {                                          // the previous step's fragment reads are done
@@ -400,10 +425,11 @@ __global__ __launch_bounds__(kThreads, DB ? 2 : ((PRO || OUT >= 3) && BN == 128 
 // 128 x 64 tile stages 24 KB and takes ~750 cycles with 256 cycles of MFMA in it - so the time of such a launch is the bytes ONE
 // workgroup stages, whatever the number of workgroups (3 and 6 images: the same 12.9 / 13.6 us for the 3x3 256 -> 256 layer).
 // 64-row tiles stage 16 KB per step on twice as many CUs.
-template <int BM, int BN, int OUT, bool CONV3>
+template <int BM, int BN, int OUT, bool CONV3, bool RT = false>
 __global__ __launch_bounds__(BM == 64 ? 384 : BM * 4, (BM + BN) * kBK * 2 * kLwStages > 80 * 1024 ? 1 : 2) void conv_lw_kernel(Args p) {
   static_assert(BM == 64 || BM == 128 || BM == 256, "64-, 128- or 256-row workgroup tiles");
   static_assert(BM != 64 || BN == 64, "the 64-row form runs its epilogue on 128 threads: 64-column tiles");
+  static_assert(!RT || (CONV3 && OUT == 0), "class-ordered rows: the plain 3x3 product");
   constexpr int NC = BM / 32, NL = BM == 64 ? 4 : BM / 32;   // MFMA waves (2 per 64 rows), loader waves
   constexpr int kStage = (BM + BN) * kBK * 2;
   constexpr int WN = BN / 2, TN = WN / 32;
@@ -417,7 +443,9 @@ __global__ __launch_bounds__(BM == 64 ? 384 : BM * 4, (BM + BN) * kBK * 2 * kLwS
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int kpt = p.K / kBK;
   int tap0 = 0, ntap = 9;
-  if (CONV3 && p.stride == 1) live_taps(m0w, min(m0w + BM, p.M), p.ohw, p.oW, p.iH, p.dil, tap0, ntap);
+  unsigned trem = 0;                                   // RT: the live taps not walked yet (the loader waves walk them)
+  if constexpr (RT) { trem = (unsigned)p.masks[tmw]; ntap = __builtin_popcount(trem); }
+  else if (CONV3 && p.stride == 1) live_taps(m0w, min(m0w + BM, p.M), p.ohw, p.oW, p.iH, p.dil, tap0, ntap);
   const int nk = CONV3 ? ntap * kpt : kpt;             // K steps of the live taps (loader and MFMA waves count the same steps)
 
   if (wave >= NC) {
@@ -436,7 +464,8 @@ __global__ __launch_bounds__(BM == 64 ? 384 : BM * 4, (BM + BN) * kBK * 2 * kLwS
       if (CONV3 || p.stride > 1) {
         const int m = m0 + row;
         const int mm = min(m, p.M - 1);
-        const int b = mm / p.ohw, rem = mm - b * p.ohw;
+        const int pix = RT ? p.perm[mm] : mm;
+        const int b = pix / p.ohw, rem = pix - b * p.ohw;
         const int oy = rem / p.oW, ox = rem - oy * p.oW;
         py[i] = m < p.M ? oy * p.stride : -(1 << 20);
         px[i] = ox * p.stride;
@@ -465,10 +494,16 @@ __global__ __launch_bounds__(BM == 64 ? 384 : BM * 4, (BM + BN) * kBK * 2 * kLwS
       }
       atap = tap;
     };
+    // RT: the fills arrive in rising step order, each new kt takes the lowest live tap left
+    int akt = -1, ctap = 0;
+    auto next_tap = [&](int kt) {
+      if (kt != akt) { ctap = __builtin_ctz(trem); trem &= trem - 1; akt = kt; }
+      return ctap;
+    };
     auto fill = [&](int kb, int st) {
       unsigned char* Ad = As + st * kStage;
       unsigned char* Bd = Bs + st * kStage;
-      const int kt = CONV3 ? kb / kpt : 0, tap = tap0 + kt;
+      const int kt = CONV3 ? kb / kpt : 0, tap = RT ? next_tap(kt) : tap0 + kt;
       const int k0 = (kb - kt * kpt) * kBK;
       if (CONV3) {
         if (tap != atap) set_tap(tap);
@@ -887,7 +922,7 @@ int pick_wgrad_chunks(int M, int N, int K) {
 
 // Launch of a DB-eligible product in the form pick_pipe / ucd_conv1x1 chose: 0 = the DB kernel, 4 / 5 / 7 = loader waves on 128- /
 // 256- / 64-row tiles.
-template <int BN, int OUT, bool CONV3>
+template <int BN, int OUT, bool CONV3, bool RT = false>
 int launch_db(int pipe, int grid, hipStream_t s, const Args& a, const char* fn) {
   constexpr size_t kOut = (size_t)64 * (BN + 4) * 4, kRed = (size_t)(kThreads / (BN / 8)) * 2 * BN * 4;
   auto lds_of = [&](int nst) {
@@ -903,8 +938,8 @@ int launch_db(int pipe, int grid, hipStream_t s, const Args& a, const char* fn) 
       const int grid256 = ceil_div(b.tiles_m, 8) * 8 * b.tiles_n;
       size_t lds = (size_t)(256 + BN) * kBK * 2 * kLwStages;
       if (lds < kOut) lds = kOut;
-      UCD_TRY_LDS((conv_lw_kernel<256, BN, OUT, CONV3>), (int)lds);
-      conv_lw_kernel<256, BN, OUT, CONV3><<<grid256, 1024, lds, s>>>(b);
+      UCD_TRY_LDS((conv_lw_kernel<256, BN, OUT, CONV3, RT>), (int)lds);
+      conv_lw_kernel<256, BN, OUT, CONV3, RT><<<grid256, 1024, lds, s>>>(b);
       return 0;
     }
     pipe = 0;
@@ -915,25 +950,29 @@ int launch_db(int pipe, int grid, hipStream_t s, const Args& a, const char* fn) 
       b.tiles_m = ceil_div(a.M, 64);
       const int grid64 = ceil_div(b.tiles_m, 8) * 8 * b.tiles_n;
       const size_t lds64 = (size_t)(64 + BN) * kBK * 2 * kLwStages;
-      conv_lw_kernel<64, BN, OUT, CONV3><<<grid64, 384, lds64, s>>>(b);
+      conv_lw_kernel<64, BN, OUT, CONV3, RT><<<grid64, 384, lds64, s>>>(b);
       return 0;
     }
     pipe = 4;
   }
   if (pipe == 4) {                  // loader waves, three 32 KB stages, one workgroup (8 waves) per CU: every epilogue fits
     const size_t lds = lds_of(kLwStages);
-    UCD_TRY_LDS((conv_lw_kernel<128, BN, OUT, CONV3>), (int)lds);
-    conv_lw_kernel<128, BN, OUT, CONV3><<<grid, 2 * kThreads, lds, s>>>(a);
+    UCD_TRY_LDS((conv_lw_kernel<128, BN, OUT, CONV3, RT>), (int)lds);
+    conv_lw_kernel<128, BN, OUT, CONV3, RT><<<grid, 2 * kThreads, lds, s>>>(a);
     return 0;
   }
-  conv1x1_kernel<BN, false, OUT, CONV3, true><<<grid, kThreads, lds_of(kDbStages), s>>>(a);
+  conv1x1_kernel<BN, false, OUT, CONV3, true, RT><<<grid, kThreads, lds_of(kDbStages), s>>>(a);
   return 0;
 }
 
 template <int BN, bool CONV3>
 int launch_db_out(int out_mode, int pipe, int grid, hipStream_t s, const Args& a, const char* fn) {
   switch (out_mode) {
-    case 0: return launch_db<BN, 0, CONV3>(pipe, grid, s, a, fn);
+    case 0:
+      if constexpr (CONV3) {
+        if (a.perm) return launch_db<BN, 0, true, true>(pipe, grid, s, a, fn);   // class-ordered rows (tap_plan_get)
+      }
+      return launch_db<BN, 0, CONV3>(pipe, grid, s, a, fn);
     case 1: return launch_db<BN, 1, CONV3>(pipe, grid, s, a, fn);
     case 2: return launch_db<BN, 2, CONV3>(pipe, grid, s, a, fn);
     case 3: return launch_db<BN, 3, CONV3>(pipe, grid, s, a, fn);
@@ -970,6 +1009,83 @@ int pick_pipe(int M, int tiles_n, int BN, int nk64, int out_mode) {
   // 33.4 -> 31.6; two rounds of it (512 -> 512: 412 workgroups) measured slower (139 vs 132), the four-stage forms slower as well
   if (BN == 128 && out_mode <= 2 && wg256 <= 256 && nk64 >= 4) return 5;
   return 0;
+}
+
+// Rows of the workgroup tile that launch_db / the single-stage launch give a product (the tile height of its tap masks).
+int tile_rows_of(bool db_launch, int pipe, int BN, int out_mode) {
+  if (!db_launch) return kBM;
+  if (pipe == 5 && BN == 128 && out_mode <= 2) return 256;
+  if (pipe == 7 && BN == 64) return 64;
+  return kBM;
+}
+
+// UCD_CONV3_TAP_CLASSES (read at the first use; ucd_conv3_tap_classes sets it inside a process): the stand-alone dilated 3x3
+// products on class-ordered rows.  0: exactly the launches without it.
+// 2: also the launches the gate in ucd_conv1x1 would leave in raster order (tests, probes).
+int g_tap_classes = -1;
+std::mutex g_tap_mutex;
+int tap_classes_mode() {
+  std::lock_guard<std::mutex> lock(g_tap_mutex);
+  if (g_tap_classes < 0) {
+    const char* e = getenv("UCD_CONV3_TAP_CLASSES");
+    g_tap_classes = e && !strcmp(e, "0") ? 0 : e && !strcmp(e, "2") ? 2 : 1;
+  }
+  return g_tap_classes;
+}
+
+// The plans of conv3_taps.h in device memory, one per (device, B, H, W, d, tile rows), built at the first call that needs one and
+// kept for the life of the process (33 x 33 at 24 images: 105 KB each).  A plan is allocated and copied with blocking calls, which a
+// stream capture does not take: a call that arrives under capture without its plan returns NULL and runs in raster order.
+// max_on / max_off: taps of the heaviest tile in class order / in raster order (the kernel-row rule of live_taps).
+struct TapPlan { int dev, B, H, W, d, rows; int* perm; int* masks; int max_on, max_off; };
+std::vector<TapPlan> g_tap_plans;
+constexpr size_t kMaxTapPlans = 64;
+long long g_tap_launches = 0;      // launches that took the class-ordered kernels
+int g_tap_last_rows = 0, g_tap_last_rt = 0;   // tile rows and path of the latest stand-alone dilated 3x3 product
+
+// live_taps on the host: taps of the heaviest raster tile
+int heaviest_raster_tile(int B, int H, int W, int d, int rows) {
+  const int hw = H * W, M = B * hw;
+  int best = 0;
+  for (int m0 = 0; m0 < M; m0 += rows) {
+    const int m1 = m0 + rows < M ? m0 + rows : M;
+    int nt = 9;
+    if (m1 - m0 < hw) {
+      const int first = m0 % hw, last = (m1 - 1) % hw;
+      int ymin = first / W, ymax = last / W;
+      if (first > last) { ymin = 0; ymax = H - 1; }
+      if (ymax < d) nt -= 3;
+      if (ymin >= H - d) nt -= 3;
+    }
+    if (nt > best) best = nt;
+  }
+  return best;
+}
+
+const TapPlan* tap_plan_get(int B, int H, int W, int d, int rows, hipStream_t s) {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+  std::lock_guard<std::mutex> lock(g_tap_mutex);
+  for (const TapPlan& t : g_tap_plans)
+    if (t.dev == dev && t.B == B && t.H == H && t.W == W && t.d == d && t.rows == rows) return &t;
+  if (g_tap_plans.size() >= kMaxTapPlans) return nullptr;   // a full table builds nothing: further shapes run in raster order
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(s, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) { (void)hipGetLastError(); return nullptr; }
+  const int M = B * H * W, tiles = ceil_div(M, rows);
+  std::vector<int32_t> host((size_t)M + tiles);
+  conv3_tap_plan_fill(B, H, W, d, rows, host.data(), host.data() + M);
+  int* devp = nullptr;
+  if (hipMalloc((void**)&devp, host.size() * sizeof(int32_t)) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+  if (hipMemcpy(devp, host.data(), host.size() * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipGetLastError();
+    (void)hipFree(devp);
+    return nullptr;
+  }
+  int max_on = 0;
+  for (int t = 0; t < tiles; ++t) max_on = std::max(max_on, __builtin_popcount((unsigned)host[(size_t)M + t]));
+  g_tap_plans.reserve(kMaxTapPlans);                // the pointers handed out stay valid
+  g_tap_plans.push_back(TapPlan{dev, B, H, W, d, rows, devp, devp + M, max_on, heaviest_raster_tile(B, H, W, d, rows)});
+  return &g_tap_plans.back();
 }
 
 }  // namespace
@@ -1046,6 +1162,7 @@ int ucd_conv1x1(const ucd_conv1x1_desc* d, ucd_stream_t stream) {
   a.stride = stride; a.oW = oW > 0 ? oW : 1; a.ohw = oH * oW > 0 ? oH * oW : 1; a.a_rows = (int)a_rows;
   a.stat_acc = d->out_mode >= 2 ? d->stat_acc : nullptr; a.stat_shift = d->stat_shift; a.stat_acc2 = d->stat_acc2;
   a.stat_rep = d->stat_rep > 1 ? d->stat_rep : 1;
+  a.perm = nullptr; a.masks = nullptr;
   UCD_REQUIRE((a.stat_rep & (a.stat_rep - 1)) == 0, UCD_EINVAL, "%s: stat_rep must be a power of two", fn);
   UCD_REQUIRE(!a.stat_acc || d->out_mode != 2 || (d->stat_shift && aligned16(d->stat_shift)), UCD_EINVAL,
               "%s: out_mode 2 with stat_acc needs a 16-byte aligned stat_shift", fn);
@@ -1079,6 +1196,24 @@ int ucd_conv1x1(const ucd_conv1x1_desc* d, ucd_stream_t stream) {
   // BM = 64) - statistics / link sums only through the atomic accumulators (64-row tiles have no rows in the per-tile partial buffers)
   static const int lw64_below = getenv("UCD_CONV_LW64_TILES") ? atoi(getenv("UCD_CONV_LW64_TILES")) : 128;
   if (db && !pro && pipe == 4 && BN == 64 && (long long)a.tiles_m * a.tiles_n <= lw64_below && (d->out_mode < 2 || a.stat_acc)) pipe = 7;
+  // stand-alone dilated 3x3 products (the ASPP branches, forward and input gradient): class-ordered rows and per-tile tap masks
+  if (conv3 && stride == 1 && d->dilation > 1 && d->out_mode == 0) {
+    const int mode = tap_classes_mode(), rows = tile_rows_of(db && !pro, pipe, BN, d->out_mode);
+    const TapPlan* tp = mode ? tap_plan_get(d->M / (d->H * d->W), d->H, d->W, d->dilation, rows, s) : nullptr;
+    // Gate (mode 1): a launch of at most one 64-row workgroup per CU lasts as long as its heaviest tile; where the class order leaves
+    // that tile its taps, the row table only adds its dependent read in front of the first fill - 3 images, d = 6 / 12: 72 -> 75 us
+    // (profiles/conv3_tap_classes.md).  The 256-row launches of that regime measured level or faster and keep the class order.
+    if (tp && mode == 1 && rows == 64 && tp->max_on >= tp->max_off) {
+      int dev = 0, cus = 0;
+      if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess &&
+          (long long)ceil_div(d->M, rows) * a.tiles_n <= cus)
+        tp = nullptr;
+    }
+    if (tp) { a.perm = tp->perm; a.masks = tp->masks; }
+    std::lock_guard<std::mutex> lock(g_tap_mutex);
+    g_tap_launches += tp != nullptr;
+    g_tap_last_rows = rows; g_tap_last_rt = tp != nullptr;
+  }
   if (db && !pro) {
     int rc;
     if (conv3) rc = BN == 128 ? launch_db_out<128, true>(d->out_mode, pipe, grid, s, a, fn) : launch_db_out<64, true>(d->out_mode, pipe, grid, s, a, fn);
@@ -1096,7 +1231,10 @@ int ucd_conv1x1(const ucd_conv1x1_desc* d, ucd_stream_t stream) {
   }
 #define UCD_C3_OUT(BNV)                                                                        \
   switch (d->out_mode) {                                                                       \
-    case 0: conv1x1_kernel<BNV, false, 0, true, false><<<grid, kThreads, lds, s>>>(a); break;  \
+    case 0:                                                                                    \
+      if (a.perm) conv1x1_kernel<BNV, false, 0, true, false, true><<<grid, kThreads, lds, s>>>(a); \
+      else conv1x1_kernel<BNV, false, 0, true, false><<<grid, kThreads, lds, s>>>(a);           \
+      break;                                                                                   \
     case 1: conv1x1_kernel<BNV, false, 1, true, false><<<grid, kThreads, lds, s>>>(a); break;  \
     case 2: conv1x1_kernel<BNV, false, 2, true, false><<<grid, kThreads, lds, s>>>(a); break;  \
     case 4: UCD_REQUIRE(false, UCD_EINVAL, "%s: out_mode 4 belongs to the 1x1 products", fn);  \
@@ -1112,6 +1250,37 @@ int ucd_conv1x1(const ucd_conv1x1_desc* d, ucd_stream_t stream) {
 #undef UCD_C3_OUT
 #undef UCD_C1_OUT
   return check_launch(fn);
+}
+
+int ucd_conv3_tap_classes(int mode) {
+  const int cur = tap_classes_mode();
+  if (mode < 0) return cur;
+  std::lock_guard<std::mutex> lock(g_tap_mutex);
+  g_tap_classes = mode >= 2 ? 2 : mode;
+  return g_tap_classes;
+}
+
+int ucd_conv3_tap_stats(long long* launches, int* last_tile_rows, int* last_class_ordered) {
+  std::lock_guard<std::mutex> lock(g_tap_mutex);
+  if (launches) *launches = g_tap_launches;
+  if (last_tile_rows) *last_tile_rows = g_tap_last_rows;
+  if (last_class_ordered) *last_class_ordered = g_tap_last_rt;
+  return 0;
+}
+
+int ucd_conv3_tap_plan(int B, int H, int W, int dilation, int tile_rows, int* perm, int* masks, int* n_classes) {
+  static const char* fn = "ucd_conv3_tap_plan";
+  UCD_REQUIRE(B > 0 && H > 0 && W > 0 && dilation >= 1 && perm && masks, UCD_EINVAL, "%s: bad arguments", fn);
+  UCD_REQUIRE(tile_rows == 64 || tile_rows == 128 || tile_rows == 256, UCD_EINVAL, "%s: tile_rows must be 64, 128 or 256", fn);
+  UCD_REQUIRE((long long)B * H * W < 0x7FFFFFFF, UCD_EUNSUPPORTED, "%s: more than 2^31 rows", fn);
+  const int n = conv3_tap_plan_fill(B, H, W, dilation, tile_rows, perm, masks);
+  if (n_classes) *n_classes = n;
+  return 0;
+}
+
+int ucd_conv3_tap_plans_resident(void) {
+  std::lock_guard<std::mutex> lock(g_tap_mutex);
+  return (int)g_tap_plans.size();
 }
 
 size_t ucd_conv1x1_stats_partial_bytes(int M, int C) { return (size_t)ceil_div(M, kBM) * 3 * C * sizeof(float); }

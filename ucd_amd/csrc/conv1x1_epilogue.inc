@@ -15,6 +15,11 @@
 #endif
 // UCD_EPI_THREADS (default: kThreads = 256) / UCD_EPI_HALVES (default: 2) - the 64-row workgroup tiles of round 6 (two MFMA waves,
 // one 64-row half): 128 epilogue threads, one pass.  kEpilogueBarriersH<OUT, halves> counts the barriers either way.
+// UCD_EPI_ROW(r) (default: r) - the row of Y (and of the old y that OUT 0 accumulates into) that GEMM row r of the tile belongs to
+// (a kernel that maps rows has OUT == 0: the only side input is that old y).
+#ifndef UCD_EPI_ROW
+#define UCD_EPI_ROW(r) (r)
+#endif
 #ifndef UCD_EPI_THREADS
 #define UCD_EPI_THREADS kThreads
 #define UCD_EPI_HALVES 2
@@ -68,7 +73,7 @@
     if (has_side && UCD_EPI_ACTIVE) {
 #pragma unroll
       for (int i = 0; i < RPT; ++i)
-        side[i] = *reinterpret_cast<const uint4*>(sp + (size_t)min(m0 + half * 64 + r0 + RSTEP * i, p.M - 1) * lds_ + ncol);
+        side[i] = *reinterpret_cast<const uint4*>(sp + (size_t)UCD_EPI_ROW(min(m0 + half * 64 + r0 + RSTEP * i, p.M - 1)) * lds_ + ncol);
     }
     if (OUT == 4) {
 #pragma unroll
@@ -176,7 +181,7 @@
           }
         }
       }
-      if (live) *reinterpret_cast<uint4*>(p.Y + (size_t)grow * p.ldy + ncol) = packed;
+      if (live) *reinterpret_cast<uint4*>(p.Y + (size_t)UCD_EPI_ROW(grow) * p.ldy + ncol) = packed;
     }
   }
   if (OUT >= 2) {

@@ -117,6 +117,10 @@ SIGNATURES = {
     "ucd_conv1x1_stats_partial_bytes": (_z, [_i, _i]),
     "ucd_conv1x1": (_i, [C.POINTER(Conv1x1Desc), _p]),
     "ucd_conv1x1_stats_finalize": (_i, [_p, _i, _i, _p, _p, _p, _f, _f, _p, _p, _i, _p]),
+    "ucd_conv3_tap_plan": (_i, [_i, _i, _i, _i, _i, _p, _p, _p]),
+    "ucd_conv3_tap_classes": (_i, [_i]),
+    "ucd_conv3_tap_plans_resident": (_i, []),
+    "ucd_conv3_tap_stats": (_i, [_p, _p, _p]),
     "ucd_abn_reduce_partials": (_i, [_p, _i, _i, _p, _p, _p, _i, _p]),
     "ucd_conv1x1_wgrad_workspace_bytes": (_z, [_i, _i, _i]),
     "ucd_conv1x1_wgrad": (_i, [_p, _i, _p, _i, _i, _i, _i, _p, _p, _p, _i, _f, _p, _p, _z, _p]),
@@ -420,6 +424,39 @@ def pixcon_loss_plan(BHW, K, precision="f32", use_prob=True, temperature=0.07):
                                     C.addressof(wsb)), "ucd_pixcon_loss_plan")
     return {"path": PIXCON_PATHS[path.value], "class_chunk": chunk.value, "nsplit1": n1.value, "nsplit2": n2.value,
             "lds_sweep1": l1.value, "lds_sweep2": l2.value, "workspace_bytes": wsb.value}
+
+
+def conv3_tap_plan(B, H, W, dilation, tile_rows):
+    """Host-only ``ucd_conv3_tap_plan``: the class-ordered rows of a stand-alone dilated 3x3 product.  Returns
+    ``(perm, masks, n_classes)``: GEMM row ``r`` is pixel ``perm[r]`` of the ``[B, H, W]`` raster, ``masks[t]`` is the 9-bit set
+    of taps (bit ``kh * 3 + kw``) that row tile ``t`` of ``tile_rows`` rows walks.  Needs no GPU."""
+    import numpy as np
+    M = int(B) * int(H) * int(W)
+    perm = np.empty(M, dtype=np.int32)
+    masks = np.empty((M + int(tile_rows) - 1) // int(tile_rows), dtype=np.int32)
+    n = C.c_int(0)
+    _check(load().ucd_conv3_tap_plan(int(B), int(H), int(W), int(dilation), int(tile_rows), perm.ctypes.data, masks.ctypes.data,
+                                     C.addressof(n)), "ucd_conv3_tap_plan")
+    return perm, masks, n.value
+
+
+def conv3_tap_classes(mode=None):
+    """Read (``mode=None``) or set the library's ``UCD_CONV3_TAP_CLASSES`` switch inside this process: 0 off, 1 on, 2 on also for
+    the launches mode 1 leaves in raster order (include/ucd_hip.h); returns the value in force."""
+    return load().ucd_conv3_tap_classes(-1 if mode is None else int(mode))
+
+
+def conv3_tap_stats():
+    """``(launches, last_tile_rows, last_class_ordered)``: launches that took the class-ordered kernels so far; tile rows and
+    path of the latest stand-alone dilated 3x3 product."""
+    n, rows, rt = C.c_longlong(0), C.c_int(0), C.c_int(0)
+    load().ucd_conv3_tap_stats(C.addressof(n), C.addressof(rows), C.addressof(rt))
+    return n.value, rows.value, bool(rt.value)
+
+
+def conv3_tap_plans_resident():
+    """Number of tap-class plans the library holds in device memory."""
+    return load().ucd_conv3_tap_plans_resident()
 
 
 _gemm_ready = None

@@ -31,6 +31,7 @@ DEFAULTS = {
     "UCD_CONV_LW64_TILES": "128",  # round 6: launches of at most this many 128 x 64 tiles run on 64-row loader-wave tiles - twice the CUs at 3 images per GPU (0: never; read by the library)
     "UCD_WGRAD_DEFER": "1",        # round 6: the slab sum of a weight gradient rides in the NEXT weight-gradient launch (0: a launch of its own behind every product)
     "UCD_WGRAD_STREAM": "1",       # round 6: the nodes' weight gradients run on a side stream of the library between the wrapper's flushes - off the chain of input-gradient products (0: on the compute stream); each one is launched one call behind its fork point, on a lowest-priority stream
+    "UCD_CONV3_TAP_CLASSES": "1",  # stand-alone dilated 3x3 products (ASPP, forward and input gradient): rows ordered by tap class, every row tile walks only its live taps - same outputs bit for bit (0: raster order; 2: also the single-wave 64-row launches whose heaviest tile keeps its taps, which 1 leaves in raster order; read by the library, hip.conv3_tap_classes sets it inside a process)
     "UCD_CONV3_MIN_ROWS": "0",     # stand-alone 3x3 layers (ASPP) below this many rows stay on the library path (round 6: 0 - the own kernels win at 3 / 6 images too: 9.33 -> 9.03 / 12.46 -> 11.97 ms)
     "UCD_STAT_ATOMIC": "1",        # conv + ABN nodes: statistics / link sums by fp32 atomics into arena slots, finalised by the apply passes (0: per-tile rows + reduction launches, bit-reproducible)
     "UCD_SEG_PK": "1",             # fused logit losses: packed math, fp64 LDS accumulators (0: the round-3 register form; read by the library)
