@@ -477,8 +477,9 @@ int ucd_pixcon_scatter_grad(const float* grad_a, const float* chat, int ldc, con
  * the count of cells depends on how the tiles fall on the source grid, so ask ucd_seg_losses_plan).
  * Returns UCD_EINVAL (NULL sem_s / labels / loss_out / d_sem / workspace; a size < 1; K < 1 or K > Ctot; a leading dimension
  * below its class count; H < h or W < w), UCD_EUNSUPPORTED (a factor below 4 or above 64; no form fits the LDS - the message
- * names the factors and the bytes asked for), UCD_EWORKSPACE (workspace_bytes below ucd_seg_losses_workspace_bytes), or
- * the hipError_t of a failed launch.  On a negative code nothing was launched and no output was written.
+ * names the factors and the bytes asked for; ucd_seg_losses_gather below serves those geometries), UCD_EWORKSPACE (workspace_bytes
+ * below ucd_seg_losses_workspace_bytes), or the hipError_t of a failed launch.  On a negative code nothing was launched and no
+ * output was written.
  *
  * ucd_seg_losses_plan touches no device (it answers on a machine without a GPU): for a geometry, a class split, has_teacher
  * (sem_t != NULL), d_sem_aligned (16-byte) and pk (1 / 0: the packed forms allowed / not; -1: as UCD_SEG_PK says) it returns
@@ -523,6 +524,41 @@ int ucd_seg_losses_ex(const float* sem_s, int ld_s, const float* sem_t, int ld_t
                       int B, int H, int W, int h, int w, int Ctot, int K, int ce_old_cl, int kd_mode, float alpha,
                       int ignore_index, float ce_weight, float kd_weight, float* loss_out, float* d_sem, int ld_d,
                       void* workspace, size_t workspace_bytes, ucd_stream_t stream);
+
+/* The GATHER form of the same losses (csrc/seglogit_loss.hip): for the geometries no tiled form above
+ * serves - ADE at --output_stride 8 (151 + 101 classes on 64 x 64 cells under a 512-pixel crop: 207 456 bytes of LDS), any
+ * up-sampling factor below 4 - and for a caller that wants a gradient with the same bits on every run where the tiled form adds with
+ * fp32 atomics.  Arguments, loss_out[0], loss_out[1] and d_sem[:, :Ctot] mean exactly what they mean for ucd_seg_losses_ex: unbiased
+ * or plain cross entropy through ce_old_cl, unbiased or plain distillation through kd_mode, any finite non-zero alpha (applied to
+ * the staged teacher rows), sem_t == NULL for the cross entropy alone.
+ * One wave owns one low-resolution cell: it stages the 3 x 3 cells around it (9 (Ctot + K) floats of LDS, K counted with a teacher
+ * only), walks the pixels whose bilinear footprint contains the cell (lanes over classes, the pixels one after another; the
+ * normalisers are wave reductions) and keeps weight * dL/dz per class in registers.  A pixel's normalisers are formed by each of its
+ * (up to) four cells; a pixel's LOSS is counted by the cell of its (y0, x0) corner alone, and a second launch adds the per-cell pairs
+ * in index order.  No atomics, no fixed point, reductions in a fixed order: the same inputs give the same bits on every run.
+ *   d_sem      may be NULL: only the losses are formed, and loss_out has the same bits.  Otherwise every row is written, columns
+ *              < Ctot, each element ONCE: the call does not accumulate, needs no memset and does not touch columns Ctot .. ld_d - 1
+ *              (ucd_seg_losses clears them; as ucd_seg_bce).
+ *   labels     ignore_index: the pixel adds nothing to the cross entropy (it still distils).  A label that is no class is read as
+ *              the tiled kernels read it: a negative one is the background (class 0, pooled with [0, ce_old_cl) like a real 0); one
+ *              in [Ctot, ...) matches no class - the pixel's cross entropy is LSE(z) (the label's logit counts as 0) and its gradient
+ *              softmax(z), no class being subtracted.  (The tiled forms pad their class rows to a multiple of 4 and their packed
+ *              slot groups with -1e30 and give that rule from the end of the padding on; the reference raises for such a label.)
+ *   factors    any H / h >= 1, W / w >= 1.
+ *   classes    any Ctot (and K) whose neighbourhood 9 (Ctot + K) floats fits 64 KB of LDS (1820 classes); beyond that
+ *              UCD_EUNSUPPORTED, the message states the bytes asked for.
+ * workspace: ucd_seg_losses_gather_workspace_bytes(B, h, w) bytes (one pair of floats per cell; 0 for a size below 1).
+ * Checked on the host before any device call, the message names the argument: UCD_EINVAL as ucd_seg_losses_ex (NULL sem_s / labels /
+ * loss_out / workspace; a size < 1; K < 1 or K > Ctot; ld_s < Ctot; ld_t < K with a teacher; ld_d < Ctot with d_sem; H < h or W < w;
+ * kd_mode, alpha, ce_old_cl as there), UCD_EWORKSPACE (a short workspace), UCD_EUNSUPPORTED; else the hipError_t of a failed launch.
+ * On a negative code nothing was launched and no output was written.  No allocation, no host synchronisation: the call captures
+ * into graphs. */
+size_t ucd_seg_losses_gather_workspace_bytes(int B, int h, int w);
+int ucd_seg_losses_gather(const float* sem_s, int ld_s, const float* sem_t, int ld_t, const int64_t* labels,
+                          int B, int H, int W, int h, int w, int Ctot, int K, int ce_old_cl, int kd_mode, float alpha,
+                          int ignore_index, float ce_weight, float kd_weight, float* loss_out /*[2]*/,
+                          float* d_sem /* NULL: losses only */, int ld_d,
+                          void* workspace, size_t workspace_bytes, ucd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Fused full-resolution BINARY cross entropy losses: --bce, --icarl, --method LWF-MC (csrc/seg_bce.hip).

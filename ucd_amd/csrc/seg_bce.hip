@@ -21,15 +21,7 @@ namespace {
 constexpr int kChunk = 24;        // classes whose gradient sums a lane keeps in registers; more classes: the pixels are walked again
 constexpr float kL2e = 1.4426950408889634f, kLn2 = 0.6931471805599453f;
 
-// the pixels of one dimension that can touch cell i: src = scale * (p + 0.5) - 0.5 in (i - 1, i + 1).  The bounds are strict, so
-// floor / ceil of the real-valued ends already take one pixel more on either side than the footprint has: rounding (of these
-// ends, of up_src) moves nothing by a pixel.  Outside the footprint the weight is zero; no exact inverse is needed.
-__device__ __forceinline__ void scan_range(int i, int out, float inv_scale, int& lo, int& hi) {
-  lo = (int)floorf(((float)i - 0.5f) * inv_scale - 0.5f);
-  hi = (int)ceilf(((float)i + 1.5f) * inv_scale - 0.5f);
-  lo = lo < 0 ? 0 : lo;
-  hi = hi > out - 1 ? out - 1 : hi;
-}
+// scan_range (the pixels of one dimension that can touch a cell): upsample_index.h
 
 // e = exp(-|z|): sigmoid(z) = z >= 0 ? 1 / (1 + e) : e / (1 + e), softplus(-|z|) = log1p(e); nothing overflows at any z
 __device__ __forceinline__ float exp_neg_abs(float z) { return __builtin_amdgcn_exp2f(-fabsf(z) * kL2e); }

@@ -27,4 +27,15 @@ __host__ __device__ __forceinline__ void tile_span(int t0, int tile, int out, in
   count = last - first + 1;
 }
 
+// The gather forms (seg_bce.hip, seg_losses_gather_kernel): the pixels of one dimension that can touch cell i, src = scale * (p + 0.5)
+// - 0.5 in (i - 1, i + 1).  The bounds are strict, so floor / ceil of the real-valued ends already take one pixel more on either
+// side than the footprint has: rounding (of these ends, of up_src) moves nothing by a pixel.  Outside the footprint the weight is
+// zero; no exact inverse is needed.
+__device__ __forceinline__ void scan_range(int i, int out, float inv_scale, int& lo, int& hi) {
+  lo = (int)floorf(((float)i - 0.5f) * inv_scale - 0.5f);
+  hi = (int)ceilf(((float)i + 1.5f) * inv_scale - 0.5f);
+  lo = lo < 0 ? 0 : lo;
+  hi = hi > out - 1 ? out - 1 : hi;
+}
+
 }  // namespace ucd

@@ -23,6 +23,7 @@ PIX_TILE = 128          # kPixTile of csrc/pixcon.h
 PIXCON_LD = 256         # feature rows of the contrast matrix are padded to 256 columns
 PIXCON_F32, PIXCON_F16, PIXCON_F16_SPLIT = 0, 1, 2
 KD_UNBIASED, KD_PLAIN = 0, 1              # enum ucd_seg_kd_mode
+EUNSUPPORTED = -4                         # enum ucd_status: a shape outside what the kernels are built for
 # enum ucd_seg_form (include/ucd_hip.h): the kernel ucd_seg_losses_plan names
 SEG_FORMS = {1: "pk<16,8>", 2: "pk<20,4>", 3: "pk<12,12>", 4: "reg<24,16>", 5: "reg<24,24>", 6: "wide/fixed", 7: "wide/f32"}
 # enum ucd_pixcon_path (include/ucd_hip.h): the kernels ucd_pixcon_loss_plan names
@@ -169,6 +170,8 @@ SIGNATURES = {
     "ucd_seg_bce": (_i, [_p, _i, _p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _p, _p, _i, _p, _z, _p]),
     "ucd_seg_losses_plan_ex": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p]),
     "ucd_seg_losses_ex": (_i, [_p, _i, _p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _f, _f, _p, _p, _i, _p, _z, _p]),
+    "ucd_seg_losses_gather_workspace_bytes": (_z, [_i, _i, _i]),
+    "ucd_seg_losses_gather": (_i, [_p, _i, _p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _f, _f, _p, _p, _i, _p, _z, _p]),
 }
 
 _lib = None

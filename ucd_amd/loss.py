@@ -5,10 +5,13 @@
 (the unfused path: the CPU, ``UCD_SEG_KD_EX=0``, tests).  The training step itself calls ``fused_seg_losses``: bilinear
 x16 up-sampling + (unbiased or plain) CE + (unbiased or plain) KD at any ``--alpha`` + the gradient w.r.t. the
 LOW-resolution logits in one HIP kernel (``ucd_seg_losses`` / ``ucd_seg_losses_ex``, csrc/seglogit_loss.hip; SURVEY.md
-section 8-f1) - the ``[B, Ctot, H, W]`` tensors never exist.
+section 8-f1) - the ``[B, Ctot, H, W]`` tensors never exist.  A geometry whose tiles do not fit the LDS of those kernels (ADE at
+``--output_stride 8``) goes to the gather form of the same file (``ucd_seg_losses_gather``; ``seg_losses_route`` says which).
 The contrastive loss lives in :mod:`ucd_amd.contrastive`.
 """
 from __future__ import annotations
+
+import functools
 
 import torch
 import torch.nn as nn
@@ -24,7 +27,8 @@ class _FusedSegLosses(torch.autograd.Function):
     ``ce_old_cl`` is None for the call as it always was (one class count K for both losses, unbiased KD, alpha 1)."""
 
     @staticmethod
-    def forward(ctx, sem, sem_old, labels, old_cl, ce_weight, kd_weight, ignore_index, ce_old_cl=None, kd_mode=0, alpha=1.0):
+    def forward(ctx, sem, sem_old, labels, old_cl, ce_weight, kd_weight, ignore_index, ce_old_cl=None, kd_mode=0, alpha=1.0,
+                form="tiled"):
         lib = hip.load()
         B, Ctot, h, w = sem.shape
         H, W = labels.shape[-2:]
@@ -35,20 +39,32 @@ class _FusedSegLosses(torch.autograd.Function):
             t = sem_old.detach().permute(0, 2, 3, 1).reshape(B * h * w, K).float().contiguous()
         labels = labels.contiguous()
         out = torch.empty(2, dtype=torch.float32, device=sem.device)
-        d = torch.empty(B * h * w, Ctot, dtype=torch.float32, device=sem.device)
-        nbytes = lib.ucd_seg_losses_workspace_bytes(B, H, W)
-        ws = hip.workspace(nbytes, sem.device, "seglosses")
-        with hip._timed("ucd_seg_losses", B * H * W * 8 + 2 * B * h * w * (2 * Ctot + K) * 4):
-            if ce_old_cl is None:
-                hip._check(lib.ucd_seg_losses(hip.ptr(s), Ctot, hip.ptr(t), K, hip.ptr(labels), B, H, W, h, w, Ctot, max(K, 1),
-                                              int(ignore_index), float(ce_weight), float(kd_weight), hip.ptr(out), hip.ptr(d),
-                                              Ctot, hip.ptr(ws), nbytes, hip.stream()), "ucd_seg_losses")
-            else:
-                hip._check(lib.ucd_seg_losses_ex(hip.ptr(s), Ctot, hip.ptr(t), K, hip.ptr(labels), B, H, W, h, w, Ctot, max(K, 1),
-                                                 int(ce_old_cl), int(kd_mode), float(alpha), int(ignore_index), float(ce_weight),
-                                                 float(kd_weight), hip.ptr(out), hip.ptr(d), Ctot, hip.ptr(ws), nbytes,
-                                                 hip.stream()), "ucd_seg_losses_ex")
-        ctx.save_for_backward(d)
+        if form == "gather":
+            # one wave per low-resolution cell: no gradient to form, no d_sem (the same loss bits)
+            d = torch.empty(B * h * w, Ctot, dtype=torch.float32, device=sem.device) if ctx.needs_input_grad[0] else None
+            nbytes = lib.ucd_seg_losses_gather_workspace_bytes(B, h, w)
+            ws = hip.workspace(nbytes, sem.device, "seglosses_gather")
+            with hip._timed("ucd_seg_losses_gather", B * H * W * 8 + B * h * w * (2 * Ctot + K) * 4):
+                hip._check(lib.ucd_seg_losses_gather(hip.ptr(s), Ctot, hip.ptr(t), K, hip.ptr(labels), B, H, W, h, w, Ctot, max(K, 1),
+                                                     max(K, 1) if ce_old_cl is None else int(ce_old_cl), int(kd_mode), float(alpha),
+                                                     int(ignore_index), float(ce_weight), float(kd_weight), hip.ptr(out), hip.ptr(d),
+                                                     Ctot, hip.ptr(ws), nbytes, hip.stream()), "ucd_seg_losses_gather")
+        else:
+            d = torch.empty(B * h * w, Ctot, dtype=torch.float32, device=sem.device)
+            nbytes = lib.ucd_seg_losses_workspace_bytes(B, H, W)
+            ws = hip.workspace(nbytes, sem.device, "seglosses")
+            with hip._timed("ucd_seg_losses", B * H * W * 8 + 2 * B * h * w * (2 * Ctot + K) * 4):
+                if ce_old_cl is None:
+                    hip._check(lib.ucd_seg_losses(hip.ptr(s), Ctot, hip.ptr(t), K, hip.ptr(labels), B, H, W, h, w, Ctot, max(K, 1),
+                                                  int(ignore_index), float(ce_weight), float(kd_weight), hip.ptr(out), hip.ptr(d),
+                                                  Ctot, hip.ptr(ws), nbytes, hip.stream()), "ucd_seg_losses")
+                else:
+                    hip._check(lib.ucd_seg_losses_ex(hip.ptr(s), Ctot, hip.ptr(t), K, hip.ptr(labels), B, H, W, h, w, Ctot, max(K, 1),
+                                                     int(ce_old_cl), int(kd_mode), float(alpha), int(ignore_index), float(ce_weight),
+                                                     float(kd_weight), hip.ptr(out), hip.ptr(d), Ctot, hip.ptr(ws), nbytes,
+                                                     hip.stream()), "ucd_seg_losses_ex")
+        if d is not None:
+            ctx.save_for_backward(d)
         ctx.meta = (B, Ctot, h, w, sem.dtype)
         ce, kd = out[0], out[1]
         total = ce_weight * ce + kd_weight * kd
@@ -60,7 +76,7 @@ class _FusedSegLosses(torch.autograd.Function):
         (d,) = ctx.saved_tensors
         B, Ctot, h, w, dtype = ctx.meta
         grad = (d * g).view(B, h, w, Ctot).permute(0, 3, 1, 2).to(dtype)
-        return grad, None, None, None, None, None, None, None, None, None
+        return grad, None, None, None, None, None, None, None, None, None, None
 
 
 class _FusedSegBCE(torch.autograd.Function):
@@ -160,22 +176,52 @@ def fused_attn_mse(x_s_raw, x_t_raw, weight=1.0):
 KD_MODES = {"unbiased": hip.KD_UNBIASED, "plain": hip.KD_PLAIN}
 
 
-def fused_seg_losses(sem, sem_old, labels, old_cl, ce_weight=1.0, kd_weight=0.0, ignore_index=255, *, kd="unbiased", alpha=1.0):
+SEG_LOSS_FORMS = ("auto", "tiled", "gather")
+
+
+@functools.lru_cache(maxsize=None)
+def seg_losses_route(H, W, h, w, Ctot, K, has_teacher, ce_old_cl=None):
+    """``"tiled"`` or ``"gather"``: which kernel ``fused_seg_losses(form="auto")`` launches for a geometry and a class split.  A pure
+    host function: it asks ``ucd_seg_losses_plan_ex`` (a 16-byte aligned ``d_sem``, the packed forms as ``UCD_SEG_PK`` says) and
+    answers ``"gather"`` exactly when no tiled form serves the geometry (``UCD_EUNSUPPORTED``).  Arguments the plan calls illegal
+    stay ``"tiled"``: the call itself then reports them, under its own name, as it always did.  ``K`` is the teacher's class count
+    (without a teacher: the cross entropy's ``old_cl``), ``ce_old_cl`` the cross entropy's when it differs.  Cached per argument
+    tuple: the plan walks every tile of the label map."""
+    K = max(int(K), 1)
+    rc = hip.load().ucd_seg_losses_plan_ex(int(H), int(W), int(h), int(w), int(Ctot), K, K if ce_old_cl is None else int(ce_old_cl),
+                                           hip.KD_UNBIASED, int(bool(has_teacher)), 1, -1, None, None, None, None)
+    return "gather" if rc == hip.EUNSUPPORTED else "tiled"
+
+
+def fused_seg_losses(sem, sem_old, labels, old_cl, ce_weight=1.0, kd_weight=0.0, ignore_index=255, *, kd="unbiased", alpha=1.0,
+                     form="auto"):
     """Returns (ce_weight*CE + kd_weight*KD [differentiable w.r.t. ``sem``], CE, KD) where CE / KD are the
     reference's ``UnbiasedCrossEntropy(old_cl)(up(sem), labels).mean()`` (``old_cl`` 1: ``nn.CrossEntropyLoss``) and
     ``UnbiasedKnowledgeDistillationLoss(alpha=alpha)(up(sem), up(sem_old))`` or, with ``kd="plain"``,
     ``KnowledgeDistillationLoss(alpha=alpha)(...)`` (``up`` = bilinear to the label size).
 
-    With a teacher of K classes ``old_cl`` is 1 or K (the reference produces no other pair; the kernel refuses one)."""
+    With a teacher of K classes ``old_cl`` is 1 or K (the reference produces no other pair; the kernel refuses one).
+
+    ``form``: ``"tiled"`` is the scatter kernels (``ucd_seg_losses`` / ``ucd_seg_losses_ex``), which refuse a geometry whose tiles do
+    not fit their LDS; ``"gather"`` is ``ucd_seg_losses_gather`` - any up-sampling factor >= 1, a gradient with the same bits on every
+    run, and, under ``torch.no_grad()`` or with a ``sem`` that needs no gradient, the losses alone; ``"auto"`` is ``"tiled"`` wherever
+    that serves (the call, and the bits, it always was) and ``"gather"`` elsewhere (``seg_losses_route``)."""
     if not sem.is_cuda:
         raise RuntimeError("ucd_amd.loss.fused_seg_losses runs on the GPU only (there is no CPU fallback)")
     if kd not in KD_MODES:
         raise ValueError(f"kd must be 'unbiased' or 'plain', not {kd!r}")
-    if kd == "unbiased" and float(alpha) == 1.0 and (sem_old is None or int(old_cl) == sem_old.shape[1]):
+    if form not in SEG_LOSS_FORMS:
+        raise ValueError(f"form must be 'auto', 'tiled' or 'gather', not {form!r}")
+    default_pair = kd == "unbiased" and float(alpha) == 1.0 and (sem_old is None or int(old_cl) == sem_old.shape[1])
+    if form == "auto":
+        K = int(old_cl) if sem_old is None else sem_old.shape[1]
+        form = seg_losses_route(labels.shape[-2], labels.shape[-1], sem.shape[2], sem.shape[3], sem.shape[1], K, sem_old is not None,
+                                None if default_pair else int(old_cl))
+    if default_pair:
         # the pair the kernel was built for: the call, and the bits, of every build so far
-        return _FusedSegLosses.apply(sem, sem_old, labels, old_cl, ce_weight, kd_weight, ignore_index)
+        return _FusedSegLosses.apply(sem, sem_old, labels, old_cl, ce_weight, kd_weight, ignore_index, None, 0, 1.0, form)
     return _FusedSegLosses.apply(sem, sem_old, labels, old_cl, ce_weight, kd_weight, ignore_index, int(old_cl), KD_MODES[kd],
-                                 float(alpha))
+                                 float(alpha), form)
 
 
 def _wide(x):
