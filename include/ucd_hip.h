@@ -525,7 +525,7 @@ int ucd_seg_losses_ex(const float* sem_s, int ld_s, const float* sem_t, int ld_t
                       int ignore_index, float ce_weight, float kd_weight, float* loss_out, float* d_sem, int ld_d,
                       void* workspace, size_t workspace_bytes, ucd_stream_t stream);
 
-/* The GATHER form of the same losses (csrc/seglogit_loss.hip): for the geometries no tiled form above
+/* The GATHER form of the same losses (csrc/seg_gather.hip): for the geometries no tiled form above
  * serves - ADE at --output_stride 8 (151 + 101 classes on 64 x 64 cells under a 512-pixel crop: 207 456 bytes of LDS), any
  * up-sampling factor below 4 - and for a caller that wants a gradient with the same bits on every run where the tiled form adds with
  * fp32 atomics.  Arguments, loss_out[0], loss_out[1] and d_sem[:, :Ctot] mean exactly what they mean for ucd_seg_losses_ex: unbiased
@@ -561,7 +561,7 @@ int ucd_seg_losses_gather(const float* sem_s, int ld_s, const float* sem_t, int 
                           void* workspace, size_t workspace_bytes, ucd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
- * Fused full-resolution BINARY cross entropy losses: --bce, --icarl, --method LWF-MC (csrc/seg_bce.hip).
+ * Fused full-resolution BINARY cross entropy losses: --bce, --icarl, --method LWF-MC (csrc/seg_gather.hip).
  * Rows as for ucd_seg_losses: sem_s [B*h*w, ld_s >= Ctot] / sem_t [B*h*w, ld_t >= K] float32 (sem_t may be NULL), labels int64
  * [B, H, W].  With z = up(sem_s) [B, Ctot, H, W], zt = up(sem_t) [B, K, H, W] (up: bilinear, align_corners=False, as
  * F.interpolate computes it), y the labels, s() the logistic function and

@@ -1,4 +1,4 @@
-"""CPU: the host half of the fused BCE losses (ucd_seg_bce, csrc/seg_bce.hip) - the exported symbols, every host-side rejection
+"""CPU: the host half of the fused BCE losses (ucd_seg_bce, csrc/seg_gather.hip) - the exported symbols, every host-side rejection
 (decided before any device call: no GPU is needed to hear them), the float64 restatement of the formulas (seg_bce_ref.py) against
 the reference's own numbers (tests/golden/bce_losses.npz), and the Trainer's refusals: the BCE family exists on the GPU only,
 --icarl_disjoint with a teacher not at all."""

@@ -1,4 +1,4 @@
-"""GPU: the fused BCE losses (ucd_seg_bce, csrc/seg_bce.hip; ucd_amd.loss.fused_seg_bce) against the float64 restatement of their
+"""GPU: the fused BCE losses (ucd_seg_bce, csrc/seg_gather.hip; ucd_amd.loss.fused_seg_bce) against the float64 restatement of their
 formulas (seg_bce_ref.py) and the reference's own numbers (tests/golden/bce_losses.npz).
 
 Bounds: the project's own for the fused logit losses (tests/test_seglosses_gpu.py:47-53, tests/test_kd_losses_gpu.py): losses rel
@@ -207,3 +207,28 @@ def test_with_kd_the_gradients_add():
     print("BCE + 100 KD: grad max err / max", (g - grad).abs().max().item() / grad.abs().max().item(), "L2", ((g - grad).norm() / grad.norm()).item())
     assert (g - grad).abs().max().item() / grad.abs().max().item() < 1e-3
     assert ((g - grad).norm() / grad.norm()).item() < 1e-4
+
+
+def test_the_kernel_reproduces_the_recorded_bits():
+    """The kernel takes its cell walk from csrc/seg_cell.h, which it shares with the soft-max gather kernel: the arithmetic it
+    carried in a copy of its own, expression for expression, so every output must be BIT-identical to that build's.
+    tests/golden/seg_gather_bits.json holds the SHA-256 of loss_out, d_sem and the per-cell pairs as that build wrote them
+    (tests/golden/make_seg_gather_bits_golden.py): Ctot 24, 25 and 49 (one, two and three register chunks), K = 7 and K = Ctot, on
+    factor 1, ragged non-square factors, h = 1 and factor 64 x 8; no teacher, no d_sem, padded leading dimensions, labels outside
+    [0, Ctot), logits of +-90.  The same calls are replayed here."""
+    import importlib.util
+    import json
+    import os
+    golden = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+    spec = importlib.util.spec_from_file_location("make_seg_gather_bits_golden", os.path.join(golden, "make_seg_gather_bits_golden.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    with open(os.path.join(golden, "seg_gather_bits.json")) as f:
+        recorded = json.load(f)["cases"]
+    assert set(recorded) == set(gen.CASES)
+    bad = []
+    for case in gen.BCE_CASES:
+        got = gen.run_case(case)
+        assert set(got) == set(recorded[case]), f"{case}: outputs {sorted(set(got) ^ set(recorded[case]))}"
+        bad += [f"{case}: {name}" for name in got if got[name] != recorded[case][name]]
+    assert not bad, "outputs whose bits differ from the recorded build's: " + ", ".join(bad)

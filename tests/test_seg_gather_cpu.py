@@ -1,4 +1,4 @@
-"""CPU: the host half of the gather form of the fused logit losses (ucd_seg_losses_gather, csrc/seglogit_loss.hip; DESIGN.md
+"""CPU: the host half of the gather form of the fused logit losses (ucd_seg_losses_gather, csrc/seg_gather.hip; DESIGN.md
 section 3.5.5) - which geometries ``seg_losses_route`` sends to it (exactly those ucd_seg_losses_plan_ex refuses as unsupported) and
 every host-side rejection of the entry point (decided before any device call: no GPU is needed to hear them)."""
 import ctypes as C

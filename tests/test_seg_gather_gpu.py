@@ -1,4 +1,4 @@
-"""GPU: the gather form of the fused logit losses (ucd_seg_losses_gather, csrc/seglogit_loss.hip) at the
+"""GPU: the gather form of the fused logit losses (ucd_seg_losses_gather, csrc/seg_gather.hip) at the
 geometries no tiled form serves (ADE at --output_stride 8, small factors, factor 1) and - forced with form="gather" - at geometries
 the tiled forms serve too.  Inputs, float64 references and bounds are those of tests/test_seglosses_gpu.py (unbiased pair) and
 tests/test_kd_losses_gpu.py (the loss pairs of ucd_seg_losses_ex), by import; the gather form has no fixed point: A = 0."""
@@ -327,3 +327,32 @@ def test_labels_that_are_no_class_read_as_in_the_tiled_forms():
     A = T._fixed_point_allowance(case, T.WIDE_FX)
     assert np.isfinite(a[2]).all() and abs(a[0] - b[0]) <= 1e-5 * abs(b[0]) and abs(a[1] - b[1]) <= 1e-5 * abs(b[1])
     assert float(np.abs(a[2] - b[2]).max()) <= A + 2 * R
+
+
+def _recorded_bits():
+    import importlib.util
+    import json
+    golden = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+    spec = importlib.util.spec_from_file_location("make_seg_gather_bits_golden", os.path.join(golden, "make_seg_gather_bits_golden.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    with open(os.path.join(golden, "seg_gather_bits.json")) as f:
+        return gen, json.load(f)["cases"]
+
+
+def test_the_kernel_reproduces_the_recorded_bits():
+    """The kernel takes its cell walk - staging, scan ranges, a pixel's weights, owner and corner rows, the four-corner
+    interpolation - from csrc/seg_cell.h, which it shares with the BCE kernel.  The walk is the arithmetic each kernel carried in
+    a copy of its own, expression for expression (the library is built without fp contraction), so every output must be
+    BIT-identical to that build's.  tests/golden/seg_gather_bits.json holds the SHA-256 of loss_out, d_sem and the per-cell pairs
+    as that build wrote them (tests/golden/make_seg_gather_bits_golden.py): factor 1, ragged non-square factors, h = 1, factor
+    64 x 8; one class split per instantiation (NR 1, 2, 3, 8, 29); no teacher, plain KD, alpha 0.5, plain cross entropy, no d_sem,
+    padded leading dimensions, labels that are no class, the rescue branch.  The same calls are replayed here."""
+    gen, recorded = _recorded_bits()
+    assert set(recorded) == set(gen.CASES)
+    bad = []
+    for case in gen.SM_CASES:
+        got = gen.run_case(case)
+        assert set(got) == set(recorded[case]), f"{case}: outputs {sorted(set(got) ^ set(recorded[case]))}"
+        bad += [f"{case}: {name}" for name in got if got[name] != recorded[case][name]]
+    assert not bad, "outputs whose bits differ from the recorded build's: " + ", ".join(bad)

@@ -393,7 +393,7 @@ def test_every_form_vs_float64(case):
     the class SUBSETS (old classes; background + new classes) from exponentials relative to the maximum over ALL classes, so
     a subset more than ~87 below that maximum summed to 0 in fp32 - CE = inf, KD and gradient NaN in all seven paths (float64
     CE 44.18, torch fp32 off by 2.9e-6).  The kernels now take such a pixel's subset sums around the subset's own maximum
-    (kSubsetTiny in csrc/seglogit_loss.hip)."""
+    (kSubsetTiny in csrc/seg_loss_common.h)."""
     inputs = _inputs(case)
     form = _expected_form(case)
     got = _launch(case, inputs)

@@ -16,12 +16,12 @@
 // global atomic per cell and class: 32-bit fixed-point words in the packed and the many-class form (integer
 // addition has no order: the same bits on every run), fp32 atomics in the register form and for a d_sem that
 // is not 16-byte aligned (last bits run-dependent).  The loss sums use a fixed order in every form.
-// Geometries whose tiles do not fit the LDS (ADE at --output_stride 8, factors below 4) are served by the gather form at the end of
-// the kernels (seg_losses_gather_kernel, ucd_seg_losses_gather): one wave per low-resolution cell, nothing accumulated in memory.
+// Geometries whose tiles do not fit the LDS (ADE at --output_stride 8, factors below 4) are served by the gather form of seg_gather.hip
+// (seg_losses_gather_kernel, ucd_seg_losses_gather): one wave per low-resolution cell, nothing accumulated in memory.  This unit
+// keeps the tiled forms, their plan and the confusion kernel; what both units need is in seg_loss_common.h.
 #include "common.h"
+#include "seg_loss_common.h"
 #include "upsample_index.h"
-
-#include <cmath>
 
 namespace ucd {
 namespace {
@@ -29,11 +29,7 @@ namespace {
 constexpr int kThreads = 256;
 constexpr int kTileY = 64, kTileX = 64;     // a thread walks kRows consecutive rows of one pixel column
 constexpr int kRows = kTileY / 4;
-// The sums over the class subsets (old classes; background + new classes) are taken from the exponentials relative to the maximum
-// over ALL classes.  A subset that trails that maximum by more than ~87 underflows to a zero sum (log -> -inf, 1 / sum -> inf):
-// below this threshold a pixel takes its subset sums again around each subset's own maximum (what torch.logsumexp does).  Rare in
-// training (a class set 70 below the leader), so a branch: the common path keeps its arithmetic.
-constexpr float kSubsetTiny = 1e-30f;
+// kSubsetTiny (when a pixel takes its class-subset sums again around the subset's own maximum): seg_loss_common.h
 
 // up_src (torch's align_corners=False source index) and tile_span (the cells under a run of pixels): upsample_index.h
 
@@ -918,251 +914,6 @@ __global__ __launch_bounds__(kThreads) void seg_grad_unfix_kernel(float* __restr
   }
 }
 
-__global__ __launch_bounds__(1024) void seg_losses_reduce_kernel(const float* __restrict__ part, int n, float inv_pix,
-                                                                float* __restrict__ out) {
-  __shared__ double red[2][16];
-  double a = 0.0, b = 0.0;
-  for (int i = threadIdx.x; i < n; i += 1024) { a += part[2 * i]; b += part[2 * i + 1]; }
-  for (int off = 32; off > 0; off >>= 1) { a += __shfl_xor(a, off, 64); b += __shfl_xor(b, off, 64); }
-  if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = a; red[1][threadIdx.x >> 6] = b; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double sa = 0.0, sb = 0.0;
-    for (int i = 0; i < 16; ++i) { sa += red[0][i]; sb += red[1][i]; }
-    out[0] = (float)(sa * inv_pix);   // mean over ALL pixels, ignored ones count as 0 (train.py:116 .mean())
-    out[1] = (float)(sb * inv_pix);   // KD mean over all pixels (loss.py:178)
-  }
-}
-
-// ---- the GATHER form (ucd_seg_losses_gather) ---------------------------------------------------------------
-// The forms above scatter: a pixel tile stages every low-resolution cell under it plus per-cell accumulators, which at small
-// up-sampling factors (ADE at --output_stride 8: 207 456 bytes) no longer fits the LDS.  Here, as in seg_bce.hip, one wave owns one
-// low-resolution cell (b, i, j): it stages the 3 x 3 cells around it (read only), walks the pixels whose bilinear footprint contains
-// the cell, and sums weight * dL/dz_pc in registers - no accumulators in LDS, no atomics, no fixed point, each element of d_sem
-// written once, the same bits on every run, any factor >= 1.  A pixel's normalisers are formed again by each of its (up to) four
-// cells: that is the price (section 3.5.4), paid only where nothing else runs.
-// Lanes lie over CLASSES (lane l keeps classes l, 64 + l, ... of NR rounds), not over pixels: the wave walks the pixels one after
-// another, so labels, corners and weights are wave-uniform, lane c rebuilds z_pc from four conflict-free LDS reads (consecutive
-// lanes, consecutive words), the normalisers are wave reductions (butterfly: a fixed order) and a lane keeps one gradient sum per
-// round.  The pixels of the footprint are prepared 64 at a time, one per lane (source index, weight, label: the label loads of a
-// chunk are in flight together), and the wave then visits only those a ballot found to matter.
-// The arithmetic per pixel is that of seg_losses_wide_kernel: the same constants, the same kSubsetTiny rescue.
-__device__ __forceinline__ int lane_get(int v, int k) { return __builtin_amdgcn_readlane(v, k); }
-__device__ __forceinline__ float lane_get(float v, int k) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), k)); }
-// a value every lane holds alike (the result of a butterfly), moved to a scalar register
-__device__ __forceinline__ float uniform(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
-
-// part: [B * h * w][2] (ce sum, kd sum) of the pixels whose (y0, x0) cell this is; d_sem (may be NULL): the cell's row
-template <int NR>
-__global__ __launch_bounds__(kWave) void seg_losses_gather_kernel(
-    const float* __restrict__ sem_s, int ld_s, const float* __restrict__ sem_t, int ld_t, const int64_t* __restrict__ labels,
-    int H, int W, int h, int w, int Ctot, int K, int ignore_index, float scale_h, float scale_w, float inv_scale_h,
-    float inv_scale_w, float ce_scale, float kd_scale, float* __restrict__ part, float* __restrict__ d_sem, int ld_d, int kce,
-    int kd_plain, float alpha) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  constexpr float kL2e = 1.4426950408889634f, kLn2 = 0.6931471805599453f, kNegBig = -1e30f;
-  const int cell = blockIdx.x, lane = threadIdx.x;
-  const int j = cell % w, i = (cell / w) % h, b = cell / (w * h);
-  // the 3 x 3 cells around (i, j): [9][Ctot] student, [9][K] teacher logits (times alpha: the up-sampling is linear).  Cells
-  // outside the map are never indexed (up_src clamps to the map); they are staged as zeros
-  float* s_log = smem;
-  float* t_log = smem + 9 * Ctot;
-  for (int n = lane; n < 9 * Ctot; n += kWave) {
-    const int q = n / Ctot, c = n - q * Ctot;
-    const int cy = i - 1 + q / 3, cx = j - 1 + q % 3;
-    const bool in = cy >= 0 && cy < h && cx >= 0 && cx < w;
-    s_log[n] = in ? sem_s[((size_t)(b * h + cy) * w + cx) * ld_s + c] : 0.f;
-  }
-  if (sem_t)
-    for (int n = lane; n < 9 * K; n += kWave) {
-      const int q = n / K, c = n - q * K;
-      const int cy = i - 1 + q / 3, cx = j - 1 + q % 3;
-      const bool in = cy >= 0 && cy < h && cx >= 0 && cx < w;
-      t_log[n] = in ? alpha * sem_t[((size_t)(b * h + cy) * w + cx) * ld_t + c] : 0.f;
-    }
-  __syncthreads();
-
-  int ylo, yhi, xlo, xhi;
-  scan_range(i, H, inv_scale_h, ylo, yhi);
-  scan_range(j, W, inv_scale_w, xlo, xhi);
-  const int ncol = xhi - xlo + 1, npix = (yhi - ylo + 1) * ncol;
-  const bool want_grad = d_sem != nullptr;
-  const bool plain = kd_plain != 0, pool = kce == K;
-  const int q_lo = plain ? 0 : 1;                 // first class whose teacher probability enters the per-class KD terms
-  const float invK = 1.f / (float)K;
-  const float kdw = sem_t ? kd_scale * invK : 0.f;
-  float ce_sum = 0.f, kd_sum = 0.f;               // wave-uniform: every lane adds the same numbers
-  float acc[NR];
-#pragma unroll
-  for (int r = 0; r < NR; ++r) acc[r] = 0.f;
-
-  for (int p0 = 0; p0 < npix; p0 += kWave) {
-    // ---- one pixel per lane: where it reads, what it weighs, its label ---------------------------------------------------------
-    const int p = p0 + lane;
-    int code = 0, lab = 0;
-    float ly0 = 0.f, ly1 = 0.f, lx0 = 0.f, lx1 = 0.f, wgt = 0.f;
-    bool act = false;
-    if (p < npix) {
-      const int ry = p / ncol;
-      const int Y = ylo + ry, X = xlo + (p - ry * ncol);
-      int y0, y1, x0, x1;
-      up_src(Y, h, scale_h, y0, y1, ly0, ly1);
-      up_src(X, w, scale_w, x0, x1, lx0, lx1);
-      // the pixel's weight on this cell, from the interpolation itself (at the clamped last row y0 == y1: the parts add to 1)
-      const float wy = (y0 == i ? ly0 : 0.f) + (y1 == i ? ly1 : 0.f);
-      const float wx = (x0 == j ? lx0 : 0.f) + (x1 == j ? lx1 : 0.f);
-      wgt = wy * wx;
-      const bool owner = y0 == i && x0 == j;          // this cell counts the pixel's loss
-      act = owner || (want_grad && wgt != 0.f);
-      if (act) {
-        // from here on y0, y1 in [i - 1, i + 1] and x0, x1 in [j - 1, j + 1]: rows 0 .. 8 of the staged neighbourhood
-        const int q00 = (y0 - i + 1) * 3 + (x0 - j + 1), q01 = (y0 - i + 1) * 3 + (x1 - j + 1);
-        const int q10 = (y1 - i + 1) * 3 + (x0 - j + 1), q11 = (y1 - i + 1) * 3 + (x1 - j + 1);
-        const int64_t lab64 = labels[((size_t)b * H + Y) * W + X];
-        const bool ignored = lab64 == ignore_index;
-        // as the scatter kernels read a label (include/ucd_hip.h): negative -> background, Ctot and above -> no class
-        lab = ignored ? 0 : (int)(lab64 < 0 ? 0 : lab64 > Ctot ? Ctot : lab64);
-        if (lab < kce) lab = 0;                       // loss.py:104-105
-        code = q00 | (q01 << 4) | (q10 << 8) | (q11 << 12) | ((int)owner << 16) | ((int)ignored << 17);
-      }
-    }
-    // ---- the wave visits the pixels that matter, one after another: everything about the pixel is uniform -------------------------
-    for (unsigned long long todo = __ballot(act); todo; todo &= todo - 1) {
-      const int k = __builtin_ctzll(todo);
-      const int pc = lane_get(code, k), plab = lane_get(lab, k);
-      const float a0 = lane_get(ly0, k), a1 = lane_get(ly1, k), b0 = lane_get(lx0, k), b1 = lane_get(lx1, k);
-      const float pw = want_grad ? lane_get(wgt, k) : 0.f;
-      const bool owner = (pc >> 16) & 1, ignored = (pc >> 17) & 1;
-      const int q00 = pc & 15, q01 = (pc >> 4) & 15, q10 = (pc >> 8) & 15, q11 = (pc >> 12) & 15;
-      // torch's up-sampling arithmetic: h0*(w0*v00 + w1*v01) + h1*(w0*v10 + w1*v11)
-      auto interp = [&](const float* base, int stride, int c) {
-        return a0 * (b0 * base[q00 * stride + c] + b1 * base[q01 * stride + c]) +
-               a1 * (b0 * base[q10 * stride + c] + b1 * base[q11 * stride + c]);
-      };
-      float z[NR], e[NR];
-      float m = kNegBig;
-#pragma unroll
-      for (int r = 0; r < NR; ++r) {
-        const int c = r * kWave + lane;
-        z[r] = c < Ctot ? interp(s_log, Ctot, c) : kNegBig;      // classes past Ctot: exponentials that are exact zeros
-        m = fmaxf(m, z[r]);
-      }
-      const float mz = uniform(wave_max(m)), mzl = mz * kL2e;
-      float so = 0.f, sn = 0.f;
-#pragma unroll
-      for (int r = 0; r < NR; ++r) {
-        const int c = r * kWave + lane;
-        e[r] = __builtin_amdgcn_exp2f(__builtin_fmaf(z[r], kL2e, -mzl));
-        so += c < K ? e[r] : 0.f;
-        sn += c < K ? 0.f : e[r];
-      }
-      const float s_old = uniform(wave_sum(so)), s_new = uniform(wave_sum(sn)), e0 = lane_get(e[0], 0);
-      const float s_all = s_old + s_new, s_bn = s_new + e0;
-      const float den = mz + kLn2 * __builtin_amdgcn_logf(s_all);
-      float lse_old = mz + kLn2 * __builtin_amdgcn_logf(s_old), lse_bn = mz + kLn2 * __builtin_amdgcn_logf(s_bn);
-      float inv_old = 1.f / s_old, inv_bn = 1.f / s_bn, m_o = 0.f, m_b = 0.f, r_o = 0.f, r_b = 0.f;
-      const bool rescue = s_old < kSubsetTiny || s_bn < kSubsetTiny;
-      if (rescue) {                                  // a class subset ~87 below the leader: its sums again around its own maximum
-        float mo = kNegBig, mb = kNegBig;
-#pragma unroll
-        for (int r = 0; r < NR; ++r) {
-          const int c = r * kWave + lane;
-          mo = c < K ? fmaxf(mo, z[r]) : mo;
-          mb = (c == 0 || c >= K) ? fmaxf(mb, z[r]) : mb;
-        }
-        m_o = uniform(wave_max(mo));
-        m_b = uniform(wave_max(mb));
-        float so2 = 0.f, sb2 = 0.f;
-#pragma unroll
-        for (int r = 0; r < NR; ++r) {
-          const int c = r * kWave + lane;
-          so2 += c < K ? __builtin_amdgcn_exp2f((z[r] - m_o) * kL2e) : 0.f;
-          sb2 += (c == 0 || c >= K) ? __builtin_amdgcn_exp2f((z[r] - m_b) * kL2e) : 0.f;
-        }
-        const float so_r = uniform(wave_sum(so2)), sb_r = uniform(wave_sum(sb2));
-        lse_old = m_o + kLn2 * __builtin_amdgcn_logf(so_r);
-        lse_bn = m_b + kLn2 * __builtin_amdgcn_logf(sb_r);
-        r_o = 1.f / so_r; r_b = 1.f / sb_r;
-        inv_old = 0.f; inv_bn = 0.f;                 // the subset terms of the gradient come from r_o / r_b below
-      }
-      const bool lab0 = pool && plab == 0;           // the label is the pooled background (plain CE: a one-hot like any)
-      if (owner && !ignored) {
-        const float z_lab = plab < Ctot ? interp(s_log, Ctot, plab) : 0.f;       // a label that is no class: as the scatter kernels
-        ce_sum += -(lab0 ? lse_old - den : z_lab - den);
-      }
-      // teacher soft-max over the old classes; q_c = te_c / sum te
-      float te[NR];
-      float inv_st = 0.f, q0 = 0.f;
-      if (sem_t) {
-        float tz[NR];
-        float mt = kNegBig;
-#pragma unroll
-        for (int r = 0; r < NR; ++r) {
-          const int c = r * kWave + lane;
-          tz[r] = c < K ? interp(t_log, K, c) : kNegBig;
-          mt = fmaxf(mt, tz[r]);
-        }
-        const float mtl = uniform(wave_max(mt)) * kL2e;
-        float st = 0.f;
-#pragma unroll
-        for (int r = 0; r < NR; ++r) {
-          te[r] = __builtin_amdgcn_exp2f(__builtin_fmaf(tz[r], kL2e, -mtl));
-          st += te[r];
-        }
-        inv_st = 1.f / uniform(wave_sum(st));
-        q0 = lane_get(te[0], 0) * inv_st;
-        if (owner) {
-          // unbiased: q_0 (LSE_bn - den) + sum_{1<=c<K} q_c (z_c - den); plain: sum_{c<K} q_c (z_c - LSE_old)
-          const float kd_ref = plain ? lse_old : den;
-          float t1 = 0.f;
-#pragma unroll
-          for (int r = 0; r < NR; ++r) {
-            const int c = r * kWave + lane;
-            t1 = __builtin_fmaf((c >= q_lo && c < K) ? te[r] : 0.f, z[r] - kd_ref, t1);
-          }
-          const float kd_pix = (plain ? 0.f : q0 * (lse_bn - den)) + inv_st * uniform(wave_sum(t1));
-          kd_sum += -kd_pix * invK;
-        }
-      } else {
-#pragma unroll
-        for (int r = 0; r < NR; ++r) te[r] = 0.f;
-      }
-      if (pw != 0.f) {
-        // g_c = e_c (a_all - a_old [c<K] - b_bn [c in bkg/new]) - hot [c == label] - b_q te_c [q_lo<=c<K]  (seg_losses_wide_kernel)
-        const float ce_w = ignored ? 0.f : ce_scale;
-        const float a_all = (ce_w + (plain ? 0.f : kdw)) / s_all;
-        const float a_old = (lab0 ? ce_w * inv_old : 0.f) - (plain ? kdw * inv_old : 0.f);
-        const float b_bn = plain ? 0.f : kdw * q0 * inv_bn;
-        const float hot = lab0 ? 0.f : ce_w, b_q = kdw * inv_st;
-        const float rco = (lab0 ? ce_w * r_o : 0.f) - (plain ? kdw * r_o : 0.f), rcb = plain ? 0.f : kdw * q0 * r_b;
-#pragma unroll
-        for (int r = 0; r < NR; ++r) {
-          const int c = r * kWave + lane;
-          const float coef = a_all - (c < K ? a_old : 0.f) - ((c == 0 || c >= K) ? b_bn : 0.f);
-          float g = e[r] * coef - (c == plab ? hot : 0.f);
-          g = __builtin_fmaf(-b_q, (c >= q_lo && c < K) ? te[r] : 0.f, g);
-          if (rescue) {
-            if (c < K) g -= rco * __builtin_amdgcn_exp2f((z[r] - m_o) * kL2e);
-            if (c == 0 || c >= K) g -= rcb * __builtin_amdgcn_exp2f((z[r] - m_b) * kL2e);
-          }
-          acc[r] = __builtin_fmaf(pw, g, acc[r]);
-        }
-      }
-    }
-  }
-  if (want_grad) {
-#pragma unroll
-    for (int r = 0; r < NR; ++r) {
-      const int c = r * kWave + lane;
-      if (c < Ctot) d_sem[(size_t)cell * ld_d + c] = acc[r];     // one store per element
-    }
-  }
-  if (lane == 0) {
-    part[2 * cell + 0] = ce_sum;
-    part[2 * cell + 1] = kd_sum;
-  }
-}
-
 }  // namespace
 }  // namespace ucd
 
@@ -1252,18 +1003,6 @@ int ucd_seg_losses_plan(int H, int W, int h, int w, int Ctot, int K, int has_tea
 
 namespace {
 
-// the argument rules of ucd_seg_losses_ex / ucd_seg_losses_plan_ex that ucd_seg_losses cannot break (host only, before anything else)
-int seg_ex_check(const char* fn, int Ctot, int K, int ce_old_cl, int kd_mode, float alpha, int has_teacher) {
-  UCD_REQUIRE(Ctot > 0 && K >= 1 && K <= Ctot, UCD_EINVAL, "%s: bad sizes", fn);
-  UCD_REQUIRE(ce_old_cl >= 1 && ce_old_cl <= Ctot, UCD_EINVAL, "%s: ce_old_cl = %d is outside [1, Ctot = %d]", fn, ce_old_cl, Ctot);
-  UCD_REQUIRE(kd_mode == UCD_KD_UNBIASED || kd_mode == UCD_KD_PLAIN, UCD_EINVAL,
-              "%s: kd_mode = %d is neither UCD_KD_UNBIASED (0) nor UCD_KD_PLAIN (1)", fn, kd_mode);
-  UCD_REQUIRE(std::isfinite(alpha) && alpha != 0.f, UCD_EINVAL, "%s: alpha = %g must be finite and non-zero", fn, (double)alpha);
-  UCD_REQUIRE(!has_teacher || ce_old_cl == 1 || ce_old_cl == K, UCD_EINVAL,
-              "%s: with a teacher ce_old_cl = %d must be 1 (plain cross entropy) or K = %d", fn, ce_old_cl, K);
-  return 0;
-}
-
 // opt every instantiation of one EX value in to the LDS budget, launch the planned form
 template <bool EX>
 int seg_launch(const char* fn, int form, dim3 grid, size_t lds, hipStream_t s, const float* sem_s, int ld_s, const float* sem_t, int ld_t,
@@ -1341,8 +1080,7 @@ int seg_losses_impl(const char* fn, const float* sem_s, int ld_s, const float* s
     rc = check_launch(fn);
     if (rc) return rc;
   }
-  seg_losses_reduce_kernel<<<1, 1024, 0, s>>>(part, B * tiles_x * tiles_y, inv_pix, loss_out);
-  return check_launch(fn);
+  return seg_pair_reduce(fn, part, B * tiles_x * tiles_y, inv_pix, loss_out, s);
 }
 
 }  // namespace
@@ -1371,61 +1109,6 @@ int ucd_seg_losses_ex(const float* sem_s, int ld_s, const float* sem_t, int ld_t
                       ucd_stream_t stream) {
   return seg_losses_impl("ucd_seg_losses_ex", sem_s, ld_s, sem_t, ld_t, labels, B, H, W, h, w, Ctot, K, ce_old_cl, kd_mode, alpha,
                          ignore_index, ce_weight, kd_weight, loss_out, d_sem, ld_d, workspace, workspace_bytes, stream);
-}
-
-size_t ucd_seg_losses_gather_workspace_bytes(int B, int h, int w) {
-  if (B <= 0 || h <= 0 || w <= 0) return 0;
-  return (size_t)B * h * w * 2 * sizeof(float);       // one (ce, kd) pair per low-resolution cell
-}
-
-int ucd_seg_losses_gather(const float* sem_s, int ld_s, const float* sem_t, int ld_t, const int64_t* labels, int B, int H, int W,
-                          int h, int w, int Ctot, int K, int ce_old_cl, int kd_mode, float alpha, int ignore_index, float ce_weight,
-                          float kd_weight, float* loss_out, float* d_sem, int ld_d, void* workspace, size_t workspace_bytes,
-                          ucd_stream_t stream) {
-  static const char* fn = "ucd_seg_losses_gather";
-  UCD_REQUIRE(sem_s && labels && loss_out && workspace, UCD_EINVAL, "%s: NULL argument (%s)", fn,
-              !sem_s ? "sem_s" : !labels ? "labels" : !loss_out ? "loss_out" : "workspace");
-  UCD_REQUIRE(B > 0 && H > 0 && W > 0 && h > 0 && w > 0 && Ctot > 0, UCD_EINVAL,
-              "%s: bad sizes (B %d, H %d, W %d, h %d, w %d, Ctot %d must be positive)", fn, B, H, W, h, w, Ctot);
-  UCD_REQUIRE(K >= 1 && K <= Ctot, UCD_EINVAL, "%s: bad sizes (K = %d is outside [1, Ctot = %d])", fn, K, Ctot);
-  UCD_REQUIRE(ld_s >= Ctot, UCD_EINVAL, "%s: bad leading dimension (ld_s = %d below Ctot = %d)", fn, ld_s, Ctot);
-  UCD_REQUIRE(!sem_t || ld_t >= K, UCD_EINVAL, "%s: bad leading dimension (ld_t = %d below K = %d)", fn, ld_t, K);
-  UCD_REQUIRE(!d_sem || ld_d >= Ctot, UCD_EINVAL, "%s: bad leading dimension (ld_d = %d below Ctot = %d)", fn, ld_d, Ctot);
-  UCD_REQUIRE(H >= h && W >= w, UCD_EINVAL, "%s: bad scale (the label map H x W = %d x %d is smaller than the logits h x w = %d x %d)", fn,
-              H, W, h, w);
-  int rc = seg_ex_check(fn, Ctot, K, ce_old_cl, kd_mode, alpha, sem_t != nullptr);
-  if (rc) return rc;
-  UCD_REQUIRE((long long)B * h * w <= 0x3fffffffLL, UCD_EINVAL, "%s: %lld low-resolution cells exceed the grid", fn, (long long)B * h * w);
-  UCD_REQUIRE(workspace_bytes >= ucd_seg_losses_gather_workspace_bytes(B, h, w), UCD_EWORKSPACE,
-              "%s: workspace too small (workspace_bytes = %zu, %zu needed)", fn, workspace_bytes,
-              ucd_seg_losses_gather_workspace_bytes(B, h, w));
-  // without a teacher the only class split is the cross entropy's (as seg_losses_impl)
-  if (!sem_t) K = ce_old_cl;
-  const size_t lds = (size_t)9 * (Ctot + (sem_t ? K : 0)) * sizeof(float);
-  UCD_REQUIRE(lds <= 64 * 1024, UCD_EUNSUPPORTED,
-              "%s: the 3 x 3 neighbourhood of a cell takes %zu bytes of LDS for %d + %d classes, over the 65536 the gather form has", fn,
-              lds, Ctot, sem_t ? K : 0);
-  hipStream_t s = (hipStream_t)stream;
-  const int cells = B * h * w, kd_plain = kd_mode == UCD_KD_PLAIN;
-  const float inv_pix = 1.f / ((float)B * H * W);
-  float* part = (float*)workspace;
-  // torch computes the up-sampling scale as float(in) / out
-#define UCD_SEG_GATHER(NR)                                                                                                          \
-  seg_losses_gather_kernel<NR><<<cells, kWave, lds, s>>>(sem_s, ld_s, sem_t, ld_t, labels, H, W, h, w, Ctot, K, ignore_index,             \
-                                                        (float)h / (float)H, (float)w / (float)W, (float)H / (float)h,              \
-                                                        (float)W / (float)w, ce_weight * inv_pix, kd_weight * inv_pix, part, d_sem, \
-                                                        ld_d, ce_old_cl, kd_plain, alpha)
-  const int rounds = ceil_div(Ctot, kWave);           // 64 KB of LDS hold 1820 classes: at most 29 rounds
-  if (rounds <= 1) UCD_SEG_GATHER(1);
-  else if (rounds <= 2) UCD_SEG_GATHER(2);
-  else if (rounds <= 3) UCD_SEG_GATHER(3);
-  else if (rounds <= 8) UCD_SEG_GATHER(8);
-  else UCD_SEG_GATHER(29);
-#undef UCD_SEG_GATHER
-  rc = check_launch(fn);
-  if (rc) return rc;
-  seg_losses_reduce_kernel<<<1, 1024, 0, s>>>(part, cells, inv_pix, loss_out);
-  return check_launch(fn);
 }
 
 int ucd_seg_confusion(const float* sem, int ld_s, const int64_t* labels, int B, int H, int W, int h, int w, int Ctot,

@@ -1,5 +1,5 @@
 // The source-index arithmetic of the bilinear up-sampling (F.interpolate, align_corners=False), shared by the kernels that
-// rebuild full-resolution logits from the low-resolution ones (seglogit_loss.hip, seg_bce.hip).  One copy: host and device,
+// rebuild full-resolution logits from the low-resolution ones (seglogit_loss.hip, seg_cell.h).  One copy: host and device,
 // under -ffp-contract=off on both sides, so a plan computed on the host rounds exactly as the kernel it sizes.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -27,7 +27,7 @@ __host__ __device__ __forceinline__ void tile_span(int t0, int tile, int out, in
   count = last - first + 1;
 }
 
-// The gather forms (seg_bce.hip, seg_losses_gather_kernel): the pixels of one dimension that can touch cell i, src = scale * (p + 0.5)
+// The gather forms (seg_cell.h: the walk of seg_gather.hip's kernels): the pixels of one dimension that can touch cell i, src = scale * (p + 0.5)
 // - 0.5 in (i - 1, i + 1).  The bounds are strict, so floor / ceil of the real-valued ends already take one pixel more on either
 // side than the footprint has: rounding (of these ends, of up_src) moves nothing by a pixel.  Outside the footprint the weight is
 // zero; no exact inverse is needed.

@@ -4,9 +4,9 @@
 ``UnbiasedKnowledgeDistillationLoss`` (:139-184) keep the reference's module interface on full-resolution logits
 (the unfused path: the CPU, ``UCD_SEG_KD_EX=0``, tests).  The training step itself calls ``fused_seg_losses``: bilinear
 x16 up-sampling + (unbiased or plain) CE + (unbiased or plain) KD at any ``--alpha`` + the gradient w.r.t. the
-LOW-resolution logits in one HIP kernel (``ucd_seg_losses`` / ``ucd_seg_losses_ex``, csrc/seglogit_loss.hip; SURVEY.md
-section 8-f1) - the ``[B, Ctot, H, W]`` tensors never exist.  A geometry whose tiles do not fit the LDS of those kernels (ADE at
-``--output_stride 8``) goes to the gather form of the same file (``ucd_seg_losses_gather``; ``seg_losses_route`` says which).
+LOW-resolution logits in one HIP kernel (``ucd_seg_losses_ex``, csrc/seglogit_loss.hip) - the
+``[B, Ctot, H, W]`` tensors never exist.  A geometry whose tiles do not fit the LDS of those kernels (ADE at ``--output_stride 8``)
+goes to the gather form (``ucd_seg_losses_gather``, csrc/seg_gather.hip; ``seg_losses_route`` says which).
 The contrastive loss lives in :mod:`ucd_amd.contrastive`.
 """
 from __future__ import annotations
@@ -21,103 +21,85 @@ from . import hip
 from .contrastive import PixelConLossV2, pre_contractive_pixel, ucd_contrastive_loss  # noqa: F401
 
 
-class _FusedSegLosses(torch.autograd.Function):
-    """total = ce_weight * mean(CE) + kd_weight * mean(KD) from the LOW-resolution logits; the up-sampled
-    [B, Ctot, H, W] tensors never exist (ucd_seg_losses / ucd_seg_losses_ex).
-    ``ce_old_cl`` is None for the call as it always was (one class count K for both losses, unbiased KD, alpha 1)."""
+class _LowResLogitLoss(torch.autograd.Function):
+    """What the fused logit-loss Functions share.  A library call takes the LOW-resolution logits as ``[B*h*w, C]`` fp32 rows and
+    writes two loss means and, where asked, ``d_sem``: the gradient of ``w0 * loss0 + w1 * loss1`` w.r.t. the student rows.  The
+    up-sampled [B, Ctot, H, W] tensors never exist.  A subclass keeps its library call and its weights; ``sem``, the first input,
+    is the only one with a gradient."""
 
     @staticmethod
-    def forward(ctx, sem, sem_old, labels, old_cl, ce_weight, kd_weight, ignore_index, ce_old_cl=None, kd_mode=0, alpha=1.0,
-                form="tiled"):
-        lib = hip.load()
+    def operands(ctx, sem, sem_old, labels, K, want_d):
+        """(student rows, teacher rows or None, K - with a teacher: its class count -, labels, out[2], d_sem or None,
+        (B, H, W, h, w, Ctot)).  ``want_d``: the call writes the gradient rows, kept for ``backward``."""
         B, Ctot, h, w = sem.shape
         H, W = labels.shape[-2:]
         s = sem.detach().permute(0, 2, 3, 1).reshape(B * h * w, Ctot).float().contiguous()
-        t, K = None, int(old_cl)
+        t = None
         if sem_old is not None:
             K = sem_old.shape[1]
             t = sem_old.detach().permute(0, 2, 3, 1).reshape(B * h * w, K).float().contiguous()
-        labels = labels.contiguous()
         out = torch.empty(2, dtype=torch.float32, device=sem.device)
-        if form == "gather":
-            # one wave per low-resolution cell: no gradient to form, no d_sem (the same loss bits)
-            d = torch.empty(B * h * w, Ctot, dtype=torch.float32, device=sem.device) if ctx.needs_input_grad[0] else None
-            nbytes = lib.ucd_seg_losses_gather_workspace_bytes(B, h, w)
-            ws = hip.workspace(nbytes, sem.device, "seglosses_gather")
-            with hip._timed("ucd_seg_losses_gather", B * H * W * 8 + B * h * w * (2 * Ctot + K) * 4):
-                hip._check(lib.ucd_seg_losses_gather(hip.ptr(s), Ctot, hip.ptr(t), K, hip.ptr(labels), B, H, W, h, w, Ctot, max(K, 1),
-                                                     max(K, 1) if ce_old_cl is None else int(ce_old_cl), int(kd_mode), float(alpha),
-                                                     int(ignore_index), float(ce_weight), float(kd_weight), hip.ptr(out), hip.ptr(d),
-                                                     Ctot, hip.ptr(ws), nbytes, hip.stream()), "ucd_seg_losses_gather")
-        else:
-            d = torch.empty(B * h * w, Ctot, dtype=torch.float32, device=sem.device)
-            nbytes = lib.ucd_seg_losses_workspace_bytes(B, H, W)
-            ws = hip.workspace(nbytes, sem.device, "seglosses")
-            with hip._timed("ucd_seg_losses", B * H * W * 8 + 2 * B * h * w * (2 * Ctot + K) * 4):
-                if ce_old_cl is None:
-                    hip._check(lib.ucd_seg_losses(hip.ptr(s), Ctot, hip.ptr(t), K, hip.ptr(labels), B, H, W, h, w, Ctot, max(K, 1),
-                                                  int(ignore_index), float(ce_weight), float(kd_weight), hip.ptr(out), hip.ptr(d),
-                                                  Ctot, hip.ptr(ws), nbytes, hip.stream()), "ucd_seg_losses")
-                else:
-                    hip._check(lib.ucd_seg_losses_ex(hip.ptr(s), Ctot, hip.ptr(t), K, hip.ptr(labels), B, H, W, h, w, Ctot, max(K, 1),
-                                                     int(ce_old_cl), int(kd_mode), float(alpha), int(ignore_index), float(ce_weight),
-                                                     float(kd_weight), hip.ptr(out), hip.ptr(d), Ctot, hip.ptr(ws), nbytes,
-                                                     hip.stream()), "ucd_seg_losses_ex")
-        if d is not None:
+        d = torch.empty(B * h * w, Ctot, dtype=torch.float32, device=sem.device) if want_d else None
+        if want_d:
             ctx.save_for_backward(d)
         ctx.meta = (B, Ctot, h, w, sem.dtype)
-        ce, kd = out[0], out[1]
-        total = ce_weight * ce + kd_weight * kd
-        ctx.mark_non_differentiable(ce, kd)
-        return total, ce, kd
+        return s, t, K, labels.contiguous(), out, d, (B, H, W, h, w, Ctot)
 
     @staticmethod
-    def backward(ctx, g, _gce, _gkd):
+    def weighted(ctx, out, w0, w1):
+        loss0, loss1 = out[0], out[1]
+        ctx.mark_non_differentiable(loss0, loss1)
+        return w0 * loss0 + w1 * loss1, loss0, loss1
+
+    @staticmethod
+    def backward(ctx, g, _g0, _g1):
         (d,) = ctx.saved_tensors
         B, Ctot, h, w, dtype = ctx.meta
         grad = (d * g).view(B, h, w, Ctot).permute(0, 3, 1, 2).to(dtype)
-        return grad, None, None, None, None, None, None, None, None, None, None
+        return (grad,) + (None,) * (len(ctx.needs_input_grad) - 1)
 
 
-class _FusedSegBCE(torch.autograd.Function):
-    """total = hard_weight * BCE + soft_weight * soft from the LOW-resolution logits (ucd_seg_bce, csrc/seg_bce.hip): BCE is the
-    reference's ``BCEWithLogitsLossWithIgnoreIndex(reduction='none')(up(sem), labels).mean()``, soft its combined iCaRL term
+class _FusedSegLosses(_LowResLogitLoss):
+    """total = ce_weight * mean(CE) + kd_weight * mean(KD) (ucd_seg_losses_ex, or ucd_seg_losses_gather for ``form="gather"``;
+    SURVEY.md section 8-f1).  Every call names its loss pair: the cross entropy pools ``max(old_cl, 1)`` classes.  The pair the
+    kernels were first built for (one class count for both losses, unbiased KD, alpha 1) is the launch, and the bits, of
+    ucd_seg_losses: the library picks its kernels by these values, not by the entry."""
+
+    @staticmethod
+    def forward(ctx, sem, sem_old, labels, old_cl, ce_weight, kd_weight, ignore_index, kd_mode, alpha, form):
+        lib = hip.load()
+        gather = form == "gather"
+        # the gather form writes d_sem only where asked (the same loss bits without); the tiled forms always accumulate into it
+        s, t, K, labels, out, d, (B, H, W, h, w, Ctot) = _LowResLogitLoss.operands(ctx, sem, sem_old, labels, int(old_cl),
+                                                                                   ctx.needs_input_grad[0] or not gather)
+        name = "ucd_seg_losses_gather" if gather else "ucd_seg_losses_ex"
+        nbytes = lib.ucd_seg_losses_gather_workspace_bytes(B, h, w) if gather else lib.ucd_seg_losses_workspace_bytes(B, H, W)
+        ws = hip.workspace(nbytes, sem.device, "seglosses_gather" if gather else "seglosses")
+        # one wave per cell reads its rows once; a tiled form also adds into them
+        with hip._timed("ucd_seg_losses_gather" if gather else "ucd_seg_losses",
+                        B * H * W * 8 + (1 if gather else 2) * B * h * w * (2 * Ctot + K) * 4):
+            hip._check(getattr(lib, name)(hip.ptr(s), Ctot, hip.ptr(t), K, hip.ptr(labels), B, H, W, h, w, Ctot, max(K, 1),
+                                          max(int(old_cl), 1), int(kd_mode), float(alpha), int(ignore_index), float(ce_weight),
+                                          float(kd_weight), hip.ptr(out), hip.ptr(d), Ctot, hip.ptr(ws), nbytes, hip.stream()), name)
+        return _LowResLogitLoss.weighted(ctx, out, ce_weight, kd_weight)
+
+
+class _FusedSegBCE(_LowResLogitLoss):
+    """total = hard_weight * BCE + soft_weight * soft (ucd_seg_bce, csrc/seg_gather.hip): BCE is the reference's
+    ``BCEWithLogitsLossWithIgnoreIndex(reduction='none')(up(sem), labels).mean()``, soft its combined iCaRL term
     ``K * BCEWithLogitsLoss()(up(sem)[:, :K], sigmoid(up(sem_old)))``.  Without a gradient to form, the kernel gets no ``d_sem``."""
 
     @staticmethod
     def forward(ctx, sem, sem_old, labels, hard_weight, soft_weight, ignore_index):
         lib = hip.load()
-        B, Ctot, h, w = sem.shape
-        H, W = labels.shape[-2:]
-        s = sem.detach().permute(0, 2, 3, 1).reshape(B * h * w, Ctot).float().contiguous()
-        t, K = None, 1
-        if sem_old is not None:
-            K = sem_old.shape[1]
-            t = sem_old.detach().permute(0, 2, 3, 1).reshape(B * h * w, K).float().contiguous()
-        labels = labels.contiguous()
-        out = torch.empty(2, dtype=torch.float32, device=sem.device)
-        need_grad = ctx.needs_input_grad[0]
-        d = torch.empty(B * h * w, Ctot, dtype=torch.float32, device=sem.device) if need_grad else None
+        s, t, K, labels, out, d, (B, H, W, h, w, Ctot) = _LowResLogitLoss.operands(ctx, sem, sem_old, labels, 1, ctx.needs_input_grad[0])
         nbytes = lib.ucd_seg_bce_workspace_bytes(B, h, w)
         ws = hip.workspace(nbytes, sem.device, "seg_bce")
         with hip._timed("ucd_seg_bce", B * H * W * 8 + B * h * w * (2 * Ctot + K) * 4):
             hip._check(lib.ucd_seg_bce(hip.ptr(s), Ctot, hip.ptr(t), K, hip.ptr(labels), B, H, W, h, w, Ctot, K, int(ignore_index),
                                        float(hard_weight), float(soft_weight), hip.ptr(out), hip.ptr(d), Ctot, hip.ptr(ws), nbytes,
                                        hip.stream()), "ucd_seg_bce")
-        if need_grad:
-            ctx.save_for_backward(d)
-        ctx.meta = (B, Ctot, h, w, sem.dtype)
-        bce, soft = out[0], out[1]
-        total = hard_weight * bce + soft_weight * soft
-        ctx.mark_non_differentiable(bce, soft)
-        return total, bce, soft
-
-    @staticmethod
-    def backward(ctx, g, _gbce, _gsoft):
-        (d,) = ctx.saved_tensors
-        B, Ctot, h, w, dtype = ctx.meta
-        grad = (d * g).view(B, h, w, Ctot).permute(0, 3, 1, 2).to(dtype)
-        return grad, None, None, None, None, None
+        return _LowResLogitLoss.weighted(ctx, out, hard_weight, soft_weight)
 
 
 def fused_seg_bce(sem, sem_old, labels, hard_weight=1.0, soft_weight=0.0, ignore_index=255):
@@ -202,7 +184,7 @@ def fused_seg_losses(sem, sem_old, labels, old_cl, ce_weight=1.0, kd_weight=0.0,
 
     With a teacher of K classes ``old_cl`` is 1 or K (the reference produces no other pair; the kernel refuses one).
 
-    ``form``: ``"tiled"`` is the scatter kernels (``ucd_seg_losses`` / ``ucd_seg_losses_ex``), which refuse a geometry whose tiles do
+    ``form``: ``"tiled"`` is the scatter kernels (``ucd_seg_losses_ex``), which refuse a geometry whose tiles do
     not fit their LDS; ``"gather"`` is ``ucd_seg_losses_gather`` - any up-sampling factor >= 1, a gradient with the same bits on every
     run, and, under ``torch.no_grad()`` or with a ``sem`` that needs no gradient, the losses alone; ``"auto"`` is ``"tiled"`` wherever
     that serves (the call, and the bits, it always was) and ``"gather"`` elsewhere (``seg_losses_route``)."""
@@ -212,16 +194,11 @@ def fused_seg_losses(sem, sem_old, labels, old_cl, ce_weight=1.0, kd_weight=0.0,
         raise ValueError(f"kd must be 'unbiased' or 'plain', not {kd!r}")
     if form not in SEG_LOSS_FORMS:
         raise ValueError(f"form must be 'auto', 'tiled' or 'gather', not {form!r}")
-    default_pair = kd == "unbiased" and float(alpha) == 1.0 and (sem_old is None or int(old_cl) == sem_old.shape[1])
     if form == "auto":
         K = int(old_cl) if sem_old is None else sem_old.shape[1]
         form = seg_losses_route(labels.shape[-2], labels.shape[-1], sem.shape[2], sem.shape[3], sem.shape[1], K, sem_old is not None,
-                                None if default_pair else int(old_cl))
-    if default_pair:
-        # the pair the kernel was built for: the call, and the bits, of every build so far
-        return _FusedSegLosses.apply(sem, sem_old, labels, old_cl, ce_weight, kd_weight, ignore_index, None, 0, 1.0, form)
-    return _FusedSegLosses.apply(sem, sem_old, labels, old_cl, ce_weight, kd_weight, ignore_index, int(old_cl), KD_MODES[kd],
-                                 float(alpha), form)
+                                max(int(old_cl), 1))
+    return _FusedSegLosses.apply(sem, sem_old, labels, old_cl, ce_weight, kd_weight, ignore_index, KD_MODES[kd], float(alpha), form)
 
 
 def _wide(x):

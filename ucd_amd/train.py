@@ -21,7 +21,7 @@ come from one fused HIP kernel on the low-resolution logits (``UCD_SEG_KD_EX=0``
 KD); ILT's encoder term is one HIP operation on the raw maps (``UCD_FUSED_LDE=0``: torch), which puts ILT inside the graphs.
 EWC / PI / RW (``--method EWC|PI|RW``) add the weight-space penalty of ucd_amd.regularizer between the gradient
 all-reduce and the optimiser (train.py:139-145).  ``--bce``, ``--icarl`` and ``--method LWF-MC`` take the per-class binary cross
-entropy and the combined iCaRL term (train.py:119-124) from their own fused HIP kernel (``fused_seg_bce``, csrc/seg_bce.hip),
+entropy and the combined iCaRL term (train.py:119-124) from their own fused HIP kernel (``fused_seg_bce``, csrc/seg_gather.hip),
 inside the graphs like the others.  Out of scope (raise ``NotImplementedError``): ``--icarl_disjoint`` with a teacher, and any BCE
 run on a CPU device.
 """
