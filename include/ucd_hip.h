@@ -602,6 +602,46 @@ int ucd_seg_bce(const float* sem_s, int ld_s, const float* sem_t, int ld_t, cons
 int ucd_seg_confusion(const float* sem, int ld_s, const int64_t* labels, int B, int H, int W, int h, int w, int Ctot,
                       int n_classes, int64_t* hist, int64_t* pred, ucd_stream_t stream);
 
+/* The output side of an evaluation run (the reference's test.py / Trainer.test, train.py:271-375) in one pass over the
+ * full-resolution pixel grid of a batch; only uint8 maps (and the fp32 attention map) leave the device.  Inputs:
+ *   sem      fp32 rows [B*h*w, ld_s >= Ctot], the low-resolution logits (as ucd_seg_confusion takes them); Ctot <= 255
+ *   labels   int64 [B, H, W], may be NULL
+ *   image    fp32, element (b, c, y, x) at image[b sb + c sc + y sh + x sw], c < 3: the normalised input in NCHW or channels-last
+ *            (strides in elements, as ucd_stem_conv7x7 takes them); may be NULL
+ *   mean_*, std_*   the normalisation that the data pipeline applied, by value
+ *   cmap     uint8 [256][3] in device memory, the palette
+ *   att_low  fp32 [B, ha, wa], may be NULL: a low-resolution map (ucd_attn_energy) on a grid independent of h x w
+ * Outputs, each optional (NULL: not produced, and nothing of it is touched):
+ *   pred_u8   [B, H, W]     arg-max over the classes of the bilinearly up-sampled logits (align_corners = False), first maximum
+ *                           wins: the same arithmetic, and the same bits, as the pred of ucd_seg_confusion
+ *   pred_rgb  [B, H, W, 3]  cmap[pred]
+ *   label_rgb [B, H, W, 3]  cmap[label & 255]
+ *   image_u8  [B, H, W, 3]  trunc(clamp((x * std + mean) * 255, 0, 255)) in fp32 (the reference's astype(uint8) wraps values
+ *                           outside the range; the clamp is the one difference)
+ *   att       [B, H, W] fp32  att_low up-sampled bilinearly with the same source-index arithmetic
+ * Every byte of a requested output is written exactly once.  One launch, no allocation, no host synchronisation: the call can be
+ * captured into a graph.  Tiling: ucd_seg_confusion's (64 x 64 pixel tiles, the cells under a tile in LDS); a wave exchanges the
+ * packed pixels of a tile row by shuffles and stores aligned dwords of the RGB rows, bytes only at the ends of a row segment.
+ * Checked on the host before any device call, the message names the argument: UCD_EINVAL (NULL sem or cmap; B, H, W, h, w or
+ * Ctot below 1; ld_s < Ctot; Ctot > 255; every output NULL; label_rgb without labels; image_u8 without image; att without
+ * att_low, or with ha / wa below 1), UCD_EUNSUPPORTED (an up-sampling factor H / h or W / w below 4; more than 150 KB of LDS for
+ * the cells under a tile - the limits of ucd_seg_confusion); else the hipError_t of a failed launch.  On a negative code nothing
+ * was launched. */
+int ucd_seg_render(const float* sem, int ld_s, const int64_t* labels, const float* image, long long sb, long long sc, long long sh,
+                   long long sw, float mean_r, float mean_g, float mean_b, float std_r, float std_g, float std_b, const uint8_t* cmap,
+                   const float* att_low, int ha, int wa, int B, int H, int W, int h, int w, int Ctot, uint8_t* pred_u8,
+                   uint8_t* pred_rgb, uint8_t* label_rgb, uint8_t* image_u8, float* att, ucd_stream_t stream);
+
+/* The attention map of the reference's Trainer.test (train.py:339-342) from a RAW map: a[b, p] = sum_c x[b, p, c]^2, divided by
+ * the Frobenius norm of its image's map (the factor ucd_attmap multiplies with, kept instead of applied).
+ *   x  channels-last rows [B*HW, ld >= C], dtype UCD_F32 or UCD_BF16;  a  fp32 [B*HW], written in full
+ * 16-byte loads when the base pointer and the row pitch are 16-byte aligned, element loads otherwise: no alignment is required.
+ * Two launches (per-cell sums of squares; one workgroup per image for the norm and the division), no workspace, no float
+ * atomics, every sum in a fixed order: same inputs, same bits.  An all-zero image divides by zero like the reference (NaN).
+ * Checked on the host before any device call: UCD_EINVAL (NULL x or a, unknown dtype, B / HW / C below 1, ld < C, more than
+ * 2^29 rows); else the hipError_t of a failed launch. */
+int ucd_attn_energy(const void* x, int ld, int dtype, int B, int HW, int C, float* a, ucd_stream_t stream);
+
 /* ---- label path of the training data pipeline on the device (first piece) ------------------------
  * Replaces, for the label maps of a batch, the reference's host-side RandomResizedCrop (crop + PIL NEAREST resize,
  * dataset/transform.py:481-553), RandomHorizontalFlip (:300-318) and the per-pixel Python lambda that remaps labels for

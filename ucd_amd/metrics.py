@@ -34,9 +34,10 @@ class StreamSegMetrics:
         hist = torch.bincount(idx, minlength=n * n).reshape(n, n).double()
         self.confusion_matrix = hist if self.confusion_matrix is None else self.confusion_matrix + hist
 
-    def update_from_logits(self, label_trues, sem):
+    def update_from_logits(self, label_trues, sem, pred=None):
         """``update(labels, upsample(sem).argmax(1))`` without the full-resolution logits: bilinear up-sampling, arg-max and
-        the histogram in one kernel (``ucd_seg_confusion``; ``sem`` = the model's low-resolution logits [B, Ctot, h, w])."""
+        the histogram in one kernel (``ucd_seg_confusion``; ``sem`` = the model's low-resolution logits [B, Ctot, h, w]).
+        ``pred`` (optional, contiguous int64 [B, H, W] on the device) receives the arg-max map the histogram was built from."""
         from . import hip
         B, Ctot, h, w = sem.shape
         H, W = label_trues.shape[-2:]
@@ -46,7 +47,10 @@ class StreamSegMetrics:
         if lab.dtype != torch.int64:
             lab = lab.long()
         hist = torch.zeros(n, n, dtype=torch.int64, device=sem.device)
-        hip._check(hip.load().ucd_seg_confusion(hip.ptr(s), Ctot, hip.ptr(lab), B, H, W, h, w, Ctot, n, hip.ptr(hist), None,
+        if pred is not None and (pred.dtype != torch.int64 or tuple(pred.shape) != (B, H, W) or not pred.is_contiguous()
+                                 or pred.device != sem.device):
+            raise ValueError(f"pred must be a contiguous int64 [{B}, {H}, {W}] tensor on {sem.device}")
+        hip._check(hip.load().ucd_seg_confusion(hip.ptr(s), Ctot, hip.ptr(lab), B, H, W, h, w, Ctot, n, hip.ptr(hist), hip.ptr(pred),
                                                 hip.stream()), "ucd_seg_confusion")
         self.total_samples += B
         hist = hist.double()

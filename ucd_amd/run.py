@@ -6,6 +6,9 @@ best_score, trainer_state).  Data: with a VOC tree under ``--data_root`` (``spli
 ``SegmentationClassAug/``) the reference's incremental dataset is used - host decode, batch transform on the device
 (``ucd_amd/dataset.py``); ``--data_root synthetic`` - and only that - trains on the closed-form
 synthetic batches the benchmark uses; a data root without ``splits/`` raises like the reference's dataset classes do.
+``--lr_policy step`` selects ``StepLR`` (run.py:186-189); ``--sample_num N`` keeps N validation samples per epoch as ``image |
+target | prediction`` strips under ``<logdir>/<task>-<dataset>/<name>/samples/epoch_E/`` (the reference hands them to tensorboard).
+``ucd_amd/evaluate.py`` is the reference's ``test.py``.
 """
 from __future__ import annotations
 
@@ -52,6 +55,30 @@ def make_optimizer(opts, model):
         return SGD(groups, lr=opts.lr, momentum=0.9, nesterov=True)
     kw = {"fused": True} if next(net.parameters()).is_cuda else {}
     return torch.optim.SGD(groups, lr=opts.lr, momentum=0.9, nesterov=True, **kw)
+
+
+def make_scheduler(opts, optimizer, iters_per_epoch):
+    """--lr_policy poly | step (run.py:186-189 of the reference); both are stepped once per iteration."""
+    if opts.lr_policy == "poly":
+        return PolyLR(optimizer, max_iters=opts.epochs * iters_per_epoch, power=opts.lr_power)
+    if opts.lr_policy == "step":
+        return torch.optim.lr_scheduler.StepLR(optimizer, step_size=opts.lr_decay_step, gamma=opts.lr_decay_factor)
+    raise NotImplementedError(opts.lr_policy)
+
+
+def save_sample_strips(directory, samples, cmap=None):
+    """The validation samples of an epoch (run.py:343-349 of the reference hands them to tensorboard) as ``image | target |
+    prediction`` strips, one PNG per sample: the de-normalised image (clamped, see ucd_amd.visual) beside the two colour-coded
+    maps."""
+    from PIL import Image
+    from . import visual
+    cmap = visual.color_map() if cmap is None else cmap
+    os.makedirs(directory, exist_ok=True)
+    mean, std = np.asarray(visual.MEAN, np.float32)[:, None, None], np.asarray(visual.STD, np.float32)[:, None, None]
+    for k, (img, target, pred) in enumerate(samples):
+        rgb = np.clip((img * std + mean) * 255.0, 0, 255).astype(np.uint8).transpose(1, 2, 0)
+        strip = np.concatenate((rgb, cmap[target.astype(np.int64) & 255], cmap[pred.astype(np.int64) & 255]), axis=1)
+        Image.fromarray(strip).save(os.path.join(directory, f"sample_{k}.png"))
 
 
 class SyntheticSegmentation(torch.utils.data.Dataset):
@@ -209,7 +236,7 @@ def main(opts):
     train_loader, val_dst, val_loader_of, real = get_dataset(opts, device, world_size, rank, labels, labels_old)
     model, model_old = build_models(opts, device, classes)
     optimizer = make_optimizer(opts, model)
-    scheduler = PolyLR(optimizer, max_iters=opts.epochs * len(train_loader), power=opts.lr_power)
+    scheduler = make_scheduler(opts, optimizer, len(train_loader))
     model = DistributedDataParallel(model, delay_allreduce=True,
                                     bf16_weights=getattr(opts, "opt_level", "O0") != "O0" and getattr(opts, "bf16_weights", True))
     trainer_state = None
@@ -244,6 +271,10 @@ def main(opts):
         if "trainer_state" in ckpt:                                       # run.py:258-259
             trainer.load_state_dict(ckpt["trainer_state"])
     ckpt_path = f"checkpoints/step/{task_name}_{opts.name}_{opts.step}.pth"
+    sample_ids = None
+    if rank == 0 and opts.sample_num > 0:                                 # run.py:269-273: batches whose first image is kept
+        sample_ids = np.random.choice(len(val_loader), min(opts.sample_num, len(val_loader)), replace=False)
+        logger.info(f"The samples id are {sample_ids}")
     while cur_epoch < opts.epochs and not opts.test:
         epoch_loss = trainer.train(cur_epoch=cur_epoch, optim=optimizer, train_loader=train_loader,
                                    scheduler=scheduler, print_int=opts.print_interval, logger=logger)
@@ -251,7 +282,10 @@ def main(opts):
         if (cur_epoch + 1) % opts.val_interval == 0:                     # run.py:304-316
             logger.info("validate on val set...")
             model.eval()
-            val_loss, val_score, _ = trainer.validate(loader=val_loader, metrics=val_metrics, logger=logger)
+            val_loss, val_score, ret_samples = trainer.validate(loader=val_loader, metrics=val_metrics,
+                                                                ret_samples_ids=sample_ids, logger=logger)
+            if ret_samples:                                               # run.py:343-349, as files: there is no tensorboard here
+                save_sample_strips(f"{opts.logdir}/{task_name}/{opts.name}/samples/epoch_{cur_epoch}", ret_samples)
             logger.info(f"End of Validation {cur_epoch}/{opts.epochs}, Validation Loss={float(val_loss[0]) + float(val_loss[1])},"
                         f" Class Loss={float(val_loss[0])}, Reg Loss={float(val_loss[1])}")
             if rank == 0:

@@ -22,7 +22,8 @@ KD); ILT's encoder term is one HIP operation on the raw maps (``UCD_FUSED_LDE=0`
 EWC / PI / RW (``--method EWC|PI|RW``) add the weight-space penalty of ucd_amd.regularizer between the gradient
 all-reduce and the optimiser (train.py:139-145).  ``--bce``, ``--icarl`` and ``--method LWF-MC`` take the per-class binary cross
 entropy and the combined iCaRL term (train.py:119-124) from their own fused HIP kernel (``fused_seg_bce``, csrc/seg_gather.hip),
-inside the graphs like the others.  Out of scope (raise ``NotImplementedError``): ``--icarl_disjoint`` with a teacher, and any BCE
+inside the graphs like the others.  ``validate`` and ``test`` (train.py:185-375) share one loop: losses and confusion matrix on the
+device, the teacher-side terms evaluated eagerly, ``test`` rendering its outputs through ``ucd_amd.visual``.  Out of scope (raise ``NotImplementedError``): ``--icarl_disjoint`` with a teacher, and any BCE
 run on a CPU device.
 """
 from __future__ import annotations
@@ -430,10 +431,36 @@ class Trainer:
             from .comm import check_mailbox
             check_mailbox(None)
 
-    def validate(self, loader, metrics, ret_samples_ids=None, logger=None):
-        """Evaluation loop (train.py:185-270): class loss + confusion matrix, accumulated on the device.  Under BCE the class loss is
-        the fused BCE on the low-resolution logits.  Validation runs no teacher, so the teacher-side terms (KD, encoder, iCaRL) are
-        not evaluated and its "Reg Loss" stays 0, for every method."""
+    def _eval_terms(self, images, labels, sem, outputs, feats, up):
+        """The reference's unscaled regularisation terms of one evaluation batch (train.py:207-240) as a device scalar: the KD value
+        (``lkd_flag``), the encoder term on the body maps (``lde_flag``), the combined iCaRL term (``icarl_combined``) - the teacher
+        runs eagerly, once, when any of the three is on - and the regulariser's penalty, which needs no teacher."""
+        reg = torch.zeros((), device=self.device)
+        if self.model_old is not None and (self.lde_flag or self.lkd_flag or self.icarl_combined):
+            if self._teacher_w16 is not None:
+                self._teacher_w16.refresh_if_stale()
+            outputs_old, feats_old = self._teacher_eager(images, up)        # no graph replay: validation shapes differ
+            if self.lkd_flag:
+                if outputs is None:
+                    reg = reg + fused_seg_losses(sem, feats_old["sem"], labels, 1 if self.bce else (self.old_classes if self.unce else 1),
+                                                 0.0, 1.0, kd=self.kd_mode, alpha=self.alpha)[2]
+                else:
+                    reg = reg + self.lkd_loss(outputs.float(), outputs_old.float())
+            if self.lde_flag:
+                if self.fused_lde:
+                    reg = reg + fused_attn_mse(_raw(feats, "body"), _raw(feats_old, "body"), 1.0)
+                else:
+                    reg = reg + self.lde_loss(feats["body"].float(), feats_old["body"].float())
+            if self.icarl_combined:
+                reg = reg + self.icarl * fused_seg_bce(sem, feats_old["sem"], labels)[2]
+        if self.regularizer_flag:
+            reg = reg + self.regularizer.penalty()
+        return reg
+
+    def _evaluate(self, loader, metrics, logger, on_batch, want_pred):
+        """The loop ``validate`` and ``test`` share (train.py:185-270 and :271-375): class loss, regularisation terms and confusion
+        matrix accumulated on the device, reduced to rank 0 and divided by ranks and batches.  ``want_pred(i)`` says whether batch
+        ``i`` needs its int64 arg-max map; ``on_batch(i, images, labels, feats, prediction or None)`` sees every batch."""
         metrics.reset()
         model = self.model
         dev = self.device
@@ -442,12 +469,14 @@ class Trainer:
         model.eval()
         n = 0
         with torch.no_grad():
-            for images, labels in loader:
+            for i, (images, labels) in enumerate(loader):
                 images = images.to(dev, dtype=torch.float32)
                 labels = labels.to(dev, dtype=torch.long)
+                pred = None
                 if self.fuse_logit_losses and hasattr(metrics, "update_from_logits"):
                     # low-resolution logits only: loss and confusion matrix come from the fused kernels (the reference
                     # up-samples, copies predictions to the host and histograms there, train.py:236-246)
+                    up, outputs = {"upsample": False}, None
                     with self._autocast():
                         _, feats = model(images, ret_intermediate=False, upsample=False)
                     sem = feats["sem"]
@@ -455,30 +484,93 @@ class Trainer:
                         class_loss += fused_seg_bce(sem, None, labels)[1]
                     else:
                         class_loss += fused_seg_losses(sem, None, labels, self.old_classes if self.unce else 1, 1.0, 0.0)[1]
-                    metrics.update_from_logits(labels, sem)
-                elif self.bce:
-                    # metrics without update_from_logits: the up-sampled logits only feed the arg-max, the loss stays on the kernel
+                    if want_pred(i):
+                        # the arg-max map the histogram is built from: no second pass over the logits
+                        pred = torch.empty(labels.shape, dtype=torch.int64, device=dev)
+                        metrics.update_from_logits(labels, sem, pred=pred)
+                    else:
+                        metrics.update_from_logits(labels, sem)
+                else:
+                    up = {}
                     with self._autocast():
                         outputs, feats = model(images, ret_intermediate=False)
-                    class_loss += fused_seg_bce(feats["sem"], None, labels)[1]
-                    metrics.update(labels, outputs.argmax(dim=1))
-                else:
-                    with self._autocast():
-                        outputs, _ = model(images, ret_intermediate=False)
-                    class_loss += self.criterion(outputs.float(), labels.clone()).mean()
-                    metrics.update(labels, outputs.argmax(dim=1))
+                    sem = feats["sem"]
+                    if self.bce:
+                        # metrics without update_from_logits: the up-sampled logits only feed the arg-max, the loss stays on the kernel
+                        class_loss += fused_seg_bce(sem, None, labels)[1]
+                    else:
+                        class_loss += self.criterion(outputs.float(), labels.clone()).mean()
+                    pred = outputs.argmax(dim=1)
+                    metrics.update(labels, pred)
+                    if self.bce:
+                        outputs = None                      # the teacher-side terms of a BCE run come from the fused kernels
+                if self.model_old is not None or self.regularizer_flag:
+                    reg_loss += self._eval_terms(images, labels, sem, outputs, feats, up)
+                if on_batch is not None:
+                    on_batch(i, images, labels, feats, pred)
                 n += 1
             metrics.synch(dev)
             score = metrics.get_results()
         if dist.is_available() and dist.is_initialized():
             dist.reduce(class_loss, dst=0)
+            dist.reduce(reg_loss, dst=0)
             world = dist.get_world_size()
         else:
             world = 1
         class_loss = class_loss / world / max(n, 1)
+        reg_loss = reg_loss / world / max(n, 1)
         if logger is not None:
             logger.info(f"Validation, Class Loss={class_loss}, Reg Loss={reg_loss} (without scaling)")
-        return (class_loss, reg_loss), score, []
+        return (class_loss, reg_loss), score
+
+    def validate(self, loader, metrics, ret_samples_ids=None, logger=None):
+        """Evaluation loop (train.py:185-270): ``((class_loss, reg_loss), score, samples)``, the losses as device scalars.
+
+        The class loss and the confusion matrix come from the fused kernels on the low-resolution logits (under BCE: the fused BCE).
+        With a teacher and any of ``--loss_kd``, ``--loss_de`` or the combined iCaRL term, the teacher runs eagerly per batch and
+        "Reg Loss" is the mean over batches of the reference's unscaled terms (train.py:228-240): the KD value, the encoder term on
+        the body maps, ``icarl_importance`` times the combined iCaRL term; with a regulariser (EWC / PI / RW) its penalty is added,
+        which needs no teacher.  Without a teacher and a regulariser it is exactly 0.
+
+        ``ret_samples_ids``: batch indices for which ``(images[0] as float32 numpy [3, H, W], labels[0], prediction[0])`` (numpy
+        int64 [H, W] each) is appended to ``samples``; the prediction is the arg-max map the confusion matrix was built from.
+        With ``None`` nothing extra is computed or copied."""
+        ids = None if ret_samples_ids is None else {int(v) for v in ret_samples_ids}
+        samples = []
+
+        def on_batch(i, images, labels, feats, pred):
+            if i in ids:
+                samples.append((images[0].detach().float().cpu().numpy(), labels[0].cpu().numpy(), pred[0].cpu().numpy()))
+
+        losses, score = self._evaluate(loader, metrics, logger, on_batch if ids else None,
+                                       (lambda i: i in ids) if ids else (lambda i: False))
+        return losses, score, samples
+
+    def test(self, loader, metrics, logger=None, sink=None):
+        """The reference's ``Trainer.test`` (train.py:271-375): losses and metrics as in ``validate``, over every image.
+
+        Without ``sink`` the samples are the reference's 4-tuples ``(image float32 [3, H, W], label, prediction, att)`` as numpy
+        arrays, one per image; ``att`` is the attention map of train.py:339-343 (``ucd_amd.visual.attn_energy`` of the raw body map,
+        up-sampled bilinearly to the image) - the whole test set then sits on the host, as in the reference.  With ``sink`` each
+        batch is rendered on the device (``ucd_amd.visual.render``: prediction, colour-coded prediction and labels, de-normalised
+        image, attention map) and ``sink(batch_index, rendered)`` receives the dict of device tensors, ``uint8`` but for ``att``; the
+        sample list stays empty.  The rendered ``pred_u8`` has the bits of the map the confusion matrix is built from."""
+        from . import visual
+        samples = []
+
+        def on_batch(i, images, labels, feats, pred):
+            body = _raw(feats, "body")
+            if sink is not None:
+                sink(i, visual.render(feats["sem"], labels, images, body))
+                return
+            import torch.nn.functional as F
+            att = F.interpolate(visual.attn_energy(body).unsqueeze(1), size=images.shape[-2:], mode="bilinear",
+                                align_corners=False).squeeze(1)
+            img, lab, prd, att = images.detach().float().cpu().numpy(), labels.cpu().numpy(), pred.cpu().numpy(), att.cpu().numpy()
+            samples.extend((img[j], lab[j], prd[j], att[j]) for j in range(img.shape[0]))
+
+        losses, score = self._evaluate(loader, metrics, logger, on_batch, lambda i: sink is None)
+        return losses, score, samples
 
     def state_dict(self):
         return {"regularizer": self.regularizer.state_dict() if self.regularizer_flag else None}
