@@ -735,15 +735,32 @@ typedef struct ucd_conv1x1_desc {
   int stat_rep;
 } ucd_conv1x1_desc;
 
-/* Kernel forms behind ucd_conv1x1 (chosen per launch by the grid; results do not depend on the choice - tests/
- * test_conv1x1_fused_gpu.py::test_every_pipeline_form... holds every form bit-exact on integers): single LDS stage at four workgroups
- * per CU (full grids), double buffer at two (<= 640 tiles, out_mode 4), and since round 4 the loader-wave forms - MFMA waves that
- * only multiply and loader waves that only stage - on 128-row tiles for grids of <= 256 tiles and on 256-row tiles for grids of
- * 257 .. 640 tiles that fit the chip as 256-row tiles.  The environment variable UCD_CONV_PIPE (read once per process: 2x64, lw64,
- * lw256; auto or unset = by the grid) forces one form for every double-buffer-eligible launch; it exists for probes and A/B runs.
- * Any other value makes every ucd_conv1x1 call fail with UCD_EINVAL.
- * Launches of at most 128 (128 x 128) tiles (3 - 6 images per GPU) run on 128 x 64 tiles - same outputs bit for bit, twice the
- * workgroups; UCD_CONV_BN64_TILES (read once per process) sets that bound, 0 = never. */
+/* Kernel forms behind ucd_conv1x1 (results do not depend on the choice - tests/test_conv1x1_fused_gpu.py::
+ * test_every_pipeline_form... holds every form bit-exact on integers).  ucd_conv1x1_plan is the one statement of which form, tile,
+ * grid and LDS a call gets, and ucd_conv1x1 launches with exactly its numbers (rules and the network's shapes: DESIGN.md section
+ * 3.1.1; restated by tests/test_conv1x1_plan_cpu.py).  It reads only M, N, K, taps, stride, out_mode and whether in_scale and
+ * stat_acc are NULL - no operand is dereferenced and no device touched, so it answers on a machine without a GPU - and returns
+ * the code ucd_conv1x1 would return for these fields.
+ * Three environment variables, read once per process, exist for probes and A/B runs: UCD_CONV_PIPE (2x64, lw64 = loader waves on
+ * 128-row tiles, lw256; auto or unset = by the grid) forces one form for every double-buffer-eligible launch - any other value
+ * makes the plan, and with it every ucd_conv1x1 call, fail with UCD_EINVAL; UCD_CONV_BN64_TILES (default 128, 0 = never) is the
+ * largest grid of 128 x 128 tiles that runs on 128 x 64 tiles instead; UCD_CONV_LW64_TILES (default 128, 0 = never) is the largest
+ * grid of 128 x 64 loader-wave tiles that runs on 64-row tiles instead. */
+enum ucd_conv_form {
+  UCD_CONV_SINGLE = 0,  /* conv1x1_kernel, one LDS stage, four workgroups per CU */
+  UCD_CONV_DB = 1,      /* conv1x1_kernel, two LDS stages */
+  UCD_CONV_LW128 = 2,   /* conv_lw_kernel, loader waves on 128-row tiles */
+  UCD_CONV_LW256 = 3,   /* conv_lw_kernel, loader waves on 256-row tiles */
+  UCD_CONV_LW64 = 4     /* conv_lw_kernel, loader waves on 64-row tiles */
+};
+#define UCD_CONV_FORM_NAMES {"single", "2x64", "lw/128", "lw/256", "lw/64"}   /* indexed by enum ucd_conv_form */
+typedef struct ucd_conv1x1_plan_t {
+  int form;                  /* enum ucd_conv_form */
+  int tile_rows, tile_cols;  /* 64 / 128 / 256 rows, 64 / 128 columns */
+  int tiles_m, tiles_n, grid, threads, lds_bytes;
+  int param_off;             /* LDS byte offset of the input-transform constants (0 without an input transform) */
+} ucd_conv1x1_plan_t;
+int ucd_conv1x1_plan(const ucd_conv1x1_desc* desc, ucd_conv1x1_plan_t* plan);
 int ucd_conv1x1_row_tiles(int M);
 int ucd_conv1x1_stat_replicas(int M);   /* replicas of an atomic statistics accumulator for a product of M rows (1 .. 64) */
 size_t ucd_conv1x1_stats_partial_bytes(int M, int C);

@@ -1064,13 +1064,21 @@ def test_projection_block_alias_equals_the_separate_gradient_add(cin, chans, str
 
 # ---- every pipeline form of the GEMM kernel (UCD_CONV_PIPE is read once per process: one child process per form) ----------------------
 _PIPE_CHILD = r"""
-import sys, torch
+import os, sys, torch
 sys.path.insert(0, %(root)r)
 from ucd_amd import hip
 dev = torch.device("cuda:0")
 g = torch.Generator(dev).manual_seed(11)
 def ints(*shape, hi):
     return torch.randint(-hi, hi + 1, shape, device=dev, generator=g).bfloat16()
+def planned(M, K, N, sp, mode):
+    # the form the plan names is the forced one - or what a forced form becomes where its kernel does not exist: every grid here is
+    # double-buffer eligible; those of at most 128 tiles of 128 x 128 run on 64-column tiles, where lw256 is the double buffer and
+    # the 128-row loader waves (lw64) become 64-row tiles unless the epilogue writes per-tile partial rows (out_mode 2)
+    wide = N %% 128 == 0 and -(-M // 128) * (N // 128) > 128
+    want = {"2x64": "2x64", "lw256": "lw/256" if wide else "2x64", "lw64": "lw/128" if wide or mode == 2 else "lw/64"}[os.environ["UCD_CONV_PIPE"]]
+    got = hip.conv1x1_plan(M, N, K, taps=9 if sp else 1, out_mode=mode)
+    assert got["form"] == want and got["tile_cols"] == (128 if wide else 64), (M, K, N, sp, mode, got, want)
 # (M, K, N, conv3 = (H, W, d) or None): ragged row counts, both tile widths, 1x1 and 3x3, grids below and above 256 tiles
 for M, K, N, sp in ((2 * 9 * 11, 128, 64, (9, 11, 1)), (777, 256, 128, None), (2178, 128, 256, (33, 33, 2)), (26136, 256, 256, (33, 33, 1)),
                     (26136, 1024, 256, None), (4 * 33 * 33 - 0, 64, 128, (33, 33, 6))):
@@ -1086,10 +1094,12 @@ for M, K, N, sp in ((2 * 9 * 11, 128, 64, (9, 11, 1)), (777, 256, 128, None), (2
     else:
         ref = a.float() @ w.float().t()
     assert ref.abs().max().item() <= 256
+    planned(M, K, N, sp, 0)
     hip.conv1x1(a, w, y, conv3=sp)
     assert torch.equal(y.float(), ref), ("plain", M, K, N, sp)
     part = hip.conv1x1_stats_partial(M, N, dev)
     y.fill_(float("nan"))
+    planned(M, K, N, sp, 2)
     hip.conv1x1(a, w, y, out_mode=2, partial=part, conv3=sp)
     assert torch.equal(y.float(), ref), ("stats", M, K, N, sp)
     tiles = hip.load().ucd_conv1x1_row_tiles(M)
@@ -1100,6 +1110,7 @@ for M, K, N, sp in ((2 * 9 * 11, 128, 64, (9, 11, 1)), (777, 256, 128, None), (2
         assert torch.equal(p[t, 1], (rows - k).sum(0)) and torch.equal(p[t, 2], ((rows - k) ** 2).sum(0)), ("partials", M, K, N, sp, t)
     res = ints(M, N, hi=3)
     one, zero = torch.ones(N, device=dev), torch.zeros(N, device=dev)
+    planned(M, K, N, sp, 1)
     hip.conv1x1(a, w, y, out_mode=1, out_norm=(zero, one, zero, None, hip.ACT_LEAKY_RELU, 0.5), residual=res, conv3=sp)
     z = ref + res.float()
     assert torch.equal(y.float(), torch.where(z > 0, z, z * 0.5).bfloat16().float()), ("affine", M, K, N, sp)

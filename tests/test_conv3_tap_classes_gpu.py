@@ -48,7 +48,8 @@ def _product(a, w, hw, d, on, accumulate_into=None):
     hip.conv3_tap_classes(int(on))
     before = hip.conv3_tap_stats()[0]
     hip.conv1x1(_rows(a), w.permute(0, 2, 3, 1).reshape(N, 9 * K), _rows(y), conv3=(hw, hw, d), accumulate=accumulate_into is not None)
-    took, _, last = hip.conv3_tap_stats()
+    took, tile_rows, last = hip.conv3_tap_stats()
+    assert tile_rows == hip.conv1x1_plan(a.shape[0] * hw * hw, N, K, taps=9)["tile_rows"], tile_rows     # the launch is the plan's
     if int(on) != 1:
         assert took - before == (1 if on else 0) and last == bool(on), (on, took - before, last)
     return y
@@ -180,6 +181,25 @@ def test_default_mode_leaves_single_wave_64_row_launches_whose_heaviest_tile_kee
             took, rows, last = hip.conv3_tap_stats()
             assert rows == 64 and last == want and took - before == int(want), (d, rows, last, took - before)
             assert torch.equal(on, off)
+    finally:
+        hip.conv3_tap_classes(was)
+
+
+def test_default_choice_of_form_is_the_launch():
+    """No forced form, the ASPP map (33 x 33, d = 12): one shape per tile height the grid rule picks, each confirmed on the plan
+    first.  The launch reports the plan's tile height, and the class-ordered output equals the raster-order one bit for bit."""
+    from ucd_amd import hip
+    dev = torch.device("cuda:0")
+    was = hip.conv3_tap_classes()
+    try:
+        for B, K, N, form, rows, tiles in ((1, 64, 64, "lw/64", 64, 18), (24, 64, 256, "lw/256", 256, 206), (24, 64, 512, "single", 128, 820)):
+            plan = hip.conv1x1_plan(B * 33 * 33, N, K, taps=9)
+            assert (plan["form"], plan["tile_rows"], plan["tiles_m"] * plan["tiles_n"]) == (form, rows, tiles), plan
+            x, w, _ = _operands(B, 33, 12, K, N, dev)
+            off = _product(x, w, 33, 12, 0)
+            on = _product(x, w, 33, 12, 1)
+            assert hip.conv3_tap_stats()[1] == plan["tile_rows"], (form, hip.conv3_tap_stats())
+            assert torch.equal(on, off), (form, (on.float() - off.float()).abs().max().item())
     finally:
         hip.conv3_tap_classes(was)
 

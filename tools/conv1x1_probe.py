@@ -122,8 +122,9 @@ def timing(M, K, N):
     t_bwd = bench(lambda: hip.conv1x1(a, w, y, out_mode=3, out_norm=(v, v, v, v, 1, 0.01), residual=res, partial=part2))
     t_full = bench(lambda: hip.conv1x1(a, w, y, in_norm=(v, v, v, 1, 0.01), out_mode=1, out_norm=(v, v, v, None, 1, 0.01), residual=res))
     byt = 2 * (M * K + M * N + N * K)
-    line = (f"M={M:6d} K={K:4d} N={N:4d}  hipBLASLt {t_lib:7.1f} us | own plain {t_plain:7.1f} us ({byt / t_plain / 1e6:5.2f} TB/s, "
-            f"{2 * M * K * N / t_plain / 1e6:6.1f} TF/s)  +stats {t_stats:6.1f} (finalize {t_fin:4.1f}) pro {t_pro:6.1f} aff {t_aff:6.1f} aff+res {t_affr:6.1f} bwdact {t_bwd:6.1f} pro+aff+res {t_full:6.1f}")
+    form = lambda mode, pro=False: hip.conv1x1_plan(M, N, K, out_mode=mode, in_transform=pro)["form"]
+    line = (f"M={M:6d} K={K:4d} N={N:4d}  hipBLASLt {t_lib:7.1f} us | own plain {t_plain:7.1f} us [{form(0)}] ({byt / t_plain / 1e6:5.2f} TB/s, "
+            f"{2 * M * K * N / t_plain / 1e6:6.1f} TF/s)  +stats {t_stats:6.1f} [{form(2)}] (finalize {t_fin:4.1f}) pro {t_pro:6.1f} [{form(0, True)}] aff {t_aff:6.1f} [{form(1)}] aff+res {t_affr:6.1f} [{form(1)}] bwdact {t_bwd:6.1f} [{form(3)}] pro+aff+res {t_full:6.1f} [{form(1, True)}]")
     if N % 128 == 0 and K % 128 == 0:
         dw = torch.empty(N, K, device=dev, dtype=torch.bfloat16)
         t_w = bench(lambda: hip.conv1x1_wgrad(res, a, dw))

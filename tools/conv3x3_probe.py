@@ -64,8 +64,9 @@ def run(B, K, N, H, W, d):
     t_dlib = bench(lambda: F.conv2d(dy, wt, None, 1, d, d))
     t_down = bench(lambda: own(dy, wt, dx, d))
     gf = 2 * B * H * W * K * N * 9 / 1e9
-    print(f"B={B} {K:4d}->{N:4d} {H}x{W} d={d:2d}  err {err:.1e} dx {errdx:.1e} | fwd MIOpen {t_lib:7.1f} us own {t_own:7.1f} ({gf / t_own * 1e3:6.0f} TF/s) "
-          f"+stats {t_stats:7.1f} affine {t_aff:7.1f} | dgrad MIOpen(fwd solver) {t_dlib:7.1f} own {t_down:7.1f}", flush=True)
+    form = lambda n, k, mode: hip.conv1x1_plan(B * H * W, n, k, taps=9, out_mode=mode)["form"]
+    print(f"B={B} {K:4d}->{N:4d} {H}x{W} d={d:2d}  err {err:.1e} dx {errdx:.1e} | fwd MIOpen {t_lib:7.1f} us own {t_own:7.1f} [{form(N, K, 0)}] ({gf / t_own * 1e3:6.0f} TF/s) "
+          f"+stats {t_stats:7.1f} [{form(N, K, 2)}] affine {t_aff:7.1f} [{form(N, K, 1)}] | dgrad MIOpen(fwd solver) {t_dlib:7.1f} own {t_down:7.1f} [{form(K, N, 0)}]", flush=True)
 
 
 def walked(B, H, W, d, rows, on):
@@ -107,7 +108,8 @@ def run_taps(B, K, N, H, W, d, rounds=7, iters=20):
         hip.conv3_tap_classes(was)
         med = {on: sorted(v)[len(v) // 2] for on, v in t.items()}
         f = {on: walked(B, H, W, d, rows_, path[on]) for on in (False, True)}
-        print(f"B={B:2d} {a.shape[1]:4d}->{n_out:4d} {H}x{W} d={d:2d} {name:5s} rows {rows_:3d} | off {med[False]:7.1f} us (min {min(t[False]):7.1f}) "
+        form = hip.conv1x1_plan(B * H * W, n_out, a.shape[1], taps=9)["form"]
+        print(f"B={B:2d} {a.shape[1]:4d}->{n_out:4d} {H}x{W} d={d:2d} {name:5s} {form} rows {rows_:3d} | off {med[False]:7.1f} us (min {min(t[False]):7.1f}) "
               f"on {med[True]:7.1f} us (min {min(t[True]):7.1f}) time x{med[True] / med[False]:.3f} | steps {f[False]:.3f} -> {f[True]:.3f} "
               f"x{f[True] / f[False]:.3f} | {'class order' if path[True] else 'raster (gate)'} | equal {torch.equal(res[False], res[True])}", flush=True)
 

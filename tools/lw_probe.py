@@ -48,7 +48,8 @@ def run3(B, K, N, H, d):
     t0 = replay_us(lambda: hip.conv1x1(rows(x), w2, rows(y), conv3=(H, H, d)))
     t2 = replay_us(lambda: hip.conv1x1(rows(x), w2, rows(y), conv3=(H, H, d), out_mode=2, partial=part))
     gf = 2 * B * H * H * K * N * 9 / 1e9
-    print(f"3x3 B={B:2d} {K:4d}->{N:4d} {H}^2 d={d:2d} | plain {t0:7.2f} us ({gf / t0 * 1e3:5.0f} TF/s)  +stats {t2:7.2f}", flush=True)
+    f0, f2 = (hip.conv1x1_plan(B * H * H, N, K, taps=9, out_mode=m)["form"] for m in (0, 2))
+    print(f"3x3 B={B:2d} {K:4d}->{N:4d} {H}^2 d={d:2d} | plain {t0:7.2f} us [{f0}] ({gf / t0 * 1e3:5.0f} TF/s)  +stats {t2:7.2f} [{f2}]", flush=True)
 
 
 def run1(M, K, N):
@@ -62,7 +63,8 @@ def run1(M, K, N):
     t2 = replay_us(lambda: hip.conv1x1(a, w, y, out_mode=2, partial=part))
     t1 = replay_us(lambda: hip.conv1x1(a, w, y, out_mode=1, out_norm=(v, v, v, None, 1, 0.01), residual=res))
     gb = 2.0 * (M * K + M * N) / 1e9
-    print(f"1x1 M={M:6d} {K:4d}->{N:4d} | plain {t0:7.2f} us ({gb / t0 * 1e3:5.2f} TB/s)  +stats {t2:7.2f}  affine+res {t1:7.2f}", flush=True)
+    f0, f2, f1 = (hip.conv1x1_plan(M, N, K, out_mode=m)["form"] for m in (0, 2, 1))
+    print(f"1x1 M={M:6d} {K:4d}->{N:4d} | plain {t0:7.2f} us [{f0}] ({gb / t0 * 1e3:5.2f} TB/s)  +stats {t2:7.2f} [{f2}]  affine+res {t1:7.2f} [{f1}]", flush=True)
 
 
 if __name__ == "__main__":

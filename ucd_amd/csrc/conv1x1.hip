@@ -31,7 +31,7 @@
 //   DB, two stages, two workgroups per CU: the fill of step k+1 is issued before the MFMAs of step k and waited for with
 //     a counted vmcnt - for grids that give a CU only one or two workgroups (chosen by the host per launch).
 //   loader waves (round 4, conv_lw_kernel below): the workgroup's MFMA waves never issue a fill and its loader waves never touch the
-//     matrix pipe - three stages, one barrier per K step, one workgroup per CU on 128- or 256-row tiles; chosen by the grid (pick_pipe).
+//     matrix pipe - three stages, one barrier per K step, one workgroup per CU on 128- or 256-row tiles; chosen by the grid (plan_launch).
 // Only the fused input transform (PRO) stages A through registers (it has to touch the values).  Rows past M are clamped,
 // never branched around and never stored.  The output tile goes through LDS (fp32, two 64-row halves) so that global
 // stores, residual loads and the per-channel reductions are row-contiguous 16-byte accesses.  blockIdx -> tile: the
@@ -920,103 +920,149 @@ int pick_wgrad_chunks(int M, int N, int K) {
 }
 
 
-// Launch of a DB-eligible product in the form pick_pipe / ucd_conv1x1 chose: 0 = the DB kernel, 4 / 5 / 7 = loader waves on 128- /
-// 256- / 64-row tiles.
-template <int BN, int OUT, bool CONV3, bool RT = false>
-int launch_db(int pipe, int grid, hipStream_t s, const Args& a, const char* fn) {
-  constexpr size_t kOut = (size_t)64 * (BN + 4) * 4, kRed = (size_t)(kThreads / (BN / 8)) * 2 * BN * 4;
-  auto lds_of = [&](int nst) {
-    size_t l = (size_t)(kBM + BN) * kBK * 2 * nst;
-    if (l < kOut) l = kOut;
-    if (l < kRed) l = kRed;
-    return l;
-  };
-  if (pipe == 5) {                  // loader waves on 256-row workgroup tiles (16 waves, one workgroup per CU): OUT 0 .. 2
-    if constexpr (OUT <= 2 && BN == 128) {
-      Args b = a;
-      b.tiles_m = ceil_div(a.M, 256);
-      const int grid256 = ceil_div(b.tiles_m, 8) * 8 * b.tiles_n;
-      size_t lds = (size_t)(256 + BN) * kBK * 2 * kLwStages;
-      if (lds < kOut) lds = kOut;
-      UCD_TRY_LDS((conv_lw_kernel<256, BN, OUT, CONV3, RT>), (int)lds);
-      conv_lw_kernel<256, BN, OUT, CONV3, RT><<<grid256, 1024, lds, s>>>(b);
-      return 0;
-    }
-    pipe = 0;
+// UCD_CONV_PIPE, UCD_CONV_BN64_TILES, UCD_CONV_LW64_TILES (include/ucd_hip.h), read once per process.  pipe: the form every
+// DB-eligible launch takes (2x64, lw64 - loader waves on 128-row tiles -, lw256), -1 by the grid (unset, empty, auto), -2: the value
+// names no form and plan_launch refuses every call.
+struct Tuning { int pipe, bn64_below, lw64_below; };
+const Tuning& tuning() {
+  static const Tuning t = [] {
+    const char *e = getenv("UCD_CONV_PIPE"), *bn = getenv("UCD_CONV_BN64_TILES"), *lw = getenv("UCD_CONV_LW64_TILES");
+    const int pipe = !e || !*e || !strcmp(e, "auto") ? -1 : !strcmp(e, "2x64") ? UCD_CONV_DB : !strcmp(e, "lw64") ? UCD_CONV_LW128
+                     : !strcmp(e, "lw256") ? UCD_CONV_LW256 : -2;
+    return Tuning{pipe, bn ? atoi(bn) : 128, lw ? atoi(lw) : 128};
+  }();
+  return t;
+}
+
+// rows of the workgroup tile, threads and LDS stages of enum ucd_conv_form
+constexpr struct { int rows, threads, stages; } kForms[] = {{128, 256, 1}, {128, 256, kDbStages}, {128, 512, kLwStages},
+                                                            {256, 1024, kLwStages}, {64, 384, kLwStages}};
+
+// ucd_conv1x1_plan: the form, tile, grid and LDS of a product, from its shape and mode alone (measured:
+// tools/conv3x3_probe.py, tools/conv1x1_probe.py, profiles/r04_conv_pipe_probe.txt).
+int plan_launch(const ucd_conv1x1_desc* d, ucd_conv1x1_plan_t* p, const char* fn) {
+  const Tuning& t = tuning();
+  UCD_REQUIRE(t.pipe != -2, UCD_EINVAL, "%s: UCD_CONV_PIPE=%s names no form (accepted: auto, 2x64, lw64, lw256)", fn,
+              getenv("UCD_CONV_PIPE"));
+  const bool conv3 = d->taps == 9, pro = d->in_scale != nullptr;
+  const int out = d->out_mode;
+  UCD_REQUIRE(d->M > 0 && d->N > 0 && d->K > 0 && (d->taps == 0 || d->taps == 1 || conv3) && out >= 0 && out <= 4, UCD_EINVAL,
+              "%s: empty product, taps not 1 or 9, or unknown out_mode", fn);
+  UCD_REQUIRE(d->K % kBK == 0 && d->N % 64 == 0, UCD_EUNSUPPORTED, "%s: K (%d) and N (%d) must be multiples of 64", fn, d->K, d->N);
+  UCD_REQUIRE(!(pro && (conv3 || d->stride > 1)) && !(out == 4 && (conv3 || pro)) && !(d->stride > 1 && out > 2), UCD_EINVAL,
+              "%s: no input transform on a 3x3 / strided product, out_mode 4 on plain 1x1 products only, strided products with out_mode <= 2",
+              fn);
+  // few row tiles (3 - 6 images per GPU, the multi-GPU split): 64-column tiles double the workgroups of a launch that would leave
+  // more than half of the CUs without one - a 52-workgroup 3x3 launch is bound by the 36 x 16 MFMAs of ONE workgroup per CU, not by
+  // its fills (a fourth LDS stage changed nothing: 18.4 vs 18.4 us).  3 images: 3x3 256 -> 256 18.6 -> 14.0 us, ASPP 102.8 -> 81.4,
+  // 1x1 2048 -> 256 15.5 -> 11.1; grids of 129 .. 256 tiles measured level or slower (256 -> 1024: 6.4 -> 7.2).  Same products bit
+  // for bit, per-tile statistics equal to fp32 rounding (tests/test_conv1x1_fused_gpu.py).
+  const int t128 = ceil_div(d->M, kBM);
+  const int BN = (d->N % 128 == 0 && (long long)t128 * (d->N / 128) > t.bn64_below) ? 128 : 64;
+  const int tiles_n = d->N / BN;
+  const long long wg128 = (long long)t128 * tiles_n, wg256 = (long long)ceil_div(d->M, 256) * tiles_n;
+  // 3x3 with a grid that leaves a CU one or two workgroups (N = 256 at 33^2: 410; tools/conv3x3_probe.py): the
+  // double-buffered form (256->256 50.6 -> 47.3 us, the ASPP branches 338-356 -> 308-314); fuller grids are faster with
+  // the single stage and four workgroups per CU (512->512 170 vs 179, 128->128 at 65^2 48.7 vs 52.6)
+  // (the 1x1 products of such grids gain too: 1024 -> 256 23.3 -> 21.7 us, with statistics 25.1 -> 23.6)
+  // out_mode 4 keeps three side tiles in registers next to the accumulators: 168 VGPRs + 96 B of scratch in the single-stage
+  // form at three workgroups per CU, 194 VGPRs and no scratch in the double-buffered form (two per CU) - it always takes that
+  const bool db = ((conv3 || !pro) && wg128 <= 640) || (out == 4 && BN == 128);
+  int form = UCD_CONV_SINGLE;
+  if (db && !pro) {
+    const int nk64 = (conv3 ? 9 : 1) * (d->K / kBK);
+    // grids that give a CU at most one workgroup (3 - 6 images per GPU, the multi-GPU split): the loader-wave form - 3x3 256 -> 256 at
+    // 3 images 26.8 -> 17.3 us, 512 -> 512 49 -> 30, the ASPP branches 169 -> 100, 1x1 1024 -> 256 12.2 -> 9.5 (profiles/r04_conv_pipe_probe.txt)
+    // 257 .. 640 128-row tiles that fit the chip as 256-row tiles (N = 256 at 33 x 33 and 24 images: 410 -> 206 workgroups): the
+    // loader-wave form on 256-row tiles - 3x3 256 -> 256 + statistics 44.1 -> 38.0 us, the ASPP branches 238 -> 214, 1x1 2048 -> 256
+    // 33.4 -> 31.6; two rounds of it (512 -> 512: 412 workgroups) measured slower (139 vs 132), the four-stage forms slower as well
+    form = t.pipe >= 0 ? t.pipe
+           : wg128 <= 256 && nk64 >= 4 ? UCD_CONV_LW128
+           : BN == 128 && out <= 2 && wg256 <= 256 && nk64 >= 4 ? UCD_CONV_LW256 : UCD_CONV_DB;
+    // grids of <= UCD_CONV_LW64_TILES (128) tiles of 128 x 64 (3 images per GPU): 64-row tiles on twice as many CUs - statistics / link
+    // sums only through the atomic accumulators (64-row tiles have no rows in the per-tile partial buffers)
+    if (form == UCD_CONV_LW128 && BN == 64 && wg128 <= t.lw64_below && (out < 2 || d->stat_acc)) form = UCD_CONV_LW64;
+    // 256-row tiles exist with 128 columns and out_mode 0 .. 2 only (16 waves, one workgroup per CU): a forced lw256 elsewhere is the DB form
+    if (form == UCD_CONV_LW256 && (BN == 64 || out > 2)) form = UCD_CONV_DB;
   }
-  if (pipe == 7) {                  // round 6: loader waves on 64-row tiles (2 MFMA + 4 loader waves), grids of <= 128 tiles of 128 x 64
-    if constexpr (BN == 64) {
-      Args b = a;
-      b.tiles_m = ceil_div(a.M, 64);
-      const int grid64 = ceil_div(b.tiles_m, 8) * 8 * b.tiles_n;
-      const size_t lds64 = (size_t)(64 + BN) * kBK * 2 * kLwStages;
-      conv_lw_kernel<64, BN, OUT, CONV3, RT><<<grid64, 384, lds64, s>>>(b);
-      return 0;
-    }
-    pipe = 4;
+  const int rows = kForms[form].rows;
+  // operand stages, the fp32 output tile (two 64-row halves) or the statistics reduction scratch, whichever is largest
+  size_t lds = std::max({(size_t)(rows + BN) * kBK * 2 * kForms[form].stages, (size_t)64 * (BN + 4) * 4,
+                         (size_t)(kThreads / (BN / 8)) * 2 * BN * 4});
+  p->param_off = 0;
+  if (pro) {
+    p->param_off = (int)align_up(lds, 16);
+    lds = p->param_off + (size_t)3 * d->K * sizeof(float);
   }
-  if (pipe == 4) {                  // loader waves, three 32 KB stages, one workgroup (8 waves) per CU: every epilogue fits
-    const size_t lds = lds_of(kLwStages);
-    UCD_TRY_LDS((conv_lw_kernel<128, BN, OUT, CONV3, RT>), (int)lds);
-    conv_lw_kernel<128, BN, OUT, CONV3, RT><<<grid, 2 * kThreads, lds, s>>>(a);
+  UCD_REQUIRE(form != UCD_CONV_SINGLE || lds <= 64 * 1024, UCD_EUNSUPPORTED, "%s: K = %d is too wide for the fused input transform", fn,
+              d->K);
+  p->form = form; p->tile_rows = rows; p->tile_cols = BN;
+  p->tiles_m = ceil_div(d->M, rows); p->tiles_n = tiles_n;
+  p->grid = ceil_div(p->tiles_m, 8) * 8 * tiles_n;
+  p->threads = kForms[form].threads; p->lds_bytes = (int)lds;
+  return 0;
+}
+
+// The instantiation of a plan's form for one (BN, out_mode, 3x3, class-ordered rows, input transform), launched with the plan's numbers.
+template <int BN, int OUT, bool CONV3, bool RT = false, bool PRO = false>
+int launch_form(const ucd_conv1x1_plan_t& p, hipStream_t s, const Args& a, const char* fn) {
+  const int lds = p.lds_bytes;
+  if (p.form == UCD_CONV_SINGLE) {
+    conv1x1_kernel<BN, PRO, OUT, CONV3, false, RT><<<p.grid, p.threads, lds, s>>>(a);
     return 0;
   }
-  conv1x1_kernel<BN, false, OUT, CONV3, true, RT><<<grid, kThreads, lds_of(kDbStages), s>>>(a);
-  return 0;
-}
-
-template <int BN, bool CONV3>
-int launch_db_out(int out_mode, int pipe, int grid, hipStream_t s, const Args& a, const char* fn) {
-  switch (out_mode) {
-    case 0:
-      if constexpr (CONV3) {
-        if (a.perm) return launch_db<BN, 0, true, true>(pipe, grid, s, a, fn);   // class-ordered rows (tap_plan_get)
-      }
-      return launch_db<BN, 0, CONV3>(pipe, grid, s, a, fn);
-    case 1: return launch_db<BN, 1, CONV3>(pipe, grid, s, a, fn);
-    case 2: return launch_db<BN, 2, CONV3>(pipe, grid, s, a, fn);
-    case 3: return launch_db<BN, 3, CONV3>(pipe, grid, s, a, fn);
-    default:
-      if constexpr (CONV3) {
-        set_error("%s: out_mode 4 belongs to the 1x1 products", fn);
-        return UCD_EINVAL;
-      } else {
-        return launch_db<BN, 4, false>(pipe, grid, s, a, fn);
-      }
+  if constexpr (!PRO) {
+    switch (p.form) {
+      case UCD_CONV_DB:
+        conv1x1_kernel<BN, false, OUT, CONV3, true, RT><<<p.grid, p.threads, lds, s>>>(a);
+        return 0;
+      case UCD_CONV_LW128:      // three 32 KB stages, one workgroup (8 waves) per CU: every epilogue fits
+        UCD_TRY_LDS((conv_lw_kernel<128, BN, OUT, CONV3, RT>), lds);
+        conv_lw_kernel<128, BN, OUT, CONV3, RT><<<p.grid, p.threads, lds, s>>>(a);
+        return 0;
+      case UCD_CONV_LW256:
+        if constexpr (OUT <= 2 && BN == 128) {
+          UCD_TRY_LDS((conv_lw_kernel<256, BN, OUT, CONV3, RT>), lds);
+          conv_lw_kernel<256, BN, OUT, CONV3, RT><<<p.grid, p.threads, lds, s>>>(a);
+          return 0;
+        }
+        break;
+      case UCD_CONV_LW64:       // round 6: 2 MFMA + 4 loader waves
+        if constexpr (BN == 64) {
+          conv_lw_kernel<64, BN, OUT, CONV3, RT><<<p.grid, p.threads, lds, s>>>(a);
+          return 0;
+        }
+        break;
+    }
   }
+  static const char* const names[] = UCD_CONV_FORM_NAMES;
+  set_error("%s: no %s kernel for %d-column tiles and out_mode %d", fn, names[p.form], BN, OUT);
+  return UCD_EINVAL;
 }
 
-// UCD_CONV_PIPE (read once per process; probes / A-B): the form every DB-eligible launch takes - 2x64 (the DB kernel, 0), lw64 (4) or
-// lw256 (5); unset, empty or auto: by the grid (-1).  -2: the value names no form, and ucd_conv1x1 refuses every call.
-int forced_pipe() {
-  static const int forced = [] {
-    const char* e = getenv("UCD_CONV_PIPE");
-    return !e || !*e || !strcmp(e, "auto") ? -1 : !strcmp(e, "2x64") ? 0 : !strcmp(e, "lw64") ? 4 : !strcmp(e, "lw256") ? 5 : -2;
-  }();
-  return forced;
-}
-
-// Pipeline of a DB launch: forced_pipe(), else by the grid (measured: tools/conv3x3_probe.py, tools/conv1x1_probe.py,
-// profiles/r04_conv_pipe_probe.txt).
-int pick_pipe(int M, int tiles_n, int BN, int nk64, int out_mode) {
-  if (forced_pipe() >= 0) return forced_pipe();
-  const long long wg128 = (long long)ceil_div(M, 128) * tiles_n, wg256 = (long long)ceil_div(M, 256) * tiles_n;
-  // grids that give a CU at most one workgroup (3 - 6 images per GPU, the multi-GPU split): the loader-wave form - 3x3 256 -> 256 at
-  // 3 images 26.8 -> 17.3 us, 512 -> 512 49 -> 30, the ASPP branches 169 -> 100, 1x1 1024 -> 256 12.2 -> 9.5 (profiles/r04_conv_pipe_probe.txt)
-  if (wg128 <= 256 && nk64 >= 4) return 4;
-  // 257 .. 640 128-row tiles that fit the chip as 256-row tiles (N = 256 at 33 x 33 and 24 images: 410 -> 206 workgroups): the
-  // loader-wave form on 256-row tiles - 3x3 256 -> 256 + statistics 44.1 -> 38.0 us, the ASPP branches 238 -> 214, 1x1 2048 -> 256
-  // 33.4 -> 31.6; two rounds of it (512 -> 512: 412 workgroups) measured slower (139 vs 132), the four-stage forms slower as well
-  if (BN == 128 && out_mode <= 2 && wg256 <= 256 && nk64 >= 4) return 5;
-  return 0;
-}
-
-// Rows of the workgroup tile that launch_db / the single-stage launch give a product (the tile height of its tap masks).
-int tile_rows_of(bool db_launch, int pipe, int BN, int out_mode) {
-  if (!db_launch) return kBM;
-  if (pipe == 5 && BN == 128 && out_mode <= 2) return 256;
-  if (pipe == 7 && BN == 64) return 64;
-  return kBM;
+template <int BN>
+int launch_plan(const ucd_conv1x1_plan_t& p, int out_mode, bool conv3, bool pro, hipStream_t s, const Args& a, const char* fn) {
+  UCD_REQUIRE(!(conv3 && out_mode == 4), UCD_EINVAL, "%s: out_mode 4 belongs to the 1x1 products", fn);
+  UCD_REQUIRE(!(pro && (conv3 || out_mode == 4)), UCD_EINVAL, "%s: no input transform on a 3x3 product or with out_mode 4", fn);
+  if (conv3) switch (out_mode) {
+    case 0: return a.perm ? launch_form<BN, 0, true, true>(p, s, a, fn) : launch_form<BN, 0, true>(p, s, a, fn);   // class-ordered rows (tap_plan_get)
+    case 1: return launch_form<BN, 1, true>(p, s, a, fn);
+    case 2: return launch_form<BN, 2, true>(p, s, a, fn);
+    default: return launch_form<BN, 3, true>(p, s, a, fn);
+  }
+  if (pro) switch (out_mode) {
+    case 0: return launch_form<BN, 0, false, false, true>(p, s, a, fn);
+    case 1: return launch_form<BN, 1, false, false, true>(p, s, a, fn);
+    case 2: return launch_form<BN, 2, false, false, true>(p, s, a, fn);
+    default: return launch_form<BN, 3, false, false, true>(p, s, a, fn);
+  }
+  switch (out_mode) {
+    case 0: return launch_form<BN, 0, false>(p, s, a, fn);
+    case 1: return launch_form<BN, 1, false>(p, s, a, fn);
+    case 2: return launch_form<BN, 2, false>(p, s, a, fn);
+    case 3: return launch_form<BN, 3, false>(p, s, a, fn);
+    default: return launch_form<BN, 4, false>(p, s, a, fn);
+  }
 }
 
 // UCD_CONV3_TAP_CLASSES (read at the first use; ucd_conv3_tap_classes sets it inside a process): the stand-alone dilated 3x3
@@ -1109,8 +1155,6 @@ int ucd_conv1x1_stat_replicas(int M) {
 
 int ucd_conv1x1(const ucd_conv1x1_desc* d, ucd_stream_t stream) {
   static const char* fn = "ucd_conv1x1";
-  UCD_REQUIRE(forced_pipe() != -2, UCD_EINVAL, "%s: UCD_CONV_PIPE=%s names no form (accepted: auto, 2x64, lw64, lw256)", fn,
-              getenv("UCD_CONV_PIPE"));
   UCD_REQUIRE(d && d->a && d->w && d->y, UCD_EINVAL, "%s: NULL operand", fn);
   UCD_REQUIRE(d->M > 0 && d->N > 0 && d->K > 0, UCD_EINVAL, "%s: empty product", fn);
   UCD_REQUIRE(d->K % kBK == 0 && d->N % 64 == 0, UCD_EUNSUPPORTED, "%s: K (%d) and N (%d) must be multiples of 64", fn, d->K, d->N);
@@ -1166,39 +1210,13 @@ int ucd_conv1x1(const ucd_conv1x1_desc* d, ucd_stream_t stream) {
   UCD_REQUIRE((a.stat_rep & (a.stat_rep - 1)) == 0, UCD_EINVAL, "%s: stat_rep must be a power of two", fn);
   UCD_REQUIRE(!a.stat_acc || d->out_mode != 2 || (d->stat_shift && aligned16(d->stat_shift)), UCD_EINVAL,
               "%s: out_mode 2 with stat_acc needs a 16-byte aligned stat_shift", fn);
-  // few row tiles (3 - 6 images per GPU, the multi-GPU split): 64-column tiles double the workgroups of a launch that would leave
-  // more than half of the CUs without one - a 52-workgroup 3x3 launch is bound by the 36 x 16 MFMAs of ONE workgroup per CU, not by
-  // its fills (a fourth LDS stage changed nothing: 18.4 vs 18.4 us).  3 images: 3x3 256 -> 256 18.6 -> 14.0 us, ASPP 102.8 -> 81.4,
-  // 1x1 2048 -> 256 15.5 -> 11.1; grids of 129 .. 256 tiles measured level or slower (256 -> 1024: 6.4 -> 7.2).  Same products bit
-  // for bit, per-tile statistics equal to fp32 rounding (tests/test_conv1x1_fused_gpu.py).  UCD_CONV_BN64_TILES overrides (0: off).
-  static const int bn64_below = getenv("UCD_CONV_BN64_TILES") ? atoi(getenv("UCD_CONV_BN64_TILES")) : 128;
-  const int BN = (d->N % 128 == 0 && (long long)ceil_div(d->M, kBM) * (d->N / 128) > bn64_below) ? 128 : 64;
-  a.tiles_m = ceil_div(d->M, kBM); a.tiles_n = d->N / BN;
-  const int grid = ceil_div(a.tiles_m, 8) * 8 * a.tiles_n;
-  // 3x3 with a grid that leaves a CU one or two workgroups (N = 256 at 33^2: 410; tools/conv3x3_probe.py): the
-  // double-buffered form (256->256 50.6 -> 47.3 us, the ASPP branches 338-356 -> 308-314); fuller grids are faster with
-  // the single stage and four workgroups per CU (512->512 170 vs 179, 128->128 at 65^2 48.7 vs 52.6)
-  // (the 1x1 products of such grids gain too: 1024 -> 256 23.3 -> 21.7 us, with statistics 25.1 -> 23.6)
-  // out_mode 4 keeps three side tiles in registers next to the accumulators: 168 VGPRs + 96 B of scratch in the single-stage
-  // form at three workgroups per CU, 194 VGPRs and no scratch in the double-buffered form (two per CU) - it always takes that
+  ucd_conv1x1_plan_t plan;
+  if (int rc = plan_launch(d, &plan, fn)) return rc;
+  a.tiles_m = plan.tiles_m; a.tiles_n = plan.tiles_n; a.param_off = plan.param_off;
   hipStream_t s = (hipStream_t)stream;
-  const bool db = ((conv3 || !d->in_scale) && (long long)ceil_div(d->M, kBM) * (d->N / BN) <= 640) || (d->out_mode == 4 && BN == 128);
-  const size_t lds_main = (size_t)(kBM + BN) * 128 * (db ? 2 : 1), lds_out = (size_t)64 * (BN + 4) * 4;
-  size_t lds = lds_main > lds_out ? lds_main : lds_out;
-  const size_t lds_red = (size_t)(kThreads / (BN / 8)) * 2 * BN * 4;       // statistics reduction scratch
-  if (lds_red > lds) lds = lds_red;
-  const bool pro = d->in_scale != nullptr;
-  a.param_off = (int)align_up(lds, 16);
-  if (pro) lds = a.param_off + (size_t)3 * d->K * sizeof(float);
-  UCD_REQUIRE(lds <= 64 * 1024, UCD_EUNSUPPORTED, "%s: K = %d is too wide for the fused input transform", fn, d->K);
-  int pipe = db ? pick_pipe(d->M, a.tiles_n, BN, (conv3 ? 9 : 1) * (d->K / 64), d->out_mode) : 0;
-  // grids of <= UCD_CONV_LW64_TILES (128) tiles of 128 x 64 (3 images per GPU): 64-row tiles on twice as many CUs (conv_lw_kernel,
-  // BM = 64) - statistics / link sums only through the atomic accumulators (64-row tiles have no rows in the per-tile partial buffers)
-  static const int lw64_below = getenv("UCD_CONV_LW64_TILES") ? atoi(getenv("UCD_CONV_LW64_TILES")) : 128;
-  if (db && !pro && pipe == 4 && BN == 64 && (long long)a.tiles_m * a.tiles_n <= lw64_below && (d->out_mode < 2 || a.stat_acc)) pipe = 7;
   // stand-alone dilated 3x3 products (the ASPP branches, forward and input gradient): class-ordered rows and per-tile tap masks
   if (conv3 && stride == 1 && d->dilation > 1 && d->out_mode == 0) {
-    const int mode = tap_classes_mode(), rows = tile_rows_of(db && !pro, pipe, BN, d->out_mode);
+    const int mode = tap_classes_mode(), rows = plan.tile_rows;
     const TapPlan* tp = mode ? tap_plan_get(d->M / (d->H * d->W), d->H, d->W, d->dilation, rows, s) : nullptr;
     // Gate (mode 1): a launch of at most one 64-row workgroup per CU lasts as long as its heaviest tile; where the class order leaves
     // that tile its taps, the row table only adds its dependent read in front of the first fill - 3 images, d = 6 / 12: 72 -> 75 us
@@ -1206,7 +1224,7 @@ int ucd_conv1x1(const ucd_conv1x1_desc* d, ucd_stream_t stream) {
     if (tp && mode == 1 && rows == 64 && tp->max_on >= tp->max_off) {
       int dev = 0, cus = 0;
       if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess &&
-          (long long)ceil_div(d->M, rows) * a.tiles_n <= cus)
+          (long long)plan.tiles_m * plan.tiles_n <= cus)
         tp = nullptr;
     }
     if (tp) { a.perm = tp->perm; a.masks = tp->masks; }
@@ -1214,42 +1232,17 @@ int ucd_conv1x1(const ucd_conv1x1_desc* d, ucd_stream_t stream) {
     g_tap_launches += tp != nullptr;
     g_tap_last_rows = rows; g_tap_last_rt = tp != nullptr;
   }
-  if (db && !pro) {
-    int rc;
-    if (conv3) rc = BN == 128 ? launch_db_out<128, true>(d->out_mode, pipe, grid, s, a, fn) : launch_db_out<64, true>(d->out_mode, pipe, grid, s, a, fn);
-    else rc = BN == 128 ? launch_db_out<128, false>(d->out_mode, pipe, grid, s, a, fn) : launch_db_out<64, false>(d->out_mode, pipe, grid, s, a, fn);
-    if (rc) return rc;
-    return check_launch(fn);
-  }
-#define UCD_C1_OUT(BNV, PROV)                                                   \
-  switch (d->out_mode) {                                                        \
-    case 0: conv1x1_kernel<BNV, PROV, 0><<<grid, kThreads, lds, s>>>(a); break; \
-    case 1: conv1x1_kernel<BNV, PROV, 1><<<grid, kThreads, lds, s>>>(a); break; \
-    case 2: conv1x1_kernel<BNV, PROV, 2><<<grid, kThreads, lds, s>>>(a); break; \
-    case 3: conv1x1_kernel<BNV, PROV, 3><<<grid, kThreads, lds, s>>>(a); break; \
-    default: conv1x1_kernel<BNV, false, 4><<<grid, kThreads, lds, s>>>(a); break; \
-  }
-#define UCD_C3_OUT(BNV)                                                                        \
-  switch (d->out_mode) {                                                                       \
-    case 0:                                                                                    \
-      if (a.perm) conv1x1_kernel<BNV, false, 0, true, false, true><<<grid, kThreads, lds, s>>>(a); \
-      else conv1x1_kernel<BNV, false, 0, true, false><<<grid, kThreads, lds, s>>>(a);           \
-      break;                                                                                   \
-    case 1: conv1x1_kernel<BNV, false, 1, true, false><<<grid, kThreads, lds, s>>>(a); break;  \
-    case 2: conv1x1_kernel<BNV, false, 2, true, false><<<grid, kThreads, lds, s>>>(a); break;  \
-    case 4: UCD_REQUIRE(false, UCD_EINVAL, "%s: out_mode 4 belongs to the 1x1 products", fn);  \
-    default: conv1x1_kernel<BNV, false, 3, true, false><<<grid, kThreads, lds, s>>>(a); break; \
-  }
-  if (conv3) {
-    if (BN == 128) { UCD_C3_OUT(128) } else { UCD_C3_OUT(64) }
-  } else if (BN == 128) {
-    if (pro) { UCD_C1_OUT(128, true) } else { UCD_C1_OUT(128, false) }
-  } else {
-    if (pro) { UCD_C1_OUT(64, true) } else { UCD_C1_OUT(64, false) }
-  }
-#undef UCD_C3_OUT
-#undef UCD_C1_OUT
+  const bool pro = d->in_scale != nullptr;
+  if (int rc = plan.tile_cols == 128 ? launch_plan<128>(plan, d->out_mode, conv3, pro, s, a, fn)
+                                     : launch_plan<64>(plan, d->out_mode, conv3, pro, s, a, fn))
+    return rc;
   return check_launch(fn);
+}
+
+int ucd_conv1x1_plan(const ucd_conv1x1_desc* d, ucd_conv1x1_plan_t* plan) {
+  static const char* fn = "ucd_conv1x1_plan";
+  UCD_REQUIRE(d && plan, UCD_EINVAL, "%s: NULL argument", fn);
+  return plan_launch(d, plan, fn);
 }
 
 int ucd_conv3_tap_classes(int mode) {

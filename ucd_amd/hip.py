@@ -28,6 +28,8 @@ EUNSUPPORTED = -4                         # enum ucd_status: a shape outside wha
 SEG_FORMS = {1: "pk<16,8>", 2: "pk<20,4>", 3: "pk<12,12>", 4: "reg<24,16>", 5: "reg<24,24>", 6: "wide/fixed", 7: "wide/f32"}
 # enum ucd_pixcon_path (include/ucd_hip.h): the kernels ucd_pixcon_loss_plan names
 PIXCON_PATHS = {1: "f32", 2: "f32/wide", 3: "f16/planned", 4: "f16/split"}
+# enum ucd_conv_form / UCD_CONV_FORM_NAMES (include/ucd_hip.h): the kernel form ucd_conv1x1_plan names
+CONV_FORMS = ("single", "2x64", "lw/128", "lw/256", "lw/64")
 PIXCON_PRECISION = {"f32": PIXCON_F32, "fp32": PIXCON_F32, "f16": PIXCON_F16, "fp16": PIXCON_F16,
                     "f16_split": PIXCON_F16_SPLIT}
 
@@ -56,6 +58,12 @@ class Conv1x1Desc(C.Structure):
                 ("taps", C.c_int), ("H", C.c_int), ("W", C.c_int), ("dilation", C.c_int),
                 ("side2", C.c_void_p), ("ld2", C.c_int), ("stride", C.c_int),
                 ("stat_acc", C.c_void_p), ("stat_shift", C.c_void_p), ("stat_acc2", C.c_void_p), ("stat_rep", C.c_int)]
+
+
+class Conv1x1Plan(C.Structure):
+    """Mirror of ``ucd_conv1x1_plan_t`` (include/ucd_hip.h)."""
+    _fields_ = [(n, C.c_int) for n in ("form", "tile_rows", "tile_cols", "tiles_m", "tiles_n", "grid", "threads", "lds_bytes",
+                                       "param_off")]
 
 
 _p, _i, _f, _z = C.c_void_p, C.c_int, C.c_float, C.c_size_t
@@ -117,6 +125,7 @@ SIGNATURES = {
     "ucd_conv1x1_row_tiles": (_i, [_i]),
     "ucd_conv1x1_stats_partial_bytes": (_z, [_i, _i]),
     "ucd_conv1x1": (_i, [C.POINTER(Conv1x1Desc), _p]),
+    "ucd_conv1x1_plan": (_i, [C.POINTER(Conv1x1Desc), C.POINTER(Conv1x1Plan)]),
     "ucd_conv1x1_stats_finalize": (_i, [_p, _i, _i, _p, _p, _p, _f, _f, _p, _p, _i, _p]),
     "ucd_conv3_tap_plan": (_i, [_i, _i, _i, _i, _i, _p, _p, _p]),
     "ucd_conv3_tap_classes": (_i, [_i]),
@@ -613,6 +622,25 @@ def attmap(x, ld_x, y, ld_y, B, HW, Cc):
 # ---------------------------------------------------------------------------------------------
 # 1x1 convolutions as fused GEMMs (csrc/conv1x1.hip)
 # ---------------------------------------------------------------------------------------------
+def _conv1x1_plan(d):
+    p = Conv1x1Plan()
+    _check(load().ucd_conv1x1_plan(C.byref(d), C.byref(p)), "ucd_conv1x1_plan")
+    out = {n: getattr(p, n) for n, _ in Conv1x1Plan._fields_}
+    out["form"] = CONV_FORMS[p.form]
+    return out
+
+
+def conv1x1_plan(M, N, K, taps=1, out_mode=0, stride=1, in_transform=False, stat_acc=False):
+    """Host-only ``ucd_conv1x1_plan``: the kernel form, tile, grid, threads and LDS bytes ``ucd_conv1x1`` gives a product of this
+    shape and mode (``in_transform`` / ``stat_acc``: whether the call passes ``in_norm`` / ``stat_acc``).  Returns a dict of the
+    fields of ``ucd_conv1x1_plan_t`` with ``form`` as a name of :data:`CONV_FORMS`; raises what the product call would raise for
+    these arguments.  Needs no GPU."""
+    d = Conv1x1Desc()
+    d.M, d.N, d.K, d.taps, d.out_mode, d.stride = int(M), int(N), int(K), int(taps), int(out_mode), int(stride)
+    d.in_scale, d.stat_acc = (16 if in_transform else None), (16 if stat_acc else None)   # only tested against NULL
+    return _conv1x1_plan(d)
+
+
 def conv1x1(a, w, y, in_norm=None, out_mode=0, out_norm=None, residual=None, partial=None, accumulate=False, conv3=None,
             side2=None, strided=None, stat_acc=None, stat_shift=None, stat_acc2=None, stat_rep=1):
     """y[M, N] = out(in(a)[M, K] . w[N, K]^T).  ``in_norm`` = (mean, scale, shift, act, slope) of the producer's ABN or None;
@@ -652,9 +680,11 @@ def conv1x1(a, w, y, in_norm=None, out_mode=0, out_norm=None, residual=None, par
     # shapes), flop for the 3x3 implicit GEMM (9 K deep: MFMA-bound)
     work = 2 * M * 9 * K * N if conv3 is not None else 2 * (M * K + M * N * (1 + (residual is not None) + bool(accumulate)
                                                                                  + (side2 is not None)))
-    # bytes staged through LDS by the tiled kernel: every (BM x BN) tile pulls (BM + BN) K values per tap; BN as the library picks it
-    bn = 128 if (N % 128 == 0 and ((M + 127) // 128) * (N // 128) > 128) else 64
-    staged = 2 * M * N * K * (9 if conv3 is not None else 1) * (1.0 / 128 + 1.0 / bn)
+    # bytes staged through LDS by the tiled kernel: every (BM x BN) tile pulls (BM + BN) K values per tap, BN from the plan; the row
+    # term stays 1 / 128 although the 64- and 256-row forms stage W twice / half as often (kept: the pass prints what it printed)
+    staged = None
+    if _timing is not None:
+        staged = 2 * M * N * K * (9 if conv3 is not None else 1) * (1.0 / 128 + 1.0 / _conv1x1_plan(d)["tile_cols"])
     with _timed("ucd_conv3x3" if conv3 is not None else "ucd_conv1x1", work, None if conv3 is not None else 2 * M * K * N, staged):
         _check(lib.ucd_conv1x1(C.byref(d), stream()), "ucd_conv1x1")
     return y
