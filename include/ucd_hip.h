@@ -602,6 +602,37 @@ int ucd_seg_bce(const float* sem_s, int ld_s, const float* sem_t, int ld_t, cons
 int ucd_seg_confusion(const float* sem, int ld_s, const int64_t* labels, int B, int H, int W, int h, int w, int Ctot,
                       int n_classes, int64_t* hist, int64_t* pred, ucd_stream_t stream);
 
+/* Evaluation with test-time views: the image was run at V scales, some of them mirrored, and the per-view class distributions are
+ * fused into one prediction per full-resolution pixel, counted into the confusion matrix of the call above - one pass, no
+ * full-resolution logits or soft-max maps.
+ *   sem[v]   fp32 rows [B*h[v]*w[v], ld[v] >= Ctot]: view v's low-resolution logits, laid out as the call above takes them
+ *   flip[v]  != 0: the view was computed from the horizontally mirrored image; its value at output pixel (Y, X) is the view's
+ *            bilinear sample at (Y, W - 1 - X)
+ *   1 <= V <= 16, Ctot <= 255, H >= h[v] and W >= w[v] for every view (any up-sampling factor >= 1)
+ * sem, ld, h, w and flip are HOST arrays: the view table travels to the kernel by value in its arguments, nothing is uploaded and
+ * the call is asynchronous on `stream`.  The device memory behind sem[v] is read when the kernel runs.
+ * Per pixel, l_v(c) is view v's logit up-sampled bilinearly (align_corners = False, the arithmetic of the call above, expression
+ * by expression) and p_v = softmax_c(l_v), shifted by the view's own maximum, in fp32.  The score of class c is
+ *   mode 0 (mean)    sum_v p_v(c)
+ *   mode 1 (max)     max_v p_v(c)
+ *   mode 2 (voting)  the number of views whose arg-max of l_v is c (first maximum per view)
+ * and the prediction is the smallest c with the largest score.  Pairs (label, prediction) with 0 <= label < n_classes and
+ * prediction < n_classes are ADDED to hist [n_classes, n_classes] int64 (zero it before the first batch) as integers - an LDS
+ * histogram for n_classes <= 64, global atomics above; pred (optional, [B, H, W] int64) receives the prediction.  The same inputs
+ * give the same bits of hist and pred on every run; voting over the single plain view is ucd_seg_confusion bit for bit.
+ * A workgroup owns a pixel tile and stages the cells of all views under it in LDS.  The plan call (host only, no device call; the
+ * one copy of the sizing arithmetic, which the launch itself asks) picks the largest tile of 32 x 64, 32 x 32, 16 x 32, 16 x 16,
+ * 8 x 16, 8 x 8 pixels for which sum_v cells_v * Ctot * 4 bytes (cells_v: the largest footprint of view v over the tiles of the
+ * grid, by the kernel's own index arithmetic; a mirrored view's columns over the mirrored pixel range), a 272-byte table and - for
+ * n_classes <= 64 - the n_classes^2 * 4 bytes of the histogram fit 150 KB.
+ * Checked on the host before any device call: UCD_EINVAL (V outside 1 .. 16; a NULL array; a size below 1; Ctot > 255; h[v] > H
+ * or w[v] > W; and for the launch a NULL sem[v], labels or hist, ld[v] < Ctot, an unknown mode), UCD_EUNSUPPORTED (no tile fits:
+ * the message names the bytes of the smallest one); else the hipError_t of a failed launch. */
+int ucd_seg_views_plan(int H, int W, int V, const int* h, const int* w, const int* flip, int Ctot, int n_classes, int* tile_y,
+                       int* tile_x, size_t* lds_bytes);
+int ucd_seg_views(const float* const* sem, const int* ld, const int* h, const int* w, const int* flip, int V, const int64_t* labels,
+                  int B, int H, int W, int Ctot, int n_classes, int mode, int64_t* hist, int64_t* pred, ucd_stream_t stream);
+
 /* The output side of an evaluation run (the reference's test.py / Trainer.test, train.py:271-375) in one pass over the
  * full-resolution pixel grid of a batch; only uint8 maps (and the fp32 attention map) leave the device.  Inputs:
  *   sem      fp32 rows [B*h*w, ld_s >= Ctot], the low-resolution logits (as ucd_seg_confusion takes them); Ctot <= 255

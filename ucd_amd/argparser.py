@@ -41,6 +41,27 @@ def _flag(name, **kw):
     return (name, kw)
 
 
+class _EvalScales(argparse.Action):
+    """--eval_scales: the plain view is always evaluated (loss and teacher terms come from it), so the list must hold 1.0"""
+
+    def __call__(self, parser, namespace, values, option_string=None):
+        if 1.0 not in values:
+            parser.error(f"{option_string} must contain 1.0 (the plain view), got {' '.join(str(v) for v in values)}")
+        if any(v <= 0 for v in values):
+            parser.error(f"{option_string} takes positive scales, got {' '.join(str(v) for v in values)}")
+        setattr(namespace, self.dest, values)
+
+
+def eval_views(opts):
+    """The test-time views of ``--eval_scales`` / ``--eval_flip`` as ``[(scale, flip), ...]``: the plain view ``(1.0, False)`` first,
+    then the other scales in the order given, each followed by its mirror under ``--eval_flip``.  ``--fusion-mode`` says how their
+    class distributions are fused (``Trainer.test``; csrc/seg_views.hip)."""
+    scales = [float(s) for s in (getattr(opts, "eval_scales", None) or [1.0])]
+    flip = bool(getattr(opts, "eval_flip", False))
+    ordered = [1.0] + [s for s in scales if s != 1.0]
+    return [(s, f) for s in ordered for f in ((False, True) if flip else (False,))]
+
+
 _ON, _OFF = dict(action="store_true", default=False), dict(action="store_false", default=True)
 _ARGS = [
     # performance
@@ -75,6 +96,8 @@ _ARGS = [
     _flag("--pooling", type=int, default=32), _flag("--temperature", type=float, default=0.07),
     # test / checkpoints
     _flag("--test", **_ON), _flag("--ckpt", default=None, type=str),
+    # test-time views (the final test pass and evaluate.py): scales of the image, each also mirrored; fused by --fusion-mode
+    _flag("--eval_scales", type=float, nargs="+", default=[1.0], action=_EvalScales), _flag("--eval_flip", **_ON),
     # distillation (ILT)
     _flag("--freeze", **_ON), _flag("--loss_de", type=float, default=0.), _flag("--loss_kd", type=float, default=0.),
     # regularisers (EWC / RW / PI; --method EWC|RW|PI): ucd_amd.regularizer, after the UCD step

@@ -78,6 +78,7 @@ def main(opts):
     metrics = StreamSegMetrics(sum(classes))
     out_dir = os.path.join(logdir, "predictions") if world_size == 1 else os.path.join(logdir, "predictions", f"rank{rank}")
     sink = visual.SampleWriter(out_dir)
+    logger.info(f"*** Views (scale, mirrored): {argparser.eval_views(opts)}, fused by {opts.fusion_mode}")
     val_loss, val_score, _ = trainer.test(loader=test_loader, metrics=metrics, logger=logger, sink=sink)
     logger.info(f"*** End of Test, Total Loss={float(val_loss[0]) + float(val_loss[1])}, Class Loss={float(val_loss[0])},"
                 f" Reg Loss={float(val_loss[1])}")

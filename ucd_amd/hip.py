@@ -172,6 +172,8 @@ SIGNATURES = {
     "ucd_pixcon_loss_given_p": (_i, [_p, _i, _i, _p, _p, _i, _p, _i, _f, _i, _p, _p, _i, _p, _p, _z, _p]),
     "ucd_pixcon_scatter_grad": (_i, [_p, _p, _i, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "ucd_seg_confusion": (_i, [_p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
+    "ucd_seg_views_plan": (_i, [_i, _i, _i, _p, _p, _p, _i, _i, _p, _p, _p]),
+    "ucd_seg_views": (_i, [_p, _p, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
     "ucd_seg_render": (_i, [_p, _i, _p, _p, C.c_longlong, C.c_longlong, C.c_longlong, C.c_longlong, _f, _f, _f, _f, _f, _f, _p, _p, _i, _i,
                             _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p]),
     "ucd_attn_energy": (_i, [_p, _i, _i, _i, _i, _i, _p, _p]),
@@ -617,6 +619,42 @@ def attmap(x, ld_x, y, ld_y, B, HW, Cc):
     ws = workspace(nbytes, x.device, "attmap")
     _check(lib.ucd_attmap(ptr(x), ld_x, ptr(y), ld_y, dtype_code(x), B, HW, Cc, ptr(ws), nbytes, stream()),
            "ucd_attmap")
+
+
+# ---------------------------------------------------------------------------------------------
+# evaluation with scaled and mirrored views (csrc/seg_views.hip)
+# ---------------------------------------------------------------------------------------------
+SEG_VIEW_MODES = {"mean": 0, "max": 1, "voting": 2}      # ucd_seg_views' mode
+
+
+def _int_array(values):
+    values = [int(v) for v in values]
+    return (C.c_int * max(len(values), 1))(*values)
+
+
+def seg_views_plan(H, W, views, Ctot, n_classes):
+    """Host-only ``ucd_seg_views_plan``: the pixel tile and the LDS bytes ``ucd_seg_views`` gives the label map ``H x W`` and the
+    ``views`` - a sequence of ``(h, w, flip)``, one per view.  Returns ``{"tile_y", "tile_x", "lds_bytes"}``; raises what the
+    launch would raise for these sizes.  Needs no GPU."""
+    views = list(views)
+    ty, tx, lds = C.c_int(0), C.c_int(0), C.c_size_t(0)
+    _check(load().ucd_seg_views_plan(int(H), int(W), len(views), _int_array(v[0] for v in views), _int_array(v[1] for v in views),
+                                     _int_array(bool(v[2]) for v in views), int(Ctot), int(n_classes), C.byref(ty), C.byref(tx),
+                                     C.byref(lds)), "ucd_seg_views_plan")
+    return {"tile_y": ty.value, "tile_x": tx.value, "lds_bytes": lds.value}
+
+
+def seg_views(rows, shapes, flips, labels, Ctot, n_classes, fusion, hist, pred=None):
+    """``ucd_seg_views``: ``rows[v]`` = view v's fp32 row matrix [B*h*w, ld >= Ctot] on the device, ``shapes[v]`` = (h, w),
+    ``flips[v]`` whether it was computed from the mirrored image; ``labels`` int64 [B, H, W]; ``hist`` int64 [n, n] is added to."""
+    B, H, W = labels.shape
+    V = len(rows)
+    sem = (C.c_void_p * max(V, 1))(*[r.data_ptr() for r in rows])
+    with _timed("ucd_seg_views", B * H * W * (8 + (8 if pred is not None else 0)) + sum(r.numel() * 4 for r in rows)):
+        _check(load().ucd_seg_views(sem, _int_array(r.stride(0) for r in rows), _int_array(s[0] for s in shapes),
+                                    _int_array(s[1] for s in shapes), _int_array(bool(f) for f in flips), V, ptr(labels), B, H, W,
+                                    int(Ctot), int(n_classes), SEG_VIEW_MODES[fusion], ptr(hist), ptr(pred), stream()),
+               "ucd_seg_views")
 
 
 # ---------------------------------------------------------------------------------------------

@@ -56,6 +56,39 @@ class StreamSegMetrics:
         hist = hist.double()
         self.confusion_matrix = hist if self.confusion_matrix is None else self.confusion_matrix + hist
 
+    def update_from_views(self, label_trues, sems, flips, fusion="mean", pred=None):
+        """``update_from_logits`` for test-time views: ``sems[v]`` = the low-resolution logits [B, Ctot, h_v, w_v] of view v (the
+        image at some scale), ``flips[v]`` whether that view was computed from the horizontally mirrored image.  Up-sampling,
+        the per-view soft-max, the fusion rule (``mean | max | voting``: sum of the probabilities, their maximum, the class most
+        views name), arg-max and the histogram are one kernel (``ucd_seg_views``, csrc/seg_views.hip); no full-resolution map is
+        built.  ``pred`` (optional, contiguous int64 [B, H, W] on the device) receives the fused prediction that was counted."""
+        from . import hip
+        sems, flips = list(sems), list(flips)
+        if len(sems) != len(flips) or not sems:
+            raise ValueError(f"update_from_views takes one flip per view and at least one view, got {len(sems)} / {len(flips)}")
+        if fusion not in hip.SEG_VIEW_MODES:
+            raise ValueError(f"fusion must be one of {' | '.join(hip.SEG_VIEW_MODES)}, got {fusion!r}")
+        if any(not s.is_cuda for s in sems) or not label_trues.is_cuda:
+            raise RuntimeError("StreamSegMetrics.update_from_views runs on the GPU only (there is no CPU fallback)")
+        B, Ctot = sems[0].shape[:2]
+        if any(s.dim() != 4 or tuple(s.shape[:2]) != (B, Ctot) for s in sems):
+            raise ValueError(f"every view must be a [{B}, {Ctot}, h, w] tensor")
+        H, W = label_trues.shape[-2:]
+        n = self.n_classes
+        rows = [s.detach().permute(0, 2, 3, 1).reshape(-1, Ctot).float().contiguous() for s in sems]
+        lab = label_trues.contiguous()
+        if lab.dtype != torch.int64:
+            lab = lab.long()
+        dev = sems[0].device
+        hist = torch.zeros(n, n, dtype=torch.int64, device=dev)
+        if pred is not None and (pred.dtype != torch.int64 or tuple(pred.shape) != (B, H, W) or not pred.is_contiguous()
+                                 or pred.device != dev):
+            raise ValueError(f"pred must be a contiguous int64 [{B}, {H}, {W}] tensor on {dev}")
+        hip.seg_views(rows, [tuple(s.shape[2:]) for s in sems], flips, lab.reshape(B, H, W), Ctot, n, fusion, hist, pred)
+        self.total_samples += B
+        hist = hist.double()
+        self.confusion_matrix = hist if self.confusion_matrix is None else self.confusion_matrix + hist
+
     def synch(self, device):
         """Sum the matrices and sample counts of all ranks onto rank 0 (stream_metrics.py:110-120)."""
         if dist.is_available() and dist.is_initialized() and self.confusion_matrix is not None:

@@ -308,7 +308,11 @@ def main(opts):
                                           idxs_path=path_base + f"/test_on_{image_set}-{opts.step}.npy")
         test_loader = val_loader_of(test_dst)
         model.eval()
-        val_loss, val_score, _ = trainer.validate(loader=test_loader, metrics=val_metrics, logger=logger)
+        views = argparser.eval_views(opts)
+        if len(views) > 1:
+            logger.info(f"*** Test views (scale, mirrored): {views}, fused by {opts.fusion_mode}")
+        val_loss, val_score, _ = trainer.validate(loader=test_loader, metrics=val_metrics, logger=logger,
+                                                  views=views if len(views) > 1 else None)
         logger.info(f"*** End of Test, Total Loss={float(val_loss[0]) + float(val_loss[1])}, Class Loss={float(val_loss[0])},"
                     f" Reg Loss={float(val_loss[1])}")
         if rank == 0:

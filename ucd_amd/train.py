@@ -116,6 +116,10 @@ class Trainer:
         # outside the teacher graph and the whole-step graph
         self.lde_lazy = self.lde_flag and not (self.fused_lde and self.fuse_logit_losses)
         self.amp = getattr(opts, "opt_level", "O0") != "O0"
+        # test-time views of the final test pass (--eval_scales / --eval_flip) and the rule that fuses them (--fusion-mode)
+        from .argparser import eval_views
+        self.eval_views = eval_views(opts)
+        self.fusion_mode = getattr(opts, "fusion_mode", "mean")
         # contrastive arithmetic: exact fp32 MFMA with fp32 activations (O0), fp16 operands otherwise
         self.pixcon_precision = getattr(opts, "pixcon_precision", None) or ("f16" if self.amp else "f32")
         # frozen teacher under autocast: static bf16 copies of its convolution weights (no per-call casts)
@@ -457,10 +461,38 @@ class Trainer:
             reg = reg + self.regularizer.penalty()
         return reg
 
-    def _evaluate(self, loader, metrics, logger, on_batch, want_pred):
+    def _view_logits(self, images, views):
+        """The low-resolution logits of the views after the plain one: the model once per ``(scale, flip)`` on the image resized
+        bilinearly to ``int(size * scale + 0.5)`` and, for a mirror, flipped horizontally."""
+        import torch.nn.functional as F
+        H, W = images.shape[-2:]
+        sems = []
+        for scale, flip in views:
+            x = images if scale == 1.0 else F.interpolate(images, size=(int(H * scale + 0.5), int(W * scale + 0.5)), mode="bilinear",
+                                                          align_corners=False)
+            if flip:
+                x = x.flip(-1)
+            with self._autocast():
+                _, f = self.model(x, ret_intermediate=False, upsample=False)
+            sems.append(f["sem"])
+        return sems
+
+    def _evaluate(self, loader, metrics, logger, on_batch, want_pred, views=None):
         """The loop ``validate`` and ``test`` share (train.py:185-270 and :271-375): class loss, regularisation terms and confusion
         matrix accumulated on the device, reduced to rank 0 and divided by ranks and batches.  ``want_pred(i)`` says whether batch
-        ``i`` needs its int64 arg-max map; ``on_batch(i, images, labels, feats, prediction or None)`` sees every batch."""
+        ``i`` needs its int64 arg-max map; ``on_batch(i, images, labels, feats, prediction or None)`` sees every batch.
+
+        ``views``: test-time views ``[(scale, flip), ...]`` with the plain view ``(1.0, False)`` first (``argparser.eval_views``).
+        With more than the plain view the model also runs once per further view; the class loss and the teacher-side terms still
+        come from the plain view, the confusion matrix and the prediction from the views fused by ``--fusion-mode`` in one kernel
+        (``metrics.update_from_views``).  ``None`` or the plain view alone: the single-view path, unchanged."""
+        views = [(float(s), bool(f)) for s, f in views] if views else [(1.0, False)]
+        if views[0] != (1.0, False):
+            raise ValueError(f"the first evaluation view must be the plain one (1.0, False), got {views[0]}")
+        multi = len(views) > 1
+        if multi and not (self.fuse_logit_losses and hasattr(metrics, "update_from_views")):
+            raise RuntimeError("evaluation with scaled or mirrored views (--eval_scales / --eval_flip) needs the fused logit path: a "
+                               "GPU device and a metrics object with update_from_views; there is no torch fall-back")
         metrics.reset()
         model = self.model
         dev = self.device
@@ -484,7 +516,12 @@ class Trainer:
                         class_loss += fused_seg_bce(sem, None, labels)[1]
                     else:
                         class_loss += fused_seg_losses(sem, None, labels, self.old_classes if self.unce else 1, 1.0, 0.0)[1]
-                    if want_pred(i):
+                    if multi:
+                        # the fused prediction is what is scored, and what on_batch sees (the rendered files show it)
+                        pred = torch.empty(labels.shape, dtype=torch.int64, device=dev) if want_pred(i) else None
+                        metrics.update_from_views(labels, [sem] + self._view_logits(images, views[1:]), [f for _, f in views],
+                                                  fusion=self.fusion_mode, pred=pred)
+                    elif want_pred(i):
                         # the arg-max map the histogram is built from: no second pass over the logits
                         pred = torch.empty(labels.shape, dtype=torch.int64, device=dev)
                         metrics.update_from_logits(labels, sem, pred=pred)
@@ -523,7 +560,7 @@ class Trainer:
             logger.info(f"Validation, Class Loss={class_loss}, Reg Loss={reg_loss} (without scaling)")
         return (class_loss, reg_loss), score
 
-    def validate(self, loader, metrics, ret_samples_ids=None, logger=None):
+    def validate(self, loader, metrics, ret_samples_ids=None, logger=None, views=None):
         """Evaluation loop (train.py:185-270): ``((class_loss, reg_loss), score, samples)``, the losses as device scalars.
 
         The class loss and the confusion matrix come from the fused kernels on the low-resolution logits (under BCE: the fused BCE).
@@ -534,7 +571,8 @@ class Trainer:
 
         ``ret_samples_ids``: batch indices for which ``(images[0] as float32 numpy [3, H, W], labels[0], prediction[0])`` (numpy
         int64 [H, W] each) is appended to ``samples``; the prediction is the arg-max map the confusion matrix was built from.
-        With ``None`` nothing extra is computed or copied."""
+        With ``None`` nothing extra is computed or copied.  ``views``: test-time views as in ``_evaluate``; only when passed - the
+        validations between epochs stay single-view."""
         ids = None if ret_samples_ids is None else {int(v) for v in ret_samples_ids}
         samples = []
 
@@ -543,7 +581,7 @@ class Trainer:
                 samples.append((images[0].detach().float().cpu().numpy(), labels[0].cpu().numpy(), pred[0].cpu().numpy()))
 
         losses, score = self._evaluate(loader, metrics, logger, on_batch if ids else None,
-                                       (lambda i: i in ids) if ids else (lambda i: False))
+                                       (lambda i: i in ids) if ids else (lambda i: False), views=views)
         return losses, score, samples
 
     def test(self, loader, metrics, logger=None, sink=None):
@@ -554,14 +592,19 @@ class Trainer:
         up-sampled bilinearly to the image) - the whole test set then sits on the host, as in the reference.  With ``sink`` each
         batch is rendered on the device (``ucd_amd.visual.render``: prediction, colour-coded prediction and labels, de-normalised
         image, attention map) and ``sink(batch_index, rendered)`` receives the dict of device tensors, ``uint8`` but for ``att``; the
-        sample list stays empty.  The rendered ``pred_u8`` has the bits of the map the confusion matrix is built from."""
+        sample list stays empty.  The rendered ``pred_u8`` has the bits of the map the confusion matrix is built from.
+
+        The views are those of ``--eval_scales`` / ``--eval_flip`` (``argparser.eval_views``), fused by ``--fusion-mode``; with more
+        than the plain view the prediction - in the samples and in the rendered ``pred_u8`` / ``pred_rgb`` - is the fused one."""
         from . import visual
         samples = []
+        views = self.eval_views
+        multi = len(views) > 1
 
         def on_batch(i, images, labels, feats, pred):
             body = _raw(feats, "body")
             if sink is not None:
-                sink(i, visual.render(feats["sem"], labels, images, body))
+                sink(i, visual.render(feats["sem"], labels, images, body, pred=pred if multi else None))
                 return
             import torch.nn.functional as F
             att = F.interpolate(visual.attn_energy(body).unsqueeze(1), size=images.shape[-2:], mode="bilinear",
@@ -569,7 +612,7 @@ class Trainer:
             img, lab, prd, att = images.detach().float().cpu().numpy(), labels.cpu().numpy(), pred.cpu().numpy(), att.cpu().numpy()
             samples.extend((img[j], lab[j], prd[j], att[j]) for j in range(img.shape[0]))
 
-        losses, score = self._evaluate(loader, metrics, logger, on_batch, lambda i: sink is None)
+        losses, score = self._evaluate(loader, metrics, logger, on_batch, lambda i: multi or sink is None, views=views)
         return losses, score, samples
 
     def state_dict(self):

@@ -71,7 +71,7 @@ def attn_energy(body):
     return a
 
 
-def render(sem, labels=None, images=None, body=None, cmap=None, mean=MEAN, std=STD, want=None):
+def render(sem, labels=None, images=None, body=None, cmap=None, mean=MEAN, std=STD, want=None, pred=None):
     """One fused pass over a batch (``ucd_seg_render``): from the LOW-resolution logits ``sem`` [B, Ctot, h, w] (and, each
     optional, ``labels`` int64 [B, H, W], the normalised ``images`` [B, 3, H, W] in any memory format, the raw ``body`` map
     [B, C, ha, wa]) to a dict of device tensors:
@@ -80,7 +80,10 @@ def render(sem, labels=None, images=None, body=None, cmap=None, mean=MEAN, std=S
     images ``image_u8`` [B, H, W, 3]; with body ``att`` fp32 [B, H, W] and ``att_low`` [B, ha, wa].
 
     The output size is that of the labels, else of the images (one of the two is required).  ``want`` restricts the kernel's outputs
-    to a subset of ``("pred_u8", "pred_rgb", "label_rgb", "image_u8", "att")``.  GPU only: a CPU tensor raises ``RuntimeError``."""
+    to a subset of ``("pred_u8", "pred_rgb", "label_rgb", "image_u8", "att")``.  With ``pred`` (an integer map [B, H, W] on the
+    device, e.g. the fused prediction of ``StreamSegMetrics.update_from_views``) ``pred_u8`` and ``pred_rgb`` show that map - a cast
+    and one colour-table index - and the kernel is asked for the other outputs only.  GPU only: a CPU tensor raises
+    ``RuntimeError``."""
     if not sem.is_cuda:
         raise RuntimeError("ucd_amd.visual.render runs on the GPU only (there is no CPU fallback)")
     if labels is None and images is None:
@@ -108,16 +111,26 @@ def render(sem, labels=None, images=None, body=None, cmap=None, mean=MEAN, std=S
     if body is not None and "att" in names:
         att_low = attn_energy(body)
         ha, wa = att_low.shape[-2:]
+    cm = _device_cmap(cmap, dev)
     out = {}
+    if pred is not None:
+        if tuple(pred.shape) != (B, H, W) or pred.device != dev or pred.dtype.is_floating_point:
+            raise ValueError(f"pred must be an integer [{B}, {H}, {W}] tensor on {dev}")
+        given = {"pred_u8": lambda: pred.to(torch.uint8), "pred_rgb": lambda: cm[pred.long()]}
+        out = {name: make() for name, make in given.items() if name in names}
+        names = names - set(given)
+    kout = {}                                   # what the kernel writes: never the maps made from a given pred
     for name in sorted(names):
         shape = (B, H, W) if name in ("pred_u8", "att") else (B, H, W, 3)
-        out[name] = torch.empty(shape, dtype=torch.float32 if name == "att" else torch.uint8, device=dev)
-    cm = _device_cmap(cmap, dev)
-    with hip._timed("ucd_seg_render", B * H * W * (8 + 12 + 14) + B * h * w * Ctot * 4):
-        hip._check(hip.load().ucd_seg_render(hip.ptr(s), Ctot, hip.ptr(lab), hip.ptr(img), *strides, *[float(v) for v in mean],
-                                             *[float(v) for v in std], hip.ptr(cm), hip.ptr(att_low), ha, wa, B, H, W, h, w, Ctot,
-                                             hip.ptr(out.get("pred_u8")), hip.ptr(out.get("pred_rgb")), hip.ptr(out.get("label_rgb")),
-                                             hip.ptr(out.get("image_u8")), hip.ptr(out.get("att")), hip.stream()), "ucd_seg_render")
+        kout[name] = torch.empty(shape, dtype=torch.float32 if name == "att" else torch.uint8, device=dev)
+    if kout:
+        with hip._timed("ucd_seg_render", B * H * W * (8 + 12 + 14) + B * h * w * Ctot * 4):
+            hip._check(hip.load().ucd_seg_render(hip.ptr(s), Ctot, hip.ptr(lab), hip.ptr(img), *strides, *[float(v) for v in mean],
+                                                 *[float(v) for v in std], hip.ptr(cm), hip.ptr(att_low), ha, wa, B, H, W, h, w, Ctot,
+                                                 hip.ptr(kout.get("pred_u8")), hip.ptr(kout.get("pred_rgb")),
+                                                 hip.ptr(kout.get("label_rgb")), hip.ptr(kout.get("image_u8")), hip.ptr(kout.get("att")),
+                                                 hip.stream()), "ucd_seg_render")
+    out.update(kout)
     if lab is not None:
         out["label_u8"] = lab.to(torch.uint8)
     if att_low is not None:
