@@ -931,6 +931,35 @@ int ucd_conv_wgrad_drop(ucd_stream_t stream);
  * knows, e.g. a failed capture); the mode is kept; returns the first error (a NULL stream cannot mean "all": it is the default stream). */
 int ucd_conv_wgrad_drop_all(void);
 
+/* Kernel forms behind ucd_conv_wgrad* (results do not depend on the choice: both 3x3 forms are exact on integers and agree bit
+ * for bit there).  ucd_conv_wgrad_plan is the one statement of which form, tile, row chunks, grid, LDS and slab sum a call gets,
+ * and ucd_conv_wgrad_ex launches with exactly its numbers - a side-stream call with the plan made AT the call (rules and the
+ * network's layers: DESIGN.md section 3.2; restated by tests/test_wgrad_plan_cpu.py).  It reads its arguments and the environment
+ * only - no operand is dereferenced and no device touched, so it answers on a machine without a GPU - and returns the code and
+ * message ucd_conv_wgrad_ex gives for these arguments (N and K multiples of 64; taps 1 or 9; H, W, dilation and M = B*OH*OW for
+ * the 3x3 / strided forms; 128-aligned channels when strided; M < 2^22), UCD_EINVAL for a NULL plan.
+ * Three environment variables exist for probes and A/B runs and are read at EVERY call of the plan (a probe or a test changes
+ * them inside one process; never cached): UCD_WGRAD_TARGET (workgroups aimed for by the tile and strided forms; unset or <= 0:
+ * 256 / 512 for 1x1, 512 / 1024 for 3x3 by the tiles of a chunk), UCD_WGRAD3_TARGET (the same for the row-3 form, default 256),
+ * UCD_WGRAD3=0 (3x3 layers keep the tile form).  ucd_conv_wgrad_workspace_bytes is the geometry-free upper bound of
+ * plan.workspace_bytes under the same variables. */
+enum ucd_wgrad_form {
+  UCD_WGRAD_TILE = 0,     /* wgrad_kernel<BN, BK, T9>: one (tile, tap, chunk) per workgroup */
+  UCD_WGRAD_STRIDED = 1,  /* wgrad_kernel<128, 128, T9, true> */
+  UCD_WGRAD_ROW3 = 2      /* wgrad3_kernel<NX>: one kernel row (three taps) per workgroup */
+};
+#define UCD_WGRAD_FORM_NAMES {"tile", "strided", "row3"}   /* indexed by enum ucd_wgrad_form */
+typedef struct ucd_conv_wgrad_plan_t {
+  int form;                  /* enum ucd_wgrad_form */
+  int tile_n, tile_k, tiles_n, tiles_k;
+  int chunks, rows_per_chunk, ksplit;   /* row chunks of whole 64-row steps; k-tile groups of a chunk that go to different XCDs */
+  int x_tile_rows;           /* ROW3: 96 or 128 (NX = 3 / 4); else 0 */
+  int grid, threads, lds_bytes;
+  int sum_lanes, sum_blocks; /* the slab sum this call launches or leaves pending: chunk lanes (1, 4, 16) and workgroups */
+  size_t workspace_bytes;    /* exactly chunks * N * taps * K * 4 for THIS call */
+} ucd_conv_wgrad_plan_t;
+int ucd_conv_wgrad_plan(int M, int N, int K, int taps, int H, int W, int dilation, int stride, ucd_conv_wgrad_plan_t* plan);
+
 /* The weights of the input-gradient convolutions of ALL stride-1 layers in one launch: for table entry e = {src offset,
  * dst offset, Co, Ci, KH*KW} (elements into the flat bf16 buffers; 4-D weights in channels-last memory order
  * [out][kh][kw][in]), dst_e = src_e.flip(2, 3).transpose(0, 1) in the same memory order.  blocks [n_blocks][4] (device,

@@ -930,6 +930,7 @@ def test_three_tap_and_nine_tap_weight_gradients_agree(M, N, K, sp, monkeypatch)
     out = {}
     for mode in ("1", "0"):
         monkeypatch.setenv("UCD_WGRAD3", mode)
+        assert hip.conv_wgrad_plan(M, N, K, conv3=sp)["form"] == {"1": "row3", "0": "tile"}[mode]      # the kernels this compares
         dw32 = torch.full((N, 9 * K), float("nan"), device=DEV)
         hip.conv_wgrad(zi, xi, None, conv3=sp, dw32=dw32)
         out[mode] = dw32
@@ -942,6 +943,55 @@ def test_three_tap_and_nine_tap_weight_gradients_agree(M, N, K, sp, monkeypatch)
         monkeypatch.setenv("UCD_WGRAD3", mode)
         res[mode] = hip.conv_wgrad(z, x, None, conv3=sp, dw32=torch.empty(N, 9 * K, device=DEV)).clone()
     assert _rel(res["1"], res["0"].float()) < 1e-5          # fp32 sums of the same products in another order
+
+
+@pytest.mark.parametrize("M,N,K,sp,form", [
+    (300, 64, 64, None, "tile"),                          # 2 chunks, the second ending inside a 64-row step
+    (1000, 128, 256, None, "tile"),                       # ksplit 2: the k tiles of a chunk on two XCDs
+    (2 * 9 * 11, 64, 128, (9, 11, 1), "tile"),            # 9 taps, one chunk
+    (8 * 33 * 33, 256, 256, (33, 33, 1), "row3"),         # 96-row X tiles; 16 chunks against a bound of 23
+    (8 * 33 * 33, 256, 256, (33, 33, 17), "row3"),        # 128-row X tiles
+    (8 * 33 * 33, 256, 256, (33, 33, 19), "tile"),        # past the row-3 form's dilations: 23 chunks
+    (2 * 5 * 6, 128, 128, (9, 11, 1, 2), "strided"),      # 3x3 stride 2 of a 2 x 9 x 11 map
+], ids=["tile", "ksplit2", "taps9", "row3-96", "row3-128", "tile-d19", "strided"])
+def test_the_launch_is_the_plans(M, N, K, sp, form, monkeypatch):
+    """ucd_conv_wgrad_ex launches what ucd_conv_wgrad_plan names: with a workspace of the geometry-free bound, filled with the word
+    0xFFFFFFFF (no finite sum has that pattern), every word below plan.workspace_bytes is written - every workgroup of the plan's
+    grid stored its slab tile - and every word from there on is untouched - the launch cut the rows into the plan's chunks, not the
+    bound's; the gradient is exact on sparse small integers."""
+    from ucd_amd import hip
+    for v in ("UCD_WGRAD3", "UCD_WGRAD_TARGET", "UCD_WGRAD3_TARGET"):
+        monkeypatch.delenv(v, raising=False)
+    lib = hip.load()
+    taps = 9 if sp else 1
+    H, W, d, stride = (tuple(sp) + (1,))[:4] if sp else (0, 0, 1, 1)
+    plan = hip.conv_wgrad_plan(M, N, K, conv3=sp)
+    assert plan["form"] == form
+    g = torch.Generator(DEV).manual_seed(M + N + K + d)
+    dens = min(0.5, (24.0 / M) ** 0.5)
+    rows_x = M if stride == 1 else M // (((H - 1) // stride + 1) * ((W - 1) // stride + 1)) * H * W
+    zi = (torch.randint(-2, 3, (M, N), device=DEV, generator=g) * (torch.rand(M, N, device=DEV, generator=g) < dens)).bfloat16()
+    xi = (torch.randint(-1, 2, (rows_x, K), device=DEV, generator=g) * (torch.rand(rows_x, K, device=DEV, generator=g) < dens)).bfloat16()
+    if stride == 1:
+        exact = _wgrad_ref(zi, xi, sp)
+    else:                                                   # the reference of test_strided_forward_statistics_and_weight_gradient
+        B, OH, OW = rows_x // (H * W), (H - 1) // stride + 1, (W - 1) // stride + 1
+        exact = torch.ops.aten.convolution_backward(zi.view(B, OH, OW, N).permute(0, 3, 1, 2).float(), xi.view(B, H, W, K).permute(0, 3, 1, 2).float(),
+                                                    torch.zeros(N, K, 3, 3, device=DEV), None, [stride, stride], [d, d], [d, d], False, [0, 0], 1,
+                                                    [False, True, False])[1].permute(0, 2, 3, 1).reshape(N, taps * K)
+    assert exact.abs().max().item() <= 256
+    bound = lib.ucd_conv_wgrad_workspace_bytes(M, N, K, taps)
+    assert bound >= plan["workspace_bytes"] == plan["chunks"] * N * taps * K * 4
+    ws = torch.full((bound // 4,), -1, device=DEV, dtype=torch.int32)
+    dw32 = torch.full((N, taps * K), float("nan"), device=DEV)
+    hip._check(lib.ucd_conv_wgrad_ex(hip.ptr(zi), N, hip.ptr(xi), K, M, N, K, taps, H, W, d, stride, None, hip.ptr(dw32), 0, hip.ptr(ws), bound, 0,
+                                     hip.stream()), "ucd_conv_wgrad")
+    assert torch.equal(dw32, exact)
+    used = plan["workspace_bytes"] // 4
+    assert not (ws[:used] == -1).any().item()
+    assert (ws[used:] == -1).all().item()
+    if form == "row3":
+        assert used < ws.numel()                            # the bound is the tile form's: the second half of the check is not empty
 
 
 # ---- the strided layers (first block of a stage: conv2 3x3 stride 2, proj_conv 1x1 stride 2; modules/residual.py:57-82) -------

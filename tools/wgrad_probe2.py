@@ -51,17 +51,20 @@ for name, B, ci, co, H, d, cnt in LAYERS:
         lib = lambda: torch.bmm(zr.view(S, M // S, co).transpose(1, 2), xr.view(S, M // S, ci)).sum(0)
     t_lib = timeit(lib)
     dw = torch.empty(co, k * k * ci, device=dev, dtype=torch.bfloat16)
-    row = []
+    row, forms = [], []
     for t in targets:
-        os.environ["UCD_WGRAD_TARGET"] = str(t)
+        os.environ["UCD_WGRAD_TARGET"] = str(t)             # read by the library at every call
         own = lambda: hip.conv_wgrad(zr, xr, dw, conv3=(H, H, d) if d else None)
         t_own = timeit(own)
         row.append(t_own)
+        p = hip.conv_wgrad_plan(M, co, ci, conv3=(H, H, d) if d else None)      # the launch just timed: form, chunks x ksplit
+        forms.append("%s %dx%d" % (p["form"], p["chunks"], p["ksplit"]))
         tot_own[t] += t_own * cnt
     ref = lib().float()
     ref = ref.permute(0, 2, 3, 1).reshape(co, -1) if ref.dim() == 4 else ref
     err = ((dw.float() - ref).norm() / ref.norm()).item()
     tot_lib += t_lib * cnt
     flop = 2.0 * M * k * k * ci * co
-    print("%-26s %10.1f | %s   (best %.0f TF/s, vs library rel %.1e)" % (name, t_lib, "  ".join("%9.1f" % v for v in row), flop / min(row) / 1e6, err))
+    print("%-26s %10.1f | %s   (best %.0f TF/s, vs library rel %.1e)" % (name, t_lib, "  ".join("%9.1f %-11s" % vf for vf in zip(row, forms)),
+                                                                         flop / min(row) / 1e6, err))
 print("per step (counts applied): library %.2f ms | own %s" % (tot_lib / 1e3, "  ".join("@%d %.2f ms" % (t, v / 1e3) for t, v in tot_own.items())))

@@ -23,6 +23,7 @@
 // three taps from one dZ tile and one X tile of 64 + 2 d rows, 6 MFMA + 2 loader waves; this 9-tap form keeps the rest.
 // Workgroup -> work: all tiles and taps of one row chunk sit on one XCD (ids congruent mod 8 share an L2), so a chunk's rows
 // of dZ and X leave HBM once and are re-read by its tiles from that L2.
+#include <algorithm>
 #include <map>
 #include <mutex>
 #include <optional>
@@ -657,91 +658,58 @@ __global__ __launch_bounds__(kThreads) void wgrad_sum_kernel(SumArgs q) {
   wgrad_sum_dispatch(q, (int)blockIdx.x, red);
 }
 
-struct Plan { int bno, bko, tiles_n, tiles_k, chunks, rows, ksplit; };
+// ---- the plan of a call (ucd_conv_wgrad_plan, include/ucd_hip.h) -------------------------------------------
+// The tuning variables, read at every call (tools/wgrad_probe2.py and the tests change them inside one process): UCD_WGRAD_TARGET
+// and UCD_WGRAD3_TARGET override the workgroups aimed for (probes), UCD_WGRAD3=0 keeps the tile form for every 3x3 layer (A/B).
+struct Tuning { int target, target3; bool row3; };
+Tuning tuning() {
+  const char *t = getenv("UCD_WGRAD_TARGET"), *t3 = getenv("UCD_WGRAD3_TARGET"), *r3 = getenv("UCD_WGRAD3");
+  return {t ? atoi(t) : 0, t3 && atoi(t3) > 0 ? atoi(t3) : 256, !(r3 && r3[0] == '0')};
+}
 
-// chunks: about `target` workgroups in all (two per CU), whole 64-row steps, at least 256 rows each; a multiple of 8 chunks
-// (one XCD each) where the output is small, else few chunks with the k tiles of a chunk split over the XCDs
-Plan make_plan(int M, int N, int K, int taps, int target) {
-  Plan pl;
-  pl.bno = N % 128 == 0 ? 128 : 64;
-  pl.bko = K % 128 == 0 ? 128 : 64;
-  pl.tiles_n = N / pl.bno; pl.tiles_k = K / pl.bko;
-  const int per_chunk = pl.tiles_n * pl.tiles_k * taps;
-  int chunks = target / per_chunk;
-  const int max_chunks = (M + 255) / 256;
-  if (chunks > max_chunks) chunks = max_chunks;
-  pl.ksplit = 1;
+// chunks: about `target` workgroups in all, whole 64-row steps, at least 256 rows each; a multiple of 8 chunks (one XCD each)
+// where the output is small, else few chunks with the k tiles of a chunk split over the XCDs
+void split_rows(int M, int per_chunk, int tiles_k, int target, ucd_conv_wgrad_plan_t* p) {
+  int chunks = std::min(target / per_chunk, (M + 255) / 256);
+  p->ksplit = 1;
   if (chunks >= 8) {
     chunks = chunks / 8 * 8;
   } else {
     if (chunks < 1) chunks = 1;
     while (chunks & (chunks - 1)) --chunks;                        // 1, 2, 4
     int ks = 8 / chunks;
-    while (ks > 1 && pl.tiles_k % ks) ks >>= 1;
-    pl.ksplit = ks;
+    while (ks > 1 && tiles_k % ks) ks >>= 1;
+    p->ksplit = ks;
   }
-  int rows = ceil_div(M, chunks);
-  rows = ceil_div(rows, kRows) * kRows;
-  pl.rows = rows;
-  pl.chunks = ceil_div(M, rows);
-  return pl;
+  p->rows_per_chunk = ceil_div(ceil_div(M, chunks), kRows) * kRows;
+  p->chunks = ceil_div(M, p->rows_per_chunk);
 }
 
-// Workgroups aimed for (tools/wgrad_probe2.py on MI355X, B = 24): the 1x1 products are bound by the slab traffic
-// (chunks x |dW| x 4 bytes written and read back) - one workgroup per CU; the 9-tap products are MFMA work at low per-workgroup
-// efficiency - four per CU (two resident, two waiting) were fastest.  UCD_WGRAD_TARGET overrides (probes).
-int wgrad_target(int taps, int per_chunk) {
-  const char* e = getenv("UCD_WGRAD_TARGET");
-  const int v = e ? atoi(e) : 0;
-  if (v > 0) return v;
-  if (taps == 1) return per_chunk >= 64 ? 512 : 256;
-  return per_chunk <= 9 && taps == 9 ? 512 : 1024;
-}
-
-// three-tap form: one workgroup (8 waves) per CU; UCD_WGRAD3_TARGET overrides (probes), UCD_WGRAD3=0 keeps the 9-tap form (A/B)
-struct Plan3 { int tiles_n, tiles_k, chunks, rows, ksplit; };
-Plan3 make_plan3(int M, int N, int K) {
-  Plan3 pl;
-  pl.tiles_n = N / 128; pl.tiles_k = K / 128;
-  const char* e = getenv("UCD_WGRAD3_TARGET");
-  const int target = e && atoi(e) > 0 ? atoi(e) : 256;
-  const int per_chunk = pl.tiles_n * pl.tiles_k * 3;
-  int chunks = target / per_chunk;
-  const int max_chunks = (M + 255) / 256;
-  if (chunks > max_chunks) chunks = max_chunks;
-  pl.ksplit = 1;
-  if (chunks >= 8) {
-    chunks = chunks / 8 * 8;
-  } else {                                                         // few chunks: their k tiles spread over the XCDs
-    if (chunks < 1) chunks = 1;
-    while (chunks & (chunks - 1)) --chunks;                        // 1, 2, 4
-    int ks = 8 / chunks;
-    while (ks > 1 && pl.tiles_k % ks) ks >>= 1;
-    pl.ksplit = ks;
-  }
-  int rows = ceil_div(M, chunks);
-  rows = ceil_div(rows, kRows) * kRows;
-  pl.rows = rows;
-  pl.chunks = ceil_div(M, rows);
-  return pl;
-}
-bool wgrad3_enabled() {
-  const char* e = getenv("UCD_WGRAD3");
-  return !(e && e[0] == '0');
+// Every number of a launch of `form`, chosen by the caller.  Workgroups aimed for (tools/wgrad_probe2.py on MI355X, B = 24): the 1x1
+// products are bound by the slab traffic (chunks x |dW| x 4 bytes written and read back) - one workgroup per CU; the 9-tap products
+// are MFMA work at low per-workgroup efficiency - four per CU (two resident, two waiting) were fastest; the row-3 form (8 waves):
+// one per CU.
+void plan_form(int form, int M, int N, int K, int taps, int dilation, const Tuning& tu, ucd_conv_wgrad_plan_t* p) {
+  const bool row3 = form == UCD_WGRAD_ROW3;
+  p->form = form;
+  p->tile_n = N % 128 == 0 ? 128 : 64; p->tile_k = K % 128 == 0 ? 128 : 64;      // (the strided and row-3 forms: 128-aligned channels)
+  p->tiles_n = N / p->tile_n; p->tiles_k = K / p->tile_k;
+  const int units = row3 ? 3 : taps;                                           // workgroups of one tile and chunk
+  const int per_chunk = p->tiles_n * p->tiles_k * units;
+  const int target = row3 ? tu.target3 : tu.target > 0 ? tu.target : taps == 1 ? (per_chunk >= 64 ? 512 : 256) : (per_chunk <= 9 ? 512 : 1024);
+  split_rows(M, per_chunk, p->tiles_k, target, p);
+  p->grid = ceil_div(p->chunks * p->ksplit, 8) * 8 * p->tiles_n * (p->tiles_k / p->ksplit) * units;
+  p->x_tile_rows = !row3 ? 0 : kRows + 2 * dilation <= 96 ? 96 : 128;
+  p->threads = row3 ? k3Threads : kThreads;
+  p->lds_bytes = row3 ? k3Stages * k3_stage_bytes(p->x_tile_rows / 32) : 2 * kRows * (p->tile_n + p->tile_k) * 2;
+  // chunk lanes of the slab sum: enough workgroups to fill the chip when the output is small and the chunks many
+  const size_t total = (size_t)N * taps * K, groups8 = total / 8;
+  p->sum_lanes = p->chunks >= 64 && groups8 <= (size_t)16 * 1024 ? 16 : p->chunks >= 16 && groups8 <= (size_t)64 * 1024 ? 4 : 1;
+  p->sum_blocks = ceil_div((int)groups8, kThreads / p->sum_lanes);             // a workgroup's 256 threads: 8 outputs x one lane each
+  p->workspace_bytes = (size_t)p->chunks * total * sizeof(float);
 }
 
 // ---- deferred slab sums and the side stream: host state (see SumArgs above) --------------------------------------------------------
-SumArgs make_sum(const void* workspace, int chunks, size_t total, void* dw, float* dw32, int accumulate32) {
-  SumArgs q;
-  q.partial = (const float*)workspace; q.chunks = chunks; q.total = total; q.dW = (bf16*)dw; q.dW32 = dw32; q.accumulate = accumulate32;
-  // chunk lanes of the sum: enough workgroups to fill the chip when the output is small and the chunks many
-  const size_t groups8 = total / 8;
-  if (chunks >= 64 && groups8 <= (size_t)16 * 1024) { q.cl = 16; q.blocks = (int)((groups8 + 15) / 16); }
-  else if (chunks >= 16 && groups8 <= (size_t)64 * 1024) { q.cl = 4; q.blocks = (int)((groups8 + 63) / 64); }
-  else { q.cl = 1; q.blocks = (int)((groups8 + kThreads - 1) / kThreads); }
-  return q;
-}
-
 // Side stream (round 6).  Nothing in the backward pass waits for a weight gradient before the optimiser, but on the caller's stream
 // every one of them sits in the chain of input-gradient products: at 3 - 6 images per GPU (the per-rank batch of the 8-GPU run) a
 // step is ~850 launches of ~10 us, each waiting for the one before, on a chip the small launches fill to a quarter.  A call that
@@ -761,9 +729,31 @@ SumArgs make_sum(const void* workspace, int chunks, size_t total, void* dw, floa
 struct ExArgs {
   const void* dz; int ld_dz; const void* x; int ld_x; int M, N, K, taps, H, W, dilation, stride;
   void* dw; float* dw32; int accumulate32; void* workspace; size_t workspace_bytes; int flags;
+  // filled by plan_call: the output map and the rows of X of a strided call (else H, W, M), and the plan the call launches with -
+  // made AT the call, also for a call armed on the side stream: the bytes checked there are the bytes written later
+  int oH, oW; long long x_rows;
+  ucd_conv_wgrad_plan_t plan;
 };
-bool wgrad_three(const ExArgs& q, int oW, int oH);
-int wgrad_launch_on(const ExArgs& q, hipStream_t s, SumArgs& pending);
+
+// The shape checks of a call in the order a call reports them, its derived geometry and its plan: ucd_conv_wgrad_plan.
+int plan_call(ExArgs& q, const char* fn) {
+  const int M = q.M, N = q.N, K = q.K, taps = q.taps, H = q.H, W = q.W, dilation = q.dilation;
+  UCD_REQUIRE(M > 0 && N > 0 && K > 0 && N % 64 == 0 && K % 64 == 0, UCD_EUNSUPPORTED, "%s: N (%d) and K (%d) must be multiples of 64", fn, N, K);
+  UCD_REQUIRE(taps == 1 || taps == 9, UCD_EINVAL, "%s: taps must be 1 or 9", fn);
+  const bool str = q.stride > 1;
+  q.oH = str && H > 0 ? (H - 1) / q.stride + 1 : H; q.oW = str && W > 0 ? (W - 1) / q.stride + 1 : W;
+  UCD_REQUIRE((taps == 1 && !str) || (H > 0 && W > 0 && dilation >= 1 && (long long)M % ((long long)q.oH * q.oW) == 0 && H < 32768 && W < 32768),
+              UCD_EINVAL, "%s: the 3x3 / strided forms need H, W, dilation and M = B*OH*OW", fn);
+  UCD_REQUIRE(!str || (N % 128 == 0 && K % 128 == 0), UCD_EUNSUPPORTED, "%s: the strided form takes N and K multiples of 128", fn);
+  UCD_REQUIRE(M < (1 << 22), UCD_EUNSUPPORTED, "%s: M = %d rows exceed the index arithmetic of the 3x3 form (2^22)", fn, M);
+  q.x_rows = str ? (long long)(M / (q.oH * q.oW)) * H * W : M;
+  const Tuning tu = tuning();
+  // the row-3 form (wgrad3_kernel): 3x3, stride 1, 128-aligned channels, an X tile of 64 + 2 d rows in 128 LDS rows, maps on which a
+  // 64-row step wraps at most one image row at a time, and 8192 rows (small maps, 3 images per GPU: level with the tile form or behind it)
+  const bool row3 = taps == 9 && !str && N % 128 == 0 && K % 128 == 0 && dilation <= 18 && dilation < W && kRows / W + 1 <= H && M >= 8192 && tu.row3;
+  plan_form(row3 ? UCD_WGRAD_ROW3 : str ? UCD_WGRAD_STRIDED : UCD_WGRAD_TILE, M, N, K, taps, dilation, tu, &q.plan);
+  return 0;
+}
 
 // Everything the library keeps for one CALLER stream.  A launch on a stream carries that stream's pending sum (ucd_conv_wgrad_ex
 // flags & 1 under mode bit 0 leaves its own there instead of launching it); the side stream's pending sum lives in the record of
@@ -782,7 +772,50 @@ std::mutex g_mu;
 std::map<hipStream_t, StreamState> g_streams;      // by the caller's stream
 int g_mode = 0;
 
+// the kernel of a plan: every product kernel takes (WArgs, the rider sum, its own workgroups)
+typedef void (*Product)(WArgs, SumArgs, int);
+template <int BN, int BK>
+Product tile_kernel(bool t9) { return t9 ? wgrad_kernel<BN, BK, true> : wgrad_kernel<BN, BK, false>; }
+Product kernel_of(const ucd_conv_wgrad_plan_t& p, bool t9) {
+  if (p.form == UCD_WGRAD_ROW3) return p.x_tile_rows == 96 ? wgrad3_kernel<3> : wgrad3_kernel<4>;
+  if (p.form == UCD_WGRAD_STRIDED) return t9 ? wgrad_kernel<128, 128, true, true> : wgrad_kernel<128, 128, false, true>;
+  if (p.tile_n == 128) return p.tile_k == 128 ? tile_kernel<128, 128>(t9) : tile_kernel<128, 64>(t9);
+  return p.tile_k == 128 ? tile_kernel<64, 128>(t9) : tile_kernel<64, 64>(t9);
+}
+
 // ---- under g_mu ----
+// the product of q's plan on `s`, carrying the sum `pending` holds; this call's own sum is left there or launched behind the product
+int wgrad_launch_on(const ExArgs& q, hipStream_t s, SumArgs& pending) {
+  static const char* fn = "ucd_conv_wgrad";
+  const ucd_conv_wgrad_plan_t& pl = q.plan;
+  const bool map = q.taps == 9 || q.stride > 1;          // the rows are pixels of a map (else one row of M pixels)
+  WArgs a;
+  a.dZ = (const bf16*)q.dz; a.ldz = q.ld_dz; a.X = (const bf16*)q.x; a.ldx = q.ld_x;
+  a.M = q.M; a.N = q.N; a.K = q.K; a.taps = q.taps; a.H = map ? q.H : 1; a.W = map ? q.W : q.M; a.dil = q.dilation;
+  a.stride = q.stride > 1 ? q.stride : 1; a.oH = q.stride > 1 ? q.oH : a.H; a.oW = q.stride > 1 ? q.oW : a.W; a.x_rows = (int)q.x_rows;
+  a.inv_ow = 1.f / (float)a.oW; a.inv_ohw = 1.f / ((float)a.oH * (float)a.oW);
+  a.chunks = pl.chunks; a.rows_per_chunk = pl.rows_per_chunk; a.tiles_n = pl.tiles_n; a.tiles_k = pl.tiles_k; a.ksplit = pl.ksplit;
+  a.partial = (float*)q.workspace;
+  a.inv_w = 1.f / (float)a.W; a.inv_hw = 1.f / ((float)a.H * (float)a.W);
+  // the pending slab sum of this stream (a deferred earlier call) rides behind this launch's own workgroups; this call's own sum
+  // is left pending when the caller allows it (flags & 1) and deferral is on, else launched right behind the product
+  const SumArgs pend = pending;
+  pending = SumArgs{};
+  const Product product = kernel_of(pl, q.taps == 9);
+  UCD_TRY_LDS(product, pl.lds_bytes);
+  product<<<pl.grid + std::max(pend.blocks, 0), pl.threads, pl.lds_bytes, s>>>(a, pend, pl.grid);
+  int rc = check_launch(fn);
+  if (rc) return rc;
+  const SumArgs mine{(const float*)q.workspace, pl.chunks, (unsigned long long)q.N * q.taps * q.K, (bf16*)q.dw, q.dw32, q.accumulate32,
+                     pl.sum_lanes, pl.sum_blocks};
+  if ((g_mode & 1) && (q.flags & 1)) {
+    pending = mine;
+    return 0;
+  }
+  wgrad_sum_kernel<<<mine.blocks, kThreads, 0, s>>>(mine);
+  return check_launch(fn);
+}
+
 int join_side(StreamState& st, hipStream_t main, const char* fn) {
   if (!st.active) return 0;
   st.active = false;
@@ -867,11 +900,6 @@ int drop(StreamState& st, hipStream_t main, const char* fn) {
   return join_side(st, main, fn);
 }
 
-int plan_target(int N, int K, int taps) {
-  const int per_chunk = (N / (N % 128 == 0 ? 128 : 64)) * (K / (K % 128 == 0 ? 128 : 64)) * taps;
-  return wgrad_target(taps, per_chunk);
-}
-
 }  // namespace
 }  // namespace ucd
 
@@ -881,13 +909,22 @@ extern "C" {
 
 size_t ucd_conv_wgrad_workspace_bytes(int M, int N, int K, int taps) {
   if (M <= 0 || N <= 0 || K <= 0 || N % 64 || K % 64 || (taps != 1 && taps != 9)) return 0;
-  const Plan pl = make_plan(M, N, K, taps, plan_target(N, K, taps));
-  int chunks = pl.chunks;
-  if (taps == 9 && N % 128 == 0 && K % 128 == 0) {     // the three-tap form may cut the rows differently
-    const Plan3 p3 = make_plan3(M, N, K);
-    if (p3.chunks > chunks) chunks = p3.chunks;
-  }
-  return (size_t)chunks * N * taps * K * sizeof(float);
+  // no geometry here: the larger of the forms a call of this shape can get (the strided form cuts like the tile form)
+  const Tuning tu = tuning();
+  ucd_conv_wgrad_plan_t tile, row3;
+  plan_form(UCD_WGRAD_TILE, M, N, K, taps, 1, tu, &tile);
+  if (!(taps == 9 && N % 128 == 0 && K % 128 == 0)) return tile.workspace_bytes;
+  plan_form(UCD_WGRAD_ROW3, M, N, K, taps, 1, tu, &row3);
+  return std::max(tile.workspace_bytes, row3.workspace_bytes);
+}
+
+int ucd_conv_wgrad_plan(int M, int N, int K, int taps, int H, int W, int dilation, int stride, ucd_conv_wgrad_plan_t* plan) {
+  UCD_REQUIRE(plan, UCD_EINVAL, "ucd_conv_wgrad_plan: NULL plan");
+  ExArgs q{};
+  q.M = M; q.N = N; q.K = K; q.taps = taps; q.H = H; q.W = W; q.dilation = dilation; q.stride = stride;
+  const int rc = plan_call(q, "ucd_conv_wgrad");
+  if (rc == 0) *plan = q.plan;
+  return rc;
 }
 
 int ucd_conv_wgrad(const void* dz, int ld_dz, const void* x, int ld_x, int M, int N, int K, int taps, int H, int W, int dilation,
@@ -944,28 +981,15 @@ int ucd_conv_wgrad_ex(const void* dz, int ld_dz, const void* x, int ld_x, int M,
                       ucd_stream_t stream) {
   static const char* fn = "ucd_conv_wgrad";
   UCD_REQUIRE(dz && x && (dw || dw32) && workspace, UCD_EINVAL, "%s: NULL argument", fn);
-  UCD_REQUIRE(M > 0 && N > 0 && K > 0 && N % 64 == 0 && K % 64 == 0, UCD_EUNSUPPORTED, "%s: N (%d) and K (%d) must be multiples of 64", fn, N, K);
-  UCD_REQUIRE(taps == 1 || taps == 9, UCD_EINVAL, "%s: taps must be 1 or 9", fn);
-  const bool str = stride > 1;
-  const int oH = str && H > 0 ? (H - 1) / stride + 1 : H, oW = str && W > 0 ? (W - 1) / stride + 1 : W;
-  UCD_REQUIRE((taps == 1 && !str) || (H > 0 && W > 0 && dilation >= 1 && (long long)M % ((long long)oH * oW) == 0 && H < 32768 && W < 32768),
-              UCD_EINVAL, "%s: the 3x3 / strided forms need H, W, dilation and M = B*OH*OW", fn);
-  UCD_REQUIRE(!str || (N % 128 == 0 && K % 128 == 0), UCD_EUNSUPPORTED, "%s: the strided form takes N and K multiples of 128", fn);
-  UCD_REQUIRE(M < (1 << 22), UCD_EUNSUPPORTED, "%s: M = %d rows exceed the index arithmetic of the 3x3 form (2^22)", fn, M);
-  const long long x_rows = str ? (long long)(M / (oH * oW)) * H * W : M;
-  UCD_REQUIRE((size_t)M * ld_dz * 2 < 0x7FFFFFF0u && (size_t)x_rows * ld_x * 2 < 0x7FFFFFF0u, UCD_EUNSUPPORTED,
+  ExArgs q{dz, ld_dz, x, ld_x, M, N, K, taps, H, W, dilation, stride, dw, dw32, accumulate32, workspace, workspace_bytes, flags};
+  const int rc = plan_call(q, fn);
+  if (rc) return rc;
+  UCD_REQUIRE((size_t)M * ld_dz * 2 < 0x7FFFFFF0u && (size_t)q.x_rows * ld_x * 2 < 0x7FFFFFF0u, UCD_EUNSUPPORTED,
               "%s: operands beyond 2 GiB exceed the 32-bit offsets of the staging loads", fn);
   UCD_REQUIRE(aligned16(dz) && aligned16(x) && (!dw || aligned16(dw)) && (!dw32 || aligned16(dw32)) && ld_dz % 8 == 0 && ld_x % 8 == 0 &&
                   ld_dz >= N && ld_x >= K,
               UCD_EALIGN, "%s: operands must be 16-byte aligned with leading dimensions that are multiples of 8", fn);
-  ExArgs q{dz, ld_dz, x, ld_x, M, N, K, taps, H, W, dilation, stride, dw, dw32, accumulate32, workspace, workspace_bytes, flags};
-  {
-    // enough workspace?  (checked here, at the call, also for a call armed on the side stream)
-    Plan pl = make_plan(M, N, K, taps, plan_target(N, K, taps));
-    int chunks = pl.chunks;
-    if (wgrad_three(q, oW, oH)) chunks = make_plan3(M, N, K).chunks;
-    UCD_REQUIRE(workspace_bytes >= (size_t)chunks * N * taps * K * sizeof(float), UCD_EWORKSPACE, "%s: workspace too small", fn);
-  }
+  UCD_REQUIRE(workspace_bytes >= q.plan.workspace_bytes, UCD_EWORKSPACE, "%s: workspace too small", fn);
   const hipStream_t s = (hipStream_t)stream;
   std::lock_guard<std::mutex> lock(g_mu);
   StreamState& st = g_streams[s];
@@ -974,99 +998,3 @@ int ucd_conv_wgrad_ex(const void* dz, int ld_dz, const void* x, int ld_x, int M,
 }
 
 }  // extern "C"
-
-namespace ucd {
-namespace {
-
-bool wgrad_three(const ExArgs& q, int oW, int oH) {
-  (void)oH;
-  // the three-tap form (wgrad3_kernel): 3x3, stride 1, 128-aligned channels, an X tile of 64 + 2 d rows in 128 LDS rows, maps on
-  // which a 64-row step wraps at most one image row at a time
-  return q.taps == 9 && q.stride <= 1 && q.N % 128 == 0 && q.K % 128 == 0 && q.dilation <= 18 && q.dilation < q.W && kRows / q.W + 1 <= q.H &&
-         q.M >= 8192 && wgrad3_enabled();      // (small maps, 3 images per GPU: level with the 9-tap form or behind it)
-}
-
-// under g_mu: the product on `s` carrying the sum `pending` holds, this call's own sum left there or launched behind the product
-int wgrad_launch_on(const ExArgs& q, hipStream_t s, SumArgs& pending) {
-  static const char* fn = "ucd_conv_wgrad";
-  const void *dz = q.dz, *x = q.x;
-  void *dw = q.dw, *workspace = q.workspace;
-  float* dw32 = q.dw32;
-  const int ld_dz = q.ld_dz, ld_x = q.ld_x, M = q.M, N = q.N, K = q.K, taps = q.taps, H = q.H, W = q.W, dilation = q.dilation,
-            stride = q.stride, accumulate32 = q.accumulate32, flags = q.flags;
-  const bool str = stride > 1;
-  const int oH = str && H > 0 ? (H - 1) / stride + 1 : H, oW = str && W > 0 ? (W - 1) / stride + 1 : W;
-  const long long x_rows = str ? (long long)(M / (oH * oW)) * H * W : M;
-  Plan pl = make_plan(M, N, K, taps, plan_target(N, K, taps));
-  const size_t total = (size_t)N * taps * K;
-  // the three-tap form (wgrad3_kernel): 3x3, stride 1, 128-aligned channels, an X tile of 64 + 2 d rows in 128 LDS rows, maps on
-  // which a 64-row step wraps at most one image row at a time
-  const bool three = wgrad_three(q, oW, oH);
-  Plan3 p3{0, 0, 0, 0, 1};
-  if (three) {
-    p3 = make_plan3(M, N, K);
-    pl.chunks = p3.chunks;
-  }
-  WArgs a;
-  a.dZ = (const bf16*)dz; a.ldz = ld_dz; a.X = (const bf16*)x; a.ldx = ld_x;
-  a.M = M; a.N = N; a.K = K; a.taps = taps; a.H = (taps == 9 || str) ? H : 1; a.W = (taps == 9 || str) ? W : M; a.dil = dilation;
-  a.stride = str ? stride : 1; a.oH = str ? oH : a.H; a.oW = str ? oW : a.W; a.x_rows = (int)x_rows;
-  a.inv_ow = 1.f / (float)a.oW; a.inv_ohw = 1.f / ((float)a.oH * (float)a.oW);
-  a.chunks = pl.chunks; a.rows_per_chunk = pl.rows; a.tiles_n = pl.tiles_n; a.tiles_k = pl.tiles_k; a.ksplit = pl.ksplit;
-  a.partial = (float*)workspace;
-  a.inv_w = 1.f / (float)a.W; a.inv_hw = 1.f / ((float)a.H * (float)a.W);
-  const int groups = pl.chunks * pl.ksplit;
-  const int per_group = pl.tiles_n * (pl.tiles_k / pl.ksplit) * taps;
-  const int grid = ceil_div(groups, 8) * 8 * per_group;
-  const size_t lds = (size_t)2 * kRows * (pl.bno + pl.bko) * 2;
-  // the pending slab sum of this stream (a deferred earlier call) rides behind this launch's own workgroups; this call's own sum
-  // is left pending when the caller allows it (flags & 1) and deferral is on, else launched right behind the product
-  const SumArgs pend = pending;
-  pending = SumArgs{};
-  const int extra = pend.blocks > 0 ? pend.blocks : 0;
-#define UCD_WG_LAUNCH(BN_, BK_)                                                             \
-  {                                                                                         \
-    if (taps == 9) {                                                                        \
-      UCD_TRY_LDS((wgrad_kernel<BN_, BK_, true>), (int)lds);                                \
-      wgrad_kernel<BN_, BK_, true><<<grid + extra, kThreads, lds, s>>>(a, pend, grid);      \
-    } else {                                                                                \
-      UCD_TRY_LDS((wgrad_kernel<BN_, BK_, false>), (int)lds);                               \
-      wgrad_kernel<BN_, BK_, false><<<grid + extra, kThreads, lds, s>>>(a, pend, grid);     \
-    }                                                                                       \
-  }
-  if (three) {
-    a.chunks = p3.chunks; a.rows_per_chunk = p3.rows; a.tiles_n = p3.tiles_n; a.tiles_k = p3.tiles_k; a.ksplit = p3.ksplit;
-    const int grid3 = ceil_div(p3.chunks * p3.ksplit, 8) * 8 * p3.tiles_n * (p3.tiles_k / p3.ksplit) * 3;
-    if (kRows + 2 * dilation <= 96) {
-      UCD_TRY_LDS((wgrad3_kernel<3>), k3Stages * k3_stage_bytes(3));
-      wgrad3_kernel<3><<<grid3 + extra, k3Threads, k3Stages * k3_stage_bytes(3), s>>>(a, pend, grid3);
-    } else {
-      UCD_TRY_LDS((wgrad3_kernel<4>), k3Stages * k3_stage_bytes(4));
-      wgrad3_kernel<4><<<grid3 + extra, k3Threads, k3Stages * k3_stage_bytes(4), s>>>(a, pend, grid3);
-    }
-  } else if (str) {
-    if (taps == 9) {
-      UCD_TRY_LDS((wgrad_kernel<128, 128, true, true>), (int)lds);
-      wgrad_kernel<128, 128, true, true><<<grid + extra, kThreads, lds, s>>>(a, pend, grid);
-    } else {
-      UCD_TRY_LDS((wgrad_kernel<128, 128, false, true>), (int)lds);
-      wgrad_kernel<128, 128, false, true><<<grid + extra, kThreads, lds, s>>>(a, pend, grid);
-    }
-  } else if (pl.bno == 128 && pl.bko == 128) UCD_WG_LAUNCH(128, 128)
-  else if (pl.bno == 128) UCD_WG_LAUNCH(128, 64)
-  else if (pl.bko == 128) UCD_WG_LAUNCH(64, 128)
-  else UCD_WG_LAUNCH(64, 64)
-#undef UCD_WG_LAUNCH
-  int rc = check_launch(fn);
-  if (rc) return rc;
-  const SumArgs mine = make_sum(workspace, pl.chunks, total, dw, dw32, accumulate32);
-  if ((g_mode & 1) && (flags & 1)) {
-    pending = mine;
-    return 0;
-  }
-  wgrad_sum_kernel<<<mine.blocks, kThreads, 0, s>>>(mine);
-  return check_launch(fn);
-}
-
-}  // namespace
-}  // namespace ucd

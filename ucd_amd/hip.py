@@ -30,6 +30,8 @@ SEG_FORMS = {1: "pk<16,8>", 2: "pk<20,4>", 3: "pk<12,12>", 4: "reg<24,16>", 5: "
 PIXCON_PATHS = {1: "f32", 2: "f32/wide", 3: "f16/planned", 4: "f16/split"}
 # enum ucd_conv_form / UCD_CONV_FORM_NAMES (include/ucd_hip.h): the kernel form ucd_conv1x1_plan names
 CONV_FORMS = ("single", "2x64", "lw/128", "lw/256", "lw/64")
+# enum ucd_wgrad_form / UCD_WGRAD_FORM_NAMES (include/ucd_hip.h): the kernel form ucd_conv_wgrad_plan names
+WGRAD_FORMS = ("tile", "strided", "row3")
 PIXCON_PRECISION = {"f32": PIXCON_F32, "fp32": PIXCON_F32, "f16": PIXCON_F16, "fp16": PIXCON_F16,
                     "f16_split": PIXCON_F16_SPLIT}
 
@@ -64,6 +66,13 @@ class Conv1x1Plan(C.Structure):
     """Mirror of ``ucd_conv1x1_plan_t`` (include/ucd_hip.h)."""
     _fields_ = [(n, C.c_int) for n in ("form", "tile_rows", "tile_cols", "tiles_m", "tiles_n", "grid", "threads", "lds_bytes",
                                        "param_off")]
+
+
+class Conv_WgradPlan(C.Structure):
+    """Mirror of ``ucd_conv_wgrad_plan_t`` (include/ucd_hip.h)."""
+    _fields_ = [(n, C.c_int) for n in ("form", "tile_n", "tile_k", "tiles_n", "tiles_k", "chunks", "rows_per_chunk", "ksplit",
+                                       "x_tile_rows", "grid", "threads", "lds_bytes", "sum_lanes", "sum_blocks")] + \
+               [("workspace_bytes", C.c_size_t)]
 
 
 _p, _i, _f, _z = C.c_void_p, C.c_int, C.c_float, C.c_size_t
@@ -150,6 +159,7 @@ SIGNATURES = {
     "ucd_conv_wgrad_flush": (_i, [_p]),
     "ucd_conv_wgrad_drop": (_i, [_p]),
     "ucd_conv_wgrad_drop_all": (_i, []),
+    "ucd_conv_wgrad_plan": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(Conv_WgradPlan)]),
     "ucd_transpose_bf16": (_i, [_p, _i, _i, _p, _p]),
     "ucd_conv_f32": (_i, [_p, _i, _p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
     "ucd_conv_f32_wgrad_workspace_bytes": (_z, [_i, _i, _i, _i]),
@@ -873,6 +883,30 @@ def wgrad_drop_all():
 _wgrad_turn = {}
 
 
+def _wgrad_geometry(conv3, strided):
+    """(taps, H, W, dilation, stride) of ``conv_wgrad``'s ``conv3`` / ``strided`` arguments."""
+    H, W, d = (int(conv3[0]), int(conv3[1]), int(conv3[2])) if conv3 is not None else (0, 0, 1)
+    stride = 1
+    if conv3 is not None and len(conv3) > 3:
+        stride = int(conv3[3])
+    elif strided is not None:              # 1x1 with a stride: (H, W, stride) of the input map behind x
+        H, W, stride = int(strided[0]), int(strided[1]), int(strided[2])
+    return (9 if conv3 is not None else 1), H, W, d, stride
+
+
+def conv_wgrad_plan(M, N, K, conv3=None, strided=None):
+    """Host-only ``ucd_conv_wgrad_plan``: the kernel form, tile, row chunks, grid, threads, LDS bytes, slab sum and workspace bytes
+    ``conv_wgrad`` gives a [M, N] x [M, K] call with the same ``conv3`` / ``strided``, under the environment as it is NOW
+    (``UCD_WGRAD3``, ``UCD_WGRAD_TARGET``, ``UCD_WGRAD3_TARGET`` are read at every call).  Returns a dict of the fields of
+    ``ucd_conv_wgrad_plan_t`` with ``form`` as a name of :data:`WGRAD_FORMS`; raises what the call would raise for this shape.
+    Needs no GPU."""
+    p = Conv_WgradPlan()
+    _check(load().ucd_conv_wgrad_plan(int(M), int(N), int(K), *_wgrad_geometry(conv3, strided), C.byref(p)), "ucd_conv_wgrad_plan")
+    out = {n: getattr(p, n) for n, _ in Conv_WgradPlan._fields_}
+    out["form"] = WGRAD_FORMS[p.form]
+    return out
+
+
 def conv_wgrad(dz, x, dw=None, conv3=None, dw32=None, accumulate32=False, strided=None, defer=False, side=False):
     """Weight gradient of a stride-1 convolution (ucd_conv_wgrad): ``dz`` [M, N] and ``x`` [M, K] bf16 row matrices ->
     ``dw`` [N, taps * K] bf16 (channels-last weight order [N][kh][kw][K]) and / or ``dw32`` fp32 (+= when ``accumulate32``);
@@ -881,13 +915,7 @@ def conv_wgrad(dz, x, dw=None, conv3=None, dw32=None, accumulate32=False, stride
     lib = load()
     M, N = dz.shape
     K = x.shape[1]
-    taps = 9 if conv3 is not None else 1
-    H, W, d = (int(conv3[0]), int(conv3[1]), int(conv3[2])) if conv3 is not None else (0, 0, 1)
-    stride = 1
-    if conv3 is not None and len(conv3) > 3:
-        stride = int(conv3[3])
-    elif strided is not None:              # 1x1 with a stride: (H, W, stride) of the input map behind x
-        H, W, stride = int(strided[0]), int(strided[1]), int(strided[2])
+    taps, H, W, d, stride = _wgrad_geometry(conv3, strided)
     nbytes = lib.ucd_conv_wgrad_workspace_bytes(M, N, K, taps)
     # ``defer``: the caller does not read the gradient before the next weight-gradient call or wgrad_flush() - the library may then
     # carry this call's slab sum in the next launch (two slab buffers in turn: a call's slabs outlive the next call)
