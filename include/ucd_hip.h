@@ -695,6 +695,37 @@ int ucd_image_path(const uint8_t* const* src, const int* desc, int B, int S, int
                    float mean_b, float std_r, float std_g, float std_b, int* coeff_ws, uint8_t* tmp, float* out,
                    ucd_stream_t stream);
 
+/* ---- the validation transforms on the device: Resize + CenterCrop, and full size (run.py:58-73) ------------------
+ * The second geometry of the same pipeline: resize the WHOLE image [H0][W0] to (oh, ow), then cut the window
+ * [i, i + out_h) x [j, j + out_w) out of the result - Pillow's resize((ow, oh)) followed by crop().  The tables belong to
+ * the full axis H0 -> oh / W0 -> ow and are evaluated at the window's indices only; the horizontal pass runs over the
+ * source rows the vertical window reads.  Full-size validation is oh = H0, ow = W0, i = j = 0, out_h = H0, out_w = W0: the
+ * identity coefficients {1 << 22, 0} give the source byte back.  The output is rectangular and common to the batch.
+ *   src   B device pointers to decoded uint8 RGB images [H0_b][W0_b][3]
+ *   desc  int32 [B][8] in device memory: {H0, W0, oh, ow, i, j, 0, 0}.  The caller checks 0 <= i <= oh - out_h and
+ *         0 <= j <= ow - out_w (the descriptors are device memory: this library cannot); an image whose descriptor fails
+ *         that is skipped by every kernel - nothing of it is read and its part of the output is not written
+ *   kmax  >= ceil(max(1, H0 / oh, W0 / ow over the batch)) * 2 + 1
+ *   hmax  >= min(H0, floor((out_h - 1) * H0 / oh + 2 * max(1, H0 / oh)) + 2) over the batch: rows of the intermediate
+ *   scale_mode  ToTensor as 0: v / 255.f (the expression of ucd_image_path), 1: v * (1.f / 255.f) (what torch computes for a
+ *         tensor divided by the scalar 255 on the device); the two differ in the last bit for about half the byte values
+ *   coeff_ws int32 [B][out_h + out_w][kmax + 2];   tmp uint8 [B][hmax][out_w][3]
+ *   out   float32 [B][out_h][out_w][3] = the channels-last storage of the [B, 3, out_h, out_w] batch
+ * Checked on the host before any launch: UCD_EINVAL (a NULL pointer, B / out_h / out_w / hmax below 1, kmax below 3, B,
+ * out_h or hmax above 65535, an unknown scale_mode); else the hipError_t of a failed launch. */
+int ucd_val_image_path(const uint8_t* const* src, const int* desc, int B, int out_h, int out_w, int kmax, int hmax, int scale_mode,
+                       float mean_r, float mean_g, float mean_b, float std_r, float std_g, float std_b, int* coeff_ws, uint8_t* tmp,
+                       float* out, ucd_stream_t stream);
+
+/* Label half: Pillow's NEAREST resize((ow, oh)) + crop() + the step's table.  Pillow picks source indices by a running
+ * double sum from output index 0 of the full axis (xo = a / 2; idx = (int)xo; xo += a with a = in / out_full), so the tables
+ * are accumulated from 0 through off + out - 1 and kept from off on - not restarted at the window.
+ *   src, desc  as above, label maps [H0_b][W0_b] uint8;   lut  uint8 [256]
+ *   tables  int32 workspace [B][out_h + out_w];   out  int64 [B][out_h][out_w]
+ * UCD_EINVAL (a NULL pointer, B / out_h / out_w below 1, B or out_h above 65535) before any launch. */
+int ucd_val_label_path(const uint8_t* const* src, const int* desc, int B, int out_h, int out_w, const uint8_t* lut, int* tables,
+                       int64_t* out, ucd_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * 1x1 convolutions as row-matrix GEMMs on the bf16 matrix cores with the neighbouring ABN work fused (SURVEY.md
  * section 8-f4).  Replaces the cuDNN 1x1 convolutions of the bottleneck blocks and of the head -

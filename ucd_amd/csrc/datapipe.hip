@@ -54,15 +54,9 @@ __global__ __launch_bounds__(256) void label_gather_kernel(const uint8_t* const*
 // normalize_coeffs_8bpc, ImagingResampleHorizontal/Vertical_8bpc), pinned bit-for-bit by tests/golden.
 constexpr int kPrecisionBits = 22;
 
-// coefficient tables: co[b][axis][xx] = {xmin, count, k[0..kmax)}
-__global__ void image_coeff_kernel(const int* __restrict__ desc, int B, int S, int kmax, int* __restrict__ co) {
-  const int xx = blockIdx.x * blockDim.x + threadIdx.x;
-  const int axis = blockIdx.y, b = blockIdx.z;
-  if (xx >= S) return;
-  const int* d = desc + 8 * b;
-  const int in_size = axis == 0 ? d[4] : d[5];          // axis 0: vertical (h), axis 1: horizontal (w)
-  int* o = co + (((size_t)b * 2 + axis) * S + xx) * (kmax + 2);
-  const double scale = (double)in_size / (double)S;
+// one entry {xmin, count, k[0..kmax)} of a coefficient table: output index xx of the resize in_size -> out_size
+__device__ __forceinline__ void image_coeff_entry(int in_size, int out_size, int xx, int kmax, int* __restrict__ o) {
+  const double scale = (double)in_size / (double)out_size;
   const double filterscale = scale < 1.0 ? 1.0 : scale;
   const double support = 1.0 * filterscale;
   const double center = ((double)xx + 0.5) * scale;
@@ -91,6 +85,16 @@ __global__ void image_coeff_kernel(const int* __restrict__ desc, int B, int S, i
     }
     o[2 + x] = w < 0.0 ? (int)(-0.5 + w * (double)(1 << kPrecisionBits)) : (int)(0.5 + w * (double)(1 << kPrecisionBits));
   }
+}
+
+// coefficient tables: co[b][axis][xx] = {xmin, count, k[0..kmax)}
+__global__ void image_coeff_kernel(const int* __restrict__ desc, int B, int S, int kmax, int* __restrict__ co) {
+  const int xx = blockIdx.x * blockDim.x + threadIdx.x;
+  const int axis = blockIdx.y, b = blockIdx.z;
+  if (xx >= S) return;
+  const int* d = desc + 8 * b;
+  const int in_size = axis == 0 ? d[4] : d[5];          // axis 0: vertical (h), axis 1: horizontal (w)
+  image_coeff_entry(in_size, S, xx, kmax, co + (((size_t)b * 2 + axis) * S + xx) * (kmax + 2));
 }
 
 __device__ __forceinline__ int clip8(int v) {
@@ -149,6 +153,117 @@ __global__ __launch_bounds__(256) void image_vpass_kernel(const int* __restrict_
   q[2] = ((float)clip8(s2) / 255.f - m2) / d2;
 }
 
+// ---- validation geometry: resize the WHOLE image to (oh, ow), then cut the window [i, i + out_h) x [j, j + out_w) out of
+// it (Resize + CenterCrop, run.py:58-65; full size is oh = H0, ow = W0, i = j = 0).  Descriptor {H0, W0, oh, ow, i, j, 0, 0}.
+// The tables belong to the full axis in -> out_full and are kept for the window's indices only:
+// co[b] = {out_h vertical entries, out_w horizontal entries}, tables[b] = {out_h row indices, out_w column indices}.
+__device__ __forceinline__ bool val_desc_ok(const int* d, int out_h, int out_w) {
+  return d[0] > 0 && d[1] > 0 && d[4] >= 0 && d[5] >= 0 && d[4] <= d[2] - out_h && d[5] <= d[3] - out_w;
+}
+
+__global__ void val_label_tables_kernel(const int* __restrict__ desc, int B, int out_h, int out_w, int* __restrict__ tables) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= 2 * B) return;
+  const int b = t >> 1, axis = t & 1;                 // axis 0: rows, axis 1: columns
+  const int* d = desc + 8 * b;
+  if (!val_desc_ok(d, out_h, out_w)) return;
+  const int extent = d[axis], off = d[4 + axis], out = axis == 0 ? out_h : out_w;
+  const double a = (double)extent / (double)d[2 + axis];
+  double xo = a * 0.5;
+  int* tab = tables + (size_t)b * (out_h + out_w) + (axis == 0 ? 0 : out_h);
+  for (int x = 0; x < off + out; ++x) {               // Pillow's running sum starts at index 0 of the full axis
+    int v = (int)xo;
+    if (x >= off) tab[x - off] = v < extent ? v : extent - 1;
+    xo += a;
+  }
+}
+
+__global__ __launch_bounds__(256) void val_label_gather_kernel(const uint8_t* const* __restrict__ src,
+                                                               const int* __restrict__ desc, int out_h, int out_w,
+                                                               const uint8_t* __restrict__ lut, const int* __restrict__ tables,
+                                                               int64_t* __restrict__ out) {
+  const int b = blockIdx.z, y = blockIdx.y;
+  const int x = blockIdx.x * blockDim.x + threadIdx.x;
+  const int* d = desc + 8 * b;
+  if (x >= out_w || !val_desc_ok(d, out_h, out_w)) return;
+  const int* ytab = tables + (size_t)b * (out_h + out_w);
+  const int* xtab = ytab + out_h;
+  const uint8_t v = src[b][(size_t)ytab[y] * d[1] + xtab[x]];
+  out[((size_t)b * out_h + y) * out_w + x] = (int64_t)lut[v];
+}
+
+__global__ void val_image_coeff_kernel(const int* __restrict__ desc, int out_h, int out_w, int kmax, int* __restrict__ co) {
+  const int xx = blockIdx.x * blockDim.x + threadIdx.x;
+  const int axis = blockIdx.y, b = blockIdx.z;
+  const int* d = desc + 8 * b;
+  if (xx >= (axis == 0 ? out_h : out_w) || !val_desc_ok(d, out_h, out_w)) return;
+  int* o = co + ((size_t)b * (out_h + out_w) + (axis == 0 ? 0 : out_h) + xx) * (kmax + 2);
+  image_coeff_entry(d[axis], d[2 + axis], xx + d[4 + axis], kmax, o);
+}
+
+// horizontal pass over the source rows [r0, r1) the vertical window reads: tmp[b][r - r0][xx][c]
+__global__ __launch_bounds__(256) void val_image_hpass_kernel(const uint8_t* const* __restrict__ src, const int* __restrict__ desc,
+                                                              int out_h, int out_w, int kmax, const int* __restrict__ co,
+                                                              int hmax, uint8_t* __restrict__ tmp) {
+  const int b = blockIdx.z, r = blockIdx.y;
+  const int xx = blockIdx.x * blockDim.x + threadIdx.x;
+  const int* d = desc + 8 * b;
+  if (xx >= out_w || !val_desc_ok(d, out_h, out_w)) return;
+  const int* vco = co + (size_t)b * (out_h + out_w) * (kmax + 2);
+  const int* last = vco + (size_t)(out_h - 1) * (kmax + 2);
+  const int r0 = vco[0], r1 = last[0] + last[1];
+  if (r >= r1 - r0) return;
+  const int* o = vco + (size_t)(out_h + xx) * (kmax + 2);
+  const int xmin = o[0], cnt = o[1];
+  const uint8_t* row = src[b] + ((size_t)(r0 + r) * d[1] + xmin) * 3;
+  int s0 = 1 << (kPrecisionBits - 1), s1 = s0, s2 = s0;
+  for (int x = 0; x < cnt; ++x) {
+    const int k = o[2 + x];
+    s0 += (int)row[3 * x + 0] * k;
+    s1 += (int)row[3 * x + 1] * k;
+    s2 += (int)row[3 * x + 2] * k;
+  }
+  uint8_t* t = tmp + (((size_t)b * hmax + r) * out_w + xx) * 3;
+  t[0] = (uint8_t)clip8(s0);
+  t[1] = (uint8_t)clip8(s1);
+  t[2] = (uint8_t)clip8(s2);
+}
+
+// vertical pass + ToTensor + Normalize: out[b][yy][xx][c] (channels-last storage of [B, 3, out_h, out_w])
+template <bool kMul255>
+__global__ __launch_bounds__(256) void val_image_vpass_kernel(const int* __restrict__ desc, int out_h, int out_w, int kmax,
+                                                              const int* __restrict__ co, int hmax, const uint8_t* __restrict__ tmp,
+                                                              float m0, float m1, float m2, float d0, float d1, float d2,
+                                                              float* __restrict__ out) {
+  const int b = blockIdx.z, yy = blockIdx.y;
+  const int xx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (xx >= out_w || !val_desc_ok(desc + 8 * b, out_h, out_w)) return;
+  const int* vco = co + (size_t)b * (out_h + out_w) * (kmax + 2);
+  const int* o = vco + (size_t)yy * (kmax + 2);
+  const int r = o[0] - vco[0];                         // first row of this output row inside tmp[b]
+  const int cnt = r + o[1] <= hmax ? o[1] : hmax - r;  // hmax too small: stay inside tmp
+  const uint8_t* col = tmp + (((size_t)b * hmax + r) * out_w + xx) * 3;
+  int s0 = 1 << (kPrecisionBits - 1), s1 = s0, s2 = s0;
+  for (int y = 0; y < cnt; ++y) {
+    const int k = o[2 + y];
+    const uint8_t* p = col + (size_t)y * out_w * 3;
+    s0 += (int)p[0] * k;
+    s1 += (int)p[1] * k;
+    s2 += (int)p[2] * k;
+  }
+  float* q = out + (((size_t)b * out_h + yy) * out_w + xx) * 3;
+  if (kMul255) {                                       // torch's division of a tensor by the scalar 255: x * (1 / 255)
+    const float inv = 1.f / 255.f;
+    q[0] = ((float)clip8(s0) * inv - m0) / d0;
+    q[1] = ((float)clip8(s1) * inv - m1) / d1;
+    q[2] = ((float)clip8(s2) * inv - m2) / d2;
+  } else {
+    q[0] = ((float)clip8(s0) / 255.f - m0) / d0;
+    q[1] = ((float)clip8(s1) / 255.f - m1) / d1;
+    q[2] = ((float)clip8(s2) / 255.f - m2) / d2;
+  }
+}
+
 }  // namespace
 }  // namespace ucd
 
@@ -181,5 +296,45 @@ extern "C" int ucd_label_path(const uint8_t* const* src, const int* desc, int B,
   int rc = check_launch(fn);
   if (rc) return rc;
   label_gather_kernel<<<dim3(ceil_div(S, 256), S, B), 256, 0, s>>>(src, desc, S, lut, tables, out);
+  return check_launch(fn);
+}
+
+extern "C" int ucd_val_image_path(const uint8_t* const* src, const int* desc, int B, int out_h, int out_w, int kmax, int hmax,
+                                  int scale_mode, float mean_r, float mean_g, float mean_b, float std_r, float std_g, float std_b,
+                                  int* coeff_ws, uint8_t* tmp, float* out, ucd_stream_t stream) {
+  static const char* fn = "ucd_val_image_path";
+  UCD_REQUIRE(src && desc && coeff_ws && tmp && out && B > 0 && out_h > 0 && out_w > 0 && kmax >= 3 && hmax > 0, UCD_EINVAL,
+              "%s: bad arguments", fn);
+  UCD_REQUIRE(B <= 65535 && out_h <= 65535 && hmax <= 65535, UCD_EINVAL, "%s: B, out_h and hmax are grid extents (65535 at most)", fn);
+  UCD_REQUIRE(scale_mode == 0 || scale_mode == 1, UCD_EINVAL, "%s: scale_mode %d is neither 0 (v / 255) nor 1 (v * (1 / 255))", fn,
+              scale_mode);
+  hipStream_t s = (hipStream_t)stream;
+  const int omax = out_h > out_w ? out_h : out_w;
+  val_image_coeff_kernel<<<dim3(ceil_div(omax, 64), 2, B), 64, 0, s>>>(desc, out_h, out_w, kmax, coeff_ws);
+  int rc = check_launch(fn);
+  if (rc) return rc;
+  val_image_hpass_kernel<<<dim3(ceil_div(out_w, 256), hmax, B), 256, 0, s>>>(src, desc, out_h, out_w, kmax, coeff_ws, hmax, tmp);
+  rc = check_launch(fn);
+  if (rc) return rc;
+  const dim3 grid(ceil_div(out_w, 256), out_h, B);
+  if (scale_mode)
+    val_image_vpass_kernel<true><<<grid, 256, 0, s>>>(desc, out_h, out_w, kmax, coeff_ws, hmax, tmp, mean_r, mean_g, mean_b, std_r,
+                                                      std_g, std_b, out);
+  else
+    val_image_vpass_kernel<false><<<grid, 256, 0, s>>>(desc, out_h, out_w, kmax, coeff_ws, hmax, tmp, mean_r, mean_g, mean_b, std_r,
+                                                       std_g, std_b, out);
+  return check_launch(fn);
+}
+
+extern "C" int ucd_val_label_path(const uint8_t* const* src, const int* desc, int B, int out_h, int out_w, const uint8_t* lut,
+                                  int* tables, int64_t* out, ucd_stream_t stream) {
+  static const char* fn = "ucd_val_label_path";
+  UCD_REQUIRE(src && desc && lut && tables && out && B > 0 && out_h > 0 && out_w > 0, UCD_EINVAL, "%s: bad arguments", fn);
+  UCD_REQUIRE(B <= 65535 && out_h <= 65535, UCD_EINVAL, "%s: B and out_h are grid extents (65535 at most)", fn);
+  hipStream_t s = (hipStream_t)stream;
+  val_label_tables_kernel<<<ceil_div(2 * B, 64), 64, 0, s>>>(desc, B, out_h, out_w, tables);
+  int rc = check_launch(fn);
+  if (rc) return rc;
+  val_label_gather_kernel<<<dim3(ceil_div(out_w, 256), out_h, B), 256, 0, s>>>(src, desc, out_h, out_w, lut, tables, out);
   return check_launch(fn);
 }

@@ -10,6 +10,11 @@ of the whole batch is one ``ucd_label_path`` call on label maps that stay reside
 ``DeviceImagePath`` is the image half: crop + Pillow's BILINEAR resize (its 8-bit separable resampler with 22-bit
 fixed-point coefficients, bit-exact) + flip + ``ToTensor`` + ``Normalize`` (``transform.py:37-86``, ``run.py:49-55``) for
 decoded uint8 RGB images resident in HBM; JPEG decoding itself stays on the host.
+
+``DeviceValImagePath`` / ``DeviceValLabelPath`` are the validation transforms (``run.py:58-73``): ``Resize`` + ``CenterCrop``, or
+the full image.  Their geometry is the other way round - resize the whole image, then cut a window - so the coefficient and
+index tables belong to the full axis and only the window's entries are kept (``ucd_val_image_path``, ``ucd_val_label_path``);
+``resize_center_crop_params`` is the reference's size and offset arithmetic.
 """
 from __future__ import annotations
 
@@ -171,3 +176,97 @@ class DeviceImagePath:
         hip._check(hip.load().ucd_image_path(hip.ptr(ptrs), hip.ptr(desc), B, S, kmax, hmax, *self.mean, *self.std,
                                              hip.ptr(coeff), hip.ptr(tmp), hip.ptr(out), hip.stream()), "ucd_image_path")
         return out.permute(0, 3, 1, 2)            # [B, 3, S, S] with channels-last strides
+
+
+def resize_center_crop_params(height, width, size):
+    """``Resize(size)`` + ``CenterCrop(size)`` of run.py:58-65 as numbers: ``(oh, ow, i, j)`` - the smaller edge goes to ``size``
+    and the other to ``int(size * long / short)`` (transform.py ``Resize``), the window starts at
+    ``int(round((extent - size) / 2.0))`` (``CenterCrop``; Python's ``round``: halves go to the even neighbour)."""
+    if width <= height:
+        ow, oh = size, int(size * height / width)
+    else:
+        oh, ow = size, int(size * width / height)
+    return oh, ow, int(round((oh - size) / 2.0)), int(round((ow - size) / 2.0))
+
+
+def _val_descriptors(sources, params, out_hw, what):
+    """int32 [B][8] rows ``{H0, W0, oh, ow, i, j, 0, 0}`` of the validation geometry after the checks the library cannot make
+    (its descriptors live in device memory): every window lies inside its resized extent."""
+    out_h, out_w = int(out_hw[0]), int(out_hw[1])
+    if len(sources) == 0 or len(sources) != len(params) or out_h <= 0 or out_w <= 0:
+        raise ValueError(f"{len(sources)} {what}s, {len(params)} parameter tuples, output {(out_h, out_w)}")
+    rows = []
+    for m, (oh, ow, i, j) in zip(sources, params):
+        if not (0 <= i and 0 <= j and i + out_h <= oh and j + out_w <= ow):
+            raise ValueError(f"window {(i, j, out_h, out_w)} outside the resized extent {(oh, ow)} of a {tuple(m.shape)} {what}")
+        rows.append([m.shape[0], m.shape[1], oh, ow, i, j, 0, 0])
+    return torch.tensor(rows, dtype=torch.int32), out_h, out_w
+
+
+def _require_gpu(t):
+    if t.device.type != "cuda":
+        raise RuntimeError("ucd_amd.datapipe runs on the GPU only (there is no CPU fallback)")
+
+
+class DeviceValLabelPath:
+    """labels of a validation batch: ``__call__(label_maps, params, out_hw) -> int64 [B, out_h, out_w]`` on the device - Pillow's
+    NEAREST ``resize((ow, oh))`` + ``crop`` + the step's table as one ``ucd_val_label_path`` call.  ``label_maps``: list of uint8
+    device tensors [H0_b, W0_b]; ``params``: list of ``(oh, ow, i, j)`` (``resize_center_crop_params``; ``(H0, W0, 0, 0)`` with
+    ``out_hw = (H0, W0)`` is full-size validation)."""
+
+    def __init__(self, lut):
+        self.lut = lut
+
+    def __call__(self, label_maps, params, out_hw):
+        for m in label_maps:
+            if m.dtype != torch.uint8 or m.dim() != 2 or m.numel() == 0:
+                raise ValueError("label maps must be [H, W] uint8")
+        desc, out_h, out_w = _val_descriptors(label_maps, params, out_hw, "label map")
+        dev = label_maps[0].device
+        _require_gpu(label_maps[0])
+        B = len(label_maps)
+        maps = [m.contiguous() for m in label_maps]
+        lut = self.lut.to(dev)
+        desc = desc.to(dev, non_blocking=True)
+        ptrs = torch.tensor([m.data_ptr() for m in maps], dtype=torch.int64).to(dev, non_blocking=True)
+        tables = torch.empty(B * (out_h + out_w), dtype=torch.int32, device=dev)
+        out = torch.empty(B, out_h, out_w, dtype=torch.int64, device=dev)
+        hip._check(hip.load().ucd_val_label_path(hip.ptr(ptrs), hip.ptr(desc), B, out_h, out_w, hip.ptr(lut), hip.ptr(tables),
+                                                 hip.ptr(out), hip.stream()), "ucd_val_label_path")
+        return out
+
+
+class DeviceValImagePath:
+    """images of a validation batch: ``__call__(images, params, out_hw) -> float32 [B, 3, out_h, out_w]`` (channels-last storage)
+    on the device - Pillow's BILINEAR ``resize((ow, oh))`` + ``crop`` + ``ToTensor`` + ``Normalize`` as one ``ucd_val_image_path``
+    call, arguments as ``DeviceValLabelPath`` with ``images`` a list of uint8 device tensors [H0_b, W0_b, 3].  ``scale_mode``
+    picks the rounding of ``ToTensor``: 0 divides by 255 like ``DeviceImagePath``, 1 multiplies by the fp32 reciprocal like
+    torch's own ``div_(255.0)`` on the device."""
+
+    def __init__(self, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), scale_mode=0):
+        self.mean, self.std = tuple(float(v) for v in mean), tuple(float(v) for v in std)
+        self.scale_mode = int(scale_mode)
+
+    def __call__(self, images, params, out_hw):
+        for m in images:
+            if m.dtype != torch.uint8 or m.dim() != 3 or m.shape[2] != 3 or m.numel() == 0:
+                raise ValueError("images must be [H, W, 3] uint8 RGB")
+        desc, out_h, out_w = _val_descriptors(images, params, out_hw, "image")
+        dev = images[0].device
+        _require_gpu(images[0])
+        B = len(images)
+        imgs = [m.contiguous() for m in images]
+        scale = max(max(m.shape[0] / p[0], m.shape[1] / p[1]) for m, p in zip(imgs, params))
+        kmax = int(math.ceil(max(1.0, scale))) * 2 + 1
+        # rows of the intermediate: what the vertical window of out_h outputs can read (include/ucd_hip.h)
+        hmax = max(min(m.shape[0], int((out_h - 1) * (m.shape[0] / p[0]) + 2 * max(1.0, m.shape[0] / p[0])) + 2)
+                   for m, p in zip(imgs, params))
+        desc = desc.to(dev, non_blocking=True)
+        ptrs = torch.tensor([m.data_ptr() for m in imgs], dtype=torch.int64).to(dev, non_blocking=True)
+        coeff = torch.empty(B * (out_h + out_w) * (kmax + 2), dtype=torch.int32, device=dev)
+        tmp = torch.empty(B * hmax * out_w * 3, dtype=torch.uint8, device=dev)
+        out = torch.empty(B, out_h, out_w, 3, dtype=torch.float32, device=dev)
+        hip._check(hip.load().ucd_val_image_path(hip.ptr(ptrs), hip.ptr(desc), B, out_h, out_w, kmax, hmax, self.scale_mode,
+                                                 *self.mean, *self.std, hip.ptr(coeff), hip.ptr(tmp), hip.ptr(out), hip.stream()),
+                   "ucd_val_image_path")
+        return out.permute(0, 3, 1, 2)            # [B, 3, out_h, out_w] with channels-last strides

@@ -13,8 +13,9 @@ re-ordering - split where the hardware wants it:
   (``ucd_amd.datapipe``: bit-exact against Pillow / the reference's per-pixel lambda).  The reference does all of it per sample
   on the host with ``num_workers=0`` (37 img/s measured against 142 846 on the device, tests/diag/datapipe_bench.py).
 
-Validation with ``--crop_val`` (``Resize`` + ``CenterCrop``, run.py:58-65) resizes on the host with Pillow (exact by
-construction) and normalises on the device.  ADE20K (dataset/ade.py) and Cityscapes (dataset/cityscape.py) follow the same
+Validation (``Resize`` + ``CenterCrop`` with ``--crop_val``, run.py:58-65, or the full image, :66-73) runs on the device as well:
+the second geometry of the same Pillow restatement, resize the whole image and cut a window (``ucd_val_image_path``,
+``ucd_val_label_path``; ``UCD_VAL_DEVICE=0`` resizes on the host with Pillow instead).  ADE20K (dataset/ade.py) and Cityscapes (dataset/cityscape.py) follow the same
 split: their listings, filters and label tables are mirrored here (the Cityscapes raw-id -> class table is composed with the
 step's table into ONE device gather).  ``DeviceLoader`` puts the decode into DataLoader worker processes.
 """
@@ -27,7 +28,7 @@ import numpy as np
 import torch
 import torch.utils.data as data
 
-from . import datapipe
+from . import datapipe, switches
 
 
 def _open_rgb(path):
@@ -292,8 +293,11 @@ class DeviceBatcher:
     train:  RandomResizedCrop(S, (0.5, 2.0)) + RandomHorizontalFlip + ToTensor + Normalize   (run.py:49-55) - parameters
             drawn on the host exactly like dataset/transform.py (``random`` module, per sample: crop box, then flip coin),
             pixels on the device;
-    val:    Resize(S) + CenterCrop(S) + ToTensor + Normalize when ``crop`` (run.py:58-65; Pillow on the host, then the device
-            path with the identity box), else ToTensor + Normalize on the full image (batch size 1, run.py:66-73)."""
+    val:    Resize(S) + CenterCrop(S) + ToTensor + Normalize when ``crop`` (run.py:58-65), else ToTensor + Normalize on the full
+            image (batch size 1, run.py:66-73) - raw samples copied like the train branch, one ``ucd_val_image_path`` and one
+            ``ucd_val_label_path`` call per batch (``datapipe.DeviceValImagePath`` / ``DeviceValLabelPath``).  ``UCD_VAL_DEVICE=0``
+            keeps the earlier form, same bits: Pillow on the host per sample, then the train path with the identity box; torch
+            element-wise launches for the full image."""
 
     def __init__(self, device, size, lut, train=True, crop=True, scale=(0.5, 2.0), mean=(0.485, 0.456, 0.406),
                  std=(0.229, 0.224, 0.225)):
@@ -302,6 +306,21 @@ class DeviceBatcher:
         self.images = datapipe.DeviceImagePath(self.size, mean, std)
         self.labels = datapipe.DeviceLabelPath(self.size, lut)
         self.mean, self.std, self.lut = mean, std, lut
+        # validation on the device: the cropped batch rounds ToTensor like DeviceImagePath, the full-size batch like torch's
+        # div_(255.0) (scale_mode 1) - bit for bit what UCD_VAL_DEVICE=0 computes in either branch
+        self.val_images = datapipe.DeviceValImagePath(mean, std, scale_mode=0 if crop else 1)
+        self.val_labels = datapipe.DeviceValLabelPath(lut)
+
+    def _validation_on_device(self, samples):
+        dev, S = self.device, self.size
+        if self.crop:
+            params, out_hw = [datapipe.resize_center_crop_params(img.shape[0], img.shape[1], S) for img, _ in samples], (S, S)
+        else:                                                        # full size: the loader hands out one sample (run.py:66-73)
+            H, W = samples[0][0].shape[:2]
+            params, out_hw = [(img.shape[0], img.shape[1], 0, 0) for img, _ in samples], (H, W)
+        imgs = [s[0].to(dev, non_blocking=True) for s in samples]
+        labs = [s[1].to(dev, non_blocking=True) for s in samples]
+        return self.val_images(imgs, params, out_hw), self.val_labels(labs, params, out_hw)
 
     def __call__(self, samples):
         dev, S = self.device, self.size
@@ -313,7 +332,9 @@ class DeviceBatcher:
             imgs = [s[0].to(dev, non_blocking=True) for s in samples]
             labs = [s[1].to(dev, non_blocking=True) for s in samples]
             return self.images(imgs, boxes, flips), self.labels(labs, boxes, flips)
-        if self.crop:
+        if switches.get("UCD_VAL_DEVICE") == "1":
+            return self._validation_on_device(samples)
+        if self.crop:                                                # UCD_VAL_DEVICE=0: Pillow on the host, per sample
             from PIL import Image
             imgs, labs = [], []
             for img, lab in samples:
