@@ -917,17 +917,13 @@ int ucd_stem_pool_backward(const void* z, const void* dpool, const uint8_t* idx,
  * run the three-tap form (one kernel row per workgroup, round 4); UCD_WGRAD3=0 in the environment keeps the 9-tap form for them
  * (both are exact on integer operands and agree bit for bit there: tests/test_conv1x1_fused_gpu.py). */
 size_t ucd_conv_wgrad_workspace_bytes(int M, int N, int K, int taps);
-int ucd_conv_wgrad(const void* dz, int ld_dz, const void* x, int ld_x, int M, int N, int K, int taps, int H, int W, int dilation,
-                   void* dw, float* dw32, int accumulate32, void* workspace, size_t workspace_bytes, ucd_stream_t stream);
-/* The same for the strided layers (modules/residual.py:57-73 conv2 with stride 2, :79 proj_conv 1x1 stride 2): x is the
- * [B, H, W, K] input map, dz the [M = B*OH*OW][N] output gradient with OH = (H - 1) / stride + 1; N and K multiples of 128.
- * stride <= 1 is ucd_conv_wgrad. */
-int ucd_conv_wgrad_strided(const void* dz, int ld_dz, const void* x, int ld_x, int M, int N, int K, int taps, int H, int W,
-                           int dilation, int stride, void* dw, float* dw32, int accumulate32, void* workspace, size_t workspace_bytes,
-                           ucd_stream_t stream);
-/* Round 6: the slab sum of a weight gradient may be DEFERRED into the next weight-gradient launch on the same stream (it rides as
- * extra workgroups behind that product's own: no launch, no kernel boundary; bit-identical result).  ucd_conv_wgrad_ex = the call
- * above plus flags: bit 0 = the caller does not read dw / dw32, nor reuses `workspace`, before the next ucd_conv_wgrad* call on
+/* The entry point is ucd_conv_wgrad_ex (below), with stride <= 1 and flags 0 for the plain call described above.  stride > 1: the
+ * strided layers (modules/residual.py:57-73 conv2 with stride 2, :79 proj_conv 1x1 stride 2): x is the [B, H, W, K] input map, dz
+ * the [M = B*OH*OW][N] output gradient with OH = (H - 1) / stride + 1; N and K multiples of 128.
+ *
+ * Round 6: the slab sum of a weight gradient may be DEFERRED into the next weight-gradient launch on the same stream (it rides as
+ * extra workgroups behind that product's own: no launch, no kernel boundary; bit-identical result).
+ * flags: bit 0 = the caller does not read dw / dw32, nor reuses `workspace`, before the next ucd_conv_wgrad* call on
  * this stream or ucd_conv_wgrad_flush(stream).  Deferral happens only while ucd_conv_wgrad_defer(1) is in force (returns the
  * previous setting; the gradient-bucket wrapper switches it on for its backward passes and flushes in front of its bucket copies);
  * ucd_conv_wgrad_flush launches the stream's pending sum, ucd_conv_wgrad_drop forgets it (an aborted backward).  The autograd

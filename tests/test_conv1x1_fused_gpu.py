@@ -368,7 +368,7 @@ def test_conv3x3_implicit_gemm_mode(B, K, N, H, W, d):
 def test_residual_block_training_with_own_3x3(cin, chans, dil, hw):
     """Training forward + backward with the 3x3 convolution + ABN as one node on the implicit-GEMM kernel (forward with the
     statistics epilogue, input gradient on the cached flipped weight) against the module path (MIOpen + separate ABN): wide and
-    narrow bottlenecks, B large enough for the own kernel to be chosen.  Both are bf16 implementations of the same block, so
+    narrow bottlenecks.  Both are bf16 implementations of the same block, so
     the yardstick is the fp32 run of the block: the fused path must not be further from it than the module path is (every
     stored map differs by bf16 rounding, which flips the leaky-ReLU branch of the elements nearest zero in each of the
     three normalisations - a few percent on the input gradient for either path)."""
@@ -377,7 +377,7 @@ def test_residual_block_training_with_own_3x3(cin, chans, dil, hw):
     from ucd_amd.ddp import DistributedDataParallel
     norm = partial(abn.InPlaceABNSync, activation="leaky_relu", activation_param=0.01)
     B, H, W = 24, hw, hw
-    assert blocks._own_conv3x3(B * H * W, chans[0], chans[1])
+    assert chans[0] % 64 == 0 and chans[1] % 64 == 0          # what the own 3x3 kernel asks of a layer (blocks._conv_abn_route)
     x0 = synth.t_normal(9, (B, cin, H, W), stream=1).to(DEV).bfloat16().contiguous(memory_format=torch.channels_last)
     dy = synth.t_normal(10, (B, chans[2], H, W), stream=1).to(DEV).bfloat16().contiguous(memory_format=torch.channels_last)
     outs = []
@@ -1011,7 +1011,7 @@ def _strided_ref(x4, w4, taps, d):
 @pytest.mark.parametrize("B,H,W,K,N,taps,d", STRIDED_CASES)
 def test_strided_forward_statistics_and_weight_gradient(B, H, W, K, N, taps, d):
     """ucd_conv1x1 with stride 2 (the 1x1 row gather and the 3x3 implicit GEMM over the strided pixels) and
-    ucd_conv_wgrad_strided against F.conv2d / its weight gradient: exact on sparse small integers (every sum an exactly
+    the strided weight gradient (ucd_conv_wgrad_ex, stride 2) against F.conv2d / its weight gradient: exact on sparse small integers (every sum an exactly
     representable integer), then at bf16 rounding on random operands; the out_mode-2 partials give the batch statistics of the
     strided product."""
     from ucd_amd import hip

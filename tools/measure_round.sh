@@ -12,8 +12,6 @@ brief() { python -c "import sys,json; d=json.loads(sys.stdin.read().strip().spli
   for v in 0 1; do UCD_WGRAD_DEFER=$v timeout 300 python bench.py --steps 20 --warmup 6 --no_cpu_baseline --no_kernel_timing 2>/dev/null | brief "rep $rep 24 images UCD_WGRAD_DEFER=$v"; done
   for v in 0 1; do UCD_WGRAD_DEFER=$v timeout 300 python bench.py --steps 20 --warmup 6 --global_batch 3 --no_cpu_baseline --no_kernel_timing 2>/dev/null | brief "rep $rep 3 images UCD_WGRAD_DEFER=$v"; done
   for v in 0 128; do UCD_CONV_LW64_TILES=$v timeout 300 python bench.py --steps 20 --warmup 6 --global_batch 3 --no_cpu_baseline --no_kernel_timing 2>/dev/null | brief "rep $rep 3 images UCD_CONV_LW64_TILES=$v"; done
-  for v in 8192 0; do UCD_CONV3_MIN_ROWS=$v timeout 300 python bench.py --steps 20 --warmup 6 --global_batch 3 --no_cpu_baseline --no_kernel_timing 2>/dev/null | brief "rep $rep 3 images UCD_CONV3_MIN_ROWS=$v"; done
-  for v in 8192 0; do UCD_CONV3_MIN_ROWS=$v timeout 300 python bench.py --steps 20 --warmup 6 --global_batch 6 --no_cpu_baseline --no_kernel_timing 2>/dev/null | brief "rep $rep 6 images UCD_CONV3_MIN_ROWS=$v"; done
 done) > $O/kernel_ab.txt 2>&1
 # the multi-rank step with its collectives, as far as one GPU can run it: eager first, then captured (bench.py --force_dist)
 (for gb in 3 6 12; do timeout 400 python bench.py --force_dist --steps 16 --warmup 6 --global_batch $gb --no_cpu_baseline --no_kernel_timing 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('--force_dist global_batch $gb', 'ms_per_step', round(d['ms_per_step'],3), 'eager_ms', d['execution']['eager_ms'], 'graph_ms', d['execution']['graph_ms'], d['execution']['step_graph_error'])"; done) > $O/forced_collectives.txt 2>&1

@@ -20,7 +20,6 @@ fall back to the literal op sequence of the reference.
 """
 from __future__ import annotations
 
-import os
 from collections import OrderedDict
 from typing import NamedTuple
 
@@ -51,7 +50,7 @@ def _env(name, default):
 
 
 def _own_wgrad() -> bool:
-    """Weight gradients on the own kernel (csrc/wgrad.hip: ucd_conv_wgrad) instead of MIOpen's weight-gradient solvers / the
+    """Weight gradients on the own kernel (csrc/wgrad.hip: ucd_conv_wgrad_ex) instead of MIOpen's weight-gradient solvers / the
     batched split-M library products; ``UCD_OWN_WGRAD=0`` restores those (the A/B reference of the tests and probes)."""
     return _env("UCD_OWN_WGRAD", "1") != "0"
 
@@ -131,6 +130,29 @@ class Conv2d(nn.Conv2d):
         return self._conv_forward(x, w, self.bias)
 
 
+def _rows(t):
+    """[B, C, H, W] map -> its [B*H*W, C] row matrix.  A view only of a dense channels-last map: every caller has checked that
+    layout, or made it (``.contiguous(memory_format=torch.channels_last)``), before it hands the rows to a kernel that writes them."""
+    return t.permute(0, 2, 3, 1).reshape(t.shape[0] * t.shape[2] * t.shape[3], t.shape[1])
+
+
+def _w16(conv, x):
+    """The layer's weight in the dtype of its input ``x``: the bf16 working copy where one is attached and autocast is on
+    (``Conv2d.working_weight``), else a per-call cast of the master weight."""
+    w = conv.working_weight()
+    return w if w is not None else conv.weight.to(x.dtype)
+
+
+def _cached_flip(conv):
+    """The flipped / transposed twin ucd_amd.master.Bf16Weights keeps next to the working copy, when that copy is the weight in use."""
+    return conv._w16_flip if conv.working_weight() is not None else None
+
+
+def _w_matrix(w):
+    """[N, K, k, k] weight in channels-last memory order -> its [N, k k K] matrix (tap-major; [N, 9 K] of a 3x3 layer), a view."""
+    return _rows(w).reshape(w.shape[0], -1)
+
+
 def try_index(scalar_or_list, i):
     """``x[i]`` when indexable, else ``x`` (reference ``models/util.py:1-5``)."""
     try:
@@ -188,7 +210,6 @@ def _conv_wgrad(dz, x, w4, d, route, fallback, lib=None):
     short to split run on ``lib``'s hipBLASLt entry point, or through torch when it is None.  The gradient has the weight's sizes,
     in the weight's own memory order on the own and split routes."""
     N, K, k = w4.shape[0], w4.shape[1], w4.shape[2]
-    rows = lambda t: t.permute(0, 2, 3, 1).reshape(t.shape[0] * t.shape[2] * t.shape[3], t.shape[1])
     if route == WGRAD_OWN:
         if x.dim() == 2:
             ok = x.is_contiguous()
@@ -205,11 +226,11 @@ def _conv_wgrad(dz, x, w4, d, route, fallback, lib=None):
             if not dz.is_contiguous(memory_format=torch.channels_last):
                 dz = dz.contiguous(memory_format=torch.channels_last)
             H, W = x.shape[2], x.shape[3]
-            hip.conv_wgrad(rows(dz), rows(x), dw, conv3=(H, W, d) if k == 3 else None)
+            hip.conv_wgrad(_rows(dz), _rows(x), dw, conv3=(H, W, d) if k == 3 else None)
             return dw.view(N, k, k, K).permute(0, 3, 1, 2)
         route = fallback
     if route == WGRAD_SPLIT and k == 1:
-        dzr, xr = (dz, x) if x.dim() == 2 else (rows(dz), rows(x))
+        dzr, xr = (dz, x) if x.dim() == 2 else (_rows(dz), _rows(x))
         M = dzr.shape[0]
         S = _wgrad_split(M)
         if S > 1:      # K = B*H*W is long: 8 batched chunks + a sum beat every single-kernel candidate (41 vs 96 us)
@@ -230,8 +251,7 @@ def _own3x3(x, w, d):
     B, K, H, W = x.shape
     N = w.shape[0]
     y = torch.empty((B, N, H, W), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
-    rows = lambda t: t.permute(0, 2, 3, 1).reshape(t.shape[0] * t.shape[2] * t.shape[3], t.shape[1])
-    hip.conv1x1(rows(x), w.permute(0, 2, 3, 1).reshape(N, 9 * K), rows(y), conv3=(H, W, d))
+    hip.conv1x1(_rows(x), _w_matrix(w), _rows(y), conv3=(H, W, d))
     return y
 
 
@@ -298,9 +318,7 @@ def _f32_conv_ok(conv, x):
 
 def _f32_rows(t):
     """[B, C, H, W] fp32 map -> its channels-last [B*H*W, C] row matrix (a view of a channels-last tensor, else a copy)."""
-    if not t.is_contiguous(memory_format=torch.channels_last):
-        t = t.contiguous(memory_format=torch.channels_last)
-    return t.permute(0, 2, 3, 1).reshape(t.shape[0] * t.shape[2] * t.shape[3], t.shape[1])
+    return _rows(t.contiguous(memory_format=torch.channels_last))
 
 
 def _f32_conv_fwd(x, w, d):
@@ -309,7 +327,7 @@ def _f32_conv_fwd(x, w, d):
     B, K, H, W = x.shape
     N = w.shape[0]
     y = torch.empty((B, N, H, W), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
-    wm = w.permute(0, 2, 3, 1).reshape(N, -1)            # [N, taps K] in the weight's channels-last order
+    wm = _w_matrix(w)                                    # [N, taps K] in the weight's channels-last order
     if wm.stride(1) != 1 or (wm.data_ptr() & 15):
         wm = wm.contiguous()
     hip.conv_f32(_f32_rows(x), wm, _f32_rows(y), conv3=(H, W, d) if d > 0 else None)
@@ -371,22 +389,15 @@ class Conv3x3(Conv2d):
     def forward(self, x):
         if _f32_conv_ok(self, x):
             return _f32_conv(self, x)
-        M = x.shape[0] * x.shape[2] * x.shape[3] if x.dim() == 4 else 0
+        # forward and input gradient on the own kernel wherever the layout allows it
         own = _own3x3_ok(self, x) and self.weight.is_contiguous(memory_format=torch.channels_last)
         if (x.is_cuda and torch.is_grad_enabled() and self.weight.requires_grad and self.bias is None
-                and x.dtype == torch.bfloat16 and M >= int(_env("UCD_CONV3_MIN_ROWS", "0")) and _env("UCD_DGRAD_VIA_FWD", "1") != "0"):
-            own_fwd = own and _own_conv3x3(M, self.in_channels, self.out_channels)
-            own_dgrad = own and _own_conv3x3(M, self.out_channels, self.in_channels)
-            w = self.working_weight()
-            if w is None:
-                w = self.weight.to(x.dtype)
-                return _stride_one_conv(x, w, self.dilation[0], None, own_fwd and w.is_contiguous(memory_format=torch.channels_last),
-                                        own_dgrad)
-            return _stride_one_conv(x, w, self.dilation[0], self._w16_flip, own_fwd, own_dgrad)
-        if own and not torch.is_grad_enabled() and _own_conv3x3(M, self.in_channels, self.out_channels):
-            w = self.working_weight()                      # the frozen teacher's ASPP branches
-            if w is None:
-                w = self.weight.to(x.dtype)
+                and x.dtype == torch.bfloat16 and _env("UCD_DGRAD_VIA_FWD", "1") != "0"):
+            w = _w16(self, x)               # the working copy has the master weight's layout; so has a cast
+            return _stride_one_conv(x, w, self.dilation[0], _cached_flip(self),
+                                    own and w.is_contiguous(memory_format=torch.channels_last), own)
+        if own and not torch.is_grad_enabled():
+            w = _w16(self, x)                              # the frozen teacher's ASPP branches
             if w.is_contiguous(memory_format=torch.channels_last):
                 return _own3x3(x, w, self.dilation[0])
         return super().forward(x)
@@ -426,25 +437,19 @@ class Conv1x1(Conv2d):
             if (x.is_cuda and x.dim() == 4 and x.dtype == torch.bfloat16 and torch.is_grad_enabled() and self.bias is None
                     and self.weight.requires_grad and x.shape[0] * x.shape[2] * x.shape[3] >= 8192
                     and _env("UCD_DGRAD_VIA_FWD", "1") != "0"):
-                w = self.working_weight()
-                if w is None:
-                    return _stride_one_conv(x, self.weight.to(x.dtype), 1)
-                return _stride_one_conv(x, w, 1, self._w16_flip)                                  # narrow layer: MIOpen
+                return _stride_one_conv(x, _w16(self, x), 1, _cached_flip(self))                  # narrow layer: MIOpen
             return super().forward(x)
         B, C, H, W = x.shape
-        rows = x.permute(0, 2, 3, 1)                      # a view of a channels-last tensor
-        if not rows.is_contiguous():
-            rows = rows.contiguous()
-        rows = rows.reshape(B * H * W, C)
-        w16 = self.working_weight()
+        rows = _rows(x.contiguous(memory_format=torch.channels_last))      # a view of a channels-last tensor
         if self.bias is None and rows.dtype != torch.float32 and torch.is_grad_enabled() and self.weight.requires_grad:
-            w4 = w16 if w16 is not None else self.weight.to(rows.dtype)
+            w4 = _w16(self, rows)
             node = _gemm_node() if rows.dtype == torch.bfloat16 else None
             if node is not None:          # same library calls, autograd node in C++ (host time per layer 71 -> ~25 us)
                 y = node.gemm1x1(rows, w4, _hip_stream(), _own_wgrad())
             else:
                 y = _Gemm1x1.apply(rows, w4)
         else:
+            w16 = self.working_weight()
             w = w16 if (w16 is not None and rows.dtype == w16.dtype) else self.weight
             w = w.reshape(self.out_channels, C)
             if self.bias is None and not torch.is_grad_enabled() and rows.dtype == torch.bfloat16:
@@ -465,29 +470,14 @@ def _conv1_with_skip(conv, x):
     if node is None or not hasattr(node, "gemm1x1_skip"):
         return None
     B, C, H, W = x.shape
-    rows = x.permute(0, 2, 3, 1)
-    if not rows.is_contiguous():
+    if not x.is_contiguous(memory_format=torch.channels_last):
         return None
-    w16 = conv.working_weight()
-    y, skip = node.gemm1x1_skip(rows.reshape(B * H * W, C), w16 if w16 is not None else conv.weight.to(x.dtype), _hip_stream(),
-                                _own_wgrad())
+    y, skip = node.gemm1x1_skip(_rows(x), _w16(conv, x), _hip_stream(), _own_wgrad())
     return (y.view(B, H, W, conv.out_channels).permute(0, 3, 1, 2), skip.view(B, H, W, C).permute(0, 3, 1, 2))
 
 
 def _is_fused_abn(m) -> bool:
     return getattr(m, "ucd_fused_abn", False)
-
-
-def _own_gemm_with_stats(K, N):
-    """Forward kernel choice of a conv + training-ABN pair, from tools/conv1x1_probe.py on MI355X (M = 26 136,
-    profiles/r03_conv1x1_probe.txt): the fused GEMM with the statistics epilogue costs its plain time + 1-6 us; the tuned library
-    GEMM needs a statistics pass over its output on top (11-30 us).  Since the staging loads go through buffer descriptors the own
-    kernel is level or ahead on every layer of the network, the two large products included (2048 -> 512: 59.6 against 43.5 + 16;
-    1024 -> 2048: 110.8 against 93.1 + 30), so every aligned 1x1 layer takes it; ``UCD_LIB_GEMM_WIDE=1`` restores the library
-    for those two (A/B)."""
-    if _env("UCD_LIB_GEMM_WIDE", "0") == "1":
-        return not (K * N >= (1 << 20) and K >= 1024)
-    return True
 
 
 def _own_stride(conv):
@@ -503,20 +493,6 @@ def _own_stride(conv):
     if conv.kernel_size == (3, 3) and conv.padding == conv.dilation and conv.dilation[0] == conv.dilation[1]:
         return conv.stride[0]
     return 0
-
-
-def _own_conv3x3(M, K, N):
-    """The implicit-GEMM 3x3 (csrc/conv1x1.hip, taps = 9) instead of MIOpen: measured on MI355X (tools/conv3x3_probe.py,
-    B = 24, profiles/r03_conv3x3_probe.txt): 256->256 at 33^2 40 vs 58 us, 512->512 (dilation 2) 132 vs 142, 128->128 at 65^2
-    42 vs 48, 64->64 at 129^2 51 vs 63, the ASPP branches 229-252 vs 386-391 - and the following ABN's statistics for +1 us
-    instead of a separate pass.  Maps too small to give every CU a tile (3-12 images per GPU, the multi-GPU split of the batch) take
-    it as well: the kernel alone is level with MIOpen's there (23 vs 27 us at 3 images) but the step saves MIOpen's weight-gradient
-    zero fills / casts and the separate statistics passes - kernel time per step 16.0 -> 14.3 ms at 3 images, 20.0 -> 17.5 at 6
-    (profiles/r03_small_batch.txt).  ``UCD_OWN3X3_MIN_TILES=256`` restores the library below 256 tiles (A/B)."""
-    tiles = ((M + 127) // 128) * max(1, N // 128)
-    if K >= 512 and N >= 512 and _env("UCD_OWN3X3_WIDE", "1") == "0":      # A/B switch: the 512 -> 512 layers on MIOpen
-        return False
-    return tiles >= int(_env("UCD_OWN3X3_MIN_TILES", "1"))
 
 
 LINK_CHAIN, LINK_BLOCK = 1, 3     # csrc/abn_node.cpp Link::Kind
@@ -550,35 +526,25 @@ class _ConvABNFunction(torch.autograd.Function):
     The complete implementation and the fallback; bench.py's instrumented pass runs it (every library call visible)."""
 
     @staticmethod
-    def forward(ctx, x, w4, weight, bias, residual, running_mean, running_var, momentum, eps, act, slope, fused, dilation=0,
-                wflip=None, own_dgrad=False, wgrad_conv=False, make_link=False, link=None, with_skip=False):
+    def forward(ctx, x, w4, weight, bias, residual, running_mean, running_var, momentum, eps, act, slope, dilation=0, wflip=None,
+                own_dgrad=False, wgrad_conv=False, make_link=False, link=None, with_skip=False):
         from . import hip
         B, K, H, W = x.shape
         N = w4.shape[0]
         M, HW = B * H * W, H * W
-        rows = lambda t: t.permute(0, 2, 3, 1).reshape(t.shape[0] * t.shape[2] * t.shape[3], t.shape[1])
         z = torch.empty((B, N, H, W), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
         y = torch.empty_like(z)
         buf = torch.empty(6 * N, dtype=torch.float32, device=x.device)
         conv3 = dilation > 0
-        w2 = w4.permute(0, 2, 3, 1).reshape(N, 9 * K) if conv3 else w4.reshape(N, K)
+        w2 = _w_matrix(w4) if conv3 else w4.reshape(N, K)
         ctx.conv3 = (dilation, wflip, own_dgrad, wgrad_conv)
         ctx.link = link                                 # the Link consumed (see ConvABNTrainNode), or None
         ctx.my_link = None
-        if conv3 and not fused:
-            z = F.conv2d(x, w4, None, 1, dilation, dilation).contiguous(memory_format=torch.channels_last)
-            hip.abn_forward(z, N, y, N, residual, N if residual is not None else 0, M, N, None, HW, weight, bias, running_mean,
-                            running_var, momentum, eps, True, buf, None, act, slope)
-        elif fused:
-            part = hip.conv1x1_stats_partial(M, N, x.device)
-            hip.conv1x1(rows(x), w2, rows(z), out_mode=2, partial=part, conv3=(H, W, dilation) if conv3 else None)
-            hip.conv1x1_stats_finalize(part, M, N, weight, running_mean, running_var, momentum, eps, buf, None, act)
-            hip.abn_apply(z, N, y, N, residual, N if residual is not None else 0, M, N, None, HW, buf[3 * N:4 * N], buf[5 * N:],
-                          bias, act, slope)
-        else:
-            hip.gemm_bf16(0, rows(x), w2, rows(z))
-            hip.abn_forward(z, N, y, N, residual, N if residual is not None else 0, M, N, None, HW, weight, bias, running_mean,
-                            running_var, momentum, eps, True, buf, None, act, slope)
+        part = hip.conv1x1_stats_partial(M, N, x.device)
+        hip.conv1x1(_rows(x), w2, _rows(z), out_mode=2, partial=part, conv3=(H, W, dilation) if conv3 else None)
+        hip.conv1x1_stats_finalize(part, M, N, weight, running_mean, running_var, momentum, eps, buf, None, act)
+        hip.abn_apply(z, N, y, N, residual, N if residual is not None else 0, M, N, None, HW, buf[3 * N:4 * N], buf[5 * N:],
+                      bias, act, slope)
         needs_y = residual is not None and (act & hip.ACT_MASK) != hip.ACT_IDENTITY
         ctx.save_for_backward(x, w4, z, y if needs_y else None, weight, bias, buf)
         ctx.cfg = (act, slope, residual is not None)
@@ -598,7 +564,6 @@ class _ConvABNFunction(torch.autograd.Function):
         B, K, H, W = x.shape
         N = w4.shape[0]
         M, HW = B * H * W, H * W
-        rows = lambda t: t.permute(0, 2, 3, 1).reshape(t.shape[0] * t.shape[2] * t.shape[3], t.shape[1])
         if ctx.my_link is not None and ctx.my_link[1][0] == 1 and (dy.data_ptr() != ctx.my_link[1][1]
                                                                    or dy._version != ctx.my_link[1][2]):
             ctx.my_link[1][0] = 0
@@ -632,10 +597,10 @@ class _ConvABNFunction(torch.autograd.Function):
             link.flag[:3] = 1, dx.data_ptr(), dx._version
             mean, invstd = link.buf[3 * C:4 * C], link.buf[4 * C:5 * C]
             if link.kind == LINK_BLOCK:        # out_mode 4 against the block in front
-                return dict(out_mode=4, out_norm=(mean, None, None, invstd, hip.ACT_LEAKY_RELU, link.slope), residual=rows(x),
-                            side2=rows(link.z), partial=link.partial)
+                return dict(out_mode=4, out_norm=(mean, None, None, invstd, hip.ACT_LEAKY_RELU, link.slope), residual=_rows(x),
+                            side2=_rows(link.z), partial=link.partial)
             return dict(out_mode=3, out_norm=(mean, link.buf[5 * C:], link.bias, invstd, link.act & hip.ACT_MASK, link.slope),
-                        residual=rows(link.z), partial=link.partial)
+                        residual=_rows(link.z), partial=link.partial)
         dx = None
         if dilation > 0:
             if ctx.needs_input_grad[0]:
@@ -643,7 +608,7 @@ class _ConvABNFunction(torch.autograd.Function):
                     wflip = w4.flip(2, 3).transpose(0, 1).contiguous(memory_format=torch.channels_last)
                 if own_dgrad:
                     dx = torch.empty_like(x)
-                    hip.conv1x1(rows(dz), wflip.permute(0, 2, 3, 1).reshape(K, 9 * N), rows(dx), conv3=(H, W, dilation),
+                    hip.conv1x1(_rows(dz), _w_matrix(wflip), _rows(dx), conv3=(H, W, dilation),
                                 **(serve(dx) if link is not None else {}))
                 else:
                     dx = F.conv2d(dz, wflip, None, 1, dilation, dilation)
@@ -654,21 +619,20 @@ class _ConvABNFunction(torch.autograd.Function):
             if own_dgrad and wflip is not None:
                 # a chain link needs dx to be the whole gradient; a block link also takes the shortcut's folded in
                 served = link is not None and (dskip is None or (fold and link.kind == LINK_BLOCK))
-                hip.conv1x1(rows(dz), wflip.reshape(K, N), rows(dx), accumulate=fold, **(serve(dx) if served else {}))
+                hip.conv1x1(_rows(dz), wflip.reshape(K, N), _rows(dx), accumulate=fold, **(serve(dx) if served else {}))
             else:
-                hip.gemm_bf16(1, rows(dz), w4.reshape(N, K), rows(dx))
+                hip.gemm_bf16(1, _rows(dz), w4.reshape(N, K), _rows(dx))
             if dskip is not None and not fold:
                 dx = dx + dskip
         # the own kernel's fallback is MIOpen here, where the C++ node falls back to the split products on a 1x1 layer
         dw = _conv_wgrad(dz, x, w4, dilation or 1, wgrad_conv, WGRAD_LIBRARY) if ctx.needs_input_grad[1] else None
-        return (dx, dw, sums[N:], sums[:N], dres) + (None,) * 14
+        return (dx, dw, sums[N:], sums[:N], dres) + (None,) * 13
 
 
 class _Route(NamedTuple):
     """What ``_conv_abn_route`` decided for one conv + ABN pair (the arguments of the node of the same names)."""
     is3: bool
     stride: int          # 0: not one of the own strided layers
-    fused: bool
     dilation: int
     own_dgrad: bool
     wflip: object        # the cached flipped / transposed bf16 weight, where there is one
@@ -703,23 +667,16 @@ def _conv_abn_route(conv, bn, x, residual, with_skip, make_link):
         # gradient stays with the library's backward-data solver; no link consumed (the producer falls back to its own reduction)
         if is3 and not conv.weight.is_contiguous(memory_format=torch.channels_last):
             return None
-        dilation, fused, link = (conv.dilation[0] if is3 else 0), True, None
+        dilation, link = (conv.dilation[0] if is3 else 0), None
     elif is3:
         if not (conv.stride == (1, 1) and conv.padding == conv.dilation and conv.dilation[0] == conv.dilation[1]
                 and conv.groups == 1 and not with_skip and conv.weight.is_contiguous(memory_format=torch.channels_last)):
             return None
-        M = x.shape[0] * x.shape[2] * x.shape[3]
-        dilation = conv.dilation[0]
-        fused = _own_conv3x3(M, conv.in_channels, conv.out_channels)
-        own_dgrad = _own_conv3x3(M, conv.out_channels, conv.in_channels)
-        if not fused and not own_dgrad:
-            return None                         # nothing of ours to gain: the module path (MIOpen + ABN node) stays
-        wflip = conv._w16_flip if conv.working_weight() is not None else None
+        dilation, own_dgrad, wflip = conv.dilation[0], True, _cached_flip(conv)
     else:
-        fused = _own_gemm_with_stats(conv.in_channels, conv.out_channels)
         own_dgrad = conv.own_dgrad or (link is not None and conv.link_dgrad and (link.kind == LINK_BLOCK or not with_skip))
         # the transposed weight: cached with the bf16 working copies, else made per call (same kernels either way)
-        wflip = conv._w16_flip if (own_dgrad and conv.working_weight() is not None) else None
+        wflip = _cached_flip(conv) if own_dgrad else None
         # narrow layers (<= 512 channels at 65^2 / 129^2): MIOpen's weight-gradient solver beats the split-M products
         wgrad_conv = WGRAD_SPLIT if conv.wide else WGRAD_LIBRARY
     if _own_wgrad():
@@ -727,7 +684,7 @@ def _conv_abn_route(conv, bn, x, residual, with_skip, make_link):
     # the consumer's input gradient must run on the own kernel; a chain link wants no shortcut next to it, a block link a 1x1 layer
     if link is not None and (not own_dgrad or (is3 if link.kind == LINK_BLOCK else with_skip)):
         link = None
-    return _Route(is3, stride, bool(fused), dilation, bool(own_dgrad), wflip, int(wgrad_conv), link, make_link)
+    return _Route(is3, stride, dilation, bool(own_dgrad), wflip, int(wgrad_conv), link, make_link)
 
 
 def _conv_abn_train(conv, bn, x, residual=None, activation=None, activation_param=None, with_skip=False, make_link=False):
@@ -763,9 +720,7 @@ def _conv_abn_train(conv, bn, x, residual=None, activation=None, activation_para
         comm = _abn.direct_comm(group) if sync else None
         if sync and comm is None:
             return None
-    w16 = conv.working_weight()
-    if w16 is None:
-        w16 = conv.weight.to(x.dtype)
+    w16 = _w16(conv, x)
     wflip = r.wflip
     if r.own_dgrad and not r.is3 and wflip is None:
         wflip = w16.reshape(conv.out_channels, conv.in_channels).t().contiguous().view(conv.in_channels, conv.out_channels, 1, 1)
@@ -774,11 +729,11 @@ def _conv_abn_train(conv, bn, x, residual=None, activation=None, activation_para
     bn.__dict__.pop("_eval_cache", None)
     if node is None:
         return _ConvABNFunction.apply(x, w16, bn.weight, bn.bias, residual, bn.running_mean, bn.running_var, bn.momentum, bn.eps,
-                                      act, slope, r.fused, r.dilation, wflip, r.own_dgrad, r.wgrad_conv, r.make_link, r.link,
+                                      act, slope, r.dilation, wflip, r.own_dgrad, r.wgrad_conv, r.make_link, r.link,
                                       bool(with_skip))
     out = node.conv_abn_train(x, w16, bn.weight, bn.bias, residual, bn.running_mean, bn.running_var, bn.momentum, bn.eps, act,
                               slope, comm.handle if comm is not None else 0, world, _hip_stream(), bn._direct_grad_ptr(),
-                              bool(with_skip), r.fused, r.dilation, wflip, r.own_dgrad, r.wgrad_conv, r.make_link, r.link,
+                              bool(with_skip), r.dilation, wflip, r.own_dgrad, r.wgrad_conv, r.make_link, r.link,
                               r.stride or 1, _env("UCD_STAT_ATOMIC", "1") != "0")
     k = 2 if with_skip else 1
     if len(out) > k:                             # the node made a link: (z, buf, partial, flag) follow the regular outputs
@@ -877,74 +832,58 @@ class ResidualBlock(nn.Module):
         return (m.running_mean, consts[1], m.bias, None, hip.ACT_CODES[a], m.activation_param if slope is None else slope)
 
     def _forward_eval_fused(self, x):
-        """conv1 + bn1 -> one GEMM with the affine + activation epilogue; conv3 + bn3 + shortcut + block activation -> one
-        GEMM with the affine + residual + activation epilogue (csrc/conv1x1.hip); conv2 stays MIOpen, bn2 its in-place
-        apply.  Same arithmetic as the layer-by-layer path with the conv outputs kept in fp32 up to the activation."""
+        """Every convolution with the ABN behind it as ONE product with the affine + activation epilogue (csrc/conv1x1.hip): conv1 +
+        bn1, conv2 + bn2 (3x3 implicit GEMM; stride 1, or the stride of a stage's first block), the projection + proj_bn likewise,
+        conv3 + bn3 + shortcut + block activation.  A conv2 / projection the kernels do not take runs its modules.  Same arithmetic as
+        the layer-by-layer path with the conv outputs kept in fp32 up to the activation."""
         from . import hip
         c = self.convs
         B, C, H, W = x.shape
         cl = torch.channels_last
 
-        def rows(t):
-            b, ch, h, w = t.shape
-            return t.permute(0, 2, 3, 1).reshape(b * h * w, ch)
+        def new_map(channels, stride=1):
+            return torch.empty((B, channels, (H - 1) // stride + 1, (W - 1) // stride + 1), dtype=x.dtype, device=x.device,
+                               memory_format=cl)
 
-        def w2d(conv, like):
-            w = conv.working_weight()
-            if w is None:
-                w = conv.weight.to(like.dtype)
-            return w.reshape(conv.out_channels, conv.in_channels)
+        def w2d(conv):
+            return _w16(conv, x).reshape(conv.out_channels, conv.in_channels)
 
-        xr = rows(x)
-        h1 = torch.empty((B, c.conv1.out_channels, H, W), dtype=x.dtype, device=x.device, memory_format=cl)
-        hip.conv1x1(xr, w2d(c.conv1, x), rows(h1), out_mode=1, out_norm=self._eval_norm(c.bn1))
+        xr = _rows(x)
+        h1 = new_map(c.conv1.out_channels)
+        hip.conv1x1(xr, w2d(c.conv1), _rows(h1), out_mode=1, out_norm=self._eval_norm(c.bn1))
         cv = c.conv2
         if (isinstance(cv, Conv3x3) and cv.stride == (1, 1) and cv.padding == cv.dilation and cv.bias is None
-                and cv.in_channels % 64 == 0 and cv.out_channels % 64 == 0
-                and _own_conv3x3(B * H * W, cv.in_channels, cv.out_channels)):
-            w3 = cv.working_weight()
-            if w3 is None:
-                w3 = cv.weight.to(x.dtype)
-            if not w3.is_contiguous(memory_format=cl):
-                w3 = w3.contiguous(memory_format=cl)
-            h2 = torch.empty((B, cv.out_channels, H, W), dtype=x.dtype, device=x.device, memory_format=cl)
-            hip.conv1x1(rows(h1), w3.permute(0, 2, 3, 1).reshape(cv.out_channels, 9 * cv.in_channels), rows(h2), out_mode=1,
-                        out_norm=self._eval_norm(c.bn2), conv3=(H, W, cv.dilation[0]))       # conv2 + bn2: one kernel
-        elif _own_stride(cv) and cv.kernel_size == (3, 3):          # the stage's first block: conv2 with a stride, + bn2
-            st = _own_stride(cv)
-            w3 = cv.working_weight()
-            if w3 is None:
-                w3 = cv.weight.to(x.dtype)
-            if not w3.is_contiguous(memory_format=cl):
-                w3 = w3.contiguous(memory_format=cl)
-            h2 = torch.empty((B, cv.out_channels, (H - 1) // st + 1, (W - 1) // st + 1), dtype=x.dtype, device=x.device,
-                             memory_format=cl)
-            hip.conv1x1(rows(h1), w3.permute(0, 2, 3, 1).reshape(cv.out_channels, 9 * cv.in_channels), rows(h2), out_mode=1,
-                        out_norm=self._eval_norm(c.bn2), conv3=(H, W, cv.dilation[0], st))
+                and cv.in_channels % 64 == 0 and cv.out_channels % 64 == 0):
+            st = 1
+        else:
+            st = _own_stride(cv) if cv.kernel_size == (3, 3) else 0          # the stage's first block: conv2 with a stride
+        if st:                                                               # conv2 + bn2: one kernel
+            w3 = _w16(cv, x).contiguous(memory_format=cl)
+            h2 = new_map(cv.out_channels, st)
+            hip.conv1x1(_rows(h1), _w_matrix(w3), _rows(h2), out_mode=1, out_norm=self._eval_norm(c.bn2),
+                        conv3=(H, W, cv.dilation[0]) if st == 1 else (H, W, cv.dilation[0], st))
         else:
             h2 = c.bn2(c.conv2(h1))                                # in place under no_grad (InPlaceABN contract)
         if hasattr(self, "proj_conv"):
-            pst = _own_stride(self.proj_conv)
-            if isinstance(self.proj_conv, Conv1x1) and self.proj_conv.in_channels % 64 == 0:
-                res = torch.empty((B, self.proj_conv.out_channels, H, W), dtype=x.dtype, device=x.device, memory_format=cl)
-                hip.conv1x1(xr, w2d(self.proj_conv, x), rows(res), out_mode=1, out_norm=self._eval_norm(self.proj_bn))
-            elif pst and self.proj_conv.kernel_size == (1, 1):     # strided shortcut projection + proj_bn: one row-gather product
-                res = torch.empty((B, self.proj_conv.out_channels, (H - 1) // pst + 1, (W - 1) // pst + 1), dtype=x.dtype,
-                                  device=x.device, memory_format=cl)
-                hip.conv1x1(xr, w2d(self.proj_conv, x), rows(res), out_mode=1, out_norm=self._eval_norm(self.proj_bn),
-                            strided=(H, W, pst))
+            pc = self.proj_conv
+            if isinstance(pc, Conv1x1) and pc.in_channels % 64 == 0:
+                st = 1
             else:
-                res = self.proj_bn(self.proj_conv(x))
+                st = _own_stride(pc) if pc.kernel_size == (1, 1) else 0      # strided shortcut projection: a row-gather product
+            if st:                                                           # projection + proj_bn: one kernel
+                res = new_map(pc.out_channels, st)
+                hip.conv1x1(xr, w2d(pc), _rows(res), out_mode=1, out_norm=self._eval_norm(self.proj_bn),
+                            strided=None if st == 1 else (H, W, st))
+            else:
+                res = self.proj_bn(pc(x))
         else:
             res = x
-        if not h2.is_contiguous(memory_format=cl):
-            h2 = h2.contiguous(memory_format=cl)
-        if not res.is_contiguous(memory_format=cl):
-            res = res.contiguous(memory_format=cl)
+        h2 = h2.contiguous(memory_format=cl)
+        res = res.contiguous(memory_format=cl)
         out = torch.empty((h2.shape[0], c.conv3.out_channels, h2.shape[2], h2.shape[3]), dtype=x.dtype, device=x.device,
                           memory_format=cl)
-        hip.conv1x1(rows(h2), w2d(c.conv3, x), rows(out), out_mode=1,
-                    out_norm=self._eval_norm(c.bn3, c.bn1.activation, c.bn1.activation_param), residual=rows(res))
+        hip.conv1x1(_rows(h2), w2d(c.conv3), _rows(out), out_mode=1,
+                    out_norm=self._eval_norm(c.bn3, c.bn1.activation, c.bn1.activation_param), residual=_rows(res))
         return out
 
     def forward(self, x):

@@ -374,7 +374,7 @@ template <class R, class... A> variable_list no_grads(R (*)(AutogradContext*, A.
 at::Tensor or_undefined(const c10::optional<at::Tensor>& t) { return t.has_value() ? *t : at::Tensor(); }
 
 // Training-mode ABN forward, y = act(BN_batch(in) [+ residual]) with the statistics left in buf (comm != 0: SyncBN through the
-// library's communicator): ABNTrainNode, and the unfused arm of ConvABNTrainNode on the convolution's output.
+// library's communicator): ABNTrainNode.
 void abn_batch_forward(int64_t comm, int64_t world, const at::Tensor& in, const at::Tensor& y, const at::Tensor& residual, int64_t M,
                        int64_t C, int64_t HW, const at::Tensor& weight, const at::Tensor& bias, const at::Tensor& running_mean,
                        const at::Tensor& running_var, double momentum, double eps, float* buf, int64_t act, double slope, void* ws,
@@ -654,9 +654,8 @@ at::Tensor conv_stride1(at::Tensor x, at::Tensor w, int64_t d, c10::optional<at:
 
 // ---- 1x1 convolution + training-mode ABN as ONE node ------------------------------------------------------
 // forward   z = x . w^T with the statistics of z accumulated in the GEMM's epilogue (ucd_conv1x1 out_mode 2: no statistics
-//           pass over z) -> finalize (or the SyncBN exchange) -> y = act(norm(z) [+ residual])
-//           (for the shapes where the tuned library GEMM is faster than the fused kernel by more than the statistics pass
-//           costs, `fused` is 0: library GEMM + ucd_abn_forward - the same arithmetic)
+//           pass over z) -> finalize (or the SyncBN exchange) -> y = act(norm(z) [+ residual]); every layer the node takes runs
+//           this way (the library products + a statistics pass it once chose between: DESIGN.md section 10)
 // backward  ABN backward (d z, d residual, parameter gradients) -> d x = d z . w (+ the shortcut's gradient, beta = 1)
 //           -> d w = d z^T . x as batched split-M products
 // with_skip: x is also the block's identity shortcut; the node returns (y, alias of x) so that x has one consumer and the
@@ -825,7 +824,7 @@ class ConvABNTrainNode : public torch::autograd::Function<ConvABNTrainNode> {
   static variable_list forward(AutogradContext* ctx, at::Tensor x, at::Tensor w4, at::Tensor weight, at::Tensor bias,
                                c10::optional<at::Tensor> residual_, at::Tensor running_mean, at::Tensor running_var,
                                double momentum, double eps, int64_t act, double slope, int64_t comm, int64_t world,
-                               int64_t stream, int64_t param_grad, bool with_skip, bool fused, int64_t dilation,
+                               int64_t stream, int64_t param_grad, bool with_skip, int64_t dilation,
                                c10::optional<at::Tensor> wflip_, bool own_dgrad, int64_t wgrad_conv, bool make_link,
                                c10::optional<at::Tensor> lk_z_, c10::optional<at::Tensor> lk_buf_,
                                c10::optional<at::Tensor> lk_bias_, c10::optional<at::Tensor> lk_partial_,
@@ -834,8 +833,8 @@ class ConvABNTrainNode : public torch::autograd::Function<ConvABNTrainNode> {
     // stat_atomic (round 5): statistics and link sums through fp32 atomics into arena slots, finalised in the prologue of the apply
     // passes (no tile_stats_reduce / reduce_bands launches); off: the deterministic per-tile rows + second-stage kernels
     // stride > 1: the strided layers of the first block of a stage (conv2 3x3 stride 2 with padding = dilation, proj_conv 1x1
-    // stride 2): forward and weight gradient on the own kernels (the strided row gather / implicit GEMM, ucd_conv_wgrad_strided),
-    // input gradient through the library's backward-data solver; no shortcut fold, no link consumed (it may still MAKE one).
+    // stride 2): forward and weight gradient on the own kernels (the strided row gather / implicit GEMM, the strided weight-gradient
+    // form), input gradient through the library's backward-data solver; no shortcut fold, no link consumed (it may still MAKE one).
     // make_link: offer a backward link (LinkFlag above) - also return (z, buf, partial, flag).  lk_*: the Link consumed; under
     // SyncBN its producer all-reduces the sums.
     // dilation = 0: 1x1 convolution; dilation >= 1: 3x3, stride 1, padding = dilation (implicit GEMM, taps = 9), weight in
@@ -869,65 +868,50 @@ class ConvABNTrainNode : public torch::autograd::Function<ConvABNTrainNode> {
     float* b = buf.data_ptr<float>();
     const size_t ws_bytes = ucd_abn_workspace_bytes((int)M, (int)N);
     const void* resp = has_res ? residual.data_ptr() : nullptr;
-    if (fused) {
-      size_t need = ucd_conv1x1_stats_partial_bytes((int)M, (int)N);
-      float* partial = (float*)workspace(x, need > ws_bytes ? need : ws_bytes, stream);
-      ucd_conv1x1_desc d = conv_desc(x, w4, z, M, N, K, H, W, dilation);
-      d.out_mode = 2; d.partial = partial;
-      if (stride > 1) { d.H = (int)H; d.W = (int)W; d.stride = (int)stride; }
-      int64_t gen = 0;
-      const int64_t R = ucd_conv1x1_stat_replicas((int)M);
-      at::Tensor acc = (stat_atomic && N % 8 == 0) ? arena_alloc(x, R * 2 * N, &gen, stream) : at::Tensor();
-      if (acc.defined()) {
-        // sums about the running mean (equal on every rank), straight into the layer's accumulator; SyncBN: one all-reduce of the
-        // 2 N raw sums (they are additive about a common shift) instead of gather + Chan combination
-        d.stat_acc = acc.data_ptr<float>();
-        d.stat_rep = (int)R;
-        d.stat_shift = running_mean.data_ptr<float>();
-        d.partial = b + 2 * N;                                   // the snapshot of the shift
-        check(ucd_conv1x1(&d, (ucd_stream_t)stream), "ucd_conv1x1");
-        if (sync) check(ucd_comm_all_reduce_sum((ucd_comm_t)comm, d.stat_acc, (size_t)(R * 2 * N), (ucd_stream_t)stream), "ucd_comm_all_reduce_sum");
-        check(ucd_abn_apply_stats(z.data_ptr(), (int)N, y.data_ptr(), (int)N, resp, has_res ? (int)N : 0, (int)M, (int)N, d.stat_acc,
-                                  (int)R, b + 2 * N, (float)M * (sync ? (float)world : 1.f), fptr(weight), fptr(bias),
-                                  running_mean.data_ptr<float>(), running_var.data_ptr<float>(), (float)momentum, (float)eps, b + 3 * N,
-                                  b + 4 * N, b + 5 * N, (int)act, (float)slope, (ucd_stream_t)stream),
-              "ucd_abn_apply_stats");
-      } else {
-        check(ucd_conv1x1(&d, (ucd_stream_t)stream), "ucd_conv1x1");
-        if (!sync) {
-          check(ucd_conv1x1_stats_finalize(partial, (int)M, (int)N, fptr(weight), running_mean.data_ptr<float>(),
-                                           running_var.data_ptr<float>(), (float)momentum, (float)eps, b, nullptr, (int)act,
-                                           (ucd_stream_t)stream),
-                "ucd_conv1x1_stats_finalize");
-          check(ucd_abn_apply(z.data_ptr(), (int)N, y.data_ptr(), (int)N, resp, has_res ? (int)N : 0, UCD_BF16, (int)M, (int)N, nullptr,
-                              (int)HW, b + 3 * N, b + 5 * N, fptr(bias), (int)act, (float)slope, (ucd_stream_t)stream),
-                "ucd_abn_apply");
-        } else {
-          float *pack = b + 6 * N, *gathered = b + 8 * N;
-          check(ucd_conv1x1_stats_finalize(partial, (int)M, (int)N, nullptr, nullptr, nullptr, (float)momentum, (float)eps, b, pack, 0,
-                                           (ucd_stream_t)stream),
-                "ucd_conv1x1_stats_finalize");
-          check(ucd_comm_all_gather((ucd_comm_t)comm, pack, gathered, (size_t)2 * N, (ucd_stream_t)stream), "ucd_comm_all_gather");
-          check(ucd_abn_sync_forward(z.data_ptr(), (int)N, y.data_ptr(), (int)N, resp, has_res ? (int)N : 0, UCD_BF16, (int)M, (int)N,
-                                     nullptr, (int)HW, gathered, (int)world, fptr(weight), fptr(bias), running_mean.data_ptr<float>(),
-                                     running_var.data_ptr<float>(), (float)momentum, (float)eps, b, (int)act, (float)slope,
-                                     (ucd_stream_t)stream),
-                "ucd_abn_sync_forward");
-        }
-      }
+    size_t need = ucd_conv1x1_stats_partial_bytes((int)M, (int)N);
+    float* partial = (float*)workspace(x, need > ws_bytes ? need : ws_bytes, stream);
+    ucd_conv1x1_desc d = conv_desc(x, w4, z, M, N, K, H, W, dilation);
+    d.out_mode = 2; d.partial = partial;
+    if (stride > 1) { d.H = (int)H; d.W = (int)W; d.stride = (int)stride; }
+    int64_t gen = 0;
+    const int64_t R = ucd_conv1x1_stat_replicas((int)M);
+    at::Tensor acc = (stat_atomic && N % 8 == 0) ? arena_alloc(x, R * 2 * N, &gen, stream) : at::Tensor();
+    if (acc.defined()) {
+      // sums about the running mean (equal on every rank), straight into the layer's accumulator; SyncBN: one all-reduce of the
+      // 2 N raw sums (they are additive about a common shift) instead of gather + Chan combination
+      d.stat_acc = acc.data_ptr<float>();
+      d.stat_rep = (int)R;
+      d.stat_shift = running_mean.data_ptr<float>();
+      d.partial = b + 2 * N;                                   // the snapshot of the shift
+      check(ucd_conv1x1(&d, (ucd_stream_t)stream), "ucd_conv1x1");
+      if (sync) check(ucd_comm_all_reduce_sum((ucd_comm_t)comm, d.stat_acc, (size_t)(R * 2 * N), (ucd_stream_t)stream), "ucd_comm_all_reduce_sum");
+      check(ucd_abn_apply_stats(z.data_ptr(), (int)N, y.data_ptr(), (int)N, resp, has_res ? (int)N : 0, (int)M, (int)N, d.stat_acc,
+                                (int)R, b + 2 * N, (float)M * (sync ? (float)world : 1.f), fptr(weight), fptr(bias),
+                                running_mean.data_ptr<float>(), running_var.data_ptr<float>(), (float)momentum, (float)eps, b + 3 * N,
+                                b + 4 * N, b + 5 * N, (int)act, (float)slope, (ucd_stream_t)stream),
+            "ucd_abn_apply_stats");
     } else {
-      if (conv3 || stride > 1) {
-        const int64_t pad = conv3 ? dilation : 0, dil = conv3 ? dilation : 1;
-        z = at::conv2d(x, w4, {}, {stride, stride}, {pad, pad}, {dil, dil}, 1);
-        if (!dense_channels_last(z)) z = z.contiguous(at::MemoryFormat::ChannelsLast);
+      check(ucd_conv1x1(&d, (ucd_stream_t)stream), "ucd_conv1x1");
+      if (!sync) {
+        check(ucd_conv1x1_stats_finalize(partial, (int)M, (int)N, fptr(weight), running_mean.data_ptr<float>(),
+                                         running_var.data_ptr<float>(), (float)momentum, (float)eps, b, nullptr, (int)act,
+                                         (ucd_stream_t)stream),
+              "ucd_conv1x1_stats_finalize");
+        check(ucd_abn_apply(z.data_ptr(), (int)N, y.data_ptr(), (int)N, resp, has_res ? (int)N : 0, UCD_BF16, (int)M, (int)N, nullptr,
+                            (int)HW, b + 3 * N, b + 5 * N, fptr(bias), (int)act, (float)slope, (ucd_stream_t)stream),
+              "ucd_abn_apply");
       } else {
-        const size_t wsb = ucd_gemm_workspace_bytes();
-        check(ucd_gemm_bf16(0, (int)M, (int)N, (int)K, x.data_ptr(), (int)K, w4.data_ptr(), (int)K, z.data_ptr(), (int)N,
-                            workspace(x, wsb, stream, 1), wsb, 1, (ucd_stream_t)stream),
-              "ucd_gemm_bf16");
+        float *pack = b + 6 * N, *gathered = b + 8 * N;
+        check(ucd_conv1x1_stats_finalize(partial, (int)M, (int)N, nullptr, nullptr, nullptr, (float)momentum, (float)eps, b, pack, 0,
+                                         (ucd_stream_t)stream),
+              "ucd_conv1x1_stats_finalize");
+        check(ucd_comm_all_gather((ucd_comm_t)comm, pack, gathered, (size_t)2 * N, (ucd_stream_t)stream), "ucd_comm_all_gather");
+        check(ucd_abn_sync_forward(z.data_ptr(), (int)N, y.data_ptr(), (int)N, resp, has_res ? (int)N : 0, UCD_BF16, (int)M, (int)N,
+                                   nullptr, (int)HW, gathered, (int)world, fptr(weight), fptr(bias), running_mean.data_ptr<float>(),
+                                   running_var.data_ptr<float>(), (float)momentum, (float)eps, b, (int)act, (float)slope,
+                                   (ucd_stream_t)stream),
+              "ucd_abn_sync_forward");
       }
-      abn_batch_forward(comm, world, z, y, residual, M, N, HW, weight, bias, running_mean, running_var, momentum, eps, b, act, slope,
-                        workspace(x, ws_bytes, stream), ws_bytes, stream);
     }
     const bool needs_y = has_res && (act & UCD_ACT_MASK) != UCD_ACT_IDENTITY;
     if (!link.consumable(with_skip, K)) link = Link();
@@ -1061,7 +1045,7 @@ using PyLink = std::tuple<at::Tensor, at::Tensor, c10::optional<at::Tensor>, at:
 std::vector<at::Tensor> conv_abn_train(at::Tensor x, at::Tensor w4, at::Tensor weight, at::Tensor bias,
                                        c10::optional<at::Tensor> residual, at::Tensor running_mean, at::Tensor running_var,
                                        double momentum, double eps, int64_t act, double slope, int64_t comm, int64_t world,
-                                       int64_t stream, int64_t param_grad, bool with_skip, bool fused, int64_t dilation,
+                                       int64_t stream, int64_t param_grad, bool with_skip, int64_t dilation,
                                        c10::optional<at::Tensor> wflip, bool own_dgrad, int64_t wgrad_conv, bool make_link,
                                        c10::optional<PyLink> link, int64_t stride, bool stat_atomic) {
   // the link's tensors stay arguments of the node (they keep their edges in the graph, the producer's bias among them)
@@ -1070,7 +1054,7 @@ std::vector<at::Tensor> conv_abn_train(at::Tensor x, at::Tensor w4, at::Tensor w
   double lk_slope = 0.0;
   if (link) std::tie(lk_z, lk_buf, lk_bias, lk_partial, lk_flag, lk_act, lk_slope, lk_kind) = *link;
   return ConvABNTrainNode::apply(x, w4, weight, bias, residual, running_mean, running_var, momentum, eps, act, slope, comm, world,
-                                 stream, param_grad, with_skip, fused, dilation, wflip, own_dgrad, wgrad_conv, make_link, lk_z,
+                                 stream, param_grad, with_skip, dilation, wflip, own_dgrad, wgrad_conv, make_link, lk_z,
                                  lk_buf, lk_bias, lk_partial, lk_flag, lk_act, lk_slope, lk_kind, stride, stat_atomic);
 }
 

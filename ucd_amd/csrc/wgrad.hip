@@ -927,19 +927,6 @@ int ucd_conv_wgrad_plan(int M, int N, int K, int taps, int H, int W, int dilatio
   return rc;
 }
 
-int ucd_conv_wgrad(const void* dz, int ld_dz, const void* x, int ld_x, int M, int N, int K, int taps, int H, int W, int dilation,
-                   void* dw, float* dw32, int accumulate32, void* workspace, size_t workspace_bytes, ucd_stream_t stream) {
-  return ucd_conv_wgrad_strided(dz, ld_dz, x, ld_x, M, N, K, taps, H, W, dilation, 1, dw, dw32, accumulate32, workspace, workspace_bytes,
-                                stream);
-}
-
-int ucd_conv_wgrad_strided(const void* dz, int ld_dz, const void* x, int ld_x, int M, int N, int K, int taps, int H, int W,
-                           int dilation, int stride, void* dw, float* dw32, int accumulate32, void* workspace, size_t workspace_bytes,
-                           ucd_stream_t stream) {
-  return ucd_conv_wgrad_ex(dz, ld_dz, x, ld_x, M, N, K, taps, H, W, dilation, stride, dw, dw32, accumulate32, workspace, workspace_bytes, 0,
-                           stream);
-}
-
 int ucd_conv_wgrad_defer(int mode) {
   std::lock_guard<std::mutex> lock(g_mu);
   const int was = g_mode;

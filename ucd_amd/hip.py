@@ -151,10 +151,8 @@ SIGNATURES = {
     "ucd_stem_apply_pool": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _i, _f, _p, _p, _p]),
     "ucd_stem_pool_backward": (_i, [_p, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _f, _i, _f, _p, _p, _z, _i, _p]),
     "ucd_conv_wgrad_workspace_bytes": (_z, [_i, _i, _i, _i]),
-    "ucd_conv_wgrad": (_i, [_p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _i, _p, _z, _p]),
     "ucd_stem_conv7x7": (_i, [_p, C.c_longlong, C.c_longlong, C.c_longlong, C.c_longlong, _i, _i, _i, _p, _p, _p]),
     "ucd_stem_conv_pool": (_i, [_p, C.c_longlong, C.c_longlong, C.c_longlong, C.c_longlong, _i, _i, _i, _p, _p, _p, _p, _i, _f, _p, _p]),
-    "ucd_conv_wgrad_strided": (_i, [_p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _i, _p, _z, _p]),
     "ucd_conv_wgrad_ex": (_i, [_p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _i, _p, _z, _i, _p]),
     "ucd_conv_wgrad_defer": (_i, [_i]),
     "ucd_conv_wgrad_mode": (_i, []),

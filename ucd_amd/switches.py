@@ -17,9 +17,6 @@ DEFAULTS = {
     "UCD_BLOCK_LINK": "1",         # block links across a block boundary (out_mode 4)
     "UCD_PROJ_ALIAS": "1",         # projection blocks: proj_conv reads the alias returned by conv1's node
     "UCD_DGRAD_VIA_FWD": "1",      # stride-1 input gradients on forward solvers / the own kernel
-    "UCD_LIB_GEMM_WIDE": "0",      # 1: the two large square 1x1 products on hipBLASLt
-    "UCD_OWN3X3_MIN_TILES": "1",   # own 3x3 below this many tiles -> MIOpen
-    "UCD_OWN3X3_WIDE": "1",        # 0: the 512 -> 512 3x3 layers on MIOpen
     "UCD_OWN_STRIDED": "1",        # strided conv2 / proj_conv on the own kernels
     "UCD_OWN_WGRAD": "1",          # weight gradients on csrc/wgrad.hip
     "UCD_F32_OWN_CONV": "0",       # fp32 (O0) stride-1 1x1 / 3x3 layers on csrc/conv_f32.hip: split-bf16 MFMA, ~1e-5 per product (0: MIOpen)
@@ -32,7 +29,6 @@ DEFAULTS = {
     "UCD_WGRAD_DEFER": "1",        # round 6: the slab sum of a weight gradient rides in the NEXT weight-gradient launch (0: a launch of its own behind every product)
     "UCD_WGRAD_STREAM": "1",       # round 6: the nodes' weight gradients run on a side stream of the library between the wrapper's flushes - off the chain of input-gradient products (0: on the compute stream); each one is launched one call behind its fork point, on a lowest-priority stream
     "UCD_CONV3_TAP_CLASSES": "1",  # stand-alone dilated 3x3 products (ASPP, forward and input gradient): rows ordered by tap class, every row tile walks only its live taps - same outputs bit for bit (0: raster order; 2: also the single-wave 64-row launches whose heaviest tile keeps its taps, which 1 leaves in raster order; read by the library, hip.conv3_tap_classes sets it inside a process)
-    "UCD_CONV3_MIN_ROWS": "0",     # stand-alone 3x3 layers (ASPP) below this many rows stay on the library path (round 6: 0 - the own kernels win at 3 / 6 images too: 9.33 -> 9.03 / 12.46 -> 11.97 ms)
     "UCD_STAT_ATOMIC": "1",        # conv + ABN nodes: statistics / link sums by fp32 atomics into arena slots, finalised by the apply passes (0: per-tile rows + reduction launches, bit-reproducible)
     "UCD_SEG_PK": "1",             # fused logit losses: packed math, fp64 LDS accumulators (0: the round-3 register form; read by the library)
     "UCD_SEG_KD_EX": "1",          # fused logit losses for every pair of {plain, unbiased} CE x {none, plain, unbiased} KD and any --alpha (ucd_seg_losses_ex); 0: only (any CE) or (unbiased CE + unbiased KD at alpha 1) fused, the rest on the torch modules
