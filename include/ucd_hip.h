@@ -695,6 +695,23 @@ int ucd_image_path(const uint8_t* const* src, const int* desc, int B, int S, int
                    float mean_b, float std_r, float std_g, float std_b, int* coeff_ws, uint8_t* tmp, float* out,
                    ucd_stream_t stream);
 
+/* Both halves for samples that are resident in HBM (ucd_amd/datacache.py), in ONE kernel launch with no workspace: the
+ * coefficient entries and index tables are computed by the workgroup that needs them and the horizontal pass's 8-bit rows are
+ * streamed through LDS in chunks, so any down-scaling factor works.
+ *   images  B device pointers (array in device memory) to decoded uint8 RGB images [H0_b][W0_b][3], any alignment
+ *   labels  B device pointers to the uint8 label maps [H0_b][W0_b] of the same samples
+ *   desc    int32 [B][8] in device memory: {H0, W0, i, j, h, w, flip, 0}, as ucd_image_path / ucd_label_path take it.  The
+ *           caller checks 0 <= i, 0 <= j, 0 < h, 0 < w, i + h <= H0 and j + w <= W0 (the descriptors are device memory: this
+ *           library cannot); a sample whose descriptor fails that is skipped - nothing of it is read, its outputs stay unwritten
+ *   lut     uint8 [256];   mean_* / std_*  the Normalize constants
+ *   out_images  float32 [B][S][S][3], bit-identical to ucd_image_path's `out` for the same pointers and descriptors
+ *   out_labels  int64 [B][S][S], bit-identical to ucd_label_path's `out`
+ * UCD_EINVAL (a NULL pointer, B or S below 1, B or S / 16 above 65535) before the launch; else the hipError_t of a failed
+ * launch. */
+int ucd_batch_path(const uint8_t* const* images, const uint8_t* const* labels, const int* desc, int B, int S, const uint8_t* lut,
+                   float mean_r, float mean_g, float mean_b, float std_r, float std_g, float std_b, float* out_images,
+                   int64_t* out_labels, ucd_stream_t stream);
+
 /* ---- the validation transforms on the device: Resize + CenterCrop, and full size (run.py:58-73) ------------------
  * The second geometry of the same pipeline: resize the WHOLE image [H0][W0] to (oh, ow), then cut the window
  * [i, i + out_h) x [j, j + out_w) out of the result - Pillow's resize((ow, oh)) followed by crop().  The tables belong to

@@ -67,6 +67,8 @@ _ARGS = [
     # performance
     _flag("--local_rank", type=int, default=0), _flag("--random_seed", type=int, default=42),
     _flag("--num_workers", type=int, default=0),
+    # HBM budget per process, in GiB, for decoded samples kept on the device (ucd_amd/datacache.py); 0: decode every epoch
+    _flag("--cache_gb", type=float, default=0.0),
     # dataset
     _flag("--data_root", type=str, default="data"),
     _flag("--dataset", type=str, default="voc", choices=["voc", "ade", "city"]),

@@ -11,6 +11,7 @@
 // which differs from floor((x+0.5)*a) in ~25 % of the size pairs (pinned against Pillow by tests/golden); the tables are
 // therefore built by one sequential thread per image and axis.
 #include "common.h"
+#include "datapipe_rules.h"
 
 namespace ucd {
 namespace {
@@ -21,14 +22,9 @@ __global__ void label_tables_kernel(const int* __restrict__ desc, int B, int S, 
   const int b = t >> 1, axis = t & 1;                 // axis 0: rows (h), axis 1: columns (w)
   const int* d = desc + 8 * b;
   const int extent = axis == 0 ? d[4] : d[5];
-  const double a = (double)extent / (double)S;
-  double xo = a * 0.5;
+  NearestWalk walk(extent, S);
   int* tab = tables + ((size_t)b * 2 + axis) * S;
-  for (int x = 0; x < S; ++x) {
-    int v = (int)xo;
-    tab[x] = v < extent ? v : extent - 1;
-    xo += a;
-  }
+  for (int x = 0; x < S; ++x) tab[x] = walk.next();
 }
 
 __global__ __launch_bounds__(256) void label_gather_kernel(const uint8_t* const* __restrict__ src,
@@ -52,41 +48,6 @@ __global__ __launch_bounds__(256) void label_gather_kernel(const uint8_t* const*
 // by the down-scaling factor) + flip + ToTensor (/255) + Normalize ((x - mean) / std), dataset/transform.py:481-553,
 // 300-318, 37-86 and run.py:49-55.  Restatement of Pillow's src/libImaging/Resample.c (precompute_coeffs,
 // normalize_coeffs_8bpc, ImagingResampleHorizontal/Vertical_8bpc), pinned bit-for-bit by tests/golden.
-constexpr int kPrecisionBits = 22;
-
-// one entry {xmin, count, k[0..kmax)} of a coefficient table: output index xx of the resize in_size -> out_size
-__device__ __forceinline__ void image_coeff_entry(int in_size, int out_size, int xx, int kmax, int* __restrict__ o) {
-  const double scale = (double)in_size / (double)out_size;
-  const double filterscale = scale < 1.0 ? 1.0 : scale;
-  const double support = 1.0 * filterscale;
-  const double center = ((double)xx + 0.5) * scale;
-  const double ss = 1.0 / filterscale;
-  int xmin = (int)(center - support + 0.5);
-  if (xmin < 0) xmin = 0;
-  int xmax = (int)(center + support + 0.5);
-  if (xmax > in_size) xmax = in_size;
-  xmax -= xmin;
-  if (xmax > kmax) xmax = kmax;                         // cannot happen when kmax = ceil(support) * 2 + 1
-  double ww = 0.0;
-  for (int x = 0; x < xmax; ++x) {
-    double v = ((double)(x + xmin) - center + 0.5) * ss;
-    if (v < 0.0) v = -v;
-    ww += v < 1.0 ? 1.0 - v : 0.0;
-  }
-  o[0] = xmin;
-  o[1] = xmax;
-  for (int x = 0; x < kmax; ++x) {
-    double w = 0.0;
-    if (x < xmax) {
-      double v = ((double)(x + xmin) - center + 0.5) * ss;
-      if (v < 0.0) v = -v;
-      w = v < 1.0 ? 1.0 - v : 0.0;
-      if (ww != 0.0) w /= ww;
-    }
-    o[2 + x] = w < 0.0 ? (int)(-0.5 + w * (double)(1 << kPrecisionBits)) : (int)(0.5 + w * (double)(1 << kPrecisionBits));
-  }
-}
-
 // coefficient tables: co[b][axis][xx] = {xmin, count, k[0..kmax)}
 __global__ void image_coeff_kernel(const int* __restrict__ desc, int B, int S, int kmax, int* __restrict__ co) {
   const int xx = blockIdx.x * blockDim.x + threadIdx.x;
@@ -95,11 +56,6 @@ __global__ void image_coeff_kernel(const int* __restrict__ desc, int B, int S, i
   const int* d = desc + 8 * b;
   const int in_size = axis == 0 ? d[4] : d[5];          // axis 0: vertical (h), axis 1: horizontal (w)
   image_coeff_entry(in_size, S, xx, kmax, co + (((size_t)b * 2 + axis) * S + xx) * (kmax + 2));
-}
-
-__device__ __forceinline__ int clip8(int v) {
-  v >>= kPrecisionBits;
-  return v < 0 ? 0 : (v > 255 ? 255 : v);
 }
 
 // horizontal pass over the rows of the crop: tmp[b][r][xx][c]
@@ -168,13 +124,11 @@ __global__ void val_label_tables_kernel(const int* __restrict__ desc, int B, int
   const int* d = desc + 8 * b;
   if (!val_desc_ok(d, out_h, out_w)) return;
   const int extent = d[axis], off = d[4 + axis], out = axis == 0 ? out_h : out_w;
-  const double a = (double)extent / (double)d[2 + axis];
-  double xo = a * 0.5;
+  NearestWalk walk(extent, d[2 + axis]);
   int* tab = tables + (size_t)b * (out_h + out_w) + (axis == 0 ? 0 : out_h);
   for (int x = 0; x < off + out; ++x) {               // Pillow's running sum starts at index 0 of the full axis
-    int v = (int)xo;
-    if (x >= off) tab[x - off] = v < extent ? v : extent - 1;
-    xo += a;
+    const int v = walk.next();
+    if (x >= off) tab[x - off] = v;
   }
 }
 

@@ -28,7 +28,7 @@ import numpy as np
 import torch
 import torch.utils.data as data
 
-from . import datapipe, switches
+from . import datapipe, hip, switches
 
 
 def _open_rgb(path):
@@ -270,20 +270,83 @@ class DeviceLoader:
     through shared, pinned memory; the batch transform runs in the main process on the device (``DeviceBatcher``) - no HIP call
     ever happens in a worker.  The random crop / flip parameters are drawn in the main process in sample order, i.e. the same
     ``random`` sequence as the reference's ``num_workers=0`` loader (argparser.py:53).  Iterating yields what the trainer
-    takes; ``sampler`` / ``__len__`` as the reference's loader exposes them (train.py:93, run.py:189)."""
+    takes; ``sampler`` / ``__len__`` as the reference's loader exposes them (train.py:93, run.py:189).  ``cache`` (a
+    ``datacache.DeviceSampleCache``, ``--cache_gb``) keeps the decoded samples on the device: only the samples it does not hold
+    are decoded, the batcher gets device tensors, and the batches are those of the loader without a cache, bit for bit."""
 
-    def __init__(self, dataset, batch_size, sampler, batcher, num_workers=0, drop_last=False, prefetch_factor=4):
+    def __init__(self, dataset, batch_size, sampler, batcher, num_workers=0, drop_last=False, prefetch_factor=4, cache=None):
         kw = dict(persistent_workers=True, prefetch_factor=prefetch_factor) if num_workers > 0 else {}
         self.loader = data.DataLoader(dataset, batch_size=batch_size, sampler=sampler, num_workers=num_workers, drop_last=drop_last,
                                       collate_fn=_identity, pin_memory=num_workers > 0, **kw)
         self.sampler, self.batcher, self.batch_size = sampler, batcher, batch_size
+        if cache is not None and getattr(batcher, "train", True) is False and switches.get("UCD_VAL_DEVICE") != "1":
+            cache = None                                             # validation on the host (Pillow) takes host samples
+        self.cache = cache
+        if cache is not None:
+            # the epoch's misses, one sample per item, in the order the batches need them: the workers decode ahead of the
+            # consumer exactly as they do for whole batches above
+            self._missing = _IndexList()
+            self._decoder = data.DataLoader(dataset, batch_size=None, sampler=self._missing, num_workers=num_workers,
+                                            collate_fn=_identity, pin_memory=num_workers > 0, **kw)
+            self._drop_last = drop_last
 
     def __iter__(self):
+        if self.cache is not None:
+            yield from self._cached_epoch()
+            return
         for samples in self.loader:
+            yield self.batcher(samples)
+
+    def _cached_epoch(self):
+        """One epoch over ``cache`` (``datacache.DeviceSampleCache``): the sampler's order cut into batches like DataLoader
+        cuts it; the indices of that order that are not cached are decoded once each, in that order; a batch is assembled when
+        its misses have arrived, each miss copied to the device and offered to the cache.  A sample the cache refuses serves this
+        epoch from its transient device tensors and is decoded again in the next.  The batcher gets device tensors only."""
+        cache, B = self.cache, self.batch_size
+        order = list(self.sampler)
+        stop = len(order) - len(order) % B if self._drop_last else len(order)
+        uses = {}                                                    # times this epoch still needs an index that is not cached
+        for i in order[:stop]:
+            if i not in cache:
+                uses[i] = uses.get(i, 0) + 1
+        self._missing.indices = list(uses)                           # dict order = order of first use
+        arrivals = iter(self._decoder) if uses else iter(())
+        transient = {}                                               # refused samples that a later batch of the epoch needs again
+        for at in range(0, stop, B):
+            samples = []
+            for i in order[at:at + B]:
+                pair = cache.get(i)
+                if pair is None:
+                    pair = transient.get(i)
+                    if pair is None:
+                        image, label = next(arrivals)                # the next miss in order of first use: sample i
+                        if cache.put(i, image, label):
+                            pair = cache.peek(i)
+                        else:
+                            pair = (image.to(cache.device, non_blocking=True), label.to(cache.device, non_blocking=True))
+                            if uses[i] > 1:
+                                transient[i] = pair
+                    uses[i] -= 1
+                    if uses[i] == 0:
+                        transient.pop(i, None)
+                samples.append(pair)
             yield self.batcher(samples)
 
     def __len__(self):
         return len(self.loader)
+
+
+class _IndexList(data.Sampler):
+    """A sampler over a list that the owner replaces before every epoch."""
+
+    def __init__(self):
+        self.indices = []
+
+    def __iter__(self):
+        return iter(self.indices)
+
+    def __len__(self):
+        return len(self.indices)
 
 
 class DeviceBatcher:
@@ -292,7 +355,8 @@ class DeviceBatcher:
 
     train:  RandomResizedCrop(S, (0.5, 2.0)) + RandomHorizontalFlip + ToTensor + Normalize   (run.py:49-55) - parameters
             drawn on the host exactly like dataset/transform.py (``random`` module, per sample: crop box, then flip coin),
-            pixels on the device;
+            pixels on the device; samples that are device tensors already (a loader with a cache) take one
+            ``ucd_batch_path`` launch instead of the copies and the two calls - same draws, same bits;
     val:    Resize(S) + CenterCrop(S) + ToTensor + Normalize when ``crop`` (run.py:58-65), else ToTensor + Normalize on the full
             image (batch size 1, run.py:66-73) - raw samples copied like the train branch, one ``ucd_val_image_path`` and one
             ``ucd_val_label_path`` call per batch (``datapipe.DeviceValImagePath`` / ``DeviceValLabelPath``).  ``UCD_VAL_DEVICE=0``
@@ -310,6 +374,7 @@ class DeviceBatcher:
         # div_(255.0) (scale_mode 1) - bit for bit what UCD_VAL_DEVICE=0 computes in either branch
         self.val_images = datapipe.DeviceValImagePath(mean, std, scale_mode=0 if crop else 1)
         self.val_labels = datapipe.DeviceValLabelPath(lut)
+        self._lut_resident = None                                    # the table on the device, for ucd_batch_path
 
     def _validation_on_device(self, samples):
         dev, S = self.device, self.size
@@ -329,6 +394,11 @@ class DeviceBatcher:
             for img, _ in samples:
                 boxes.append(datapipe.random_resized_crop_params(img.shape[0], img.shape[1], scale=self.scale))
                 flips.append(random.random() < 0.5)
+            if samples[0][0].device.type == "cuda":                  # resident samples (DeviceLoader with a cache): one launch
+                if self._lut_resident is None or self._lut_resident.device != samples[0][0].device:
+                    self._lut_resident = self.lut.to(samples[0][0].device)
+                return hip.batch_path([s[0] for s in samples], [s[1] for s in samples], boxes, flips, S, self._lut_resident,
+                                      self.mean, self.std)
             imgs = [s[0].to(dev, non_blocking=True) for s in samples]
             labs = [s[1].to(dev, non_blocking=True) for s in samples]
             return self.images(imgs, boxes, flips), self.labels(labs, boxes, flips)

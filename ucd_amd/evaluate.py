@@ -49,7 +49,8 @@ def main(opts):
     classes = tasks.get_per_task_classes(opts.dataset, opts.task, opts.step)
     labels, labels_old, path_base = tasks.get_task_labels(opts.dataset, opts.task, opts.step)
     seen = list(labels_old) + list(labels)
-    _, _, val_loader_of, real = get_dataset(opts, device, world_size, rank, labels, labels_old)
+    _, _, val_loader_of, real = get_dataset(opts, device, world_size, rank, labels, labels_old,
+                                             use_cache=False)     # one pass: nothing is read twice
     if real:
         # test.py:87-90: the test split with every class seen so far
         image_set = "train" if opts.val_on_trainset else "val"

@@ -93,6 +93,7 @@ SIGNATURES = {
     "ucd_abn_bwd_reduce": (_i, [_p, _i, _p, _i, _p, _i, _i, _i, _i, _p, _i, _p, _p, _p, _p, _p, _i, _f, _p, _p, _z, _p]),
     "ucd_label_path": (_i, [_p, _p, _i, _i, _p, _p, _p, _p]),
     "ucd_image_path": (_i, [_p, _p, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _p, _p, _p, _p]),
+    "ucd_batch_path": (_i, [_p, _p, _p, _i, _i, _p, _f, _f, _f, _f, _f, _f, _p, _p, _p]),
     "ucd_val_image_path": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _p, _p, _p, _p]),
     "ucd_val_label_path": (_i, [_p, _p, _i, _i, _i, _p, _p, _p, _p]),
     "ucd_gemm_load": (_i, [C.c_char_p]),
@@ -1002,3 +1003,39 @@ def conv1x1_row_tiles(M):
 def conv1x1_stats_partial(M, Cc, device):
     """Float buffer for the out_mode-2 partials of an [M, Cc] product (a triple per row tile and channel)."""
     return torch.empty(load().ucd_conv1x1_stats_partial_bytes(M, Cc) // 4, dtype=torch.float32, device=device)
+
+
+def batch_path(image_tensors, label_tensors, boxes, flips, S, lut, mean, std):
+    """The train transform of a batch of HBM-resident samples as ONE ``ucd_batch_path`` launch: ``image_tensors`` uint8 device
+    tensors [H0_b, W0_b, 3], ``label_tensors`` uint8 [H0_b, W0_b], ``boxes`` (i, j, h, w) and ``flips`` per sample ->
+    ``(images float32 [B, 3, S, S] channels-last, labels int64 [B, S, S])``, the bits of ``ucd_image_path`` / ``ucd_label_path``.
+    The pointers and descriptors travel in one pinned host buffer and one non-blocking upload."""
+    B, S = len(image_tensors), int(S)
+    if B == 0 or not (B == len(label_tensors) == len(boxes) == len(flips)) or S <= 0:
+        raise ValueError(f"{B} images, {len(label_tensors)} label maps, {len(boxes)} boxes, {len(flips)} flips, size {S}")
+    dev = image_tensors[0].device
+    for m, l in zip(image_tensors, label_tensors):
+        if m.device.type != "cuda" or l.device != m.device or m.device != dev:
+            raise RuntimeError("ucd_batch_path runs on the GPU only (there is no CPU fallback): every sample must be resident "
+                               "on one device")
+    host = torch.empty(6 * B, dtype=torch.int64, pin_memory=True)       # [B] image pointers, [B] label pointers, [B][8] int32
+    ptrs, desc = host[:2 * B].numpy(), host[2 * B:].view(torch.int32).view(B, 8).numpy()
+    for n, (m, l, (i, j, h, w), f) in enumerate(zip(image_tensors, label_tensors, boxes, flips)):
+        if m.dtype != torch.uint8 or m.dim() != 3 or m.shape[2] != 3 or not m.is_contiguous():
+            raise ValueError("images must be contiguous [H, W, 3] uint8 RGB")
+        if l.dtype != torch.uint8 or tuple(l.shape) != tuple(m.shape[:2]) or not l.is_contiguous():
+            raise ValueError(f"the label map of a {tuple(m.shape)} image must be contiguous {tuple(m.shape[:2])} uint8")
+        if not (0 <= i and 0 <= j and h > 0 and w > 0 and i + h <= m.shape[0] and j + w <= m.shape[1]):
+            raise ValueError(f"crop box {(i, j, h, w)} outside a {tuple(m.shape)} image")
+        ptrs[n], ptrs[B + n] = m.data_ptr(), l.data_ptr()
+        desc[n] = (m.shape[0], m.shape[1], i, j, h, w, int(bool(f)), 0)
+    if lut.dtype != torch.uint8 or lut.numel() != 256:
+        raise ValueError("lut must be uint8 [256]")
+    lut = lut.to(dev)
+    args = host.to(dev, non_blocking=True)
+    out_images = torch.empty(B, S, S, 3, dtype=torch.float32, device=dev)
+    out_labels = torch.empty(B, S, S, dtype=torch.int64, device=dev)
+    base = args.data_ptr()
+    _check(load().ucd_batch_path(base, base + 8 * B, base + 16 * B, B, S, ptr(lut), *(float(v) for v in mean),
+                                 *(float(v) for v in std), ptr(out_images), ptr(out_labels), stream()), "ucd_batch_path")
+    return out_images.permute(0, 3, 1, 2), out_labels            # [B, 3, S, S] with channels-last strides

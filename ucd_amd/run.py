@@ -152,10 +152,12 @@ def loader_workers(opts, world_size):
     return max(1, min(16, (os.cpu_count() or 8) // max(1, world_size)))
 
 
-def get_dataset(opts, device, world_size, rank, labels, labels_old):
+def get_dataset(opts, device, world_size, rank, labels, labels_old, use_cache=True):
     """The reference's ``get_dataset`` + loader construction (run.py:46-113, 150-164) on the device data pipeline: returns
     (train_loader, val_dst or None, val_loader_of(dataset) -> loader, real).  ``--data_root synthetic`` - and only that - gives
-    the closed-form synthetic batches; a root without the dataset's directory raises like the reference's classes."""
+    the closed-form synthetic batches; a root without the dataset's directory raises like the reference's classes.
+    ``--cache_gb`` (with ``use_cache``) keeps the decoded samples in HBM (``datacache.DeviceSampleCache``): one cache for the train
+    set, and every validation / test loader draws its own from what the others have left of the same per-process budget."""
     real = opts.data_root != "synthetic"
     if not real:
         train_dst = SyntheticSegmentation(24 * 8, opts.crop_size, [l for l in labels if l != 0] or [1], seed=opts.step)
@@ -187,6 +189,15 @@ def get_dataset(opts, device, world_size, rank, labels, labels_old):
     train_lut = train_dst.lut
     workers = loader_workers(opts, world_size)
     collate_train = DeviceBatcher(device, opts.crop_size, train_lut, train=True)
+    budget = int(getattr(opts, "cache_gb", 0.0) * 2 ** 30) if use_cache else 0
+    caches = []                                                      # every cache of this process: one budget
+
+    def new_cache():
+        if budget <= 0:
+            return None
+        from .datacache import DeviceSampleCache
+        caches.append(DeviceSampleCache(device, budget, siblings=caches))
+        return caches[-1]
     val_dst = None
     if not opts.no_cross_val:
         # run.py:95-97: the validation subset is a random split of the TRAINING set, so it goes through the training transform
@@ -199,7 +210,8 @@ def get_dataset(opts, device, world_size, rank, labels, labels_old):
                           idxs_path=path_base + f"/val-{opts.step}.npy", masking=not opts.no_mask, overlap=True)
         cross_val_batcher = None
     sampler = torch.utils.data.distributed.DistributedSampler(train_dst, num_replicas=world_size, rank=rank)
-    train_loader = DeviceLoader(train_dst, opts.batch_size, sampler, collate_train, num_workers=workers, drop_last=True)
+    train_loader = DeviceLoader(train_dst, opts.batch_size, sampler, collate_train, num_workers=workers, drop_last=True,
+                                cache=new_cache())
 
     def val_loader_of(dst):
         lut = dst.dataset.lut if hasattr(dst, "dataset") else dst.lut
@@ -208,7 +220,7 @@ def get_dataset(opts, device, world_size, rank, labels, labels_old):
         full_size = batcher is not cross_val_batcher and not opts.crop_val
         return DeviceLoader(dst, 1 if full_size else opts.batch_size,
                             torch.utils.data.distributed.DistributedSampler(dst, num_replicas=world_size, rank=rank, shuffle=False),
-                            batcher, num_workers=min(workers, 4))
+                            batcher, num_workers=min(workers, 4), cache=new_cache())
     return train_loader, val_dst, val_loader_of, True
 
 
@@ -234,6 +246,9 @@ def main(opts):
     classes = tasks.get_per_task_classes(opts.dataset, opts.task, opts.step)
     labels, labels_old, _ = tasks.get_task_labels(opts.dataset, opts.task, opts.step)
     train_loader, val_dst, val_loader_of, real = get_dataset(opts, device, world_size, rank, labels, labels_old)
+    train_cache = getattr(train_loader, "cache", None)
+    if getattr(opts, "cache_gb", 0.0) > 0 and not real:
+        logger.info("--cache_gb ignored: --data_root synthetic has nothing to decode")
     model, model_old = build_models(opts, device, classes)
     optimizer = make_optimizer(opts, model)
     scheduler = make_scheduler(opts, optimizer, len(train_loader))
@@ -276,9 +291,14 @@ def main(opts):
         sample_ids = np.random.choice(len(val_loader), min(opts.sample_num, len(val_loader)), replace=False)
         logger.info(f"The samples id are {sample_ids}")
     while cur_epoch < opts.epochs and not opts.test:
+        if train_cache is not None:
+            train_cache.reset_counters()
         epoch_loss = trainer.train(cur_epoch=cur_epoch, optim=optimizer, train_loader=train_loader,
                                    scheduler=scheduler, print_int=opts.print_interval, logger=logger)
         logger.info(f"End of Epoch {cur_epoch}/{opts.epochs}, Average Loss={float(epoch_loss[0]) + float(epoch_loss[1])}")
+        if train_cache is not None:
+            logger.info(f"cache: {len(train_cache)} samples, {train_cache.bytes_used / 2 ** 30:.3f} GB, {train_cache.hits} hits, "
+                        f"{train_cache.misses} misses")
         if (cur_epoch + 1) % opts.val_interval == 0:                     # run.py:304-316
             logger.info("validate on val set...")
             model.eval()
