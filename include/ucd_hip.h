@@ -306,6 +306,34 @@ size_t ucd_attn_mse_workspace_bytes(int B, int HW);
 int ucd_attn_mse(const void* x_s, int ld_s, const void* x_t, int ld_t, int dtype, int B, int HW, int C, float weight,
                  float* loss_out, void* d_x, int ld_d, void* workspace, size_t workspace_bytes, ucd_stream_t stream);
 
+/* Local POD feature distillation (PLOP) for one level: a student and a teacher map [B, h, w, C] as channels-last rows (dtype
+ * UCD_F32 or UCD_BF16, the same for both; row pitches in elements, at least C; base pointers and row pitches 16-byte aligned), a
+ * slope in (0, 1] and n scales, 1 <= n <= 4, each in 1 .. 8, strictly increasing, h and w at least the largest (csrc/pod.hip).
+ *   P = X >= 0 ? X : X / slope,  Q = P^2;  per scale s, kh = h / s, kw = w / s, region (i, j) = rows [i kh, (i+1) kh) x columns
+ *   [j kw, (j+1) kw): the mean of Q over the region's columns per (channel, row) and over its rows per (channel, column);
+ *   E_b = all of them, n_E = sum_s s^2 C (kh + kw) values;  E^ = E / max(|E|, 1e-12);  l_b = |E^_s - E^_t|;
+ *   loss_out[0] = mean_b l_b;  g_E [B][n_E] = d(weight * loss_out) / d E_s, each entry already divided by its pool's count.
+ * The forward pass is four launches: one trip over both maps (16-byte loads, lanes over channels) that leaves scale-free partial
+ * row and column sums per tile, then three strip kernels (pool, difference, coefficients).  The backward pass is one launch:
+ *   d_x = grad_out[0] * 2 P dQ (X >= 0 ? 1 : 1 / slope),  dQ = the g_E entries of the pools that hold the element, summed,
+ * one read of the student map and one write of d_x (map dtype).  grad_out is a device scalar.  Strip sums are fp32, norms and dot
+ * products fp64, every sum in a fixed order, no atomics: same inputs, same bits.  No allocation, no host synchronisation: the
+ * calls capture into graphs.  l_b = 0 and E = 0 give a zero loss term and zero coefficients.
+ * The plan is a pure host function (no device is touched): n_E, the workspace bytes of the forward pass for B samples and
+ * grid[4] = {workgroups of the tile pass per map (and of the backward pass), workgroups per sample of the strip kernels, row
+ * pieces, column pieces}; output pointers may be NULL.
+ * Supported C: every multiple of 8 up to 8192; h, w up to 1024.
+ * Checked on the host before any device call, the message names the argument: UCD_EINVAL (a NULL pointer; B or C below 1; n
+ * outside 1 .. 4; a scale outside 1 .. 8 or not above the one before; h or w below the largest scale; a slope outside (0, 1]; an
+ * unknown dtype; a row pitch below C), UCD_EUNSUPPORTED (C not a multiple of 8 or above 8192; h or w above 1024), UCD_EALIGN,
+ * UCD_EWORKSPACE (NULL, unaligned or short workspace); else the hipError_t of a failed launch. */
+int ucd_pod_plan(int h, int w, int C, const int* scales, int n, int B, int dtype, int* n_E, size_t* workspace_bytes, int* grid);
+int ucd_pod_forward(const void* x_s, int ld_s, const void* x_t, int ld_t, int dtype, int B, int C, int h, int w, float slope,
+                    const int* scales, int n, float weight, float* loss_out, float* g_E, void* workspace, size_t workspace_bytes,
+                    ucd_stream_t stream);
+int ucd_pod_backward(const void* x_s, int ld_s, int dtype, int B, int C, int h, int w, float slope, const int* scales, int n,
+                     const float* g_E, const float* grad_out, void* d_x, int ld_d, ucd_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Uncertainty-weighted pixel-contrastive distillation.  Replaces pre_contractive_pixel
  * (utils/utils.py:256-393; twin utils/loss.py:258-395) and PixelConLossV2.forward

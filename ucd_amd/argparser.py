@@ -52,6 +52,15 @@ class _EvalScales(argparse.Action):
         setattr(namespace, self.dest, values)
 
 
+class _PodScales(argparse.Action):
+    """--pod_scales: 1 to 4 strictly increasing scales, each in 1 .. 8 (what the Local POD kernels take)"""
+
+    def __call__(self, parser, namespace, values, option_string=None):
+        if not 1 <= len(values) <= 4 or any(not 1 <= v <= 8 for v in values) or any(b <= a for a, b in zip(values, values[1:])):
+            parser.error(f"{option_string} takes 1 to 4 strictly increasing scales in 1 .. 8, got {' '.join(str(v) for v in values)}")
+        setattr(namespace, self.dest, values)
+
+
 def eval_views(opts):
     """The test-time views of ``--eval_scales`` / ``--eval_flip`` as ``[(scale, flip), ...]``: the plain view ``(1.0, False)`` first,
     then the other scales in the order given, each followed by its mirror under ``--eval_flip``.  ``--fusion-mode`` says how their
@@ -102,6 +111,10 @@ _ARGS = [
     _flag("--eval_scales", type=float, nargs="+", default=[1.0], action=_EvalScales), _flag("--eval_flip", **_ON),
     # distillation (ILT)
     _flag("--freeze", **_ON), _flag("--loss_de", type=float, default=0.), _flag("--loss_kd", type=float, default=0.),
+    # Local POD feature distillation (PLOP): factor of the four backbone stage maps (0: off; PLOP uses 0.01), of the head output,
+    # and the pooling scales (ucd_amd.loss.fused_local_pod)
+    _flag("--pod_factor", type=float, default=0.), _flag("--pod_last_factor", type=float, default=0.0005),
+    _flag("--pod_scales", type=int, nargs="+", default=[1, 2, 4], action=_PodScales),
     # regularisers (EWC / RW / PI; --method EWC|RW|PI): ucd_amd.regularizer, after the UCD step
     _flag("--regularizer", default=None, type=str, choices=["ewc", "rw", "pi"]),
     _flag("--reg_importance", type=float, default=1.), _flag("--reg_alpha", type=float, default=0.9),

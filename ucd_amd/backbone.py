@@ -78,10 +78,20 @@ class ResNet(nn.Module):
                 return y if y is not None else pool(m.bn1(z))
         return m(x)
 
-    def forward(self, x):
+    def forward(self, x, taps=False):
+        """``taps=True`` returns ``(mod5 output, (mod2, mod3, mod4, mod5 outputs))``: the stage maps get a reader besides the next
+        stage (Local POD).  A stage's last block offers a block link on its output, which the next block's first convolution may
+        claim on the promise of being the map's only consumer; a tapped boundary (mod2 -> mod3, mod3 -> mod4, mod4 -> mod5) takes
+        the offer off the map, so the producer does its own backward reduction, as under ``UCD_BLOCK_LINK=0``.  Without taps
+        nothing changes."""
         outs = [self._stem(x)]
         for name in ("mod2", "mod3", "mod4", "mod5"):
-            outs.append(getattr(self, name)(outs[-1]))
+            y = getattr(self, name)(outs[-1])
+            if taps and name != "mod5" and hasattr(y, "_ucd_blink"):
+                del y._ucd_blink
+            outs.append(y)
+        if taps:
+            return outs[4], tuple(outs[1:5])
         if hasattr(self, "classifier"):
             outs.append(self.classifier(outs[-1]))
         return outs if self.keep_outputs else outs[-1]

@@ -23,6 +23,7 @@ PIX_TILE = 128          # kPixTile of csrc/pixcon.h
 PIXCON_LD = 256         # feature rows of the contrast matrix are padded to 256 columns
 PIXCON_F32, PIXCON_F16, PIXCON_F16_SPLIT = 0, 1, 2
 KD_UNBIASED, KD_PLAIN = 0, 1              # enum ucd_seg_kd_mode
+EINVAL, EALIGN, EWORKSPACE = -1, -2, -3   # enum ucd_error: bad argument, alignment, workspace
 EUNSUPPORTED = -4                         # enum ucd_status: a shape outside what the kernels are built for
 # enum ucd_seg_form (include/ucd_hip.h): the kernel ucd_seg_losses_plan names
 SEG_FORMS = {1: "pk<16,8>", 2: "pk<20,4>", 3: "pk<12,12>", 4: "reg<24,16>", 5: "reg<24,24>", 6: "wide/fixed", 7: "wide/f32"}
@@ -134,6 +135,9 @@ SIGNATURES = {
     "ucd_attmap": (_i, [_p, _i, _p, _i, _i, _i, _i, _i, _p, _z, _p]),
     "ucd_attn_mse_workspace_bytes": (_z, [_i, _i]),
     "ucd_attn_mse": (_i, [_p, _i, _p, _i, _i, _i, _i, _i, _f, _p, _p, _i, _p, _z, _p]),
+    "ucd_pod_plan": (_i, [_i, _i, _i, _p, _i, _i, _i, _p, _p, _p]),
+    "ucd_pod_forward": (_i, [_p, _i, _p, _i, _i, _i, _i, _i, _i, _f, _p, _i, _f, _p, _p, _p, _z, _p]),
+    "ucd_pod_backward": (_i, [_p, _i, _i, _i, _i, _i, _i, _f, _p, _i, _p, _p, _p, _i, _p]),
     "ucd_conv1x1_row_tiles": (_i, [_i]),
     "ucd_conv1x1_stats_partial_bytes": (_z, [_i, _i]),
     "ucd_conv1x1": (_i, [C.POINTER(Conv1x1Desc), _p]),
@@ -630,6 +634,23 @@ def attmap(x, ld_x, y, ld_y, B, HW, Cc):
     ws = workspace(nbytes, x.device, "attmap")
     _check(lib.ucd_attmap(ptr(x), ld_x, ptr(y), ld_y, dtype_code(x), B, HW, Cc, ptr(ws), nbytes, stream()),
            "ucd_attmap")
+
+
+def pod_scales(scales):
+    """The scale list of a Local POD call as a ctypes int array (any length: the library judges it)."""
+    scales = [int(s) for s in scales]
+    return (C.c_int * max(len(scales), 1))(*scales), len(scales)
+
+
+def pod_plan(h, w, Cc, scales=(1, 2, 4), B=1, dtype=BF16):
+    """``ucd_pod_plan``: ``{"n_E", "workspace_bytes", "grid": (tile workgroups, strip workgroups per sample, row pieces, column
+    pieces)}`` of a Local POD level (csrc/pod.hip).  A pure host function: it answers without a GPU and raises for a geometry the
+    kernels refuse."""
+    arr, n = pod_scales(scales)
+    n_E, nbytes, grid = C.c_int(0), C.c_size_t(0), (C.c_int * 4)()
+    _check(load().ucd_pod_plan(int(h), int(w), int(Cc), C.cast(arr, C.c_void_p), n, int(B), int(dtype), C.cast(C.byref(n_E), C.c_void_p),
+                               C.cast(C.byref(nbytes), C.c_void_p), C.cast(grid, C.c_void_p)), "ucd_pod_plan")
+    return {"n_E": n_E.value, "workspace_bytes": nbytes.value, "grid": tuple(grid)}
 
 
 # ---------------------------------------------------------------------------------------------

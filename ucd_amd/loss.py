@@ -18,6 +18,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import hip
+from . import switches as _switches
 from .contrastive import PixelConLossV2, pre_contractive_pixel, ucd_contrastive_loss  # noqa: F401
 
 
@@ -153,6 +154,121 @@ def fused_attn_mse(x_s_raw, x_t_raw, weight=1.0):
     if x_s_raw.shape != x_t_raw.shape:
         raise ValueError(f"student and teacher maps differ in shape: {tuple(x_s_raw.shape)} vs {tuple(x_t_raw.shape)}")
     return _FusedAttnMSE.apply(x_s_raw, x_t_raw, weight)
+
+
+POD_SCALES = (1, 2, 4)
+
+
+def _pod_check(x_s, x_t, slope, scales):
+    """The argument rules of a Local POD level (the library's, restated for the paths that never reach it)."""
+    if x_s.dim() != 4 or x_s.shape != x_t.shape:
+        raise ValueError(f"student and teacher maps must be [B, C, h, w] of one shape: {tuple(x_s.shape)} vs {tuple(x_t.shape)}")
+    if not 0.0 < float(slope) <= 1.0:
+        raise ValueError(f"the slope {slope} is outside (0, 1]")
+    scales = tuple(int(s) for s in scales)
+    if not 1 <= len(scales) <= 4 or any(not 1 <= s <= 8 for s in scales) or any(b <= a for a, b in zip(scales, scales[1:])):
+        raise ValueError(f"scales must be 1 to 4 strictly increasing values in 1 .. 8, got {scales}")
+    if min(x_s.shape[2:]) < scales[-1]:
+        raise ValueError(f"a {x_s.shape[2]} x {x_s.shape[3]} map is smaller than the largest scale {scales[-1]}")
+    return scales
+
+
+def _pod_embed(x, slope, scales):
+    """[B, n_E]: every row pool and column pool of every region of every scale of ``Q = P^2``, ``P`` the map in front of the
+    leaky-ReLU of slope ``slope``."""
+    x = _wide(x)
+    p = torch.where(x >= 0, x, x / slope)
+    q = p * p
+    B, C, h, w = q.shape
+    parts = []
+    for s in scales:
+        kh, kw = h // s, w // s
+        v = q[:, :, :s * kh, :s * kw].reshape(B, C, s, kh, s, kw)
+        parts.append(v.mean(dim=5).reshape(B, -1))         # per (channel, region row): the mean over the region's columns
+        parts.append(v.mean(dim=3).reshape(B, -1))         # per (channel, region column): the mean over the region's rows
+    return torch.cat(parts, dim=1)
+
+
+def local_pod_torch(x_s, x_t, slope=1.0, scales=POD_SCALES, weight=1.0):
+    """``weight`` times the Local POD distance of one level as a differentiable torch composition (PLOP's ``_local_pod`` on
+    ``[B, C, h, w]`` maps of any aspect): multi-scale strip pooling of the squared pre-activation maps, L2-normalised per sample,
+    ``mean_b |E^_s - E^_t|``.  The teacher is detached.  fp64 maps stay fp64 (the tests), half-precision maps compute in fp32.
+    Serves CPU devices, geometries the kernels refuse and ``UCD_FUSED_POD=0``."""
+    scales = _pod_check(x_s, x_t, slope, scales)
+    e_s = _pod_embed(x_s, slope, scales)
+    e_t = _pod_embed(x_t.detach().to(x_s.dtype), slope, scales)
+    e_s = e_s / e_s.norm(dim=1, keepdim=True).clamp_min(1e-12)
+    e_t = e_t / e_t.norm(dim=1, keepdim=True).clamp_min(1e-12)
+    return weight * (e_s - e_t).norm(dim=1).mean()
+
+
+@functools.lru_cache(maxsize=None)
+def _pod_plan(h, w, C, scales, B, dtype):
+    return hip.pod_plan(h, w, C, scales, B, dtype)
+
+
+class _FusedLocalPOD(torch.autograd.Function):
+    """weight * Local POD of one level on the HIP kernels (ucd_pod_forward / ucd_pod_backward, csrc/pod.hip).  The forward keeps
+    the coefficient strips ``g_E`` ([B, n_E] fp32: 22 % of the bytes of a bf16 map at 129 x 129, 83 % at 33 x 33 - about half of
+    the tapped maps' bytes over the five levels of a step); the backward reads the student map once more and writes ``dX`` - no
+    second resident copy of the map."""
+
+    @staticmethod
+    def forward(ctx, x_s, x_t, slope, scales, weight):
+        lib = hip.load()
+        xt = x_t.detach()
+        if xt.dtype != x_s.dtype:
+            xt = xt.to(x_s.dtype)
+        xs, M, C, HW, ld_s = hip.rows_view(x_s.detach())
+        xt, _, _, _, ld_t = hip.rows_view(xt)
+        B, _, h, w = xs.shape
+        code = hip.dtype_code(xs)
+        plan = _pod_plan(h, w, C, scales, B, code)
+        arr, n = hip.pod_scales(scales)
+        g = torch.empty(B, plan["n_E"], dtype=torch.float32, device=xs.device)
+        out = torch.empty(1, dtype=torch.float32, device=xs.device)
+        nbytes = plan["workspace_bytes"]
+        ws = hip.workspace(nbytes, xs.device, "pod")
+        # one read of each map; the tile partials and the strips are written and read once more
+        with hip._timed("ucd_pod_forward", 2 * M * C * xs.element_size()):
+            hip._check(lib.ucd_pod_forward(hip.ptr(xs), ld_s, hip.ptr(xt), ld_t, code, B, C, h, w, float(slope),
+                                           hip.C.cast(arr, hip.C.c_void_p), n, float(weight), hip.ptr(out), hip.ptr(g), hip.ptr(ws),
+                                           nbytes, hip.stream()), "ucd_pod_forward")
+        ctx.save_for_backward(xs, g)
+        ctx.meta = (ld_s, float(slope), scales)
+        return weight * out[0]
+
+    @staticmethod
+    def backward(ctx, grad):
+        xs, g = ctx.saved_tensors
+        ld_s, slope, scales = ctx.meta
+        B, C, h, w = xs.shape
+        arr, n = hip.pod_scales(scales)
+        go = grad.detach().reshape(1).to(torch.float32).contiguous()
+        d = hip.empty_like_rows(xs)
+        with hip._timed("ucd_pod_backward", 2 * B * h * w * C * xs.element_size()):
+            hip._check(hip.load().ucd_pod_backward(hip.ptr(xs), ld_s, hip.dtype_code(xs), B, C, h, w, slope,
+                                                   hip.C.cast(arr, hip.C.c_void_p), n, hip.ptr(g), hip.ptr(go), hip.ptr(d), C,
+                                                   hip.stream()), "ucd_pod_backward")
+        return d, None, None, None, None
+
+
+def pod_kernels_take(x):
+    """Do the Local POD kernels serve this map?  bf16 or fp32 on a GPU, C a multiple of 8 up to 8192, at most 1024 rows and
+    columns (ucd_pod_plan states the same bounds)."""
+    return (x.is_cuda and x.dtype in (torch.bfloat16, torch.float32) and x.shape[1] % 8 == 0 and x.shape[1] <= 8192
+            and max(x.shape[2:]) <= 1024)
+
+
+def fused_local_pod(x_s, x_t, slope=1.0, scales=POD_SCALES, weight=1.0):
+    """``weight * mean_b |E^(x_s)_b - E^(x_t)_b|``: the Local POD distance of one level (PLOP) between a student and a teacher
+    map ``[B, C, h, w]`` taken BEHIND a leaky-ReLU of slope ``slope`` (1: take the maps as they are); differentiable w.r.t.
+    ``x_s``.  On the GPU it is four HIP launches forward and one backward (csrc/pod.hip); CPU tensors, maps the kernels refuse
+    (``pod_kernels_take``) and ``UCD_FUSED_POD=0`` run ``local_pod_torch``."""
+    scales = _pod_check(x_s, x_t, slope, scales)
+    if not pod_kernels_take(x_s) or _switches.get("UCD_FUSED_POD", "1") == "0":
+        return local_pod_torch(x_s, x_t, slope, scales, weight)
+    return _FusedLocalPOD.apply(x_s, x_t, float(slope), scales, float(weight))
 
 
 KD_MODES = {"unbiased": hip.KD_UNBIASED, "plain": hip.KD_PLAIN}

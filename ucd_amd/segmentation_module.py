@@ -135,9 +135,11 @@ class Features(dict):
     """The reference's ``{"body", "pre_logits", "sem"}`` dict; the two attention-weighted maps are
     computed on first access, ``raw(name)`` returns the un-weighted map."""
 
-    def __init__(self, x_b, x_pl, sem):
+    def __init__(self, x_b, x_pl, sem, stages=None):
         super().__init__(sem=sem)
         self._raw = {"body": x_b, "pre_logits": x_pl}
+        # the raw outputs of body.mod2 .. mod5 when the forward was asked for them (``taps=True``: Local POD), else None
+        self.stages = stages
 
     def raw(self, name):
         return self._raw[name]
@@ -167,8 +169,12 @@ class IncrementalSegmentationModule(nn.Module):
         self.classes, self.head_channels = classes, head_channels
         self.tot_classes = reduce(lambda a, b: a + b, classes)
 
-    def _network(self, x, x_b_old=None, x_pl_old=None, ret_intermediate=False):
-        x_b = self.body(x)
+    def _network(self, x, x_b_old=None, x_pl_old=None, ret_intermediate=False, taps=False):
+        stages = None
+        if taps:
+            x_b, stages = self.body(x, taps=True)
+        else:
+            x_b = self.body(x)
         x_pl = self.head(x_b)
         if len(self.cls) == 1:
             c0 = self.cls[0]
@@ -177,7 +183,19 @@ class IncrementalSegmentationModule(nn.Module):
             w = torch.cat([m.weight for m in self.cls], dim=0)
             b = torch.cat([m.bias for m in self.cls], dim=0)
             x_o = _HeadProduct.apply(x_pl, w, b) if _own_heads_ok(x_pl, w) else F.conv2d(x_pl, w, b)
-        return x_o, x_b, x_pl
+        return (x_o, x_b, x_pl, stages) if taps else (x_o, x_b, x_pl)
+
+    def pod_slope(self):
+        """The slope that recovers a stage map's pre-activation values from the block output (Local POD): the block activation's
+        ``activation_param`` for ``leaky_relu``, 1 for ``identity``; any other activation cannot be undone and is refused."""
+        bn = self.body.mod2.block1.convs.bn1
+        act = getattr(bn, "activation", None)
+        if act == "leaky_relu":
+            return float(bn.activation_param)
+        if act == "identity":
+            return 1.0
+        raise ValueError(f"Local POD (--pod_factor) needs leaky_relu or identity block activations to recover the pre-activation "
+                         f"maps, not {act!r}")
 
     def init_new_classifier(self, device):
         """Balanced initialisation (segmentation_module.py:111-123): the newest head starts from the
@@ -190,9 +208,11 @@ class IncrementalSegmentationModule(nn.Module):
             cls.bias.fill_(new_bias.item())
             self.cls[0].bias[0] = new_bias.item()
 
-    def forward(self, x, x_b_old=None, x_pl_old=None, ret_intermediate=False, upsample=True):
+    def forward(self, x, x_b_old=None, x_pl_old=None, ret_intermediate=False, upsample=True, taps=False):
         """``upsample=False`` (not in the reference) skips the x16 bilinear up-sampling and returns ``None``
-        for the full-resolution logits: the trainer's fused losses read ``features["sem"]`` instead."""
+        for the full-resolution logits: the trainer's fused losses read ``features["sem"]`` instead.  ``taps=True`` also hands
+        out the raw outputs of ``body.mod2 .. mod5`` as ``features.stages`` (Local POD); nothing is materialised for it, but the
+        three stage boundaries give up their block link (``ResNet.forward``)."""
         out_size = x.shape[-2:]
         if x.is_cuda and x.dim() == 4:
             x = x.contiguous(memory_format=torch.channels_last)
@@ -203,9 +223,13 @@ class IncrementalSegmentationModule(nn.Module):
             node = _abn._abn_node()
             if node is not None and hasattr(node, "stat_arena_reset"):
                 node.stat_arena_reset(x.device.index if x.device.index is not None else torch.cuda.current_device(), hip.stream())
-        sem, x_b, x_pl = self._network(x, x_b_old, x_pl_old, ret_intermediate)
+        stages = None
+        if taps:
+            sem, x_b, x_pl, stages = self._network(x, x_b_old, x_pl_old, ret_intermediate, taps=True)
+        else:
+            sem, x_b, x_pl = self._network(x, x_b_old, x_pl_old, ret_intermediate)
         logits = F.interpolate(sem, size=out_size, mode="bilinear", align_corners=False) if upsample else None
-        return logits, Features(x_b, x_pl, sem)
+        return logits, Features(x_b, x_pl, sem, stages)
 
     def fix_bn(self):
         for m in self.modules():

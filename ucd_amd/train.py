@@ -38,7 +38,7 @@ import torch.nn as nn
 from . import switches as _switches
 from .contrastive import ucd_contrastive_loss
 from .loss import (KnowledgeDistillationLoss, UnbiasedCrossEntropy, UnbiasedKnowledgeDistillationLoss,
-                   fused_attn_mse, fused_seg_bce, fused_seg_losses)
+                   POD_SCALES, fused_attn_mse, fused_local_pod, fused_seg_bce, fused_seg_losses)
 
 
 def _raw(features, name):
@@ -79,6 +79,17 @@ class Trainer:
         self.lde_loss = nn.MSELoss()
         # the encoder term from the raw maps in one HIP operation (UCD_FUSED_LDE=0: attention maps + MSELoss in torch)
         self.fused_lde = self.lde_flag and device.type == "cuda" and _switches.get("UCD_FUSED_LDE", "1") != "0"
+        # Local POD feature distillation (PLOP, --pod_factor): the raw outputs of body.mod2 .. mod5 (factor pod_factor) and the raw
+        # pre-logits (pod_last_factor), student against teacher, each level one fused HIP operation (ucd_amd.loss.fused_local_pod);
+        # gamma = sqrt(all classes / new classes) is PLOP's adaptive factor
+        self.pod = float(getattr(opts, "pod_factor", 0.) or 0.)
+        self.pod_flag = self.pod > 0. and model_old is not None
+        if self.pod_flag:
+            self.pod_last = float(getattr(opts, "pod_last_factor", 0.0005))
+            self.pod_scales = tuple(int(s) for s in (getattr(opts, "pod_scales", None) or POD_SCALES))
+            self.pod_slope = getattr(model, "module", model).pod_slope()
+            getattr(model_old, "module", model_old).pod_slope()              # the teacher's maps are undone the same way
+            self.pod_gamma = math.sqrt(self.tot_classes / max(self.tot_classes - self.old_classes, 1))
         self.lkd = opts.loss_kd
         self.lkd_flag = self.lkd > 0. and model_old is not None
         self.lkd_loss = (UnbiasedKnowledgeDistillationLoss if opts.unkd else KnowledgeDistillationLoss)(alpha=opts.alpha)
@@ -206,7 +217,8 @@ class Trainer:
             with torch.cuda.graph(graph, capture_error_mode="thread_local"):
                 outputs_old, f = self._teacher_eager(static, up)
                 # materialise exactly what the step reads; the lazy attention maps are not part of the graph
-                out = (outputs_old, Features(f.raw("body"), f.raw("pre_logits"), f["sem"]))
+                # (the stage taps of a Local POD run ride in the tuple: the capture pool must not hand their memory out again)
+                out = (outputs_old, Features(f.raw("body"), f.raw("pre_logits"), f["sem"], f.stages))
             self._tg = {"graph": graph, "images": static, "out": out, "shape": tuple(images.shape), "up": bool(up)}
             graph.replay()
             return out
@@ -305,6 +317,8 @@ class Trainer:
         lkd = lde = zero
         fuse = self.fuse_logit_losses
         up = {} if not fuse else {"upsample": False}
+        if self.pod_flag:
+            up["taps"] = True               # both networks hand out their stage maps (the teacher's on its side stream: joined below)
         if model_old is not None:
             if self._side is not None:
                 main = torch.cuda.current_stream(self.device)
@@ -362,6 +376,9 @@ class Trainer:
         if self.lkd_flag:
             lkd = self.lkd * (kd if fuse else self.lkd_loss(outputs, outputs_old))   # train.py:131-133
         loss_tot = (total + con * self.pixcon_weight + lde) if fuse else (loss + lkd + lde)
+        if self.pod_flag:
+            lpod = self._local_pod(features, features_old)
+            loss_tot = loss_tot + lpod
         loss_tot.backward()
         if hasattr(model, "finish_grad_sync"):
             model.finish_grad_sync()
@@ -375,9 +392,25 @@ class Trainer:
                      "con": con.detach()}
         if self.regularizer_flag:
             self.last["reg"] = l_reg.detach()
+        if self.pod_flag:
+            self.last["LPOD"] = lpod.detach()
         if self.icarl_combined:
             self.last["icarl"] = (self.icarl * soft).detach()       # l_icarl of train.py:123; its gradient is part of `total`
         return self.last
+
+    def _local_pod(self, features, features_old):
+        """L_pod = gamma / L * sum_l f_l * level_l over the L = 5 levels: the four stage maps (factor pod_factor, the slope of the
+        block activation) and the raw pre-logits (pod_last_factor, slope 1).  The weight of a level goes into its call, so the sum
+        needs no further launches of that size; a level with factor 0 is skipped."""
+        levels = [(s, t, self.pod_slope, self.pod) for s, t in zip(features.stages, features_old.stages)]
+        levels.append((_raw(features, "pre_logits"), _raw(features_old, "pre_logits"), 1.0, self.pod_last))
+        lpod = None
+        for x_s, x_t, slope, factor in levels:
+            if factor == 0.:
+                continue
+            term = fused_local_pod(x_s, x_t, slope, self.pod_scales, self.pod_gamma * factor / len(levels))
+            lpod = term if lpod is None else lpod + term
+        return lpod
 
     def train(self, cur_epoch, optim, train_loader, scheduler=None, print_int=10, logger=None):
         """Train one epoch and return (epoch_loss, reg_loss) like the reference (train.py:76-183)."""
@@ -402,12 +435,20 @@ class Trainer:
             if "icarl" in r:                                    # train.py:155-156: l_icarl counts as regularisation loss
                 reg_loss += r["icarl"]
                 interval += r["icarl"]
+            if "LPOD" in r:                                     # the Local POD term counts as regularisation loss, next to lkd / lde
+                reg_loss += r["LPOD"]
+                interval += r["LPOD"]
             n += 1
             if (cur_step + 1) % print_int == 0:
                 value = (interval / print_int).item()           # the only host sync of the interval
                 self._check_mailbox()                           # a timed-out SyncBN mailbox exchange (its results are NaN) raises here
                 if logger is not None:
                     logger.info(f"Epoch {cur_epoch}, Batch {cur_step + 1}/{len(train_loader)}, Loss={value}")
+                    if "LPOD" in r and getattr(logger, "debug_flag", False):
+                        # train.py:163, for runs with the Local POD term under --debug only (the reads synchronise); every other
+                        # run logs what it always did
+                        logger.debug(f"Loss made of: CE {r['loss'].item()}, LKD {r['lkd'].item()}, LDE {r['lde'].item()}, "
+                                     f"LPOD {r['LPOD'].item()}")
                     logger.add_scalar("Loss", value, cur_epoch * len(train_loader) + cur_step + 1)
                 interval.zero_()
         if dist.is_available() and dist.is_initialized():
