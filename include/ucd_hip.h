@@ -588,6 +588,65 @@ int ucd_seg_losses_gather(const float* sem_s, int ld_s, const float* sem_t, int 
                           float* d_sem /* NULL: losses only */, int ld_d,
                           void* workspace, size_t workspace_bytes, ucd_stream_t stream);
 
+/* The same two calls with a PER-IMAGE weight on the cross entropy (the adaptive factor of the pseudo-labelling below):
+ *   loss_out[0] = 1 / (B H W) sum_b f_b sum_{p in image b} CE_p,   f_b = ce_sample_weight[b]
+ * and d_sem the gradient of ce_weight loss_out[0] + kd_weight loss_out[1]; the distillation term is untouched.
+ *   ce_sample_weight  [B] fp32 ON THE DEVICE, each in [0, 1] (the fixed-point gradient words of the packed and many-class forms
+ *                     are scaled for a pixel gradient of at most ce_weight / (B H W): a weight above 1 could wrap them; the host
+ *                     cannot check device values).  NULL: the unweighted call, launch for launch.
+ * A tile of the tiled forms and a cell of the gather form lie in one image: the weight multiplies ce_scale where a pixel's
+ * gradient coefficient is formed and the tile's or cell's cross entropy partial.  The weighted kernels are template
+ * instantiations of their own (the packed 16 + 8 and the many-class form sit at 256 VGPRs): ucd_seg_losses_ex and
+ * ucd_seg_losses_gather keep their code and their bits, and a weight of ones gives those bits too.  Plan, workspace, errors and
+ * every other argument: as the call without _w. */
+int ucd_seg_losses_ex_w(const float* sem_s, int ld_s, const float* sem_t, int ld_t, const int64_t* labels,
+                        int B, int H, int W, int h, int w, int Ctot, int K, int ce_old_cl, int kd_mode, float alpha,
+                        int ignore_index, float ce_weight, float kd_weight, const float* ce_sample_weight /*[B], NULL = 1*/,
+                        float* loss_out, float* d_sem, int ld_d, void* workspace, size_t workspace_bytes, ucd_stream_t stream);
+int ucd_seg_losses_gather_w(const float* sem_s, int ld_s, const float* sem_t, int ld_t, const int64_t* labels,
+                            int B, int H, int W, int h, int w, int Ctot, int K, int ce_old_cl, int kd_mode, float alpha,
+                            int ignore_index, float ce_weight, float kd_weight, const float* ce_sample_weight /*[B], NULL = 1*/,
+                            float* loss_out /*[2]*/, float* d_sem /* NULL: losses only */, int ld_d,
+                            void* workspace, size_t workspace_bytes, ucd_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * PLOP's pseudo-labelling (csrc/pseudo_label.hip).  sem_t [B*h*w, ld_t >= K] fp32: the frozen teacher's
+ * low-resolution logits as rows (as ucd_seg_losses takes them), labels int64 [B, H, W].  With z = up(sem_t)[b, :, y, x] (up:
+ * bilinear, align_corners=False, as F.interpolate and the loss kernels compute it), per pixel
+ *   c* = argmax_c z_c                       the first maximum (torch's rule, as ucd_seg_confusion)
+ *   u  = H(softmax z) / log K in [0, 1]     H = log S - T / S, m = max z, S = sum exp(z_c - m), T = sum (z_c - m) exp(z_c - m);
+ *                                           no epsilon; 0 for K = 1; K equal logits give exactly 1
+ *   candidate: 0 <= label < K and label != ignore_index.  Only candidates do class work.
+ * ucd_pseudo_hist   hist[c*, min(floor(u bins), bins - 1)] += 1 over the candidates.  hist [K, bins] int64 is ACCUMULATED into
+ *                   (zero it before the first batch); integer adds: exact, independent of order.  Summed per workgroup in LDS
+ *                   where K x bins words fit beside the cells (ucd_pseudo_plan says), else per wave; never one global add per pixel.
+ * ucd_pseudo_label  labels_out = c* where a candidate has u < thresholds[c*], ignore_index for any other candidate, the label
+ *                   itself elsewhere.  labels_out [B, H, W] int64 may not alias labels.  counts [B, 2] int32 = (candidates that
+ *                   passed, candidates): the call clears them itself, integer adds.  factor [B] fp32 = max(num / (den + 1e-6),
+ *                   f_min), max(0, f_min) for an image without candidates - a last small launch on the same stream (fp64, rounded
+ *                   once).  uncertainty (may be NULL; tests, diagnosis) [B, H, W] fp32 = u for candidates, 0 elsewhere.
+ *                   thresholds [K] fp32 on the device; 0 <= f_min <= 1.
+ * ucd_pseudo_plan   host only, no device call: the pixel tile, the grid over one image, the threads of a workgroup, the bytes of
+ *                   dynamic LDS and whether the histogram is summed in LDS.  bins = 0 plans the label pass.
+ * One pixel walk for both: a workgroup owns a tile of pixels (64 x 64, the larger side halved until it fits, down to 8 x 8), the
+ * teacher cells under it staged in LDS - (tile_y h / H + 3) x (tile_x w / W + 3) rows of K | 1 floats (the odd pitch spreads the
+ * banks) - and one lane per pixel, consecutive lanes along x (8-byte label loads and stores in contiguous runs).
+ * Limits: any factors H / h, W / w >= 1; K as the LDS allows - the smallest tile stages at most 11 x 11 cells, so 160 KB
+ * (163840 bytes) serve K <= 337 at every factor (ADE at --output_stride 8: K = 141 on 64 x 64 tiles, 68 KB); 2 <= bins <= 1024;
+ * B <= 65535 and H / tile_y <= 65535.
+ * Checked on the host before any device call, the message names the argument: UCD_EINVAL (a NULL pointer other than uncertainty;
+ * B, H, W, h, w or K below 1; H < h or W < w; ld_t < K; bins outside [2, 1024]; f_min outside [0, 1]; labels_out == labels),
+ * UCD_EUNSUPPORTED (no tile fits the LDS - the message states the bytes asked for; a grid limit); else the hipError_t of a failed
+ * launch.  On a negative code nothing was launched.  No allocation, no host synchronisation: the calls capture into graphs. */
+int ucd_pseudo_plan(int H, int W, int h, int w, int K, int bins, int* tile_y, int* tile_x, int* grid_y, int* grid_x, int* threads,
+                    size_t* lds_bytes, int* lds_hist);
+int ucd_pseudo_hist(const float* sem_t, int ld_t, const int64_t* labels, int B, int H, int W, int h, int w, int K,
+                    int ignore_index, int bins, int64_t* hist /*[K, bins], accumulated*/, ucd_stream_t stream);
+int ucd_pseudo_label(const float* sem_t, int ld_t, const int64_t* labels, int B, int H, int W, int h, int w, int K,
+                     int ignore_index, const float* thresholds /*[K]*/, float f_min, int64_t* labels_out,
+                     int* counts /*[B, 2]: num, den*/, float* factor /*[B]*/, float* uncertainty /*[B, H, W] or NULL*/,
+                     ucd_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Fused full-resolution BINARY cross entropy losses: --bce, --icarl, --method LWF-MC (csrc/seg_gather.hip).
  * Rows as for ucd_seg_losses: sem_s [B*h*w, ld_s >= Ctot] / sem_t [B*h*w, ld_t >= K] float32 (sem_t may be NULL), labels int64

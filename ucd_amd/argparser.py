@@ -21,6 +21,10 @@ METHOD_PRESETS = {
     "MiB": {},
     "att": {},
     "UCD": {"loss_kd": 10, "unce": True, "unkd": True, "init_balanced": True},
+    # PLOP (Douillard et al., CVPR 2021) minus its POD on the logits, which is not built: entropy pseudo-labels with the adaptive
+    # factor, Local POD on the features, plain cross entropy, no distillation of the logits, no contrastive term
+    "PLOP": {"pseudo": "entropy", "pseudo_adaptive": True, "pod_factor": 0.01, "pod_last_factor": 0.0005, "init_balanced": True,
+             "pixcon_weight": 0.0},
 }
 NUM_CLASSES = {"voc": 21, "ade": 150, "city": 20}
 
@@ -32,6 +36,9 @@ def modify_command_options(opts):
         opts.sample_num = 0
     for key, value in METHOD_PRESETS.get(opts.method, {}).items():
         setattr(opts, key, value)
+    if getattr(opts, "pseudo", None) is not None and (opts.bce or opts.icarl):
+        raise ValueError("--pseudo cannot be combined with --bce / --icarl / --method LWF-MC: the pseudo-labels carry a per-image "
+                         "weight on the cross entropy, which the BCE kernel does not take and PLOP does not define for it")
     opts.no_overlap = not opts.overlap
     opts.no_cross_val = not opts.cross_val
     return opts
@@ -50,6 +57,22 @@ class _EvalScales(argparse.Action):
         if any(v <= 0 for v in values):
             parser.error(f"{option_string} takes positive scales, got {' '.join(str(v) for v in values)}")
         setattr(namespace, self.dest, values)
+
+
+def _pseudo_bins(text):
+    """--pseudo_nb_bins: what the histogram kernel takes"""
+    value = int(text)
+    if not 2 <= value <= 1024:
+        raise argparse.ArgumentTypeError(f"the number of bins must be in 2 .. 1024, got {value}")
+    return value
+
+
+def _unit_interval(text):
+    """--pseudo_adaptive_min: a floor of the per-image weight on the cross entropy, which the loss kernels take in [0, 1]"""
+    value = float(text)
+    if not 0.0 <= value <= 1.0:
+        raise argparse.ArgumentTypeError(f"the value must be in [0, 1], got {text}")
+    return value
 
 
 class _PodScales(argparse.Action):
@@ -115,6 +138,12 @@ _ARGS = [
     # and the pooling scales (ucd_amd.loss.fused_local_pod)
     _flag("--pod_factor", type=float, default=0.), _flag("--pod_last_factor", type=float, default=0.0005),
     _flag("--pod_scales", type=int, nargs="+", default=[1, 2, 4], action=_PodScales),
+    # PLOP's pseudo-labelling (ucd_amd.loss.fused_pseudo_labels): background pixels take the teacher's class where the entropy of
+    # its soft-max, as a fraction of log K, is below the class's median over the training set (floored at --pseudo_threshold;
+    # histogram of --pseudo_nb_bins bins); --pseudo_adaptive weighs an image's cross entropy by its share of kept candidates
+    _flag("--pseudo", type=str, default=None, choices=["entropy"]), _flag("--pseudo_threshold", type=float, default=0.001),
+    _flag("--pseudo_nb_bins", type=_pseudo_bins, default=100), _flag("--pseudo_adaptive", **_ON),
+    _flag("--pseudo_adaptive_min", type=_unit_interval, default=0.0),
     # regularisers (EWC / RW / PI; --method EWC|RW|PI): ucd_amd.regularizer, after the UCD step
     _flag("--regularizer", default=None, type=str, choices=["ewc", "rw", "pi"]),
     _flag("--reg_importance", type=float, default=1.), _flag("--reg_alpha", type=float, default=0.9),

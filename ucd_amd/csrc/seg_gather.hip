@@ -119,16 +119,18 @@ __device__ __forceinline__ float lane_get(float v, int k) { return __int_as_floa
 __device__ __forceinline__ float uniform(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
 
 // part: [B * h * w][2] (ce sum, kd sum) of the pixels whose (y0, x0) cell this is; d_sem (may be NULL): the cell's row
-template <int NR>
+// SW: image walk.b weighs its cross entropy with ce_sw[walk.b] (ucd_seg_losses_gather_w; a cell lies in one image)
+template <int NR, bool SW>
 __global__ __launch_bounds__(kWave) void seg_losses_gather_kernel(
     const float* __restrict__ sem_s, int ld_s, const float* __restrict__ sem_t, int ld_t, const int64_t* __restrict__ labels,
     int H, int W, int h, int w, int Ctot, int K, int ignore_index, float scale_h, float scale_w, float inv_scale_h,
     float inv_scale_w, float ce_scale, float kd_scale, float* __restrict__ part, float* __restrict__ d_sem, int ld_d, int kce,
-    int kd_plain, float alpha) {
+    int kd_plain, float alpha, const float* __restrict__ ce_sw) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   constexpr float kNegBig = -1e30f;
   const int cell = blockIdx.x, lane = threadIdx.x;
   const CellWalk walk(cell, H, W, h, w, scale_h, scale_w, inv_scale_h, inv_scale_w);
+  const float sw = SW ? ce_sw[walk.b] : 1.f;
   // the 3 x 3 cells around (i, j): [9][Ctot] student, [9][K] teacher logits times alpha (the up-sampling is linear); dense rows
   float* s_log = smem;
   float* t_log = smem + 9 * Ctot;
@@ -263,7 +265,7 @@ __global__ __launch_bounds__(kWave) void seg_losses_gather_kernel(
       }
       if (pw != 0.f) {
         // g_c = e_c (a_all - a_old [c<K] - b_bn [c in bkg/new]) - hot [c == label] - b_q te_c [q_lo<=c<K]  (seg_losses_wide_kernel)
-        const float ce_w = ignored ? 0.f : ce_scale;
+        const float ce_w = ignored ? 0.f : (SW ? sw * ce_scale : ce_scale);
         const float a_all = (ce_w + (plain ? 0.f : kdw)) / s_all;
         const float a_old = (lab0 ? ce_w * inv_old : 0.f) - (plain ? kdw * inv_old : 0.f);
         const float b_bn = plain ? 0.f : kdw * q0 * inv_bn;
@@ -292,7 +294,7 @@ __global__ __launch_bounds__(kWave) void seg_losses_gather_kernel(
     }
   }
   if (lane == 0) {
-    part[2 * cell + 0] = ce_sum;
+    part[2 * cell + 0] = SW ? sw * ce_sum : ce_sum;
     part[2 * cell + 1] = kd_sum;
   }
 }
@@ -365,11 +367,15 @@ int ucd_seg_bce(const float* sem_s, int ld_s, const float* sem_t, int ld_t, cons
   return rc ? rc : seg_pair_reduce(fn, part, g.cells, g.inv_pix, loss_out, s);
 }
 
-int ucd_seg_losses_gather(const float* sem_s, int ld_s, const float* sem_t, int ld_t, const int64_t* labels, int B, int H, int W,
-                          int h, int w, int Ctot, int K, int ce_old_cl, int kd_mode, float alpha, int ignore_index, float ce_weight,
-                          float kd_weight, float* loss_out, float* d_sem, int ld_d, void* workspace, size_t workspace_bytes,
-                          ucd_stream_t stream) {
-  static const char* fn = "ucd_seg_losses_gather";
+}  // extern "C"
+
+namespace {
+
+// ucd_seg_losses_gather and ucd_seg_losses_gather_w: one body under the name of the entry that was called; ce_sw NULL: no weight
+int seg_losses_gather_impl(const char* fn, const float* sem_s, int ld_s, const float* sem_t, int ld_t, const int64_t* labels, int B, int H,
+                           int W, int h, int w, int Ctot, int K, int ce_old_cl, int kd_mode, float alpha, int ignore_index,
+                           float ce_weight, float kd_weight, const float* ce_sw, float* loss_out, float* d_sem, int ld_d, void* workspace,
+                           size_t workspace_bytes, ucd_stream_t stream) {
   GatherLaunch g;
   int rc = gather_prologue(fn, sem_s, ld_s, sem_t, ld_t, labels, B, H, W, h, w, Ctot, K, loss_out, d_sem, ld_d, workspace, workspace_bytes,
                            [&] { return seg_ex_check(fn, Ctot, K, ce_old_cl, kd_mode, alpha, sem_t != nullptr); },
@@ -380,11 +386,16 @@ int ucd_seg_losses_gather(const float* sem_s, int ld_s, const float* sem_t, int 
   hipStream_t s = (hipStream_t)stream;
   const int kd_plain = kd_mode == UCD_KD_PLAIN;
   float* part = (float*)workspace;
-#define UCD_SEG_GATHER(NR)                                                                                                          \
-  seg_losses_gather_kernel<NR><<<g.cells, kWave, g.lds, s>>>(sem_s, ld_s, sem_t, ld_t, labels, H, W, h, w, Ctot, K, ignore_index,    \
-                                                            g.scale_h, g.scale_w, g.inv_scale_h, g.inv_scale_w,                     \
-                                                            ce_weight * g.inv_pix, kd_weight * g.inv_pix, part, d_sem, ld_d,        \
-                                                            ce_old_cl, kd_plain, alpha)
+#define UCD_SEG_GATHER_SW(NR, SW)                                                                                                    \
+  seg_losses_gather_kernel<NR, SW><<<g.cells, kWave, g.lds, s>>>(sem_s, ld_s, sem_t, ld_t, labels, H, W, h, w, Ctot, K, ignore_index, \
+                                                                g.scale_h, g.scale_w, g.inv_scale_h, g.inv_scale_w,                  \
+                                                                ce_weight * g.inv_pix, kd_weight * g.inv_pix, part, d_sem, ld_d,     \
+                                                                ce_old_cl, kd_plain, alpha, ce_sw)
+#define UCD_SEG_GATHER(NR)                  \
+  do {                                      \
+    if (ce_sw) UCD_SEG_GATHER_SW(NR, true); \
+    else UCD_SEG_GATHER_SW(NR, false);      \
+  } while (0)
   const int rounds = ceil_div(Ctot, kWave);           // 64 KB of LDS hold 1820 classes: at most 29 rounds
   if (rounds <= 1) UCD_SEG_GATHER(1);
   else if (rounds <= 2) UCD_SEG_GATHER(2);
@@ -392,8 +403,31 @@ int ucd_seg_losses_gather(const float* sem_s, int ld_s, const float* sem_t, int 
   else if (rounds <= 8) UCD_SEG_GATHER(8);
   else UCD_SEG_GATHER(29);
 #undef UCD_SEG_GATHER
+#undef UCD_SEG_GATHER_SW
   rc = check_launch(fn);
   return rc ? rc : seg_pair_reduce(fn, part, g.cells, g.inv_pix, loss_out, s);
+}
+
+}  // namespace
+
+extern "C" {
+
+int ucd_seg_losses_gather(const float* sem_s, int ld_s, const float* sem_t, int ld_t, const int64_t* labels, int B, int H, int W,
+                          int h, int w, int Ctot, int K, int ce_old_cl, int kd_mode, float alpha, int ignore_index, float ce_weight,
+                          float kd_weight, float* loss_out, float* d_sem, int ld_d, void* workspace, size_t workspace_bytes,
+                          ucd_stream_t stream) {
+  return seg_losses_gather_impl("ucd_seg_losses_gather", sem_s, ld_s, sem_t, ld_t, labels, B, H, W, h, w, Ctot, K, ce_old_cl, kd_mode,
+                                alpha, ignore_index, ce_weight, kd_weight, nullptr, loss_out, d_sem, ld_d, workspace, workspace_bytes,
+                                stream);
+}
+
+int ucd_seg_losses_gather_w(const float* sem_s, int ld_s, const float* sem_t, int ld_t, const int64_t* labels, int B, int H, int W,
+                            int h, int w, int Ctot, int K, int ce_old_cl, int kd_mode, float alpha, int ignore_index, float ce_weight,
+                            float kd_weight, const float* ce_sample_weight, float* loss_out, float* d_sem, int ld_d, void* workspace,
+                            size_t workspace_bytes, ucd_stream_t stream) {
+  return seg_losses_gather_impl("ucd_seg_losses_gather_w", sem_s, ld_s, sem_t, ld_t, labels, B, H, W, h, w, Ctot, K, ce_old_cl,
+                                kd_mode, alpha, ignore_index, ce_weight, kd_weight, ce_sample_weight, loss_out, d_sem, ld_d, workspace,
+                                workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -43,16 +43,19 @@ __device__ __forceinline__ Footprint tile_footprint(int ty0, int tx0, int tile_y
   return f;
 }
 
-// a block's two loss sums in a fixed order: lanes, then the four waves through red[2][4]
+// a block's two loss sums in a fixed order: lanes, then the four waves through red[2][4].  SW: the block's image weighs its
+// cross entropy with sw (a tile lies in one image: blockIdx.z)
+template <bool SW>
 __device__ __forceinline__ void store_block_losses(float ce_sum, float kd_sum, float* red, float* __restrict__ loss_part, int tiles_x,
-                                                   int tiles_y) {
+                                                   int tiles_y, float sw) {
   ce_sum = wave_sum(ce_sum);
   kd_sum = wave_sum(kd_sum);
   if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = ce_sum; red[4 + (threadIdx.x >> 6)] = kd_sum; }
   __syncthreads();
   if (threadIdx.x == 0) {
     const int blk = (blockIdx.z * tiles_y + blockIdx.y) * tiles_x + blockIdx.x;
-    loss_part[2 * blk + 0] = red[0] + red[1] + red[2] + red[3];
+    const float ce = red[0] + red[1] + red[2] + red[3];
+    loss_part[2 * blk + 0] = SW ? sw * ce : ce;
     loss_part[2 * blk + 1] = red[4] + red[5] + red[6] + red[7];
   }
 }
@@ -64,15 +67,16 @@ __device__ __forceinline__ void store_block_losses(float ce_sum, float kd_sum, f
 // form below does not: UCD_SEG_PK=0, a d_sem off the 16-byte grid, accumulator copies that do not fit the LDS.
 // EX (see seg_losses_pk_kernel): cross entropy pooled over [0, kce), kce == K or 1; teacher rows staged times alpha;
 // kd_plain: KD = -sum_{c<K} q_c (z_c - LSE_old) / K.  EX == false keeps the arithmetic the kernel had.
-template <int CT, int KT, bool EX>
+template <int CT, int KT, bool EX, bool SW>
 __global__ __launch_bounds__(kThreads) void seg_losses_kernel(
     const float* __restrict__ sem_s, int ld_s, const float* __restrict__ sem_t, int ld_t, const int64_t* __restrict__ labels,
     int H, int W, int h, int w, int Ctot, int K, int ignore_index, float scale_h, float scale_w, float ce_scale,
     float kd_scale, float* __restrict__ loss_part, float* __restrict__ d_sem, int ld_d, int tiles_x, int tiles_y, int kce,
-    int kd_plain, float alpha) {
+    int kd_plain, float alpha, const float* __restrict__ ce_sw) {
   static_assert(CT > 0 && KT > 0 && KT <= CT, "the classes of a pixel live in CT + KT registers");
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int b = blockIdx.z, ty0 = blockIdx.y * kTileY, tx0 = blockIdx.x * kTileX;
+  const float sw = SW ? ce_sw[b] : 1.f;      // SW: the image's weight on the cross entropy (ucd_seg_losses_ex_w)
   const Footprint fp = tile_footprint(ty0, tx0, kTileY, H, W, h, w, scale_h, scale_w);
   const int ya = fp.ya, xa = fp.xa, nx = fp.nx, ncell = fp.ncell;
   // kRep copies of the gradient accumulators, a lane adds into copy (lane & 15): the 15-16 consecutive pixel columns under
@@ -217,7 +221,7 @@ __global__ __launch_bounds__(kThreads) void seg_losses_kernel(
       q0 = te[0] * inv_st;
       kd_pix = plain ? q0 * (zc[0] - lse_old) : q0 * (lse_bn - den);
     }
-    const float ce_w = ignored ? 0.f : ce_scale;
+    const float ce_w = ignored ? 0.f : (SW ? sw * ce_scale : ce_scale);
     const float kdw = kd_scale * invK;
     const float q0bn = q0 * inv_bn;
     const float kd_ref = plain ? lse_old : den;      // what the old classes' log-probabilities are taken against
@@ -264,7 +268,7 @@ __global__ __launch_bounds__(kThreads) void seg_losses_kernel(
       atomicAdd(&d_sem[((size_t)(b * h + cy) * w + cx) * ld_d + c], v);
     }
   }
-  store_block_losses(ce_sum, kd_sum, red, loss_part, tiles_x, tiles_y);
+  store_block_losses<SW>(ce_sum, kd_sum, red, loss_part, tiles_x, tiles_y, sw);
 }
 
 // ---- round 5: the few-class form on packed fp32 math, old and new classes in separate register groups ------------------------------
@@ -291,12 +295,12 @@ __device__ __forceinline__ f32x2 exp2_2(f32x2 a) { return f32x2{__builtin_amdgcn
 //   KD = -sum_{c<K} q_c (z_c - LSE_old) / K,   dKD/dz_c = [c < K] (e_c / sum_old - q_c) / K.
 // All three are block-uniform; the sums it needs (old slots, all slots) are the ones the unbiased pair takes already.  EX == false
 // keeps the arithmetic the kernel had (the same operations in the same order: the same bits).
-template <int KT, int NT, bool EX>
+template <int KT, int NT, bool EX, bool SW>
 __global__ __launch_bounds__(kThreads) void seg_losses_pk_kernel(
     const float* __restrict__ sem_s, int ld_s, const float* __restrict__ sem_t, int ld_t, const int64_t* __restrict__ labels,
     int H, int W, int h, int w, int Ctot, int K, int ignore_index, float scale_h, float scale_w, float ce_scale,
     float kd_scale, float* __restrict__ loss_part, float* __restrict__ d_sem, int ld_d, int tiles_x, int tiles_y, int cell_cap,
-    float fx_scale, int kce, int kd_plain, float alpha) {
+    float fx_scale, int kce, int kd_plain, float alpha, const float* __restrict__ ce_sw) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   constexpr int CT = KT + NT, NP = CT / 2, KP = KT / 2, kRep = kRepPk;
   // logit rows in LDS are CT + 1 / KT + 1 floats apart: the lanes of a wave read from ~5 cells, sixteen lanes the same address - a
@@ -306,6 +310,7 @@ __global__ __launch_bounds__(kThreads) void seg_losses_pk_kernel(
   static_assert(KT % 4 == 0 && NT % 4 == 0, "slot groups are read four at a time");
   constexpr float kL2e = 1.4426950408889634f, kLn2 = 0.6931471805599453f, kNegBig = -1e30f;
   const int b = blockIdx.z, ty0 = blockIdx.y * kTileY, tx0 = blockIdx.x * kTileX;
+  const float sw = SW ? ce_sw[b] : 1.f;
   const Footprint fp = tile_footprint(ty0, tx0, kTileY, H, W, h, w, scale_h, scale_w);
   const int ya = fp.ya, xa = fp.xa, nx = fp.nx, ncell = fp.ncell;
   // the host sized the LDS for the exact footprint it computed with the same arithmetic; a disagreement must not become a silent
@@ -481,7 +486,7 @@ __global__ __launch_bounds__(kThreads) void seg_losses_pk_kernel(
     const float logp = lab0 ? lse_old - den : z_lab - den;
     if (!ignored) ce_sum += -logp;
     const float inv_all = 1.f / s_all;
-    const float ce_w = ignored ? 0.f : ce_scale;
+    const float ce_w = ignored ? 0.f : (SW ? sw * ce_scale : ce_scale);
     // teacher soft-max over the old classes; q_c = te_c / sum te
     f32x2 te[KP];
     float inv_st = 0.f, q0 = 0.f, kd_pix = 0.f;
@@ -572,7 +577,7 @@ __global__ __launch_bounds__(kThreads) void seg_losses_pk_kernel(
       atomicAdd(reinterpret_cast<int*>(d_sem) + ((size_t)(b * h + cy) * w + cx) * ld_d + c, __double2int_rn(vd * (double)fx_scale));
     }
   }
-  store_block_losses(ce_sum, kd_sum, red, loss_part, tiles_x, tiles_y);
+  store_block_losses<SW>(ce_sum, kd_sum, red, loss_part, tiles_x, tiles_y, sw);
 }
 
 // ---- the same losses for MANY classes (ADE20K: 151 student / 101 teacher classes; any Ctot the LDS holds) ----------------------
@@ -600,17 +605,18 @@ __device__ __forceinline__ float4 interp4(const float* base, int o00, int o01, i
 
 // EX (see seg_losses_pk_kernel): cross entropy pooled over [0, kce), kce == K or 1; teacher rows staged times alpha; kd_plain:
 // KD = -sum_{c<K} q_c (z_c - LSE_old) / K - the row constants of phase A change, phase B only widens its teacher mask to class 0.
-template <bool EX>
+template <bool EX, bool SW>
 __global__ __launch_bounds__(kThreads) void seg_losses_wide_kernel(
     const float* __restrict__ sem_s, int ld_s, const float* __restrict__ sem_t, int ld_t, const int64_t* __restrict__ labels,
     int H, int W, int h, int w, int Ctot, int K, int ignore_index, float scale_h, float scale_w, float ce_scale,
     float kd_scale, float* __restrict__ loss_part, float* __restrict__ d_sem, int ld_d, int tiles_x, int tiles_y, float fx_scale,
-    int kce, int kd_plain, float alpha) {
+    int kce, int kd_plain, float alpha, const float* __restrict__ ce_sw) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   constexpr int kTY = 4 * kRW;
   constexpr float kL2e = 1.4426950408889634f, kLn2 = 0.6931471805599453f, kNegBig = -1e30f;
   const int CS = (Ctot + 3) & ~3, KS = sem_t ? ((K + 3) & ~3) : 0;
   const int b = blockIdx.z, ty0 = blockIdx.y * kTY, tx0 = blockIdx.x * kTileX;
+  const float sw = SW ? ce_sw[b] : 1.f;
   const Footprint fp = tile_footprint(ty0, tx0, kTY, H, W, h, w, scale_h, scale_w);
   const int ya = fp.ya, xa = fp.xa, nx = fp.nx, ncell = fp.ncell;
   float* s_log = smem;                         // [ncell][CS]
@@ -735,7 +741,7 @@ __global__ __launch_bounds__(kThreads) void seg_losses_wide_kernel(
     const bool lab0 = pool && lab == 0;     // the label is the pooled background (plain CE: a one-hot like any)
     const float logp = lab0 ? lse_old - den : z_lab - den;
     if (!ignored) ce_sum += -logp;
-    const float ce_w = ignored ? 0.f : ce_scale;
+    const float ce_w = ignored ? 0.f : (SW ? sw * ce_scale : ce_scale);
     float inv_st = 0.f, q0 = 0.f;
     if (sem_t) {
       inv_st = 1.f / st;
@@ -837,7 +843,7 @@ __global__ __launch_bounds__(kThreads) void seg_losses_wide_kernel(
       else atomicAdd(dst, (float)vd);
     }
   }
-  store_block_losses(ce_sum, kd_sum, red, loss_part, tiles_x, tiles_y);
+  store_block_losses<SW>(ce_sum, kd_sum, red, loss_part, tiles_x, tiles_y, sw);
 }
 
 // ---- validation: up-sampling + arg-max + confusion matrix ---------------------------------------
@@ -1004,16 +1010,17 @@ int ucd_seg_losses_plan(int H, int W, int h, int w, int Ctot, int K, int has_tea
 namespace {
 
 // opt every instantiation of one EX value in to the LDS budget, launch the planned form
-template <bool EX>
+template <bool EX, bool SW>
 int seg_launch(const char* fn, int form, dim3 grid, size_t lds, hipStream_t s, const float* sem_s, int ld_s, const float* sem_t, int ld_t,
                const int64_t* labels, int H, int W, int h, int w, int Ctot, int K, int ignore_index, float ce_scale, float kd_scale,
-               float* part, float* d_sem, int ld_d, int cells, float fx_scale, int ce_old_cl, int kd_plain, float alpha) {
-  UCD_TRY_LDS((seg_losses_pk_kernel<16, 8, EX>), 150 * 1024);
-  UCD_TRY_LDS((seg_losses_pk_kernel<20, 4, EX>), 150 * 1024);
-  UCD_TRY_LDS((seg_losses_pk_kernel<12, 12, EX>), 150 * 1024);
-  UCD_TRY_LDS((seg_losses_kernel<24, 16, EX>), 150 * 1024);
-  UCD_TRY_LDS((seg_losses_kernel<24, 24, EX>), 150 * 1024);
-  UCD_TRY_LDS(seg_losses_wide_kernel<EX>, 150 * 1024);
+               float* part, float* d_sem, int ld_d, int cells, float fx_scale, int ce_old_cl, int kd_plain, float alpha,
+               const float* ce_sw) {
+  UCD_TRY_LDS((seg_losses_pk_kernel<16, 8, EX, SW>), 150 * 1024);
+  UCD_TRY_LDS((seg_losses_pk_kernel<20, 4, EX, SW>), 150 * 1024);
+  UCD_TRY_LDS((seg_losses_pk_kernel<12, 12, EX, SW>), 150 * 1024);
+  UCD_TRY_LDS((seg_losses_kernel<24, 16, EX, SW>), 150 * 1024);
+  UCD_TRY_LDS((seg_losses_kernel<24, 24, EX, SW>), 150 * 1024);
+  UCD_TRY_LDS((seg_losses_wide_kernel<EX, SW>), 150 * 1024);
   hipError_t e = hipMemsetAsync(d_sem, 0, (size_t)grid.z * h * w * ld_d * sizeof(float), s);
   if (e != hipSuccess) { set_error("%s: %s", fn, hipGetErrorString(e)); return (int)e; }
   const int tiles_x = grid.x, tiles_y = grid.y;
@@ -1022,27 +1029,28 @@ int seg_launch(const char* fn, int form, dim3 grid, size_t lds, hipStream_t s, c
   sem_s, ld_s, sem_t, ld_t, labels, H, W, h, w, Ctot, K, ignore_index, (float)h / (float)H, (float)w / (float)W, ce_scale, kd_scale, part, \
       d_sem, ld_d, tiles_x, tiles_y
   if (form == UCD_SEG_PK_16_8)
-    seg_losses_pk_kernel<16, 8, EX><<<grid, kThreads, lds, s>>>(UCD_SEG_ARGS, cells, fx_scale, ce_old_cl, kd_plain, alpha);
+    seg_losses_pk_kernel<16, 8, EX, SW><<<grid, kThreads, lds, s>>>(UCD_SEG_ARGS, cells, fx_scale, ce_old_cl, kd_plain, alpha, ce_sw);
   else if (form == UCD_SEG_PK_20_4)
-    seg_losses_pk_kernel<20, 4, EX><<<grid, kThreads, lds, s>>>(UCD_SEG_ARGS, cells, fx_scale, ce_old_cl, kd_plain, alpha);
+    seg_losses_pk_kernel<20, 4, EX, SW><<<grid, kThreads, lds, s>>>(UCD_SEG_ARGS, cells, fx_scale, ce_old_cl, kd_plain, alpha, ce_sw);
   else if (form == UCD_SEG_PK_12_12)
-    seg_losses_pk_kernel<12, 12, EX><<<grid, kThreads, lds, s>>>(UCD_SEG_ARGS, cells, fx_scale, ce_old_cl, kd_plain, alpha);
+    seg_losses_pk_kernel<12, 12, EX, SW><<<grid, kThreads, lds, s>>>(UCD_SEG_ARGS, cells, fx_scale, ce_old_cl, kd_plain, alpha, ce_sw);
   else if (form == UCD_SEG_REG_24_16)
-    seg_losses_kernel<24, 16, EX><<<grid, kThreads, lds, s>>>(UCD_SEG_ARGS, ce_old_cl, kd_plain, alpha);
+    seg_losses_kernel<24, 16, EX, SW><<<grid, kThreads, lds, s>>>(UCD_SEG_ARGS, ce_old_cl, kd_plain, alpha, ce_sw);
   else if (form == UCD_SEG_REG_24_24)
-    seg_losses_kernel<24, 24, EX><<<grid, kThreads, lds, s>>>(UCD_SEG_ARGS, ce_old_cl, kd_plain, alpha);
+    seg_losses_kernel<24, 24, EX, SW><<<grid, kThreads, lds, s>>>(UCD_SEG_ARGS, ce_old_cl, kd_plain, alpha, ce_sw);
   else
-    seg_losses_wide_kernel<EX><<<grid, kThreads, lds, s>>>(UCD_SEG_ARGS, form == UCD_SEG_WIDE_FIXED ? fx_scale : 0.f, ce_old_cl, kd_plain,
-                                                           alpha);
+    seg_losses_wide_kernel<EX, SW><<<grid, kThreads, lds, s>>>(UCD_SEG_ARGS, form == UCD_SEG_WIDE_FIXED ? fx_scale : 0.f, ce_old_cl,
+                                                               kd_plain, alpha, ce_sw);
 #undef UCD_SEG_ARGS
   return check_launch(fn);
 }
 
-// ucd_seg_losses and ucd_seg_losses_ex: one body, the messages carry the name of the entry that was called
+// ucd_seg_losses, ucd_seg_losses_ex and ucd_seg_losses_ex_w: one body, the messages carry the name of the entry that was called.
+// ce_sw (device, [B], NULL: the kernels without a weight): image b's cross entropy counts ce_sw[b] times, in the loss and the gradient
 int seg_losses_impl(const char* fn, const float* sem_s, int ld_s, const float* sem_t, int ld_t, const int64_t* labels, int B, int H, int W,
                     int h, int w, int Ctot, int K, int ce_old_cl, int kd_mode, float alpha, int ignore_index, float ce_weight,
                     float kd_weight, float* loss_out, float* d_sem, int ld_d, void* workspace, size_t workspace_bytes,
-                    ucd_stream_t stream) {
+                    ucd_stream_t stream, const float* ce_sw = nullptr) {
   UCD_REQUIRE(sem_s && labels && loss_out && d_sem && workspace, UCD_EINVAL, "%s: NULL argument", fn);
   UCD_REQUIRE(B > 0 && H > 0 && W > 0 && h > 0 && w > 0 && Ctot > 0 && K >= 1 && K <= Ctot, UCD_EINVAL, "%s: bad sizes", fn);
   UCD_REQUIRE(ld_s >= Ctot && ld_d >= Ctot && (!sem_t || ld_t >= K), UCD_EINVAL, "%s: bad leading dimension", fn);
@@ -1069,10 +1077,13 @@ int seg_losses_impl(const char* fn, const float* sem_s, int ld_s, const float* s
   const float fx_gmax = fabsf(ce_weight * inv_pix) + 2.f * fabsf(kd_weight * inv_pix) / (float)K;
   const float fx_scale = fx_gmax > 0.f ? 131072.f / fx_gmax : 1.f;
   const dim3 grid(tiles_x, tiles_y, B);
-  rc = ex ? seg_launch<true>(fn, form, grid, lds, s, sem_s, ld_s, sem_t, ld_t, labels, H, W, h, w, Ctot, K, ignore_index,
-                             ce_weight * inv_pix, kd_weight * inv_pix, part, d_sem, ld_d, ny * nx, fx_scale, ce_old_cl, kd_plain, alpha)
-          : seg_launch<false>(fn, form, grid, lds, s, sem_s, ld_s, sem_t, ld_t, labels, H, W, h, w, Ctot, K, ignore_index,
-                              ce_weight * inv_pix, kd_weight * inv_pix, part, d_sem, ld_d, ny * nx, fx_scale, ce_old_cl, kd_plain, alpha);
+#define UCD_SEG_LAUNCH(EX, SW)                                                                                                      \
+  seg_launch<EX, SW>(fn, form, grid, lds, s, sem_s, ld_s, sem_t, ld_t, labels, H, W, h, w, Ctot, K, ignore_index, ce_weight * inv_pix, \
+                     kd_weight * inv_pix, part, d_sem, ld_d, ny * nx, fx_scale, ce_old_cl, kd_plain, alpha, ce_sw)
+  // the weighted kernels are instantiations of their own: the unweighted launches keep their code (two forms sit at 256 VGPRs)
+  rc = ce_sw ? (ex ? UCD_SEG_LAUNCH(true, true) : UCD_SEG_LAUNCH(false, true))
+             : (ex ? UCD_SEG_LAUNCH(true, false) : UCD_SEG_LAUNCH(false, false));
+#undef UCD_SEG_LAUNCH
   if (rc) return rc;
   if (packed || form == UCD_SEG_WIDE_FIXED) {
     const size_t n = (size_t)B * h * w * ld_d;
@@ -1109,6 +1120,14 @@ int ucd_seg_losses_ex(const float* sem_s, int ld_s, const float* sem_t, int ld_t
                       ucd_stream_t stream) {
   return seg_losses_impl("ucd_seg_losses_ex", sem_s, ld_s, sem_t, ld_t, labels, B, H, W, h, w, Ctot, K, ce_old_cl, kd_mode, alpha,
                          ignore_index, ce_weight, kd_weight, loss_out, d_sem, ld_d, workspace, workspace_bytes, stream);
+}
+
+int ucd_seg_losses_ex_w(const float* sem_s, int ld_s, const float* sem_t, int ld_t, const int64_t* labels, int B, int H, int W,
+                        int h, int w, int Ctot, int K, int ce_old_cl, int kd_mode, float alpha, int ignore_index, float ce_weight,
+                        float kd_weight, const float* ce_sample_weight, float* loss_out, float* d_sem, int ld_d, void* workspace,
+                        size_t workspace_bytes, ucd_stream_t stream) {
+  return seg_losses_impl("ucd_seg_losses_ex_w", sem_s, ld_s, sem_t, ld_t, labels, B, H, W, h, w, Ctot, K, ce_old_cl, kd_mode, alpha,
+                         ignore_index, ce_weight, kd_weight, loss_out, d_sem, ld_d, workspace, workspace_bytes, stream, ce_sample_weight);
 }
 
 int ucd_seg_confusion(const float* sem, int ld_s, const int64_t* labels, int B, int H, int W, int h, int w, int Ctot,

@@ -201,6 +201,12 @@ SIGNATURES = {
     "ucd_seg_losses_ex": (_i, [_p, _i, _p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _f, _f, _p, _p, _i, _p, _z, _p]),
     "ucd_seg_losses_gather_workspace_bytes": (_z, [_i, _i, _i]),
     "ucd_seg_losses_gather": (_i, [_p, _i, _p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _f, _f, _p, _p, _i, _p, _z, _p]),
+    # the same two with ce_sample_weight [B] in front of loss_out
+    "ucd_seg_losses_ex_w": (_i, [_p, _i, _p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _f, _f, _p, _p, _p, _i, _p, _z, _p]),
+    "ucd_seg_losses_gather_w": (_i, [_p, _i, _p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _f, _f, _p, _p, _p, _i, _p, _z, _p]),
+    "ucd_pseudo_plan": (_i, [_i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p]),
+    "ucd_pseudo_hist": (_i, [_p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p]),
+    "ucd_pseudo_label": (_i, [_p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _p, _f, _p, _p, _p, _p, _p]),
 }
 
 _lib = None
@@ -651,6 +657,19 @@ def pod_plan(h, w, Cc, scales=(1, 2, 4), B=1, dtype=BF16):
     _check(load().ucd_pod_plan(int(h), int(w), int(Cc), C.cast(arr, C.c_void_p), n, int(B), int(dtype), C.cast(C.byref(n_E), C.c_void_p),
                                C.cast(C.byref(nbytes), C.c_void_p), C.cast(grid, C.c_void_p)), "ucd_pod_plan")
     return {"n_E": n_E.value, "workspace_bytes": nbytes.value, "grid": tuple(grid)}
+
+
+def pseudo_plan(H, W, h, w, K, bins=0):
+    """``ucd_pseudo_plan``: ``{"tile": (tile_y, tile_x), "grid": (tiles down, tiles across) of one image, "threads", "lds_bytes",
+    "lds_hist"}`` of a pseudo-labelling pass (csrc/pseudo_label.hip); ``bins`` 0 plans the label pass, 2 .. 1024 the histogram.  A
+    pure host function: it answers without a GPU and raises for a geometry the kernels refuse."""
+    v = [C.c_int(0) for _ in range(5)]
+    lds, lh = C.c_size_t(0), C.c_int(0)
+    ref = lambda x: C.cast(C.byref(x), C.c_void_p)
+    _check(load().ucd_pseudo_plan(int(H), int(W), int(h), int(w), int(K), int(bins), *[ref(x) for x in v], ref(lds), ref(lh)),
+           "ucd_pseudo_plan")
+    return {"tile": (v[0].value, v[1].value), "grid": (v[2].value, v[3].value), "threads": v[4].value, "lds_bytes": lds.value,
+            "lds_hist": bool(lh.value)}
 
 
 # ---------------------------------------------------------------------------------------------

@@ -12,6 +12,7 @@ The contrastive loss lives in :mod:`ucd_amd.contrastive`.
 from __future__ import annotations
 
 import functools
+import math
 
 import torch
 import torch.nn as nn
@@ -64,16 +65,22 @@ class _FusedSegLosses(_LowResLogitLoss):
     """total = ce_weight * mean(CE) + kd_weight * mean(KD) (ucd_seg_losses_ex, or ucd_seg_losses_gather for ``form="gather"``;
     SURVEY.md section 8-f1).  Every call names its loss pair: the cross entropy pools ``max(old_cl, 1)`` classes.  The pair the
     kernels were first built for (one class count for both losses, unbiased KD, alpha 1) is the launch, and the bits, of
-    ucd_seg_losses: the library picks its kernels by these values, not by the entry."""
+    ucd_seg_losses: the library picks its kernels by these values, not by the entry.  ``sample_weight`` ([B] fp32 on the device, each
+    in [0, 1]; None: the calls without one, launch for launch) weighs image b's cross entropy, in the loss and the gradient
+    (ucd_seg_losses_ex_w / ucd_seg_losses_gather_w)."""
 
     @staticmethod
-    def forward(ctx, sem, sem_old, labels, old_cl, ce_weight, kd_weight, ignore_index, kd_mode, alpha, form):
+    def forward(ctx, sem, sem_old, labels, old_cl, ce_weight, kd_weight, ignore_index, kd_mode, alpha, form, sample_weight=None):
         lib = hip.load()
         gather = form == "gather"
         # the gather form writes d_sem only where asked (the same loss bits without); the tiled forms always accumulate into it
         s, t, K, labels, out, d, (B, H, W, h, w, Ctot) = _LowResLogitLoss.operands(ctx, sem, sem_old, labels, int(old_cl),
                                                                                    ctx.needs_input_grad[0] or not gather)
         name = "ucd_seg_losses_gather" if gather else "ucd_seg_losses_ex"
+        sw = ()
+        if sample_weight is not None:
+            name += "_w"
+            sw = (hip.ptr(sample_weight),)
         nbytes = lib.ucd_seg_losses_gather_workspace_bytes(B, h, w) if gather else lib.ucd_seg_losses_workspace_bytes(B, H, W)
         ws = hip.workspace(nbytes, sem.device, "seglosses_gather" if gather else "seglosses")
         # one wave per cell reads its rows once; a tiled form also adds into them
@@ -81,7 +88,7 @@ class _FusedSegLosses(_LowResLogitLoss):
                         B * H * W * 8 + (1 if gather else 2) * B * h * w * (2 * Ctot + K) * 4):
             hip._check(getattr(lib, name)(hip.ptr(s), Ctot, hip.ptr(t), K, hip.ptr(labels), B, H, W, h, w, Ctot, max(K, 1),
                                           max(int(old_cl), 1), int(kd_mode), float(alpha), int(ignore_index), float(ce_weight),
-                                          float(kd_weight), hip.ptr(out), hip.ptr(d), Ctot, hip.ptr(ws), nbytes, hip.stream()), name)
+                                          float(kd_weight), *sw, hip.ptr(out), hip.ptr(d), Ctot, hip.ptr(ws), nbytes, hip.stream()), name)
         return _LowResLogitLoss.weighted(ctx, out, ce_weight, kd_weight)
 
 
@@ -292,7 +299,7 @@ def seg_losses_route(H, W, h, w, Ctot, K, has_teacher, ce_old_cl=None):
 
 
 def fused_seg_losses(sem, sem_old, labels, old_cl, ce_weight=1.0, kd_weight=0.0, ignore_index=255, *, kd="unbiased", alpha=1.0,
-                     form="auto"):
+                     form="auto", sample_weight=None):
     """Returns (ce_weight*CE + kd_weight*KD [differentiable w.r.t. ``sem``], CE, KD) where CE / KD are the
     reference's ``UnbiasedCrossEntropy(old_cl)(up(sem), labels).mean()`` (``old_cl`` 1: ``nn.CrossEntropyLoss``) and
     ``UnbiasedKnowledgeDistillationLoss(alpha=alpha)(up(sem), up(sem_old))`` or, with ``kd="plain"``,
@@ -303,18 +310,158 @@ def fused_seg_losses(sem, sem_old, labels, old_cl, ce_weight=1.0, kd_weight=0.0,
     ``form``: ``"tiled"`` is the scatter kernels (``ucd_seg_losses_ex``), which refuse a geometry whose tiles do
     not fit their LDS; ``"gather"`` is ``ucd_seg_losses_gather`` - any up-sampling factor >= 1, a gradient with the same bits on every
     run, and, under ``torch.no_grad()`` or with a ``sem`` that needs no gradient, the losses alone; ``"auto"`` is ``"tiled"`` wherever
-    that serves (the call, and the bits, it always was) and ``"gather"`` elsewhere (``seg_losses_route``)."""
+    that serves (the call, and the bits, it always was) and ``"gather"`` elsewhere (``seg_losses_route``).
+
+    ``sample_weight`` ([B], each in [0, 1] - the adaptive factor of ``fused_pseudo_labels``): CE becomes
+    ``1 / (BHW) sum_b sample_weight[b] sum_p CE_p``; KD is untouched.  None (the default) is the call without a weight."""
     if not sem.is_cuda:
         raise RuntimeError("ucd_amd.loss.fused_seg_losses runs on the GPU only (there is no CPU fallback)")
     if kd not in KD_MODES:
         raise ValueError(f"kd must be 'unbiased' or 'plain', not {kd!r}")
     if form not in SEG_LOSS_FORMS:
         raise ValueError(f"form must be 'auto', 'tiled' or 'gather', not {form!r}")
+    if sample_weight is not None:
+        if sample_weight.shape != (sem.shape[0],) or sample_weight.device != sem.device:
+            raise ValueError(f"sample_weight must be [{sem.shape[0]}] on {sem.device}, got {tuple(sample_weight.shape)} on "
+                             f"{sample_weight.device}")
+        sample_weight = sample_weight.detach().float().contiguous()
     if form == "auto":
         K = int(old_cl) if sem_old is None else sem_old.shape[1]
         form = seg_losses_route(labels.shape[-2], labels.shape[-1], sem.shape[2], sem.shape[3], sem.shape[1], K, sem_old is not None,
                                 max(int(old_cl), 1))
-    return _FusedSegLosses.apply(sem, sem_old, labels, old_cl, ce_weight, kd_weight, ignore_index, KD_MODES[kd], float(alpha), form)
+    return _FusedSegLosses.apply(sem, sem_old, labels, old_cl, ce_weight, kd_weight, ignore_index, KD_MODES[kd], float(alpha), form,
+                                 sample_weight)
+
+
+# ---- PLOP's pseudo-labelling (csrc/pseudo_label.hip, DESIGN.md section 3.5.9) ------------------------------------------------------
+def _pseudo_check(sem_old, labels):
+    if sem_old.dim() != 4 or labels.dim() != 3 or labels.shape[0] != sem_old.shape[0] or labels.dtype != torch.int64:
+        raise ValueError(f"teacher logits [B, K, h, w] and int64 labels [B, H, W] are expected, got {tuple(sem_old.shape)} and "
+                         f"{tuple(labels.shape)} {labels.dtype}")
+    if labels.shape[1] < sem_old.shape[2] or labels.shape[2] < sem_old.shape[3]:
+        raise ValueError(f"the label map {tuple(labels.shape[1:])} is smaller than the logits {tuple(sem_old.shape[2:])}")
+
+
+def pseudo_view_torch(sem_old, labels, ignore_index=255):
+    """(candidate mask, pseudo-class c*, uncertainty u) [B, H, W] of the definitions: ``z`` the teacher logits up-sampled to the label
+    size, ``c*`` its first arg-max, ``u = H(softmax z) / log K`` (``H = log S - T / S`` around the maximum, no epsilon; 0 for
+    K = 1), candidates the pixels with ``0 <= label < K`` that are not ``ignore_index``.  fp64 logits stay fp64."""
+    _pseudo_check(sem_old, labels)
+    K = sem_old.shape[1]
+    z = F.interpolate(_wide(sem_old.detach()), size=labels.shape[-2:], mode="bilinear", align_corners=False)
+    m, arg = z.max(dim=1)
+    d = z - m.unsqueeze(1)
+    e = d.exp()
+    S = e.sum(dim=1)
+    u = (S.log() - (d * e).sum(dim=1) / S) / math.log(K) if K > 1 else torch.zeros_like(m)
+    cand = (labels >= 0) & (labels < K) & (labels != ignore_index)
+    return cand, arg, u.clamp(0., 1.)
+
+
+def pseudo_labels_torch(sem_old, labels, thresholds, f_min=0.0, ignore_index=255):
+    """``fused_pseudo_labels`` as a torch composition on the up-sampled ``[B, K, H, W]`` logits: serves CPU tensors and
+    ``UCD_FUSED_PSEUDO=0``."""
+    cand, arg, u = pseudo_view_torch(sem_old, labels, ignore_index)
+    passed = cand & (u < thresholds.to(u.dtype)[arg])
+    out = torch.where(passed, arg, torch.where(cand, torch.full_like(labels, ignore_index), labels))
+    counts = torch.stack((passed.flatten(1).sum(dim=1), cand.flatten(1).sum(dim=1)), dim=1).to(torch.int32)
+    num, den = counts[:, 0].double(), counts[:, 1].double()
+    factor = torch.where(den > 0, num / (den + 1e-6), torch.zeros_like(den)).clamp_min(float(f_min)).float()
+    return out, factor, counts
+
+
+def pseudo_hist_torch(sem_old, labels, hist, ignore_index=255):
+    """``pseudo_hist`` as a torch composition: adds ``bincount(c* bins + bin(u))`` of the candidates into ``hist`` [K, bins] int64."""
+    cand, arg, u = pseudo_view_torch(sem_old, labels, ignore_index)
+    K, bins = hist.shape
+    b = (u * bins).floor().long().clamp_max(bins - 1)
+    hist += torch.bincount((arg * bins + b)[cand], minlength=K * bins).view(K, bins)
+    return hist
+
+
+def _pseudo_rows(sem_old):
+    B, K, h, w = sem_old.shape
+    return sem_old.detach().permute(0, 2, 3, 1).reshape(B * h * w, K).float().contiguous()      # as _LowResLogitLoss.operands
+
+
+def _pseudo_fused(sem_old):
+    return sem_old.is_cuda and _switches.get("UCD_FUSED_PSEUDO", "1") != "0"
+
+
+def fused_pseudo_labels(sem_old, labels, thresholds, f_min=0.0, ignore_index=255, uncertainty=False):
+    """PLOP's pseudo-labels from the LOW-resolution teacher logits ``sem_old`` [B, K, h, w]: ``(labels_out, factor, counts)``.
+    A candidate pixel (``0 <= label < K``, not ``ignore_index``) becomes the teacher's arg-max ``c*`` where the normalised entropy
+    ``u`` of its up-sampled soft-max is below ``thresholds[c*]`` and ``ignore_index`` where not; any other pixel keeps its label.
+    ``counts`` [B, 2] int32 = (passed, candidates) per image, ``factor`` [B] = ``max(passed / (candidates + 1e-6), f_min)``: the
+    weight ``fused_seg_losses(sample_weight=...)`` takes.  ``uncertainty=True`` appends the ``u`` map (0 off the candidates).
+    On the GPU one HIP launch plus the factor launch (ucd_pseudo_label; no [B, K, H, W] tensor); CPU tensors and
+    ``UCD_FUSED_PSEUDO=0`` run ``pseudo_labels_torch``."""
+    _pseudo_check(sem_old, labels)
+    B, K, h, w = sem_old.shape
+    if thresholds.shape != (K,):
+        raise ValueError(f"thresholds must be [{K}], got {tuple(thresholds.shape)}")
+    if not 0.0 <= float(f_min) <= 1.0:          # the library's rule, for the composition too: the factor is a weight in [0, 1]
+        raise ValueError(f"f_min = {f_min} is outside [0, 1]")
+    if not _pseudo_fused(sem_old):
+        res = pseudo_labels_torch(sem_old, labels, thresholds, f_min, ignore_index)
+        if uncertainty:
+            cand, _, u = pseudo_view_torch(sem_old, labels, ignore_index)
+            res += (torch.where(cand, u, torch.zeros_like(u)).float(),)
+        return res
+    H, W = labels.shape[-2:]
+    t, labels = _pseudo_rows(sem_old), labels.contiguous()
+    thr = thresholds.detach().to(device=t.device, dtype=torch.float32).contiguous()
+    out = torch.empty_like(labels)
+    counts = torch.empty(B, 2, dtype=torch.int32, device=t.device)
+    factor = torch.empty(B, dtype=torch.float32, device=t.device)
+    unc = torch.empty(B, H, W, dtype=torch.float32, device=t.device) if uncertainty else None
+    # labels read once and written once, plus the teacher rows
+    with hip._timed("ucd_pseudo_label", B * H * W * 16 + t.numel() * 4):
+        hip._check(hip.load().ucd_pseudo_label(hip.ptr(t), K, hip.ptr(labels), B, H, W, h, w, K, int(ignore_index), hip.ptr(thr),
+                                               float(f_min), hip.ptr(out), hip.ptr(counts), hip.ptr(factor), hip.ptr(unc),
+                                               hip.stream()), "ucd_pseudo_label")
+    return (out, factor, counts, unc) if uncertainty else (out, factor, counts)
+
+
+def pseudo_hist(sem_old, labels, hist, ignore_index=255):
+    """Adds the uncertainty histogram of one batch into ``hist`` [K, bins] int64 (on the device of ``sem_old``): ``hist[c*,
+    min(floor(u bins), bins - 1)] += 1`` over the candidate pixels - what ``pseudo_median`` turns into the per-class thresholds.
+    Integer adds: exact, independent of order.  ucd_pseudo_hist on the GPU, ``pseudo_hist_torch`` on the CPU or under
+    ``UCD_FUSED_PSEUDO=0``."""
+    _pseudo_check(sem_old, labels)
+    B, K, h, w = sem_old.shape
+    if hist.dim() != 2 or hist.shape[0] != K or hist.dtype != torch.int64 or not hist.is_contiguous() or hist.device != sem_old.device:
+        raise ValueError(f"hist must be a contiguous int64 [{K}, bins] on {sem_old.device}, got {tuple(hist.shape)} {hist.dtype}")
+    if not 2 <= hist.shape[1] <= 1024:
+        raise ValueError(f"{hist.shape[1]} bins are outside [2, 1024]")
+    if not _pseudo_fused(sem_old):
+        return pseudo_hist_torch(sem_old, labels, hist, ignore_index)
+    H, W = labels.shape[-2:]
+    t, labels = _pseudo_rows(sem_old), labels.contiguous()
+    with hip._timed("ucd_pseudo_hist", B * H * W * 8 + t.numel() * 4):
+        hip._check(hip.load().ucd_pseudo_hist(hip.ptr(t), K, hip.ptr(labels), B, H, W, h, w, K, int(ignore_index), hist.shape[1],
+                                              hip.ptr(hist), hip.stream()), "ucd_pseudo_hist")
+    return hist
+
+
+def pseudo_median(hist, floor=0.0):
+    """The per-class thresholds [K] (numpy float64) of a histogram [K, bins]: the interpolated median of each row,
+    ``(j + (n / 2 - cum_<j) / hist[j]) / bins`` with ``j`` the first bin whose cumulative count reaches half of the row's ``n``,
+    floored at ``floor``; an empty row gets the floor.  (PLOP's published loop advances its running sum by the bin index; this is
+    the median its paper describes.)"""
+    import numpy as np
+    hist = np.asarray(hist.cpu() if torch.is_tensor(hist) else hist, dtype=np.float64)
+    K, bins = hist.shape
+    out = np.full(K, float(floor), dtype=np.float64)
+    cum = np.cumsum(hist, axis=1)
+    for c in range(K):
+        n = cum[c, -1]
+        if n <= 0:
+            continue
+        half = n / 2.0
+        j = int(np.argmax(cum[c] >= half))
+        out[c] = max((j + (half - (cum[c, j] - hist[c, j])) / hist[c, j]) / bins, float(floor))
+    return out
 
 
 def _wide(x):

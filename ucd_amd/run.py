@@ -285,6 +285,12 @@ def main(opts):
         cur_epoch, best_score = ckpt["epoch"] + 1, ckpt["best_score"]
         if "trainer_state" in ckpt:                                       # run.py:258-259
             trainer.load_state_dict(ckpt["trainer_state"])
+    if trainer.pseudo_flag and not opts.test:
+        if trainer.pseudo_thresholds is None:                             # one pass of the teacher over the training set
+            trainer.find_pseudo_thresholds(train_loader, logger)
+        else:
+            logger.info("Pseudo-label thresholds from the checkpoint: "
+                        + " ".join(f"{t:.4f}" for t in trainer.pseudo_thresholds.tolist()))
     ckpt_path = f"checkpoints/step/{task_name}_{opts.name}_{opts.step}.pth"
     sample_ids = None
     if rank == 0 and opts.sample_num > 0:                                 # run.py:269-273: batches whose first image is kept

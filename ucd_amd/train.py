@@ -38,7 +38,8 @@ import torch.nn as nn
 from . import switches as _switches
 from .contrastive import ucd_contrastive_loss
 from .loss import (KnowledgeDistillationLoss, UnbiasedCrossEntropy, UnbiasedKnowledgeDistillationLoss,
-                   POD_SCALES, fused_attn_mse, fused_local_pod, fused_seg_bce, fused_seg_losses)
+                   POD_SCALES, fused_attn_mse, fused_local_pod, fused_pseudo_labels, fused_seg_bce, fused_seg_losses, pseudo_hist,
+                   pseudo_median)
 
 
 def _raw(features, name):
@@ -90,6 +91,21 @@ class Trainer:
             self.pod_slope = getattr(model, "module", model).pod_slope()
             getattr(model_old, "module", model_old).pod_slope()              # the teacher's maps are undone the same way
             self.pod_gamma = math.sqrt(self.tot_classes / max(self.tot_classes - self.old_classes, 1))
+        # PLOP's pseudo-labelling (--pseudo entropy): the cross entropy sees the labels of ucd_amd.loss.fused_pseudo_labels - a
+        # background pixel takes the teacher's class where the teacher is confident, 255 where not - and, under --pseudo_adaptive,
+        # a per-image weight.  The per-class thresholds come from one pass of the teacher over the training set
+        # (find_pseudo_thresholds) and travel in the trainer state.  KD, POD, the contrastive term and validation keep the labels
+        self.pseudo_flag = getattr(opts, "pseudo", None) is not None and model_old is not None
+        self.pseudo_thresholds = self.pseudo_hist = None
+        if self.pseudo_flag:
+            if self.bce:
+                raise NotImplementedError("--pseudo with --bce / --icarl: the BCE kernel takes no per-image weight")
+            self.pseudo_floor = float(getattr(opts, "pseudo_threshold", 0.001))
+            self.pseudo_bins = int(getattr(opts, "pseudo_nb_bins", 100))
+            self.pseudo_adaptive = bool(getattr(opts, "pseudo_adaptive", False))
+            self.pseudo_f_min = float(getattr(opts, "pseudo_adaptive_min", 0.0))
+            # (trainer_state is the PREVIOUS step's: its thresholds belong to another teacher.  load_state_dict, on a resume of
+            # this step, brings this step's)
         self.lkd = opts.loss_kd
         self.lkd_flag = self.lkd > 0. and model_old is not None
         self.lkd_loss = (UnbiasedKnowledgeDistillationLoss if opts.unkd else KnowledgeDistillationLoss)(alpha=opts.alpha)
@@ -341,6 +357,15 @@ class Trainer:
         if model_old is not None and self._side is not None:
             torch.cuda.current_stream(self.device).wait_stream(self._side)     # teacher outputs are needed from here on
         soft = None
+        labels_ce, factor = labels, None
+        if self.pseudo_flag:
+            if self.pseudo_thresholds is None:
+                raise RuntimeError("--pseudo: no thresholds yet - call Trainer.find_pseudo_thresholds(train_loader) before the first "
+                                   "step (run.py does, unless the loaded trainer state carries them)")
+            labels_ce, factor, pseudo_counts = fused_pseudo_labels(features_old["sem"], labels, self.pseudo_thresholds,
+                                                                   self.pseudo_f_min)
+            if not self.pseudo_adaptive:
+                factor = None
         if self.bce:
             # train.py:112/116 with the BCE criterion, and :119-124: up-sampling + per-class BCE (+ the combined iCaRL term against
             # sigmoid(up(teacher))) + the gradient w.r.t. the low-res logits in one kernel; --unce is ignored (train.py:35-38)
@@ -353,13 +378,16 @@ class Trainer:
                 total = total + kd_total
         elif fuse:
             # one pass over the label map: bilinear up-sampling + CE (+ KD) + gradient w.r.t. the low-res logits
-            total, ce, kd = fused_seg_losses(features["sem"], features_old["sem"] if self.lkd_flag else None, labels,
+            total, ce, kd = fused_seg_losses(features["sem"], features_old["sem"] if self.lkd_flag else None, labels_ce,
                                              self.old_classes if self.unce else 1, 1.0,
                                              self.lkd if self.lkd_flag else 0.0,
                                              kd=self.kd_mode if self.lkd_flag else "unbiased",
-                                             alpha=self.alpha if self.lkd_flag else 1.0)
+                                             alpha=self.alpha if self.lkd_flag else 1.0, sample_weight=factor)
         else:
-            ce = self.criterion(outputs.float() if outputs.dtype != torch.float32 else outputs, labels).mean()
+            ce = self.criterion(outputs.float() if outputs.dtype != torch.float32 else outputs, labels_ce)
+            if factor is not None:
+                ce = ce * factor.view(-1, 1, 1)
+            ce = ce.mean()
         con = zero
         if model_old is not None and self.pixcon_weight != 0:
             con = ucd_contrastive_loss(_raw(features, "pre_logits"), labels, features_old["sem"],
@@ -394,6 +422,9 @@ class Trainer:
             self.last["reg"] = l_reg.detach()
         if self.pod_flag:
             self.last["LPOD"] = lpod.detach()
+        if self.pseudo_flag:
+            kept = pseudo_counts.sum(dim=0).float()
+            self.last["pseudo_kept"] = kept[0] / kept[1].clamp_min(1.0)      # share of the candidates that took a pseudo-label
         if self.icarl_combined:
             self.last["icarl"] = (self.icarl * soft).detach()       # l_icarl of train.py:123; its gradient is part of `total`
         return self.last
@@ -444,6 +475,8 @@ class Trainer:
                 self._check_mailbox()                           # a timed-out SyncBN mailbox exchange (its results are NaN) raises here
                 if logger is not None:
                     logger.info(f"Epoch {cur_epoch}, Batch {cur_step + 1}/{len(train_loader)}, Loss={value}")
+                    if "pseudo_kept" in r and getattr(logger, "debug_flag", False):
+                        logger.debug(f"PSEUDO {r['pseudo_kept'].item()}")      # --debug only: the read synchronises
                     if "LPOD" in r and getattr(logger, "debug_flag", False):
                         # train.py:163, for runs with the Local POD term under --debug only (the reads synchronise); every other
                         # run logs what it always did
@@ -656,9 +689,62 @@ class Trainer:
         losses, score = self._evaluate(loader, metrics, logger, on_batch, lambda i: multi or sink is None, views=views)
         return losses, score, samples
 
+    @torch.no_grad()
+    def find_pseudo_thresholds(self, loader, logger=None):
+        """One pass of the frozen teacher (eval mode) over ``loader``: the per-class histogram of the normalised entropy at the
+        candidate pixels (ucd_amd.loss.pseudo_hist; summed over the ranks with one int64 all-reduce), then the interpolated median
+        of every class, floored at ``--pseudo_threshold`` (ucd_amd.loss.pseudo_median: K x bins numbers on the host, in float64).
+        Stores ``pseudo_hist`` and ``pseudo_thresholds`` (device tensors; both travel in ``state_dict``) and returns the
+        thresholds as a numpy array."""
+        if not self.pseudo_flag:
+            raise RuntimeError("find_pseudo_thresholds needs --pseudo entropy and a teacher")
+        hist = None
+        self.model_old.eval()
+        if self._teacher_w16 is not None:
+            self._teacher_w16.refresh_if_stale()
+        for images, labels in loader:
+            images = images.to(self.device, dtype=torch.float32)
+            labels = labels.to(self.device, dtype=torch.long)
+            if self.device.type == "cuda":
+                images = images.contiguous(memory_format=torch.channels_last)
+            _, feats = self._teacher_eager(images, {"upsample": False} if self.fuse_logit_losses else {})
+            sem = feats["sem"]
+            if hist is None:
+                hist = torch.zeros(sem.shape[1], self.pseudo_bins, dtype=torch.int64, device=self.device)
+            pseudo_hist(sem, labels, hist)
+        if hist is None:
+            raise RuntimeError("find_pseudo_thresholds: the loader is empty")
+        if dist.is_available() and dist.is_initialized():
+            dist.all_reduce(hist)
+        thresholds = pseudo_median(hist, self.pseudo_floor)
+        self._set_pseudo(torch.from_numpy(thresholds), hist)
+        if logger is not None:
+            logger.info(f"Pseudo-label thresholds of the {len(thresholds)} old classes: " + " ".join(f"{t:.4f}" for t in thresholds))
+        return thresholds
+
+    def _load_pseudo(self, state):
+        # (a state of another class split - the previous step's - is not this teacher's)
+        if state is not None and self.pseudo_flag and (not self.old_classes or state["thresholds"].numel() == self.old_classes):
+            self._set_pseudo(state["thresholds"], state["hist"])
+
+    def _set_pseudo(self, thresholds, hist):
+        """New values go INTO the thresholds tensor where one exists: a captured whole-step graph reads it by address."""
+        thresholds = thresholds.to(self.device, dtype=torch.float32)
+        if self.pseudo_thresholds is not None and self.pseudo_thresholds.shape == thresholds.shape:
+            self.pseudo_thresholds.copy_(thresholds)
+        else:
+            if self._sg is not None:
+                raise RuntimeError("the pseudo-label thresholds changed their class count under a captured step graph")
+            self.pseudo_thresholds = thresholds.clone()
+        self.pseudo_hist = hist.to(self.device)
+
     def state_dict(self):
-        return {"regularizer": self.regularizer.state_dict() if self.regularizer_flag else None}
+        state = {"regularizer": self.regularizer.state_dict() if self.regularizer_flag else None}
+        if self.pseudo_thresholds is not None:              # a resumed run does not repeat the pass over the training set
+            state["pseudo"] = {"thresholds": self.pseudo_thresholds.cpu(), "hist": self.pseudo_hist.cpu()}
+        return state
 
     def load_state_dict(self, state):
         if state["regularizer"] is not None and self.regularizer is not None:
             self.regularizer.load_state_dict(state["regularizer"])
+        self._load_pseudo(state.get("pseudo"))
