@@ -334,6 +334,38 @@ int ucd_pod_forward(const void* x_s, int ld_s, const void* x_t, int ld_t, int dt
 int ucd_pod_backward(const void* x_s, int ld_s, int dtype, int B, int C, int h, int w, float slope, const int* scales, int n,
                      const float* g_E, const float* grad_out, void* d_x, int ld_d, ucd_stream_t stream);
 
+/* Local POD on the logits (PLOP's last level, `extra_channels: "sum"`): student rows [B, h, w, Ctot] and teacher rows [B, h, w, K],
+ * 1 <= K <= Ctot <= 256, channels-last fp32 (dtype must be UCD_F32), row pitches in elements, at least the channel count; base
+ * pointers need 4-byte alignment only and the pitches are free (a dense row of 21 logits is 84 bytes).
+ *   M[0] = S[0] + sum_{c >= K} S[c] (the sum first, in ascending c, fp32), M[k] = S[k] for 1 <= k < K; K == Ctot: M = S;
+ *   Q_s = M^2, Q_t = T^2; the pools, E and g_E are those of ucd_pod_forward with C = K and slope 1: n_E = sum_s s^2 K (kh + kw);
+ *   normalize = 1: E^, l_b and g_E as above;  normalize = 0: l_b = |E_s - E_t|, g_E = weight / B * (E_s - E_t) / l_b (0 where
+ *   l_b = 0), each entry divided by its pool's count;  loss_out[0] = mean_b l_b.
+ *   d_x[c] = grad_out[0] * 2 M[k(c)] dQ[k(c)], k(c) = c below K and 0 from K on: channel 0 and every new-class channel of a pixel
+ *   receive the same bits.  d_x is fp32 with its own pitch ld_d >= Ctot.  The backward call takes no normalize: g_E carries it.
+ * Four launches forward (a tile pass of its own, then the three strip kernels of ucd_pod_forward on K-channel strips; normalize = 0
+ * is an arm of the last two), one backward.  Each call picks its load width - 16, 8 or 4 bytes per lane - per map from the base
+ * pointer, the pitch and the channel count it is given; a group of lanes (the power of two that holds a pixel's channels, at most
+ * 64) walks one tile, its load covering one contiguous stretch of a row, and every lane of the group adds the new-class channels
+ * in ascending order from the lanes that loaded them.  Each element of both maps is read once forward; backward reads each
+ * student element once and writes each d_x element once.  Fixed summation order, no atomics: same inputs, same bits.  No
+ * allocation, no host synchronisation: the calls capture into graphs.
+ * The plan is a pure host function: n_E, the forward workspace bytes for B samples and grid[4] = {workgroups of the tile pass per
+ * map for dense 16-byte aligned rows, workgroups per sample of the strip kernels, row pieces, column pieces}; output pointers may
+ * be NULL.
+ * Checked on the host before any device call, the message names the argument: UCD_EINVAL (a NULL pointer; B or K below 1; K above
+ * Ctot; a row pitch below its channel count; n outside 1 .. 4, a scale outside 1 .. 8 or not above the one before, h or w below
+ * the largest scale; normalize neither 0 nor 1), UCD_EUNSUPPORTED (Ctot above 256; a dtype other than UCD_F32; h or w above 1024),
+ * UCD_EALIGN (a pointer that is not 4-byte aligned), UCD_EWORKSPACE (NULL, not 16-byte aligned or short workspace); else the
+ * hipError_t of a failed launch. */
+int ucd_pod_logits_plan(int h, int w, int Ctot, int K, const int* scales, int n, int B, int normalize, int* n_E,
+                        size_t* workspace_bytes, int* grid);
+int ucd_pod_logits_forward(const void* x_s, int ld_s, const void* x_t, int ld_t, int dtype, int B, int Ctot, int K, int h, int w,
+                           const int* scales, int n, int normalize, float weight, float* loss_out, float* g_E, void* workspace,
+                           size_t workspace_bytes, ucd_stream_t stream);
+int ucd_pod_logits_backward(const void* x_s, int ld_s, int dtype, int B, int Ctot, int K, int h, int w, const int* scales, int n,
+                            const float* g_E, const float* grad_out, float* d_x, int ld_d, ucd_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Uncertainty-weighted pixel-contrastive distillation.  Replaces pre_contractive_pixel
  * (utils/utils.py:256-393; twin utils/loss.py:258-395) and PixelConLossV2.forward

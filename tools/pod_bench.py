@@ -1,10 +1,12 @@
 #!/usr/bin/env python
 """Call-level timing of Local POD (``--pod_factor``; csrc/pod.hip) at the levels of the benchmarked step (B = 24, 513^2, bf16):
 forward and backward of ``fused_local_pod`` and of the torch composition ``local_pod_torch`` per level, against the traffic floor
-of a fused level (forward: one read of each map; backward: one read of the student map and one write of its gradient), and - with
-``--step_time`` - the whole UCD step with the term on against off.
+of a fused level (forward: one read of each map; backward: one read of the student map and one write of its gradient), the level
+on the logits (``--pod_logits``: ``fused_local_pod_logits`` against ``local_pod_logits_torch`` at VOC 15-5 and ADE 100-10 class
+counts, both ``normalize`` settings) and - with ``--step_time`` - the whole UCD step with the term off, on, and on with the level
+on the logits.
 
-    python tools/pod_bench.py [--batch 24] [--crop 513] [--iters 10] [--no_torch] [--step_time]
+    python tools/pod_bench.py [--batch 24] [--crop 513] [--iters 10] [--no_torch] [--step_time] [--only features|logits]
 
 Prints one JSON line per measurement.  Times are medians of HIP-event intervals over ``--iters`` calls after three warm-up calls.
 The two maps of the first level (204 MB each at the default shape) exceed the 256 MiB last-level cache together; the other levels
@@ -72,6 +74,35 @@ def call_level(args):
         torch.cuda.empty_cache()
 
 
+LOGIT_SPLITS = (("voc 15-5", 21, 16), ("ade 100-10 step 1", 111, 101))
+
+
+def logits_level(args):
+    """The level on the logits at the stride-16 map of the benchmarked step: fp32 channels-last rows, as the head hands them out."""
+    from ucd_amd.loss import fused_local_pod_logits, local_pod_logits_torch
+    dev = torch.device("cuda:0")
+    s16 = (args.crop - 1) // 16 + 1
+    for name, Ctot, K in LOGIT_SPLITS:
+        g = torch.Generator(device=dev).manual_seed(5)
+        mk = lambda c: torch.randn((args.batch, c, s16, s16), device=dev, generator=g).contiguous(memory_format=torch.channels_last)
+        x_s, x_t = mk(Ctot).requires_grad_(True), mk(K)
+        for normalize in (1, 0):
+            for tag, fn in (("hip", fused_local_pod_logits), ("torch", local_pod_logits_torch)):
+                if tag == "torch" and args.no_torch:
+                    continue
+                fwd = timed(lambda: fn(x_s, x_t, (1, 2, 4), 0.0005, normalize), args.iters)
+                val = fn(x_s, x_t, (1, 2, 4), 0.0005, normalize)
+
+                def bwd():
+                    x_s.grad = None
+                    val.backward(retain_graph=True)
+                t_bwd = timed(bwd, args.iters)
+                print(json.dumps({"level": "logits", "split": name, "shape": [args.batch, Ctot, K, s16, s16], "normalize": normalize,
+                                  "path": tag, "student_MB": round(x_s.numel() * 4 / 1e6, 2), "fwd_ms": round(fwd, 4),
+                                  "bwd_ms": round(t_bwd, 4), "value": val.item()}), flush=True)
+                del val
+
+
 def step_time(args):
     from ucd_amd import argparser, synth, tasks
     from ucd_amd.ddp import DistributedDataParallel
@@ -79,7 +110,7 @@ def step_time(args):
     from ucd_amd.scheduler import PolyLR
     from ucd_amd.train import Trainer
     dev = torch.device("cuda:0")
-    for extra in ((), ("--pod_factor", "0.01")):
+    for tag, extra in (("pod off", ()), ("pod on", ("--pod_factor", "0.01")), ("pod on + logits", ("--pod_factor", "0.01", "--pod_logits"))):
         opts = argparser.modify_command_options(argparser.get_argparser().parse_args(
             ["--method", "UCD", "--task", "15-5", "--dataset", "voc", "--step", "1", "--lr", "0.001", "--batch_size", str(args.batch),
              "--crop_size", str(args.crop), "--no_pretrained", "--opt_level", "O1", "--norm_act", "iabn_sync", *extra]))
@@ -100,7 +131,7 @@ def step_time(args):
         for _ in range(6):                                       # eager warm-up, capture, first replays
             trainer.train_step(images, labels, optim, sched)
         ms = timed(lambda: trainer.train_step(images, labels, optim, sched), args.iters)
-        print(json.dumps({"step": "pod on" if extra else "pod off", "batch": args.batch, "crop": args.crop, "step_ms": round(ms, 3),
+        print(json.dumps({"step": tag, "batch": args.batch, "crop": args.crop, "step_ms": round(ms, 3),
                           "graph_steps": trainer.graph_steps, "graph_error": trainer.step_graph_error,
                           "LPOD": trainer.last["LPOD"].item() if "LPOD" in trainer.last else None}), flush=True)
         del trainer, model, model_old, optim, sched
@@ -113,10 +144,14 @@ def main():
     p.add_argument("--crop", type=int, default=513)
     p.add_argument("--iters", type=int, default=10)
     p.add_argument("--no_torch", action="store_true", help="skip the torch composition")
-    p.add_argument("--step_time", action="store_true", help="also time the whole UCD step with the term on and off")
+    p.add_argument("--step_time", action="store_true", help="also time the whole UCD step with the term off, on, and on with --pod_logits")
+    p.add_argument("--only", choices=["features", "logits"], default=None, help="call-level timing of the feature levels or of the logits only")
     args = p.parse_args()
     assert torch.cuda.is_available(), "pod_bench.py needs a GPU"
-    call_level(args)
+    if args.only != "logits":
+        call_level(args)
+    if args.only != "features":
+        logits_level(args)
     if args.step_time:
         step_time(args)
 

@@ -21,8 +21,9 @@ METHOD_PRESETS = {
     "MiB": {},
     "att": {},
     "UCD": {"loss_kd": 10, "unce": True, "unkd": True, "init_balanced": True},
-    # PLOP (Douillard et al., CVPR 2021) minus its POD on the logits, which is not built: entropy pseudo-labels with the adaptive
-    # factor, Local POD on the features, plain cross entropy, no distillation of the logits, no contrastive term
+    # PLOP (Douillard et al., CVPR 2021): entropy pseudo-labels with the adaptive factor, Local POD on the features, plain cross
+    # entropy, no distillation of the logits, no contrastive term.  The preset leaves PLOP's POD on the logits off; --method PLOP
+    # --pod_logits is the complete method
     "PLOP": {"pseudo": "entropy", "pseudo_adaptive": True, "pod_factor": 0.01, "pod_last_factor": 0.0005, "init_balanced": True,
              "pixcon_weight": 0.0},
 }
@@ -138,6 +139,10 @@ _ARGS = [
     # and the pooling scales (ucd_amd.loss.fused_local_pod)
     _flag("--pod_factor", type=float, default=0.), _flag("--pod_last_factor", type=float, default=0.0005),
     _flag("--pod_scales", type=int, nargs="+", default=[1, 2, 4], action=_PodScales),
+    # PLOP's POD on the logits, next to --pod_factor: the logits become a sixth level (factor --pod_last_factor, the student's
+    # new-class channels summed into the background; ucd_amd.loss.fused_local_pod_logits) and the head output an ordinary one
+    # (factor --pod_factor); --pod_logits_norm 0: that level's embeddings are not normalised
+    _flag("--pod_logits", **_ON), _flag("--pod_logits_norm", type=int, default=1, choices=[0, 1]),
     # PLOP's pseudo-labelling (ucd_amd.loss.fused_pseudo_labels): background pixels take the teacher's class where the entropy of
     # its soft-max, as a fraction of log K, is below the class's median over the training set (floored at --pseudo_threshold;
     # histogram of --pseudo_nb_bins bins); --pseudo_adaptive weighs an image's cross entropy by its share of kept candidates

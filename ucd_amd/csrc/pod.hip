@@ -19,6 +19,9 @@
 //
 // Every sum has a fixed order (a thread over its elements, a wave by shuffles, a block over its waves, per-block partials in index
 // order); the strip sums are fp32, the norms and dot products fp64.  No atomics: same inputs, same bits.
+//
+// The level on the logits (PLOP's last one: Ctot student against K teacher channels, fp32 rows of any pitch) has a tile pass and a
+// backward pass of its own further down and shares the geometry and the three strip kernels.
 #include "common.h"
 
 namespace ucd {
@@ -62,8 +65,9 @@ int pod_cut(int dim, int piece, const int* s, const int* k, int n, short* cut, s
   return np;
 }
 
-// Validates the geometry and fills g.  Pure host code.
-int pod_geom(const char* fn, int h, int w, int C, const int* scales, int n, PodGeom* g) {
+// Validates the geometry and fills g.  Pure host code.  cmult, cmax: the channel counts the caller's tile and backward kernels
+// take (the strip kernels take any)
+int pod_geom(const char* fn, int h, int w, int C, const int* scales, int n, PodGeom* g, int cmult = 8, int cmax = 8192) {
   UCD_REQUIRE(scales, UCD_EINVAL, "%s: NULL scales", fn);
   UCD_REQUIRE(n >= 1 && n <= kPodMaxScales, UCD_EINVAL, "%s: %d scales (1 to %d are taken)", fn, n, kPodMaxScales);
   for (int q = 0; q < n; ++q) {
@@ -74,8 +78,8 @@ int pod_geom(const char* fn, int h, int w, int C, const int* scales, int n, PodG
   UCD_REQUIRE(C >= 1, UCD_EINVAL, "%s: C = %d must be at least 1", fn, C);
   UCD_REQUIRE(h >= scales[n - 1] && w >= scales[n - 1], UCD_EINVAL, "%s: a %d x %d map is smaller than the largest scale %d", fn, h, w,
               scales[n - 1]);
-  UCD_REQUIRE(C % 8 == 0, UCD_EUNSUPPORTED, "%s: C = %d is not a multiple of 8 (a lane moves 16 bytes of channels)", fn, C);
-  UCD_REQUIRE(C <= 8192, UCD_EUNSUPPORTED, "%s: C = %d is above 8192", fn, C);
+  UCD_REQUIRE(C % cmult == 0, UCD_EUNSUPPORTED, "%s: C = %d is not a multiple of %d (a lane moves 16 bytes of channels)", fn, C, cmult);
+  UCD_REQUIRE(C <= cmax, UCD_EUNSUPPORTED, "%s: C = %d is above %d", fn, C, cmax);
   UCD_REQUIRE(h <= kPodMaxDim && w <= kPodMaxDim, UCD_EUNSUPPORTED, "%s: a %d x %d map is above %d rows or columns", fn, h, w, kPodMaxDim);
   memset(g, 0, sizeof(*g));
   g->h = h, g->w = w, g->C = C, g->n = n;
@@ -94,23 +98,35 @@ int pod_geom(const char* fn, int h, int w, int C, const int* scales, int n, PodG
   return UCD_OK;
 }
 
-inline int pod_chunks(int n_E) {
-  const int c = ceil_div(n_E, kPodChunkElems);
+// Workgroups per sample of the strip kernels.  lanes: the threads that take one unit (C channels of a pool entry) in the pool and
+// coef kernels - the whole workgroup for the feature maps; for the few channels of the logits the power of two that holds them,
+// and then enough workgroups that each takes its kPodBlock / lanes units in one trip
+inline int pod_chunks(const PodGeom& g, int lanes = kPodBlock) {
+  int c = ceil_div(g.n_E, kPodChunkElems);
+  if (lanes < kPodBlock) {
+    const int u = ceil_div(g.n_E / g.C, kPodBlock / lanes);
+    c = u > c ? u : c;
+  }
   return c < kPodMaxChunks ? c : kPodMaxChunks;
+}
+inline int pod_logits_lanes(int K) {
+  int lanes = kPodBlock;
+  while (lanes / 2 >= K) lanes /= 2;
+  return lanes;
 }
 
 // workspace: rowseg [2][B][h][ncs][C], colseg [2][B][nrs][w][C], E [2][B][n_E] floats; partN, partD [2][B][chunks] doubles
 struct PodWs {
   size_t rowseg, colseg, E, partN, partD, bytes;
 };
-PodWs pod_ws(const PodGeom& g, int B) {
+PodWs pod_ws(const PodGeom& g, int B, int lanes = kPodBlock) {
   PodWs o;
   size_t off = 0;
   o.rowseg = off, off += align_up((size_t)2 * B * g.h * g.ncs * g.C * sizeof(float), 16);
   o.colseg = off, off += align_up((size_t)2 * B * g.nrs * g.w * g.C * sizeof(float), 16);
   o.E = off, off += align_up((size_t)2 * B * g.n_E * sizeof(float), 16);
-  o.partN = off, off += (size_t)2 * B * pod_chunks(g.n_E) * sizeof(double);
-  o.partD = off, off += (size_t)2 * B * pod_chunks(g.n_E) * sizeof(double);
+  o.partN = off, off += (size_t)2 * B * pod_chunks(g, lanes) * sizeof(double);
+  o.partD = off, off += (size_t)2 * B * pod_chunks(g, lanes) * sizeof(double);
   o.bytes = off;
   return o;
 }
@@ -244,7 +260,7 @@ __device__ __forceinline__ double pod_partial_sum(const double* part, int chunks
 }
 
 // pool: tile partials -> E (one division per entry), per-block partials of |E|^2.  grid (chunks, B, 2)
-__global__ __launch_bounds__(kPodBlock) void pod_pool_kernel(const PodGeom geom, int B, const float* __restrict__ rowseg,
+__global__ __launch_bounds__(kPodBlock) void pod_pool_kernel(const PodGeom geom, int B, int lanes, const float* __restrict__ rowseg,
                                                             const float* __restrict__ colseg, float* __restrict__ E,
                                                             double* __restrict__ partN) {
   __shared__ PodGeom g;
@@ -253,8 +269,10 @@ __global__ __launch_bounds__(kPodBlock) void pod_pool_kernel(const PodGeom geom,
   const int b = blockIdx.y, net = blockIdx.z, chunks = gridDim.x;
   const size_t nb = (size_t)net * B + b;
   double acc = 0.0;
-  // a workgroup takes whole units (the C channels of one pool entry): the decode is uniform, the lanes run over channels
-  for (int un = blockIdx.x; un < g.n_E / g.C; un += chunks) {
+  // a workgroup takes whole units (the C channels of one pool entry): the decode is uniform, the lanes run over channels.  With few
+  // channels (the logits) `lanes` threads take a unit and the workgroup kPodBlock / lanes units at a time
+  const int nsub = kPodBlock / lanes, lane = threadIdx.x % lanes;
+  for (int un = blockIdx.x * nsub + threadIdx.x / lanes; un < g.n_E / g.C; un += chunks * nsub) {
     const PodUnit u = pod_unit(g, un);
     const float* p;
     size_t pitch;
@@ -267,7 +285,7 @@ __global__ __launch_bounds__(kPodBlock) void pod_pool_kernel(const PodGeom geom,
       p = colseg + (nb * g.nrs * g.w + u.a) * g.C, pitch = (size_t)g.w * g.C;
       q0 = g.rfirst[u.k][u.b], q1 = g.rfirst[u.k][u.b + 1], count = (float)g.kh[u.k];
     }
-    for (int c = threadIdx.x; c < g.C; c += kPodBlock) {
+    for (int c = lane; c < g.C; c += lanes) {
       float sum = 0.f;
       for (int q = q0; q < q1; ++q) sum += p[q * pitch + c];
       const float val = sum / count;
@@ -281,13 +299,14 @@ __global__ __launch_bounds__(kPodBlock) void pod_pool_kernel(const PodGeom geom,
 
 __device__ __forceinline__ float pod_inv_norm(double sumsq) { return (float)(1.0 / fmax(sqrt(sumsq), 1e-12)); }
 
-// diff: per-block partials of |E^_s - E^_t|^2 and E^_s . (E^_s - E^_t).  grid (chunks, B)
-__global__ __launch_bounds__(kPodBlock) void pod_diff_kernel(int n_E, int B, const float* __restrict__ E, const double* __restrict__ partN,
-                                                            double* __restrict__ partD) {
+// diff: per-block partials of |E^_s - E^_t|^2 and E^_s . (E^_s - E^_t).  grid (chunks, B).  normalize = 0 (the level on the logits
+// only): E^ = E, the norms are not read
+__global__ __launch_bounds__(kPodBlock) void pod_diff_kernel(int n_E, int B, int normalize, const float* __restrict__ E,
+                                                            const double* __restrict__ partN, double* __restrict__ partD) {
   __shared__ double red[4];
   const int b = blockIdx.y, chunks = gridDim.x;
-  const float inv_s = pod_inv_norm(pod_partial_sum(partN + (size_t)b * chunks, chunks, red));
-  const float inv_t = pod_inv_norm(pod_partial_sum(partN + ((size_t)B + b) * chunks, chunks, red));
+  const float inv_s = normalize ? pod_inv_norm(pod_partial_sum(partN + (size_t)b * chunks, chunks, red)) : 1.f;
+  const float inv_t = normalize ? pod_inv_norm(pod_partial_sum(partN + ((size_t)B + b) * chunks, chunks, red)) : 1.f;
   const float* Es = E + (size_t)b * n_E;
   const float* Et = E + ((size_t)B + b) * n_E;
   double a1 = 0.0, a2 = 0.0;
@@ -304,28 +323,31 @@ __global__ __launch_bounds__(kPodBlock) void pod_diff_kernel(int n_E, int B, con
   }
 }
 
-// coef: g_E (already divided by the pool's count) and, by block (0, 0), the level value.  grid (chunks, B)
-__global__ __launch_bounds__(kPodBlock) void pod_coef_kernel(const PodGeom geom, int B, float weight, const float* __restrict__ E,
-                                                            const double* __restrict__ partN, const double* __restrict__ partD,
-                                                            float* __restrict__ gE, float* __restrict__ loss_out) {
+// coef: g_E (already divided by the pool's count) and, by block (0, 0), the level value.  grid (chunks, B).  normalize = 0:
+// g_E = weight / B * (E_s - E_t) / l_b - the projection term and the division by |E_s| drop out
+__global__ __launch_bounds__(kPodBlock) void pod_coef_kernel(const PodGeom geom, int B, int normalize, int lanes, float weight,
+                                                            const float* __restrict__ E, const double* __restrict__ partN,
+                                                            const double* __restrict__ partD, float* __restrict__ gE,
+                                                            float* __restrict__ loss_out) {
   __shared__ PodGeom g;
   __shared__ double red[4];
   pod_stage(&g, geom);
   const int b = blockIdx.y, chunks = gridDim.x;
-  const double nn_s = pod_partial_sum(partN + (size_t)b * chunks, chunks, red);
-  const float inv_s = pod_inv_norm(nn_s);
-  const float inv_t = pod_inv_norm(pod_partial_sum(partN + ((size_t)B + b) * chunks, chunks, red));
+  const double nn_s = normalize ? pod_partial_sum(partN + (size_t)b * chunks, chunks, red) : 1.0;
+  const float inv_s = normalize ? pod_inv_norm(nn_s) : 1.f;
+  const float inv_t = normalize ? pod_inv_norm(pod_partial_sum(partN + ((size_t)B + b) * chunks, chunks, red)) : 1.f;
   const double l = sqrt(pod_partial_sum(partD + (size_t)b * chunks, chunks, red));
   const double dot = pod_partial_sum(partD + ((size_t)B + b) * chunks, chunks, red);
   const bool zero = !(l > 0.0);
-  const float inv_l = zero ? 0.f : (float)(1.0 / l), kappa = zero ? 0.f : (float)(dot / l);
+  const float inv_l = zero ? 0.f : (float)(1.0 / l), kappa = zero || !normalize ? 0.f : (float)(dot / l);
   const float wn = (float)((double)weight / B / fmax(sqrt(nn_s), 1e-12));
   const float* Es = E + (size_t)b * g.n_E;
   const float* Et = E + ((size_t)B + b) * g.n_E;
-  for (int un = blockIdx.x; un < g.n_E / g.C; un += chunks) {           // whole units, as in the pool kernel
+  const int nsub = kPodBlock / lanes, lane = threadIdx.x % lanes;
+  for (int un = blockIdx.x * nsub + threadIdx.x / lanes; un < g.n_E / g.C; un += chunks * nsub) {      // whole units, as in the pool kernel
     const PodUnit u = pod_unit(g, un);
     const float count = (float)(u.col ? g.kh[u.k] : g.kw[u.k]);
-    for (int c = threadIdx.x; c < g.C; c += kPodBlock) {
+    for (int c = lane; c < g.C; c += lanes) {
       const size_t e = (size_t)un * g.C + c;
       const float es = Es[e] * inv_s, et = Et[e] * inv_t, d = es - et;
       const float ge = zero ? 0.f : wn * (d * inv_l - kappa * es);
@@ -399,11 +421,325 @@ __global__ __launch_bounds__(kPodBlock) void pod_bwd_kernel(const T* __restrict_
   }
 }
 
+// ---- the level on the logits --------------------------------------------------------------------------------------------------
+// Student rows [h, w, Ctot], teacher rows [h, w, K], fp32, any 4-byte aligned base and pitch.  M[0] = S[0] + sum_{c >= K} S[c] (the
+// sum first, in ascending c, then the addition), M[k] = S[k]; Q = M^2 against T^2, slope 1, strips of K channels.
+// Lanes.  A pixel's channels are cut into slots of VEC consecutive floats (VEC = 4, 2 or 1: the widest that the base pointer, the
+// pitch and the channel count of THAT map allow, chosen per call); slot v lies on lane v % G of a group of G lanes (the power of
+// two that holds the slots, at most 64) as its chunk v / G, so a group's load instruction covers one contiguous stretch of the
+// row and a wave holds 64 / G tiles.  A group walks one tile, as a thread of the feature kernels does.  The new-class sum is taken
+// from the lanes that loaded the channels: every lane of the group adds the same values in the same order (one cross-lane read
+// per value), nobody loads a second time and the result is on lane 0 (and everywhere else) without a reduction tree, whose order
+// would not be the ascending one.
+constexpr int kPodLogitsMaxC = 256;
+constexpr int kPodSlotFloats = kPodLogitsMaxC / 64;        // floats of a pixel that a lane holds
+
+inline int podl_vec(const void* p, int ld, int C) {
+  for (int v = 4; v > 1; v >>= 1)
+    if (reinterpret_cast<uintptr_t>(p) % (4u * v) == 0 && ld % v == 0 && C % v == 0) return v;
+  return 1;
+}
+inline int podl_vec2(const void* p, int ld, const void* q, int ldq, int C) {
+  const int a = podl_vec(p, ld, C), b = podl_vec(q, ldq, C);
+  return a < b ? a : b;
+}
+inline int podl_group(int C, int vec) {
+  int G = 1;
+  while (G < C / vec && G < 64) G *= 2;
+  return G;
+}
+inline long long podl_items(const PodGeom& g, int B, int G) { return (long long)B * g.nrs * g.ncs * G; }
+
+struct PodlTile {
+  int b, r0, nr, x0, x1, rs, cs, j;
+  bool live;
+};
+__device__ __forceinline__ PodlTile podl_tile(const PodGeom& g, int B, int G) {
+  PodlTile t;
+  long long item = ((long long)blockIdx.x * kPodBlock + threadIdx.x) / G;      // G divides the block: a group never straddles two
+  t.j = threadIdx.x & (G - 1);
+  t.live = item < (long long)B * g.nrs * g.ncs;
+  if (!t.live) item = 0;
+  t.cs = (int)(item % g.ncs);
+  item /= g.ncs;
+  t.rs = (int)(item % g.nrs);
+  t.b = (int)(item / g.nrs);
+  t.r0 = g.rcut[t.rs], t.nr = g.rcut[t.rs + 1] - t.r0;
+  t.x0 = g.ccut[t.cs], t.x1 = g.ccut[t.cs + 1];
+  return t;
+}
+
+// register i * VEC + q of a lane holds channel (i * G + j) * VEC + q
+template <int VEC>
+__device__ __forceinline__ int podl_channel(int reg, int j, int G) {
+  return ((reg / VEC) * G + j) * VEC + reg % VEC;
+}
+
+// the C channels of the pixel at p (C is a multiple of VEC: a slot is inside the row or outside)
+template <int VEC>
+__device__ __forceinline__ void podl_load(float (&v)[kPodSlotFloats], const float* __restrict__ p, int j, int G, int C) {
+#pragma unroll
+  for (int i = 0; i < kPodSlotFloats / VEC; ++i) {
+    const int c = (i * G + j) * VEC;
+    if (c < C) {
+      if (VEC == 4) {
+        const float4 q = *reinterpret_cast<const float4*>(p + c);
+        v[0] = q.x, v[1] = q.y, v[2] = q.z, v[3] = q.w;
+      } else if (VEC == 2) {
+        const float2 q = *reinterpret_cast<const float2*>(p + c);
+        v[i * 2] = q.x, v[i * 2 + 1] = q.y;
+      } else {
+        v[i] = p[c];
+      }
+    } else {
+#pragma unroll
+      for (int q = 0; q < VEC; ++q) v[i * VEC + q] = 0.f;
+    }
+  }
+}
+template <int VEC>
+__device__ __forceinline__ void podl_store(float* __restrict__ p, const float (&v)[kPodSlotFloats], int j, int G, int C) {
+#pragma unroll
+  for (int i = 0; i < kPodSlotFloats / VEC; ++i) {
+    const int c = (i * G + j) * VEC;
+    if (c < C) {
+      if (VEC == 4)
+        *reinterpret_cast<float4*>(p + c) = make_float4(v[0], v[1], v[2], v[3]);
+      else if (VEC == 2)
+        *reinterpret_cast<float2*>(p + c) = make_float2(v[i * 2], v[i * 2 + 1]);
+      else
+        p[c] = v[i];
+    }
+  }
+}
+
+// e[rr] = sum over c in [K, C) of the row's channel c, in ascending c, on every lane of the group.  The trip counts depend on
+// (K, C, G) alone: uniform over the wave, and every lane of a live group takes part (rows outside the tile hold zeros).
+template <int VEC>
+__device__ __forceinline__ void podl_extra(const float (&v)[kPodRows][kPodSlotFloats], float (&e)[kPodRows], int G, int K, int C) {
+#pragma unroll
+  for (int rr = 0; rr < kPodRows; ++rr) e[rr] = 0.f;
+#pragma unroll
+  for (int i = 0; i < kPodSlotFloats / VEC; ++i) {
+    const int lo = K / VEC - i * G, hi = C / VEC - i * G;
+    for (int jj = lo > 0 ? lo : 0; jj < (hi < G ? hi : G); ++jj) {
+#pragma unroll
+      for (int q = 0; q < VEC; ++q) {
+        const bool take = (i * G + jj) * VEC + q >= K;
+#pragma unroll
+        for (int rr = 0; rr < kPodRows; ++rr) {
+          const float s = __shfl(v[rr][i * VEC + q], jj, G);
+          if (take) e[rr] += s;
+        }
+      }
+    }
+  }
+}
+
+// One map of the tile pass.  C: the map's channels (Ctot or K); the strips hold g.C = K of them.
+template <int VEC, bool STUDENT>
+__device__ __forceinline__ void podl_tile_pass(const PodGeom& g, const float* __restrict__ x, size_t ld, int C, int G, int B, size_t net,
+                                               float* __restrict__ rowseg, float* __restrict__ colseg) {
+  const PodlTile t = podl_tile(g, B, G);
+  if (!t.live) return;
+  const int K = g.C;
+  const float* base = x + ((size_t)t.b * g.h + t.r0) * g.w * ld;
+  const size_t nb = net * B + t.b;
+  float* crow = colseg + ((nb * g.nrs + t.rs) * g.w) * K;
+  float racc[kPodRows][kPodSlotFloats];
+#pragma unroll
+  for (int rr = 0; rr < kPodRows; ++rr)
+#pragma unroll
+    for (int q = 0; q < kPodSlotFloats; ++q) racc[rr][q] = 0.f;
+  for (int xx = t.x0; xx < t.x1; ++xx) {
+    float v[kPodRows][kPodSlotFloats];
+#pragma unroll
+    for (int rr = 0; rr < kPodRows; ++rr)
+      podl_load<VEC>(v[rr], base + ((size_t)rr * g.w + xx) * ld, t.j, G, rr < t.nr ? C : 0);
+    if (STUDENT && K < C) {
+      float e[kPodRows];
+      podl_extra<VEC>(v, e, G, K, C);
+      if (t.j == 0) {
+#pragma unroll
+        for (int rr = 0; rr < kPodRows; ++rr) v[rr][0] += e[rr];
+      }
+    }
+    float csum[kPodSlotFloats];
+#pragma unroll
+    for (int q = 0; q < kPodSlotFloats; ++q) csum[q] = 0.f;
+#pragma unroll
+    for (int rr = 0; rr < kPodRows; ++rr)
+      if (rr < t.nr) {
+#pragma unroll
+        for (int q = 0; q < kPodSlotFloats; ++q) {
+          const float sq = v[rr][q] * v[rr][q];
+          racc[rr][q] += sq;
+          csum[q] += sq;
+        }
+      }
+    // the strips are 4-byte aligned only (K is free): one float per store, the lanes of a group over consecutive channels
+#pragma unroll
+    for (int q = 0; q < kPodSlotFloats; ++q) {
+      const int c = podl_channel<VEC>(q, t.j, G);
+      if (c < K) crow[(size_t)xx * K + c] = csum[q];
+    }
+  }
+#pragma unroll
+  for (int rr = 0; rr < kPodRows; ++rr)
+    if (rr < t.nr) {
+      float* rrow = rowseg + ((nb * g.h + t.r0 + rr) * g.ncs + t.cs) * K;
+#pragma unroll
+      for (int q = 0; q < kPodSlotFloats; ++q) {
+        const int c = podl_channel<VEC>(q, t.j, G);
+        if (c < K) rrow[c] = racc[rr][q];
+      }
+    }
+}
+
+struct PodlMap {
+  const float* x;
+  int ld, C, vec, G;
+};
+
+// The tile pass on the logits: blockIdx.y = 0 the student rows (Ctot channels, merged), 1 the teacher rows (K channels)
+__global__ __launch_bounds__(kPodBlock) void pod_logits_tile_kernel(const PodlMap ms, const PodlMap mt, int B, const PodGeom geom,
+                                                                   float* __restrict__ rowseg, float* __restrict__ colseg) {
+  __shared__ PodGeom g;
+  pod_stage(&g, geom);
+  if (blockIdx.y == 0) {
+    if (ms.vec == 4)
+      podl_tile_pass<4, true>(g, ms.x, ms.ld, ms.C, ms.G, B, 0, rowseg, colseg);
+    else if (ms.vec == 2)
+      podl_tile_pass<2, true>(g, ms.x, ms.ld, ms.C, ms.G, B, 0, rowseg, colseg);
+    else
+      podl_tile_pass<1, true>(g, ms.x, ms.ld, ms.C, ms.G, B, 0, rowseg, colseg);
+  } else {
+    if (mt.vec == 4)
+      podl_tile_pass<4, false>(g, mt.x, mt.ld, mt.C, mt.G, B, 1, rowseg, colseg);
+    else if (mt.vec == 2)
+      podl_tile_pass<2, false>(g, mt.x, mt.ld, mt.C, mt.G, B, 1, rowseg, colseg);
+    else
+      podl_tile_pass<1, false>(g, mt.x, mt.ld, mt.C, mt.G, B, 1, rowseg, colseg);
+  }
+}
+
+// The backward pass on the logits: dS[c] = grad_out * 2 M[k(c)] dQ[k(c)], k(c) = c below K and 0 from K on - lane 0 of the group
+// forms the value of channel 0 and the lanes of the new-class channels copy its bits
+template <int VEC>
+__global__ __launch_bounds__(kPodBlock) void pod_logits_bwd_kernel(const float* __restrict__ x, int ldx, int C, int G, int B,
+                                                                  const PodGeom geom, const float* __restrict__ gE,
+                                                                  const float* __restrict__ grad_out, float* __restrict__ dx, int ldd) {
+  __shared__ PodGeom g;
+  pod_stage(&g, geom);
+  const PodlTile t = podl_tile(g, B, G);
+  if (!t.live) return;
+  const int K = g.C;
+  const float go = grad_out[0];
+  const float* gb = gE + (size_t)t.b * g.n_E;
+  bool cover[kPodMaxScales];
+  int ri[kPodMaxScales], cj[kPodMaxScales];
+#pragma unroll
+  for (int k = 0; k < kPodMaxScales; ++k) {
+    cover[k] = k < g.n && t.r0 < g.s[k] * g.kh[k] && t.x0 < g.s[k] * g.kw[k];
+    ri[k] = cover[k] ? t.r0 / g.kh[k] : 0;
+    cj[k] = cover[k] ? t.x0 / g.kw[k] : 0;
+  }
+  int ch[kPodSlotFloats];
+#pragma unroll
+  for (int q = 0; q < kPodSlotFloats; ++q) ch[q] = podl_channel<VEC>(q, t.j, G);
+  float rco[kPodRows][kPodSlotFloats];
+#pragma unroll
+  for (int rr = 0; rr < kPodRows; ++rr) {
+#pragma unroll
+    for (int q = 0; q < kPodSlotFloats; ++q) rco[rr][q] = 0.f;
+    if (rr < t.nr) {
+#pragma unroll
+      for (int k = 0; k < kPodMaxScales; ++k)
+        if (cover[k]) {
+          const float* p = gb + g.rowoff[k] + ((size_t)(t.r0 + rr) * g.s[k] + cj[k]) * K;
+#pragma unroll
+          for (int q = 0; q < kPodSlotFloats; ++q)
+            if (ch[q] < K) rco[rr][q] += p[ch[q]];
+        }
+    }
+  }
+  const float* xbase = x + ((size_t)t.b * g.h + t.r0) * g.w * (size_t)ldx;
+  float* dbase = dx + ((size_t)t.b * g.h + t.r0) * g.w * (size_t)ldd;
+  for (int xx = t.x0; xx < t.x1; ++xx) {
+    float v[kPodRows][kPodSlotFloats];
+#pragma unroll
+    for (int rr = 0; rr < kPodRows; ++rr)
+      podl_load<VEC>(v[rr], xbase + ((size_t)rr * g.w + xx) * ldx, t.j, G, rr < t.nr ? C : 0);
+    if (K < C) {
+      float e[kPodRows];
+      podl_extra<VEC>(v, e, G, K, C);
+      if (t.j == 0) {
+#pragma unroll
+        for (int rr = 0; rr < kPodRows; ++rr) v[rr][0] += e[rr];
+      }
+    }
+    float cco[kPodSlotFloats];
+#pragma unroll
+    for (int q = 0; q < kPodSlotFloats; ++q) cco[q] = 0.f;
+#pragma unroll
+    for (int k = 0; k < kPodMaxScales; ++k)
+      if (cover[k]) {
+        const float* p = gb + g.coloff[k] + ((size_t)xx * g.s[k] + ri[k]) * K;
+#pragma unroll
+        for (int q = 0; q < kPodSlotFloats; ++q)
+          if (ch[q] < K) cco[q] += p[ch[q]];
+      }
+#pragma unroll
+    for (int rr = 0; rr < kPodRows; ++rr) {
+      float o[kPodSlotFloats];
+#pragma unroll
+      for (int q = 0; q < kPodSlotFloats; ++q) {
+        const float f = 2.f * v[rr][q];
+        o[q] = go * f * (rco[rr][q] + cco[q]);
+      }
+      const float d0 = __shfl(o[0], 0, G);                  // every lane of the group, whatever its row count: group-uniform
+#pragma unroll
+      for (int q = 0; q < kPodSlotFloats; ++q)
+        if (ch[q] >= K) o[q] = d0;
+      if (rr < t.nr) podl_store<VEC>(dbase + ((size_t)rr * g.w + xx) * ldd, o, t.j, G, C);
+    }
+  }
+}
+
+// The argument rules that the three calls on the logits share; fills g with the geometry of the K-channel strips
+int podl_args(const char* fn, int h, int w, int Ctot, int K, const int* scales, int n, int B, PodGeom* g) {
+  UCD_REQUIRE(B >= 1, UCD_EINVAL, "%s: B = %d must be at least 1", fn, B);
+  UCD_REQUIRE(K >= 1, UCD_EINVAL, "%s: K = %d must be at least 1", fn, K);
+  UCD_REQUIRE(K <= Ctot, UCD_EINVAL, "%s: K = %d is above Ctot = %d", fn, K, Ctot);
+  UCD_REQUIRE(Ctot <= kPodLogitsMaxC, UCD_EUNSUPPORTED, "%s: Ctot = %d is above %d", fn, Ctot, kPodLogitsMaxC);
+  return pod_geom(fn, h, w, K, scales, n, g, 1, kPodLogitsMaxC);
+}
+int podl_check_rows(const char* fn, const char* what, const void* p, int ld, int C, const char* cname) {
+  UCD_REQUIRE(ld >= C, UCD_EINVAL, "%s: the row pitch of %s (%d) is below %s = %d", fn, what, ld, cname, C);
+  UCD_REQUIRE(reinterpret_cast<uintptr_t>(p) % 4 == 0, UCD_EALIGN, "%s: %s must be 4-byte aligned", fn, what);
+  return UCD_OK;
+}
+
 int pod_check_map(const char* fn, const char* what, const void* p, int ld, int C, int es) {
   UCD_REQUIRE(ld >= C, UCD_EINVAL, "%s: the row pitch of %s (%d) is below C = %d", fn, what, ld, C);
   UCD_REQUIRE(aligned16(p) && ((size_t)ld * es) % 16 == 0, UCD_EALIGN, "%s: %s must be 16-byte aligned with a 16-byte multiple row pitch", fn,
               what);
   return UCD_OK;
+}
+
+// The three strip launches behind a tile pass: pool, diff, coef
+int pod_strips(const char* fn, const PodGeom& g, int B, int normalize, int lanes, float weight, char* wsp, const PodWs& ws, float* loss_out,
+               float* g_E, hipStream_t s) {
+  float *rowseg = (float*)(wsp + ws.rowseg), *colseg = (float*)(wsp + ws.colseg), *E = (float*)(wsp + ws.E);
+  double *partN = (double*)(wsp + ws.partN), *partD = (double*)(wsp + ws.partD);
+  const int chunks = pod_chunks(g, lanes);
+  int rc;
+  pod_pool_kernel<<<dim3(chunks, B, 2), kPodBlock, 0, s>>>(g, B, lanes, rowseg, colseg, E, partN);
+  if ((rc = check_launch(fn))) return rc;
+  pod_diff_kernel<<<dim3(chunks, B), kPodBlock, 0, s>>>(g.n_E, B, normalize, E, partN, partD);
+  if ((rc = check_launch(fn))) return rc;
+  pod_coef_kernel<<<dim3(chunks, B), kPodBlock, 0, s>>>(g, B, normalize, lanes, weight, E, partN, partD, g_E, loss_out);
+  return check_launch(fn);
 }
 
 }  // namespace
@@ -426,7 +762,7 @@ int ucd_pod_plan(int h, int w, int C, const int* scales, int n, int B, int dtype
   if (workspace_bytes) *workspace_bytes = pod_ws(g, B).bytes;
   if (grid) {
     grid[0] = (int)((items + kPodBlock - 1) / kPodBlock);     // workgroups of the tile pass (per map) and of the backward pass
-    grid[1] = pod_chunks(g.n_E);                              // workgroups per sample of the three strip kernels
+    grid[1] = pod_chunks(g);                                  // workgroups per sample of the three strip kernels
     grid[2] = g.nrs;                                          // row pieces
     grid[3] = g.ncs;                                          // column pieces
   }
@@ -455,22 +791,16 @@ int ucd_pod_forward(const void* x_s, int ld_s, const void* x_t, int ld_t, int dt
   UCD_REQUIRE(workspace && aligned16(workspace) && workspace_bytes >= ws.bytes, UCD_EWORKSPACE, "%s: workspace missing, unaligned or too small", fn);
   hipStream_t s = (hipStream_t)stream;
   char* wsp = (char*)workspace;
-  float *rowseg = (float*)(wsp + ws.rowseg), *colseg = (float*)(wsp + ws.colseg), *E = (float*)(wsp + ws.E);
-  double *partN = (double*)(wsp + ws.partN), *partD = (double*)(wsp + ws.partD);
+  float *rowseg = (float*)(wsp + ws.rowseg), *colseg = (float*)(wsp + ws.colseg);
   const float inv_a = (float)(1.0 / (double)slope);
-  const int blocks = (int)((items + kPodBlock - 1) / kPodBlock), chunks = pod_chunks(g.n_E);
+  const int blocks = (int)((items + kPodBlock - 1) / kPodBlock);
   if (dtype == UCD_BF16)
     pod_tile_kernel<__hip_bfloat16><<<dim3(blocks, 2), kPodBlock, 0, s>>>((const __hip_bfloat16*)x_s, ld_s, (const __hip_bfloat16*)x_t, ld_t,
                                                                          inv_a, B, g, rowseg, colseg);
   else
     pod_tile_kernel<float><<<dim3(blocks, 2), kPodBlock, 0, s>>>((const float*)x_s, ld_s, (const float*)x_t, ld_t, inv_a, B, g, rowseg, colseg);
   if ((rc = check_launch(fn))) return rc;
-  pod_pool_kernel<<<dim3(chunks, B, 2), kPodBlock, 0, s>>>(g, B, rowseg, colseg, E, partN);
-  if ((rc = check_launch(fn))) return rc;
-  pod_diff_kernel<<<dim3(chunks, B), kPodBlock, 0, s>>>(g.n_E, B, E, partN, partD);
-  if ((rc = check_launch(fn))) return rc;
-  pod_coef_kernel<<<dim3(chunks, B), kPodBlock, 0, s>>>(g, B, weight, E, partN, partD, g_E, loss_out);
-  return check_launch(fn);
+  return pod_strips(fn, g, B, 1, kPodBlock, weight, wsp, ws, loss_out, g_E, s);
 }
 
 int ucd_pod_backward(const void* x_s, int ld_s, int dtype, int B, int C, int h, int w, float slope, const int* scales, int n,
@@ -497,6 +827,83 @@ int ucd_pod_backward(const void* x_s, int ld_s, int dtype, int B, int C, int h, 
                                                                (__hip_bfloat16*)d_x, ld_d);
   else
     pod_bwd_kernel<float><<<blocks, kPodBlock, 0, s>>>((const float*)x_s, ld_s, inv_a, B, g, g_E, grad_out, (float*)d_x, ld_d);
+  return check_launch(fn);
+}
+
+int ucd_pod_logits_plan(int h, int w, int Ctot, int K, const int* scales, int n, int B, int normalize, int* n_E, size_t* workspace_bytes,
+                        int* grid) {
+  static const char* fn = "ucd_pod_logits_plan";
+  UCD_REQUIRE(normalize == 0 || normalize == 1, UCD_EINVAL, "%s: normalize = %d is neither 0 nor 1", fn, normalize);
+  PodGeom g;
+  const int rc = podl_args(fn, h, w, Ctot, K, scales, n, B, &g);
+  if (rc) return rc;
+  if (n_E) *n_E = g.n_E;
+  if (workspace_bytes) *workspace_bytes = pod_ws(g, B, pod_logits_lanes(K)).bytes;
+  if (grid) {
+    // with dense 16-byte aligned rows; the calls choose the vector width from the pointers and pitches they get
+    const int Gs = podl_group(Ctot, podl_vec(nullptr, Ctot, Ctot)), Gt = podl_group(K, podl_vec(nullptr, K, K));
+    grid[0] = (int)((podl_items(g, B, Gs > Gt ? Gs : Gt) + kPodBlock - 1) / kPodBlock);
+    grid[1] = pod_chunks(g, pod_logits_lanes(K));
+    grid[2] = g.nrs;
+    grid[3] = g.ncs;
+  }
+  return UCD_OK;
+}
+
+int ucd_pod_logits_forward(const void* x_s, int ld_s, const void* x_t, int ld_t, int dtype, int B, int Ctot, int K, int h, int w,
+                           const int* scales, int n, int normalize, float weight, float* loss_out, float* g_E, void* workspace,
+                           size_t workspace_bytes, ucd_stream_t stream) {
+  static const char* fn = "ucd_pod_logits_forward";
+  UCD_REQUIRE(x_s && x_t && loss_out && g_E, UCD_EINVAL, "%s: NULL argument (x_s, x_t, loss_out and g_E are required)", fn);
+  UCD_REQUIRE(dtype == UCD_F32, UCD_EUNSUPPORTED, "%s: dtype %d (the logits are fp32 rows, UCD_F32)", fn, dtype);
+  UCD_REQUIRE(normalize == 0 || normalize == 1, UCD_EINVAL, "%s: normalize = %d is neither 0 nor 1", fn, normalize);
+  PodGeom g;
+  int rc = podl_args(fn, h, w, Ctot, K, scales, n, B, &g);
+  if (rc) return rc;
+  if ((rc = podl_check_rows(fn, "x_s", x_s, ld_s, Ctot, "Ctot"))) return rc;
+  if ((rc = podl_check_rows(fn, "x_t", x_t, ld_t, K, "K"))) return rc;
+  UCD_REQUIRE(reinterpret_cast<uintptr_t>(g_E) % 4 == 0 && reinterpret_cast<uintptr_t>(loss_out) % 4 == 0, UCD_EALIGN,
+              "%s: g_E and loss_out must be 4-byte aligned", fn);
+  UCD_REQUIRE(B <= 65535, UCD_EUNSUPPORTED, "%s: B = %d is more than a grid holds", fn, B);
+  const int lanes = pod_logits_lanes(K);
+  const PodWs ws = pod_ws(g, B, lanes);
+  UCD_REQUIRE(workspace && aligned16(workspace) && workspace_bytes >= ws.bytes, UCD_EWORKSPACE, "%s: workspace missing, unaligned or too small", fn);
+  PodlMap ms = {(const float*)x_s, ld_s, Ctot, podl_vec(x_s, ld_s, Ctot), 0};
+  PodlMap mt = {(const float*)x_t, ld_t, K, podl_vec(x_t, ld_t, K), 0};
+  ms.G = podl_group(ms.C, ms.vec), mt.G = podl_group(mt.C, mt.vec);
+  // at most 65535 samples x kPodMaxCuts^2 tiles x 64 lanes: fewer workgroups than a grid holds
+  const long long items = podl_items(g, B, ms.G > mt.G ? ms.G : mt.G);
+  hipStream_t s = (hipStream_t)stream;
+  char* wsp = (char*)workspace;
+  pod_logits_tile_kernel<<<dim3((unsigned)((items + kPodBlock - 1) / kPodBlock), 2), kPodBlock, 0, s>>>(
+      ms, mt, B, g, (float*)(wsp + ws.rowseg), (float*)(wsp + ws.colseg));
+  if ((rc = check_launch(fn))) return rc;
+  return pod_strips(fn, g, B, normalize, lanes, weight, wsp, ws, loss_out, g_E, s);
+}
+
+int ucd_pod_logits_backward(const void* x_s, int ld_s, int dtype, int B, int Ctot, int K, int h, int w, const int* scales, int n,
+                            const float* g_E, const float* grad_out, float* d_x, int ld_d, ucd_stream_t stream) {
+  static const char* fn = "ucd_pod_logits_backward";
+  UCD_REQUIRE(x_s && g_E && grad_out && d_x, UCD_EINVAL, "%s: NULL argument (x_s, g_E, grad_out and d_x are required)", fn);
+  UCD_REQUIRE(dtype == UCD_F32, UCD_EUNSUPPORTED, "%s: dtype %d (the logits are fp32 rows, UCD_F32)", fn, dtype);
+  PodGeom g;
+  int rc = podl_args(fn, h, w, Ctot, K, scales, n, B, &g);
+  if (rc) return rc;
+  if ((rc = podl_check_rows(fn, "x_s", x_s, ld_s, Ctot, "Ctot"))) return rc;
+  if ((rc = podl_check_rows(fn, "d_x", d_x, ld_d, Ctot, "Ctot"))) return rc;
+  UCD_REQUIRE(reinterpret_cast<uintptr_t>(g_E) % 4 == 0 && reinterpret_cast<uintptr_t>(grad_out) % 4 == 0, UCD_EALIGN,
+              "%s: g_E and grad_out must be 4-byte aligned", fn);
+  const int vec = podl_vec2(x_s, ld_s, d_x, ld_d, Ctot), G = podl_group(Ctot, vec);
+  const unsigned blocks = (unsigned)((podl_items(g, B, G) + kPodBlock - 1) / kPodBlock);
+  UCD_REQUIRE(podl_items(g, B, G) / kPodBlock < 0x7FFFFFFF, UCD_EUNSUPPORTED, "%s: B = %d is more than a grid holds", fn, B);
+  hipStream_t s = (hipStream_t)stream;
+  const float* x = (const float*)x_s;
+  if (vec == 4)
+    pod_logits_bwd_kernel<4><<<blocks, kPodBlock, 0, s>>>(x, ld_s, Ctot, G, B, g, g_E, grad_out, d_x, ld_d);
+  else if (vec == 2)
+    pod_logits_bwd_kernel<2><<<blocks, kPodBlock, 0, s>>>(x, ld_s, Ctot, G, B, g, g_E, grad_out, d_x, ld_d);
+  else
+    pod_logits_bwd_kernel<1><<<blocks, kPodBlock, 0, s>>>(x, ld_s, Ctot, G, B, g, g_E, grad_out, d_x, ld_d);
   return check_launch(fn);
 }
 

@@ -138,6 +138,9 @@ SIGNATURES = {
     "ucd_pod_plan": (_i, [_i, _i, _i, _p, _i, _i, _i, _p, _p, _p]),
     "ucd_pod_forward": (_i, [_p, _i, _p, _i, _i, _i, _i, _i, _i, _f, _p, _i, _f, _p, _p, _p, _z, _p]),
     "ucd_pod_backward": (_i, [_p, _i, _i, _i, _i, _i, _i, _f, _p, _i, _p, _p, _p, _i, _p]),
+    "ucd_pod_logits_plan": (_i, [_i, _i, _i, _i, _p, _i, _i, _i, _p, _p, _p]),
+    "ucd_pod_logits_forward": (_i, [_p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _p, _i, _i, _f, _p, _p, _p, _z, _p]),
+    "ucd_pod_logits_backward": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _p, _i, _p, _p, _p, _i, _p]),
     "ucd_conv1x1_row_tiles": (_i, [_i]),
     "ucd_conv1x1_stats_partial_bytes": (_z, [_i, _i]),
     "ucd_conv1x1": (_i, [C.POINTER(Conv1x1Desc), _p]),
@@ -656,6 +659,17 @@ def pod_plan(h, w, Cc, scales=(1, 2, 4), B=1, dtype=BF16):
     n_E, nbytes, grid = C.c_int(0), C.c_size_t(0), (C.c_int * 4)()
     _check(load().ucd_pod_plan(int(h), int(w), int(Cc), C.cast(arr, C.c_void_p), n, int(B), int(dtype), C.cast(C.byref(n_E), C.c_void_p),
                                C.cast(C.byref(nbytes), C.c_void_p), C.cast(grid, C.c_void_p)), "ucd_pod_plan")
+    return {"n_E": n_E.value, "workspace_bytes": nbytes.value, "grid": tuple(grid)}
+
+
+def pod_logits_plan(h, w, Ctot, K, scales=(1, 2, 4), B=1, normalize=1):
+    """``ucd_pod_logits_plan``: ``{"n_E", "workspace_bytes", "grid"}`` of the Local POD level on the logits (``Ctot`` student and
+    ``K`` teacher channels), as ``pod_plan`` gives them; ``grid[0]`` holds for dense 16-byte aligned rows.  A pure host function."""
+    arr, n = pod_scales(scales)
+    n_E, nbytes, grid = C.c_int(0), C.c_size_t(0), (C.c_int * 4)()
+    _check(load().ucd_pod_logits_plan(int(h), int(w), int(Ctot), int(K), C.cast(arr, C.c_void_p), n, int(B), int(normalize),
+                                      C.cast(C.byref(n_E), C.c_void_p), C.cast(C.byref(nbytes), C.c_void_p), C.cast(grid, C.c_void_p)),
+           "ucd_pod_logits_plan")
     return {"n_E": n_E.value, "workspace_bytes": nbytes.value, "grid": tuple(grid)}
 
 

@@ -278,6 +278,112 @@ def fused_local_pod(x_s, x_t, slope=1.0, scales=POD_SCALES, weight=1.0):
     return _FusedLocalPOD.apply(x_s, x_t, float(slope), scales, float(weight))
 
 
+def _pod_logits_check(sem_s, sem_t, scales, normalize):
+    """The argument rules of the Local POD level on the logits; returns (scales, normalize as 0 / 1)."""
+    if sem_s.dim() != 4 or sem_t.dim() != 4 or sem_s.shape[0] != sem_t.shape[0] or sem_s.shape[2:] != sem_t.shape[2:] \
+            or not 1 <= sem_t.shape[1] <= sem_s.shape[1]:
+        raise ValueError(f"student and teacher logits must be [B, Ctot, h, w] and [B, K, h, w] with 1 <= K <= Ctot: "
+                         f"{tuple(sem_s.shape)} vs {tuple(sem_t.shape)}")
+    if normalize not in (0, 1, False, True):
+        raise ValueError(f"normalize must be 0 or 1, got {normalize!r}")
+    # the scale rules are those of every level
+    return _pod_check(sem_s, sem_s, 1.0, scales), int(normalize)
+
+
+def local_pod_logits_torch(sem_s, sem_t, scales=POD_SCALES, weight=1.0, normalize=1):
+    """``weight`` times the Local POD distance on the logits (PLOP's last level, ``extra_channels: "sum"``) as a differentiable
+    torch composition: the student's channels from ``K`` on are summed into its background channel, then the level is
+    ``local_pod_torch`` at slope 1 on ``K`` channels; ``normalize=0`` leaves the embeddings un-normalised.  The teacher is
+    detached.  fp64 logits stay fp64.  Serves CPU devices, shapes the kernels refuse and ``UCD_FUSED_POD=0``."""
+    scales, normalize = _pod_logits_check(sem_s, sem_t, scales, normalize)
+    K = sem_t.shape[1]
+    m = _wide(sem_s)
+    if K < m.shape[1]:
+        m = torch.cat([m[:, :1] + m[:, K:].sum(dim=1, keepdim=True), m[:, 1:K]], dim=1)
+    e_s = _pod_embed(m, 1.0, scales)
+    e_t = _pod_embed(sem_t.detach().to(m.dtype), 1.0, scales)
+    if normalize:
+        e_s = e_s / e_s.norm(dim=1, keepdim=True).clamp_min(1e-12)
+        e_t = e_t / e_t.norm(dim=1, keepdim=True).clamp_min(1e-12)
+    return weight * (e_s - e_t).norm(dim=1).mean()
+
+
+@functools.lru_cache(maxsize=None)
+def _pod_logits_plan(h, w, Ctot, K, scales, B, normalize):
+    return hip.pod_logits_plan(h, w, Ctot, K, scales, B, normalize)
+
+
+def _logit_rows(x):
+    """[B, C, h, w] logits -> (tensor, pitch): fp32 channels-last rows with a constant pitch.  A tensor whose strides already say
+    so (a channels_last tensor or a channel slice of one - the kernels ask for 4-byte alignment only) is taken as it is."""
+    B, Cc, h, w = x.shape
+    if x.dtype == torch.float32 and Cc > 1 and w > 1 and h > 1:
+        sb, sc, sh, sw = x.stride()
+        if sc == 1 and sw >= Cc and sh == w * sw and sb == h * w * sw:
+            return x, sw
+    return x.float().permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2), Cc
+
+
+class _FusedLocalPODLogits(torch.autograd.Function):
+    """weight * Local POD on the logits on the HIP kernels (ucd_pod_logits_forward / ucd_pod_logits_backward, csrc/pod.hip): four
+    launches forward, which keep the coefficient strips ``g_E`` ([B, n_E] fp32 on K channels), one backward, which reads the
+    student rows once more and writes ``d sem`` (fp32 rows, cast to the logits' dtype where that differs)."""
+
+    @staticmethod
+    def forward(ctx, sem_s, sem_t, scales, weight, normalize):
+        lib = hip.load()
+        xs, ld_s = _logit_rows(sem_s.detach())
+        xt, ld_t = _logit_rows(sem_t.detach())
+        B, Ctot, h, w = xs.shape
+        K = xt.shape[1]
+        plan = _pod_logits_plan(h, w, Ctot, K, scales, B, normalize)
+        arr, n = hip.pod_scales(scales)
+        g = torch.empty(B, plan["n_E"], dtype=torch.float32, device=xs.device)
+        out = torch.empty(1, dtype=torch.float32, device=xs.device)
+        nbytes = plan["workspace_bytes"]
+        ws = hip.workspace(nbytes, xs.device, "pod")
+        with hip._timed("ucd_pod_logits_forward", B * h * w * (Ctot + K) * 4):
+            hip._check(lib.ucd_pod_logits_forward(hip.ptr(xs), ld_s, hip.ptr(xt), ld_t, hip.F32, B, Ctot, K, h, w,
+                                                  hip.C.cast(arr, hip.C.c_void_p), n, normalize, float(weight), hip.ptr(out),
+                                                  hip.ptr(g), hip.ptr(ws), nbytes, hip.stream()), "ucd_pod_logits_forward")
+        ctx.save_for_backward(xs, g)
+        ctx.meta = (ld_s, K, scales, sem_s.dtype)
+        return weight * out[0]
+
+    @staticmethod
+    def backward(ctx, grad):
+        xs, g = ctx.saved_tensors
+        ld_s, K, scales, dtype = ctx.meta
+        B, Ctot, h, w = xs.shape
+        arr, n = hip.pod_scales(scales)
+        go = grad.detach().reshape(1).to(torch.float32).contiguous()
+        d = torch.empty((B, h, w, Ctot), dtype=torch.float32, device=xs.device).permute(0, 3, 1, 2)
+        with hip._timed("ucd_pod_logits_backward", 2 * B * h * w * Ctot * 4):
+            hip._check(hip.load().ucd_pod_logits_backward(hip.ptr(xs), ld_s, hip.F32, B, Ctot, K, h, w,
+                                                          hip.C.cast(arr, hip.C.c_void_p), n, hip.ptr(g), hip.ptr(go), hip.ptr(d), Ctot,
+                                                          hip.stream()), "ucd_pod_logits_backward")
+        return (d if dtype == torch.float32 else d.to(dtype)), None, None, None, None
+
+
+def pod_logits_kernels_take(sem_s):
+    """Do the kernels of the level on the logits serve these student logits?  bf16 or fp32 on a GPU, at most 256 channels, at most
+    1024 rows and columns (ucd_pod_logits_plan states the same bounds)."""
+    return (sem_s.is_cuda and sem_s.dtype in (torch.bfloat16, torch.float32) and sem_s.shape[1] <= 256
+            and max(sem_s.shape[2:]) <= 1024)
+
+
+def fused_local_pod_logits(sem_s, sem_t, scales=POD_SCALES, weight=1.0, normalize=1):
+    """``weight * mean_b |E(M)_b - E(sem_t)_b|``: PLOP's Local POD on the logits between the student's ``[B, Ctot, h, w]`` and the
+    teacher's ``[B, K, h, w]``, ``M`` the student's logits with the channels from ``K`` on summed into the background channel;
+    the embeddings L2-normalised per sample unless ``normalize=0``; differentiable w.r.t. ``sem_s``.  On the GPU it is four HIP
+    launches forward and one backward (csrc/pod.hip); CPU tensors, logits the kernels refuse (``pod_logits_kernels_take``) and
+    ``UCD_FUSED_POD=0`` run ``local_pod_logits_torch``."""
+    scales, normalize = _pod_logits_check(sem_s, sem_t, scales, normalize)
+    if not pod_logits_kernels_take(sem_s) or _switches.get("UCD_FUSED_POD", "1") == "0":
+        return local_pod_logits_torch(sem_s, sem_t, scales, weight, normalize)
+    return _FusedLocalPODLogits.apply(sem_s, sem_t, scales, float(weight), normalize)
+
+
 KD_MODES = {"unbiased": hip.KD_UNBIASED, "plain": hip.KD_PLAIN}
 
 

@@ -33,7 +33,7 @@ DEFAULTS = {
     "UCD_SEG_PK": "1",             # fused logit losses: packed math, fp64 LDS accumulators (0: the round-3 register form; read by the library)
     "UCD_SEG_KD_EX": "1",          # fused logit losses for every pair of {plain, unbiased} CE x {none, plain, unbiased} KD and any --alpha (ucd_seg_losses_ex); 0: only (any CE) or (unbiased CE + unbiased KD at alpha 1) fused, the rest on the torch modules
     "UCD_FUSED_LDE": "1",          # ILT's encoder term (--loss_de) as one HIP operation on the raw maps (ucd_attn_mse), ILT inside the teacher / whole-step graphs; 0: attention maps + MSELoss in torch, ILT eager
-    "UCD_FUSED_POD": "1",          # Local POD feature distillation (--pod_factor) on csrc/pod.hip: one trip over each tapped map forward, one read + one write backward (0: the torch composition local_pod_torch)
+    "UCD_FUSED_POD": "1",          # Local POD feature distillation (--pod_factor) on csrc/pod.hip: one trip over each tapped map forward, one read + one write backward; with --pod_logits also the level on the logits (0: the torch compositions local_pod_torch / local_pod_logits_torch)
     "UCD_FUSED_PSEUDO": "1",       # PLOP's pseudo-labelling (--pseudo entropy) on csrc/pseudo_label.hip: labels, per-image factor and the threshold histogram from the low-resolution teacher rows, one launch each (0: the torch composition pseudo_labels_torch / pseudo_hist_torch on the up-sampled [B, K, H, W] logits)
     "UCD_VAL_DEVICE": "1",         # validation transforms (Resize + CenterCrop, full size) as ucd_val_image_path / ucd_val_label_path on raw samples (0: Pillow on the host per sample + the train path with the identity box; torch launches for the full image)
     "UCD_STEM_EVAL_FUSED": "1",    # frozen-statistics stem (the teacher): conv1 + norm + activation + max pool as one kernel (0: two kernels)

@@ -38,8 +38,8 @@ import torch.nn as nn
 from . import switches as _switches
 from .contrastive import ucd_contrastive_loss
 from .loss import (KnowledgeDistillationLoss, UnbiasedCrossEntropy, UnbiasedKnowledgeDistillationLoss,
-                   POD_SCALES, fused_attn_mse, fused_local_pod, fused_pseudo_labels, fused_seg_bce, fused_seg_losses, pseudo_hist,
-                   pseudo_median)
+                   POD_SCALES, fused_attn_mse, fused_local_pod, fused_local_pod_logits, fused_pseudo_labels, fused_seg_bce,
+                   fused_seg_losses, pseudo_hist, pseudo_median)
 
 
 def _raw(features, name):
@@ -91,6 +91,10 @@ class Trainer:
             self.pod_slope = getattr(model, "module", model).pod_slope()
             getattr(model_old, "module", model_old).pod_slope()              # the teacher's maps are undone the same way
             self.pod_gamma = math.sqrt(self.tot_classes / max(self.tot_classes - self.old_classes, 1))
+        # PLOP's POD on the logits (--pod_logits, next to --pod_factor): a sixth level on features["sem"], the student's new-class
+        # channels summed into the background (ucd_amd.loss.fused_local_pod_logits); alone it requests nothing
+        self.pod_logits = self.pod_flag and bool(getattr(opts, "pod_logits", False))
+        self.pod_logits_norm = int(getattr(opts, "pod_logits_norm", 1))
         # PLOP's pseudo-labelling (--pseudo entropy): the cross entropy sees the labels of ucd_amd.loss.fused_pseudo_labels - a
         # background pixel takes the teacher's class where the teacher is confident, 255 where not - and, under --pseudo_adaptive,
         # a per-image weight.  The per-class thresholds come from one pass of the teacher over the training set
@@ -432,14 +436,22 @@ class Trainer:
     def _local_pod(self, features, features_old):
         """L_pod = gamma / L * sum_l f_l * level_l over the L = 5 levels: the four stage maps (factor pod_factor, the slope of the
         block activation) and the raw pre-logits (pod_last_factor, slope 1).  The weight of a level goes into its call, so the sum
-        needs no further launches of that size; a level with factor 0 is skipped."""
+        needs no further launches of that size; a level with factor 0 is skipped.  Under --pod_logits L = 6: the pre-logits become
+        an ordinary level (pod_factor) and the logits, the student's new-class channels summed into the background, are the last
+        one (pod_last_factor, normalised unless --pod_logits_norm 0); its gradient adds into features["sem"] next to the loss
+        kernel's, in autograd."""
         levels = [(s, t, self.pod_slope, self.pod) for s, t in zip(features.stages, features_old.stages)]
-        levels.append((_raw(features, "pre_logits"), _raw(features_old, "pre_logits"), 1.0, self.pod_last))
+        levels.append((_raw(features, "pre_logits"), _raw(features_old, "pre_logits"), 1.0, self.pod if self.pod_logits else self.pod_last))
+        L = len(levels) + int(self.pod_logits)
         lpod = None
         for x_s, x_t, slope, factor in levels:
             if factor == 0.:
                 continue
-            term = fused_local_pod(x_s, x_t, slope, self.pod_scales, self.pod_gamma * factor / len(levels))
+            term = fused_local_pod(x_s, x_t, slope, self.pod_scales, self.pod_gamma * factor / L)
+            lpod = term if lpod is None else lpod + term
+        if self.pod_logits and self.pod_last != 0.:
+            term = fused_local_pod_logits(features["sem"], features_old["sem"], self.pod_scales, self.pod_gamma * self.pod_last / L,
+                                          self.pod_logits_norm)
             lpod = term if lpod is None else lpod + term
         return lpod
 
