@@ -641,6 +641,40 @@ int ucd_seg_losses_gather_w(const float* sem_s, int ld_s, const float* sem_t, in
                             float* loss_out /*[2]*/, float* d_sem /* NULL: losses only */, int ld_d,
                             void* workspace, size_t workspace_bytes, ucd_stream_t stream);
 
+/* The same two calls with FOCAL modulation of the cross entropy (the reference's FocalLoss, utils/loss.py:6-28; DESIGN.md
+ * section 3.5.10).  Write ce_p >= 0 for pixel p's cross entropy as the calls above define it (plain, or unbiased through ce_old_cl;
+ * 0 for an ignored pixel) and w_b for ce_sample_weight[b] (NULL: 1):
+ *   p   = exp(-ce_p),   u = clamp(1 - p, 0, 1)
+ *   F_p = focal_alpha u^focal_gamma ce_p
+ *   loss_out[0] = 1 / (B H W) sum_b w_b sum_p F_p          (ignored pixels count as 0: the reference's focal_loss.mean())
+ *   dF_p/dz = focal_alpha g(ce_p) dce_p/dz,   g = u^gamma + gamma u^(gamma-1) p ce_p
+ * so a pixel's coefficient on the cross-entropy gradient is multiplied by focal_alpha g(ce_p); nothing else in the gradient
+ * arithmetic changes and the distillation term is untouched.
+ * Zero rule.  Where u rounds to 0 (ce_p below about 6e-8, an ignored pixel, or the negative "cross entropy" LSE(z) of a label
+ * >= Ctot, which the clamp catches) F_p = 0 and g = 0 for gamma > 0; for gamma == 0, F_p = focal_alpha ce_p and g = 1.
+ * 0^(gamma-1) ce is never formed: the power is taken of max(u, 2^-24), the smallest u that is not 0, and the zero case is selected.
+ * focal_gamma == 2 runs without exp2 / log; any other value goes through exp2(gamma log2 u).
+ * Bound for the fixed-point forms.  ln(1/p) <= 1/p - 1 gives p ce <= 1 - p = u, so gamma u^(gamma-1) p ce <= gamma u^gamma <= gamma
+ * and g <= 1 + gamma for every gamma >= 0 (u <= 1).  A focal call therefore scales its gradient words with
+ *   gmax = (focal_alpha (1 + focal_gamma) |ce_weight| + 2 |kd_weight| / K) / (B H W);
+ * the quantum q = gmax / 2^17, the 2^29 < 2^31 argument and the error statement of ucd_seg_losses follow from it unchanged.
+ * Additional UCD_EINVAL, checked on the host before anything else, the message names the argument: focal_gamma negative, NaN or
+ * infinite; focal_alpha zero, negative, NaN or infinite.  focal_gamma == 0 with focal_alpha == 1 is the call without focal
+ * (_ex / _ex_w, _gather / _gather_w): same kernel, same bits.  ce_sample_weight may be NULL, and a weight of ones gives the bits of
+ * NULL.  The focal kernels are template instantiations of their own (all tiled forms and the gather form), as the weighted ones
+ * are: the calls above keep their code, registers and bits.  Plan, workspace, errors and every other argument: as the call
+ * without focal. */
+int ucd_seg_losses_focal(const float* sem_s, int ld_s, const float* sem_t, int ld_t, const int64_t* labels,
+                         int B, int H, int W, int h, int w, int Ctot, int K, int ce_old_cl, int kd_mode, float alpha,
+                         int ignore_index, float ce_weight, float kd_weight, const float* ce_sample_weight /*[B], NULL = 1*/,
+                         float focal_gamma, float focal_alpha, float* loss_out, float* d_sem, int ld_d, void* workspace,
+                         size_t workspace_bytes, ucd_stream_t stream);
+int ucd_seg_losses_gather_focal(const float* sem_s, int ld_s, const float* sem_t, int ld_t, const int64_t* labels,
+                                int B, int H, int W, int h, int w, int Ctot, int K, int ce_old_cl, int kd_mode, float alpha,
+                                int ignore_index, float ce_weight, float kd_weight, const float* ce_sample_weight /*[B], NULL = 1*/,
+                                float focal_gamma, float focal_alpha, float* loss_out /*[2]*/, float* d_sem /* NULL: losses only */,
+                                int ld_d, void* workspace, size_t workspace_bytes, ucd_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * PLOP's pseudo-labelling (csrc/pseudo_label.hip).  sem_t [B*h*w, ld_t >= K] fp32: the frozen teacher's
  * low-resolution logits as rows (as ucd_seg_losses takes them), labels int64 [B, H, W].  With z = up(sem_t)[b, :, y, x] (up:

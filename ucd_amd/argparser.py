@@ -6,6 +6,7 @@ autocast with fp32 master weights) instead of an apex mode."""
 from __future__ import annotations
 
 import argparse
+import math
 
 from . import tasks
 
@@ -40,6 +41,9 @@ def modify_command_options(opts):
     if getattr(opts, "pseudo", None) is not None and (opts.bce or opts.icarl):
         raise ValueError("--pseudo cannot be combined with --bce / --icarl / --method LWF-MC: the pseudo-labels carry a per-image "
                          "weight on the cross entropy, which the BCE kernel does not take and PLOP does not define for it")
+    if getattr(opts, "focal_loss", False) and (opts.bce or opts.icarl):
+        raise ValueError("--focal_loss cannot be combined with --bce / --icarl / --method LWF-MC: the reference defines the focal "
+                         "modulation on the soft-max cross entropy only")
     opts.no_overlap = not opts.overlap
     opts.no_cross_val = not opts.cross_val
     return opts
@@ -73,6 +77,22 @@ def _unit_interval(text):
     value = float(text)
     if not 0.0 <= value <= 1.0:
         raise argparse.ArgumentTypeError(f"the value must be in [0, 1], got {text}")
+    return value
+
+
+def _focal_gamma(text):
+    """--focal_loss_gamma: the exponent of the focal modulation, finite and >= 0"""
+    value = float(text)
+    if not (math.isfinite(value) and value >= 0.0):
+        raise argparse.ArgumentTypeError(f"gamma must be finite and >= 0, got {text}")
+    return value
+
+
+def _focal_alpha(text):
+    """--focal_loss_alpha: the factor of the focal loss, finite and > 0"""
+    value = float(text)
+    if not (math.isfinite(value) and value > 0.0):
+        raise argparse.ArgumentTypeError(f"alpha must be finite and > 0, got {text}")
     return value
 
 
@@ -149,6 +169,11 @@ _ARGS = [
     _flag("--pseudo", type=str, default=None, choices=["entropy"]), _flag("--pseudo_threshold", type=float, default=0.001),
     _flag("--pseudo_nb_bins", type=_pseudo_bins, default=100), _flag("--pseudo_adaptive", **_ON),
     _flag("--pseudo_adaptive_min", type=_unit_interval, default=0.0),
+    # focal cross entropy (the reference's FocalLoss): the criterion of the train step and of validation becomes
+    # alpha (1 - p_t)^gamma CE, inside the fused logit-loss kernels (ucd_amd.loss.fused_seg_losses(focal=...)); with --unce the
+    # unbiased cross entropy is modulated, under --pseudo_adaptive the image's weight multiplies it
+    _flag("--focal_loss", **_ON), _flag("--focal_loss_gamma", type=_focal_gamma, default=2.0),
+    _flag("--focal_loss_alpha", type=_focal_alpha, default=1.0),
     # regularisers (EWC / RW / PI; --method EWC|RW|PI): ucd_amd.regularizer, after the UCD step
     _flag("--regularizer", default=None, type=str, choices=["ewc", "rw", "pi"]),
     _flag("--reg_importance", type=float, default=1.), _flag("--reg_alpha", type=float, default=0.9),

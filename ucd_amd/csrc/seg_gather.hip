@@ -120,17 +120,18 @@ __device__ __forceinline__ float uniform(float v) { return __int_as_float(__buil
 
 // part: [B * h * w][2] (ce sum, kd sum) of the pixels whose (y0, x0) cell this is; d_sem (may be NULL): the cell's row
 // SW: image walk.b weighs its cross entropy with ce_sw[walk.b] (ucd_seg_losses_gather_w; a cell lies in one image)
-template <int NR, bool SW>
+template <int NR, bool SW, bool FO>
 __global__ __launch_bounds__(kWave) void seg_losses_gather_kernel(
     const float* __restrict__ sem_s, int ld_s, const float* __restrict__ sem_t, int ld_t, const int64_t* __restrict__ labels,
     int H, int W, int h, int w, int Ctot, int K, int ignore_index, float scale_h, float scale_w, float inv_scale_h,
     float inv_scale_w, float ce_scale, float kd_scale, float* __restrict__ part, float* __restrict__ d_sem, int ld_d, int kce,
-    int kd_plain, float alpha, const float* __restrict__ ce_sw) {
+    int kd_plain, float alpha, const float* __restrict__ ce_sw, float fo_gamma, float fo_alpha) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   constexpr float kNegBig = -1e30f;
   const int cell = blockIdx.x, lane = threadIdx.x;
   const CellWalk walk(cell, H, W, h, w, scale_h, scale_w, inv_scale_h, inv_scale_w);
-  const float sw = SW ? ce_sw[walk.b] : 1.f;
+  // FO (ucd_seg_losses_gather_focal) is built with SW and takes a NULL weight as ones
+  const float sw = SW ? ((FO && !ce_sw) ? 1.f : ce_sw[walk.b]) : 1.f;
   // the 3 x 3 cells around (i, j): [9][Ctot] student, [9][K] teacher logits times alpha (the up-sampling is linear); dense rows
   float* s_log = smem;
   float* t_log = smem + 9 * Ctot;
@@ -222,7 +223,19 @@ __global__ __launch_bounds__(kWave) void seg_losses_gather_kernel(
         inv_old = 0.f; inv_bn = 0.f;                 // the subset terms of the gradient come from r_o / r_b below
       }
       const bool lab0 = pool && plab == 0;           // the label is the pooled background (plain CE: a one-hot like any)
-      if (owner && !ignored) {
+      float fo_g = 1.f;
+      if (FO) {
+        // focal: every visiting cell needs the pixel's cross entropy for fo_g, the factor on its share of the gradient; the owner counts F
+        // the label's logit is in a register of lane (plab & 63) already: a lane read instead of four more LDS reads per visit
+        float z_lab = 0.f;
+        if (plab < Ctot) {
+#pragma unroll
+          for (int r = 0; r < NR; ++r)
+            if ((plab >> 6) == r) z_lab = lane_get(z[r], plab & 63);
+        }
+        const float fv = focal_pixel(-(lab0 ? lse_old - den : z_lab - den), fo_gamma, fo_alpha, fo_g);
+        if (owner && !ignored) ce_sum += fv;
+      } else if (owner && !ignored) {
         const float z_lab = plab < Ctot ? u.interp(s_log, Ctot, plab) : 0.f;       // a label that is no class: as the scatter kernels
         ce_sum += -(lab0 ? lse_old - den : z_lab - den);
       }
@@ -265,7 +278,7 @@ __global__ __launch_bounds__(kWave) void seg_losses_gather_kernel(
       }
       if (pw != 0.f) {
         // g_c = e_c (a_all - a_old [c<K] - b_bn [c in bkg/new]) - hot [c == label] - b_q te_c [q_lo<=c<K]  (seg_losses_wide_kernel)
-        const float ce_w = ignored ? 0.f : (SW ? sw * ce_scale : ce_scale);
+        const float ce_w = ignored ? 0.f : FO ? fo_g * (sw * ce_scale) : (SW ? sw * ce_scale : ce_scale);
         const float a_all = (ce_w + (plain ? 0.f : kdw)) / s_all;
         const float a_old = (lab0 ? ce_w * inv_old : 0.f) - (plain ? kdw * inv_old : 0.f);
         const float b_bn = plain ? 0.f : kdw * q0 * inv_bn;
@@ -375,7 +388,7 @@ namespace {
 int seg_losses_gather_impl(const char* fn, const float* sem_s, int ld_s, const float* sem_t, int ld_t, const int64_t* labels, int B, int H,
                            int W, int h, int w, int Ctot, int K, int ce_old_cl, int kd_mode, float alpha, int ignore_index,
                            float ce_weight, float kd_weight, const float* ce_sw, float* loss_out, float* d_sem, int ld_d, void* workspace,
-                           size_t workspace_bytes, ucd_stream_t stream) {
+                           size_t workspace_bytes, ucd_stream_t stream, bool focal = false, float fo_gamma = 0.f, float fo_alpha = 1.f) {
   GatherLaunch g;
   int rc = gather_prologue(fn, sem_s, ld_s, sem_t, ld_t, labels, B, H, W, h, w, Ctot, K, loss_out, d_sem, ld_d, workspace, workspace_bytes,
                            [&] { return seg_ex_check(fn, Ctot, K, ce_old_cl, kd_mode, alpha, sem_t != nullptr); },
@@ -386,15 +399,17 @@ int seg_losses_gather_impl(const char* fn, const float* sem_s, int ld_s, const f
   hipStream_t s = (hipStream_t)stream;
   const int kd_plain = kd_mode == UCD_KD_PLAIN;
   float* part = (float*)workspace;
-#define UCD_SEG_GATHER_SW(NR, SW)                                                                                                    \
-  seg_losses_gather_kernel<NR, SW><<<g.cells, kWave, g.lds, s>>>(sem_s, ld_s, sem_t, ld_t, labels, H, W, h, w, Ctot, K, ignore_index, \
-                                                                g.scale_h, g.scale_w, g.inv_scale_h, g.inv_scale_w,                  \
-                                                                ce_weight * g.inv_pix, kd_weight * g.inv_pix, part, d_sem, ld_d,     \
-                                                                ce_old_cl, kd_plain, alpha, ce_sw)
-#define UCD_SEG_GATHER(NR)                  \
-  do {                                      \
-    if (ce_sw) UCD_SEG_GATHER_SW(NR, true); \
-    else UCD_SEG_GATHER_SW(NR, false);      \
+#define UCD_SEG_GATHER_SW(NR, SW, FO)                                                                                                    \
+  seg_losses_gather_kernel<NR, SW, FO><<<g.cells, kWave, g.lds, s>>>(sem_s, ld_s, sem_t, ld_t, labels, H, W, h, w, Ctot, K, ignore_index, \
+                                                                    g.scale_h, g.scale_w, g.inv_scale_h, g.inv_scale_w,                  \
+                                                                    ce_weight * g.inv_pix, kd_weight * g.inv_pix, part, d_sem, ld_d,     \
+                                                                    ce_old_cl, kd_plain, alpha, ce_sw, fo_gamma, fo_alpha)
+  // the focal kernels are instantiations of their own, as the weighted ones are
+#define UCD_SEG_GATHER(NR)                              \
+  do {                                                  \
+    if (focal) UCD_SEG_GATHER_SW(NR, true, true);       \
+    else if (ce_sw) UCD_SEG_GATHER_SW(NR, true, false); \
+    else UCD_SEG_GATHER_SW(NR, false, false);           \
   } while (0)
   const int rounds = ceil_div(Ctot, kWave);           // 64 KB of LDS hold 1820 classes: at most 29 rounds
   if (rounds <= 1) UCD_SEG_GATHER(1);
@@ -428,6 +443,20 @@ int ucd_seg_losses_gather_w(const float* sem_s, int ld_s, const float* sem_t, in
   return seg_losses_gather_impl("ucd_seg_losses_gather_w", sem_s, ld_s, sem_t, ld_t, labels, B, H, W, h, w, Ctot, K, ce_old_cl,
                                 kd_mode, alpha, ignore_index, ce_weight, kd_weight, ce_sample_weight, loss_out, d_sem, ld_d, workspace,
                                 workspace_bytes, stream);
+}
+
+int ucd_seg_losses_gather_focal(const float* sem_s, int ld_s, const float* sem_t, int ld_t, const int64_t* labels, int B, int H, int W,
+                                int h, int w, int Ctot, int K, int ce_old_cl, int kd_mode, float alpha, int ignore_index, float ce_weight,
+                                float kd_weight, const float* ce_sample_weight, float focal_gamma, float focal_alpha, float* loss_out,
+                                float* d_sem, int ld_d, void* workspace, size_t workspace_bytes, ucd_stream_t stream) {
+  static const char* fn = "ucd_seg_losses_gather_focal";
+  const int rc = seg_focal_check(fn, focal_gamma, focal_alpha);
+  if (rc) return rc;
+  // gamma 0 at alpha 1 is no modulation: the launch, and the bits, of the call without focal
+  const bool focal = !(focal_gamma == 0.f && focal_alpha == 1.f);
+  return seg_losses_gather_impl(fn, sem_s, ld_s, sem_t, ld_t, labels, B, H, W, h, w, Ctot, K, ce_old_cl, kd_mode, alpha, ignore_index,
+                                ce_weight, kd_weight, ce_sample_weight, loss_out, d_sem, ld_d, workspace, workspace_bytes, stream, focal,
+                                focal_gamma, focal_alpha);
 }
 
 }  // extern "C"

@@ -28,6 +28,36 @@ inline int seg_ex_check(const char* fn, int Ctot, int K, int ce_old_cl, int kd_m
   return 0;
 }
 
+// the argument rules of the focal entries (host only, the first thing an entry does)
+inline int seg_focal_check(const char* fn, float focal_gamma, float focal_alpha) {
+  UCD_REQUIRE(std::isfinite(focal_gamma) && focal_gamma >= 0.f, UCD_EINVAL, "%s: focal_gamma = %g must be finite and >= 0", fn,
+              (double)focal_gamma);
+  UCD_REQUIRE(std::isfinite(focal_alpha) && focal_alpha > 0.f, UCD_EINVAL, "%s: focal_alpha = %g must be finite and > 0", fn,
+              (double)focal_alpha);
+  return 0;
+}
+
+// Focal modulation of one pixel's cross entropy ce (include/ucd_hip.h): returns F = alpha u^gamma ce, u = clamp(1 - exp(-ce), 0, 1),
+// and sets g = alpha (u^gamma + gamma u^(gamma-1) exp(-ce) ce), the factor on the pixel's cross-entropy gradient coefficient.
+// Where u rounds to 0 (ce below ~6e-8, or a negative ce of a label that is no class) both are 0; gamma == 0 is alpha ce and alpha.
+// u^(gamma-1) is taken of max(u, 2^-24), the smallest u that is not 0: no infinity is ever formed.  gamma is uniform: gamma == 2
+// runs without exp2 / log.  Scalars in, scalars out: nothing here lives across a class loop.
+__device__ __forceinline__ float focal_pixel(float ce, float gamma, float alpha, float& g) {
+  if (gamma == 0.f) { g = alpha; return alpha * ce; }
+  const float p = __builtin_amdgcn_exp2f(-ce * 1.4426950408889634f);
+  const float u = fminf(fmaxf(1.f - p, 0.f), 1.f);
+  float ug, ug1;                               // u^gamma, u^(gamma-1)
+  if (gamma == 2.f) { ug = u * u; ug1 = u; }
+  else {
+    const float l = __builtin_amdgcn_logf(fmaxf(u, 5.9604644775390625e-8f));
+    ug = __builtin_amdgcn_exp2f(gamma * l);
+    ug1 = __builtin_amdgcn_exp2f((gamma - 1.f) * l);
+  }
+  const bool zero = !(u > 0.f);
+  g = zero ? 0.f : alpha * (ug + gamma * ug1 * (p * ce));
+  return zero ? 0.f : alpha * (ug * ce);
+}
+
 // part: [n][2] loss sums of tiles or cells -> out[0], out[1] = their sums in index order (fp64), times inv_pix: the means over ALL
 // pixels, ignored ones counting as 0 (train.py:116 .mean(); loss.py:178).  A fixed order: the same bits on every run
 __global__ __launch_bounds__(1024) void seg_pair_reduce_kernel(const float* __restrict__ part, int n, float inv_pix,

@@ -67,16 +67,17 @@ __device__ __forceinline__ void store_block_losses(float ce_sum, float kd_sum, f
 // form below does not: UCD_SEG_PK=0, a d_sem off the 16-byte grid, accumulator copies that do not fit the LDS.
 // EX (see seg_losses_pk_kernel): cross entropy pooled over [0, kce), kce == K or 1; teacher rows staged times alpha;
 // kd_plain: KD = -sum_{c<K} q_c (z_c - LSE_old) / K.  EX == false keeps the arithmetic the kernel had.
-template <int CT, int KT, bool EX, bool SW>
+template <int CT, int KT, bool EX, bool SW, bool FO>
 __global__ __launch_bounds__(kThreads) void seg_losses_kernel(
     const float* __restrict__ sem_s, int ld_s, const float* __restrict__ sem_t, int ld_t, const int64_t* __restrict__ labels,
     int H, int W, int h, int w, int Ctot, int K, int ignore_index, float scale_h, float scale_w, float ce_scale,
     float kd_scale, float* __restrict__ loss_part, float* __restrict__ d_sem, int ld_d, int tiles_x, int tiles_y, int kce,
-    int kd_plain, float alpha, const float* __restrict__ ce_sw) {
+    int kd_plain, float alpha, const float* __restrict__ ce_sw, float fo_gamma, float fo_alpha) {
   static_assert(CT > 0 && KT > 0 && KT <= CT, "the classes of a pixel live in CT + KT registers");
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int b = blockIdx.z, ty0 = blockIdx.y * kTileY, tx0 = blockIdx.x * kTileX;
-  const float sw = SW ? ce_sw[b] : 1.f;      // SW: the image's weight on the cross entropy (ucd_seg_losses_ex_w)
+  // SW: the image's weight on the cross entropy (ucd_seg_losses_ex_w); FO (ucd_seg_losses_focal) is built with SW and takes a NULL as ones
+  const float sw = SW ? ((FO && !ce_sw) ? 1.f : ce_sw[b]) : 1.f;
   const Footprint fp = tile_footprint(ty0, tx0, kTileY, H, W, h, w, scale_h, scale_w);
   const int ya = fp.ya, xa = fp.xa, nx = fp.nx, ncell = fp.ncell;
   // kRep copies of the gradient accumulators, a lane adds into copy (lane & 15): the 15-16 consecutive pixel columns under
@@ -197,7 +198,10 @@ __global__ __launch_bounds__(kThreads) void seg_losses_kernel(
     }
     const bool lab0 = pool && lab == 0;    // the label is the pooled background (plain CE: a one-hot like any)
     const float logp = lab0 ? lse_old - den : z_lab - den;
-    if (!ignored) ce_sum += -logp;
+    // FO: the focal modulation of the pixel (seg_loss_common.h) - its value instead of the cross entropy, fo_g on the coefficient
+    float fo_g = 1.f;
+    const float ce_pix = FO ? focal_pixel(-logp, fo_gamma, fo_alpha, fo_g) : -logp;
+    if (!ignored) ce_sum += ce_pix;
     const float inv_all = 1.f / s_all;
     // teacher soft-max
     float te[KT];
@@ -221,7 +225,7 @@ __global__ __launch_bounds__(kThreads) void seg_losses_kernel(
       q0 = te[0] * inv_st;
       kd_pix = plain ? q0 * (zc[0] - lse_old) : q0 * (lse_bn - den);
     }
-    const float ce_w = ignored ? 0.f : (SW ? sw * ce_scale : ce_scale);
+    const float ce_w = ignored ? 0.f : FO ? fo_g * (sw * ce_scale) : (SW ? sw * ce_scale : ce_scale);
     const float kdw = kd_scale * invK;
     const float q0bn = q0 * inv_bn;
     const float kd_ref = plain ? lse_old : den;      // what the old classes' log-probabilities are taken against
@@ -295,12 +299,12 @@ __device__ __forceinline__ f32x2 exp2_2(f32x2 a) { return f32x2{__builtin_amdgcn
 //   KD = -sum_{c<K} q_c (z_c - LSE_old) / K,   dKD/dz_c = [c < K] (e_c / sum_old - q_c) / K.
 // All three are block-uniform; the sums it needs (old slots, all slots) are the ones the unbiased pair takes already.  EX == false
 // keeps the arithmetic the kernel had (the same operations in the same order: the same bits).
-template <int KT, int NT, bool EX, bool SW>
+template <int KT, int NT, bool EX, bool SW, bool FO>
 __global__ __launch_bounds__(kThreads) void seg_losses_pk_kernel(
     const float* __restrict__ sem_s, int ld_s, const float* __restrict__ sem_t, int ld_t, const int64_t* __restrict__ labels,
     int H, int W, int h, int w, int Ctot, int K, int ignore_index, float scale_h, float scale_w, float ce_scale,
     float kd_scale, float* __restrict__ loss_part, float* __restrict__ d_sem, int ld_d, int tiles_x, int tiles_y, int cell_cap,
-    float fx_scale, int kce, int kd_plain, float alpha, const float* __restrict__ ce_sw) {
+    float fx_scale, int kce, int kd_plain, float alpha, const float* __restrict__ ce_sw, float fo_gamma, float fo_alpha) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   constexpr int CT = KT + NT, NP = CT / 2, KP = KT / 2, kRep = kRepPk;
   // logit rows in LDS are CT + 1 / KT + 1 floats apart: the lanes of a wave read from ~5 cells, sixteen lanes the same address - a
@@ -310,7 +314,7 @@ __global__ __launch_bounds__(kThreads) void seg_losses_pk_kernel(
   static_assert(KT % 4 == 0 && NT % 4 == 0, "slot groups are read four at a time");
   constexpr float kL2e = 1.4426950408889634f, kLn2 = 0.6931471805599453f, kNegBig = -1e30f;
   const int b = blockIdx.z, ty0 = blockIdx.y * kTileY, tx0 = blockIdx.x * kTileX;
-  const float sw = SW ? ce_sw[b] : 1.f;
+  const float sw = SW ? ((FO && !ce_sw) ? 1.f : ce_sw[b]) : 1.f;
   const Footprint fp = tile_footprint(ty0, tx0, kTileY, H, W, h, w, scale_h, scale_w);
   const int ya = fp.ya, xa = fp.xa, nx = fp.nx, ncell = fp.ncell;
   // the host sized the LDS for the exact footprint it computed with the same arithmetic; a disagreement must not become a silent
@@ -484,9 +488,12 @@ __global__ __launch_bounds__(kThreads) void seg_losses_pk_kernel(
       inv_old = 0.f; inv_bn = 0.f;                   // the subset terms of the gradient come from r_o / r_b below
     }
     const float logp = lab0 ? lse_old - den : z_lab - den;
-    if (!ignored) ce_sum += -logp;
+    // FO: the focal modulation of the pixel (seg_loss_common.h) - its value instead of the cross entropy, fo_g on the coefficient
+    float fo_g = 1.f;
+    const float ce_pix = FO ? focal_pixel(-logp, fo_gamma, fo_alpha, fo_g) : -logp;
+    if (!ignored) ce_sum += ce_pix;
     const float inv_all = 1.f / s_all;
-    const float ce_w = ignored ? 0.f : (SW ? sw * ce_scale : ce_scale);
+    const float ce_w = ignored ? 0.f : FO ? fo_g * (sw * ce_scale) : (SW ? sw * ce_scale : ce_scale);
     // teacher soft-max over the old classes; q_c = te_c / sum te
     f32x2 te[KP];
     float inv_st = 0.f, q0 = 0.f, kd_pix = 0.f;
@@ -605,18 +612,18 @@ __device__ __forceinline__ float4 interp4(const float* base, int o00, int o01, i
 
 // EX (see seg_losses_pk_kernel): cross entropy pooled over [0, kce), kce == K or 1; teacher rows staged times alpha; kd_plain:
 // KD = -sum_{c<K} q_c (z_c - LSE_old) / K - the row constants of phase A change, phase B only widens its teacher mask to class 0.
-template <bool EX, bool SW>
+template <bool EX, bool SW, bool FO>
 __global__ __launch_bounds__(kThreads) void seg_losses_wide_kernel(
     const float* __restrict__ sem_s, int ld_s, const float* __restrict__ sem_t, int ld_t, const int64_t* __restrict__ labels,
     int H, int W, int h, int w, int Ctot, int K, int ignore_index, float scale_h, float scale_w, float ce_scale,
     float kd_scale, float* __restrict__ loss_part, float* __restrict__ d_sem, int ld_d, int tiles_x, int tiles_y, float fx_scale,
-    int kce, int kd_plain, float alpha, const float* __restrict__ ce_sw) {
+    int kce, int kd_plain, float alpha, const float* __restrict__ ce_sw, float fo_gamma, float fo_alpha) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   constexpr int kTY = 4 * kRW;
   constexpr float kL2e = 1.4426950408889634f, kLn2 = 0.6931471805599453f, kNegBig = -1e30f;
   const int CS = (Ctot + 3) & ~3, KS = sem_t ? ((K + 3) & ~3) : 0;
   const int b = blockIdx.z, ty0 = blockIdx.y * kTY, tx0 = blockIdx.x * kTileX;
-  const float sw = SW ? ce_sw[b] : 1.f;
+  const float sw = SW ? ((FO && !ce_sw) ? 1.f : ce_sw[b]) : 1.f;
   const Footprint fp = tile_footprint(ty0, tx0, kTY, H, W, h, w, scale_h, scale_w);
   const int ya = fp.ya, xa = fp.xa, nx = fp.nx, ncell = fp.ncell;
   float* s_log = smem;                         // [ncell][CS]
@@ -740,8 +747,11 @@ __global__ __launch_bounds__(kThreads) void seg_losses_wide_kernel(
     }
     const bool lab0 = pool && lab == 0;     // the label is the pooled background (plain CE: a one-hot like any)
     const float logp = lab0 ? lse_old - den : z_lab - den;
-    if (!ignored) ce_sum += -logp;
-    const float ce_w = ignored ? 0.f : (SW ? sw * ce_scale : ce_scale);
+    // FO: the focal modulation of the pixel (seg_loss_common.h) - its value instead of the cross entropy, fo_g on the coefficient
+    float fo_g = 1.f;
+    const float ce_pix = FO ? focal_pixel(-logp, fo_gamma, fo_alpha, fo_g) : -logp;
+    if (!ignored) ce_sum += ce_pix;
+    const float ce_w = ignored ? 0.f : FO ? fo_g * (sw * ce_scale) : (SW ? sw * ce_scale : ce_scale);
     float inv_st = 0.f, q0 = 0.f;
     if (sem_t) {
       inv_st = 1.f / st;
@@ -1010,17 +1020,18 @@ int ucd_seg_losses_plan(int H, int W, int h, int w, int Ctot, int K, int has_tea
 namespace {
 
 // opt every instantiation of one EX value in to the LDS budget, launch the planned form
-template <bool EX, bool SW>
+// FO: the focal instantiations (ucd_seg_losses_focal), built with SW only
+template <bool EX, bool SW, bool FO>
 int seg_launch(const char* fn, int form, dim3 grid, size_t lds, hipStream_t s, const float* sem_s, int ld_s, const float* sem_t, int ld_t,
                const int64_t* labels, int H, int W, int h, int w, int Ctot, int K, int ignore_index, float ce_scale, float kd_scale,
                float* part, float* d_sem, int ld_d, int cells, float fx_scale, int ce_old_cl, int kd_plain, float alpha,
-               const float* ce_sw) {
-  UCD_TRY_LDS((seg_losses_pk_kernel<16, 8, EX, SW>), 150 * 1024);
-  UCD_TRY_LDS((seg_losses_pk_kernel<20, 4, EX, SW>), 150 * 1024);
-  UCD_TRY_LDS((seg_losses_pk_kernel<12, 12, EX, SW>), 150 * 1024);
-  UCD_TRY_LDS((seg_losses_kernel<24, 16, EX, SW>), 150 * 1024);
-  UCD_TRY_LDS((seg_losses_kernel<24, 24, EX, SW>), 150 * 1024);
-  UCD_TRY_LDS((seg_losses_wide_kernel<EX, SW>), 150 * 1024);
+               const float* ce_sw, float fo_gamma, float fo_alpha) {
+  UCD_TRY_LDS((seg_losses_pk_kernel<16, 8, EX, SW, FO>), 150 * 1024);
+  UCD_TRY_LDS((seg_losses_pk_kernel<20, 4, EX, SW, FO>), 150 * 1024);
+  UCD_TRY_LDS((seg_losses_pk_kernel<12, 12, EX, SW, FO>), 150 * 1024);
+  UCD_TRY_LDS((seg_losses_kernel<24, 16, EX, SW, FO>), 150 * 1024);
+  UCD_TRY_LDS((seg_losses_kernel<24, 24, EX, SW, FO>), 150 * 1024);
+  UCD_TRY_LDS((seg_losses_wide_kernel<EX, SW, FO>), 150 * 1024);
   hipError_t e = hipMemsetAsync(d_sem, 0, (size_t)grid.z * h * w * ld_d * sizeof(float), s);
   if (e != hipSuccess) { set_error("%s: %s", fn, hipGetErrorString(e)); return (int)e; }
   const int tiles_x = grid.x, tiles_y = grid.y;
@@ -1028,29 +1039,31 @@ int seg_launch(const char* fn, int form, dim3 grid, size_t lds, hipStream_t s, c
 #define UCD_SEG_ARGS                                                                                                               \
   sem_s, ld_s, sem_t, ld_t, labels, H, W, h, w, Ctot, K, ignore_index, (float)h / (float)H, (float)w / (float)W, ce_scale, kd_scale, part, \
       d_sem, ld_d, tiles_x, tiles_y
+#define UCD_SEG_TAIL ce_old_cl, kd_plain, alpha, ce_sw, fo_gamma, fo_alpha
   if (form == UCD_SEG_PK_16_8)
-    seg_losses_pk_kernel<16, 8, EX, SW><<<grid, kThreads, lds, s>>>(UCD_SEG_ARGS, cells, fx_scale, ce_old_cl, kd_plain, alpha, ce_sw);
+    seg_losses_pk_kernel<16, 8, EX, SW, FO><<<grid, kThreads, lds, s>>>(UCD_SEG_ARGS, cells, fx_scale, UCD_SEG_TAIL);
   else if (form == UCD_SEG_PK_20_4)
-    seg_losses_pk_kernel<20, 4, EX, SW><<<grid, kThreads, lds, s>>>(UCD_SEG_ARGS, cells, fx_scale, ce_old_cl, kd_plain, alpha, ce_sw);
+    seg_losses_pk_kernel<20, 4, EX, SW, FO><<<grid, kThreads, lds, s>>>(UCD_SEG_ARGS, cells, fx_scale, UCD_SEG_TAIL);
   else if (form == UCD_SEG_PK_12_12)
-    seg_losses_pk_kernel<12, 12, EX, SW><<<grid, kThreads, lds, s>>>(UCD_SEG_ARGS, cells, fx_scale, ce_old_cl, kd_plain, alpha, ce_sw);
+    seg_losses_pk_kernel<12, 12, EX, SW, FO><<<grid, kThreads, lds, s>>>(UCD_SEG_ARGS, cells, fx_scale, UCD_SEG_TAIL);
   else if (form == UCD_SEG_REG_24_16)
-    seg_losses_kernel<24, 16, EX, SW><<<grid, kThreads, lds, s>>>(UCD_SEG_ARGS, ce_old_cl, kd_plain, alpha, ce_sw);
+    seg_losses_kernel<24, 16, EX, SW, FO><<<grid, kThreads, lds, s>>>(UCD_SEG_ARGS, UCD_SEG_TAIL);
   else if (form == UCD_SEG_REG_24_24)
-    seg_losses_kernel<24, 24, EX, SW><<<grid, kThreads, lds, s>>>(UCD_SEG_ARGS, ce_old_cl, kd_plain, alpha, ce_sw);
+    seg_losses_kernel<24, 24, EX, SW, FO><<<grid, kThreads, lds, s>>>(UCD_SEG_ARGS, UCD_SEG_TAIL);
   else
-    seg_losses_wide_kernel<EX, SW><<<grid, kThreads, lds, s>>>(UCD_SEG_ARGS, form == UCD_SEG_WIDE_FIXED ? fx_scale : 0.f, ce_old_cl,
-                                                               kd_plain, alpha, ce_sw);
+    seg_losses_wide_kernel<EX, SW, FO><<<grid, kThreads, lds, s>>>(UCD_SEG_ARGS, form == UCD_SEG_WIDE_FIXED ? fx_scale : 0.f, UCD_SEG_TAIL);
+#undef UCD_SEG_TAIL
 #undef UCD_SEG_ARGS
   return check_launch(fn);
 }
 
 // ucd_seg_losses, ucd_seg_losses_ex and ucd_seg_losses_ex_w: one body, the messages carry the name of the entry that was called.
 // ce_sw (device, [B], NULL: the kernels without a weight): image b's cross entropy counts ce_sw[b] times, in the loss and the gradient
+// focal (ucd_seg_losses_focal): the focal instantiations modulate each pixel's cross entropy with (fo_gamma, fo_alpha); a NULL ce_sw is ones
 int seg_losses_impl(const char* fn, const float* sem_s, int ld_s, const float* sem_t, int ld_t, const int64_t* labels, int B, int H, int W,
                     int h, int w, int Ctot, int K, int ce_old_cl, int kd_mode, float alpha, int ignore_index, float ce_weight,
                     float kd_weight, float* loss_out, float* d_sem, int ld_d, void* workspace, size_t workspace_bytes,
-                    ucd_stream_t stream, const float* ce_sw = nullptr) {
+                    ucd_stream_t stream, const float* ce_sw = nullptr, bool focal = false, float fo_gamma = 0.f, float fo_alpha = 1.f) {
   UCD_REQUIRE(sem_s && labels && loss_out && d_sem && workspace, UCD_EINVAL, "%s: NULL argument", fn);
   UCD_REQUIRE(B > 0 && H > 0 && W > 0 && h > 0 && w > 0 && Ctot > 0 && K >= 1 && K <= Ctot, UCD_EINVAL, "%s: bad sizes", fn);
   UCD_REQUIRE(ld_s >= Ctot && ld_d >= Ctot && (!sem_t || ld_t >= K), UCD_EINVAL, "%s: bad leading dimension", fn);
@@ -1074,15 +1087,18 @@ int seg_losses_impl(const char* fn, const float* sem_s, int ld_s, const float* s
   float* part = (float*)workspace;
   // fixed-point scale of the packed form's gradient words: one pixel's gradient is at most ce + 2 kd / K in magnitude (unbiased KD;
   // the plain mode's |softmax_K - q| / K stays below kd / K, so the same quantum serves it - include/ucd_hip.h)
-  const float fx_gmax = fabsf(ce_weight * inv_pix) + 2.f * fabsf(kd_weight * inv_pix) / (float)K;
+  // focal: the factor on a pixel's cross-entropy coefficient is at most alpha (1 + gamma) (proof: include/ucd_hip.h)
+  const float fo_bound = focal ? fo_alpha * (1.f + fo_gamma) : 1.f;
+  const float fx_gmax = fo_bound * fabsf(ce_weight * inv_pix) + 2.f * fabsf(kd_weight * inv_pix) / (float)K;
   const float fx_scale = fx_gmax > 0.f ? 131072.f / fx_gmax : 1.f;
   const dim3 grid(tiles_x, tiles_y, B);
-#define UCD_SEG_LAUNCH(EX, SW)                                                                                                      \
-  seg_launch<EX, SW>(fn, form, grid, lds, s, sem_s, ld_s, sem_t, ld_t, labels, H, W, h, w, Ctot, K, ignore_index, ce_weight * inv_pix, \
-                     kd_weight * inv_pix, part, d_sem, ld_d, ny * nx, fx_scale, ce_old_cl, kd_plain, alpha, ce_sw)
-  // the weighted kernels are instantiations of their own: the unweighted launches keep their code (two forms sit at 256 VGPRs)
-  rc = ce_sw ? (ex ? UCD_SEG_LAUNCH(true, true) : UCD_SEG_LAUNCH(false, true))
-             : (ex ? UCD_SEG_LAUNCH(true, false) : UCD_SEG_LAUNCH(false, false));
+#define UCD_SEG_LAUNCH(EX, SW, FO)                                                                                                      \
+  seg_launch<EX, SW, FO>(fn, form, grid, lds, s, sem_s, ld_s, sem_t, ld_t, labels, H, W, h, w, Ctot, K, ignore_index, ce_weight * inv_pix, \
+                         kd_weight * inv_pix, part, d_sem, ld_d, ny * nx, fx_scale, ce_old_cl, kd_plain, alpha, ce_sw, fo_gamma, fo_alpha)
+  // the weighted and the focal kernels are instantiations of their own: the other launches keep their code (two forms sit at 256 VGPRs)
+  rc = focal ? (ex ? UCD_SEG_LAUNCH(true, true, true) : UCD_SEG_LAUNCH(false, true, true))
+       : ce_sw ? (ex ? UCD_SEG_LAUNCH(true, true, false) : UCD_SEG_LAUNCH(false, true, false))
+               : (ex ? UCD_SEG_LAUNCH(true, false, false) : UCD_SEG_LAUNCH(false, false, false));
 #undef UCD_SEG_LAUNCH
   if (rc) return rc;
   if (packed || form == UCD_SEG_WIDE_FIXED) {
@@ -1128,6 +1144,20 @@ int ucd_seg_losses_ex_w(const float* sem_s, int ld_s, const float* sem_t, int ld
                         size_t workspace_bytes, ucd_stream_t stream) {
   return seg_losses_impl("ucd_seg_losses_ex_w", sem_s, ld_s, sem_t, ld_t, labels, B, H, W, h, w, Ctot, K, ce_old_cl, kd_mode, alpha,
                          ignore_index, ce_weight, kd_weight, loss_out, d_sem, ld_d, workspace, workspace_bytes, stream, ce_sample_weight);
+}
+
+int ucd_seg_losses_focal(const float* sem_s, int ld_s, const float* sem_t, int ld_t, const int64_t* labels, int B, int H, int W,
+                         int h, int w, int Ctot, int K, int ce_old_cl, int kd_mode, float alpha, int ignore_index, float ce_weight,
+                         float kd_weight, const float* ce_sample_weight, float focal_gamma, float focal_alpha, float* loss_out,
+                         float* d_sem, int ld_d, void* workspace, size_t workspace_bytes, ucd_stream_t stream) {
+  static const char* fn = "ucd_seg_losses_focal";
+  const int rc = seg_focal_check(fn, focal_gamma, focal_alpha);
+  if (rc) return rc;
+  // gamma 0 at alpha 1 is no modulation: the launch, and the bits, of the call without focal
+  const bool focal = !(focal_gamma == 0.f && focal_alpha == 1.f);
+  return seg_losses_impl(fn, sem_s, ld_s, sem_t, ld_t, labels, B, H, W, h, w, Ctot, K, ce_old_cl, kd_mode, alpha, ignore_index, ce_weight,
+                         kd_weight, loss_out, d_sem, ld_d, workspace, workspace_bytes, stream, ce_sample_weight, focal, focal_gamma,
+                         focal_alpha);
 }
 
 int ucd_seg_confusion(const float* sem, int ld_s, const int64_t* labels, int B, int H, int W, int h, int w, int Ctot,

@@ -207,6 +207,9 @@ SIGNATURES = {
     # the same two with ce_sample_weight [B] in front of loss_out
     "ucd_seg_losses_ex_w": (_i, [_p, _i, _p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _f, _f, _p, _p, _p, _i, _p, _z, _p]),
     "ucd_seg_losses_gather_w": (_i, [_p, _i, _p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _f, _f, _p, _p, _p, _i, _p, _z, _p]),
+    # the same two with focal_gamma, focal_alpha behind ce_sample_weight
+    "ucd_seg_losses_focal": (_i, [_p, _i, _p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _f, _f, _p, _f, _f, _p, _p, _i, _p, _z, _p]),
+    "ucd_seg_losses_gather_focal": (_i, [_p, _i, _p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _f, _f, _p, _f, _f, _p, _p, _i, _p, _z, _p]),
     "ucd_pseudo_plan": (_i, [_i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p]),
     "ucd_pseudo_hist": (_i, [_p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p]),
     "ucd_pseudo_label": (_i, [_p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _p, _f, _p, _p, _p, _p, _p]),

@@ -67,10 +67,12 @@ class _FusedSegLosses(_LowResLogitLoss):
     kernels were first built for (one class count for both losses, unbiased KD, alpha 1) is the launch, and the bits, of
     ucd_seg_losses: the library picks its kernels by these values, not by the entry.  ``sample_weight`` ([B] fp32 on the device, each
     in [0, 1]; None: the calls without one, launch for launch) weighs image b's cross entropy, in the loss and the gradient
-    (ucd_seg_losses_ex_w / ucd_seg_losses_gather_w)."""
+    (ucd_seg_losses_ex_w / ucd_seg_losses_gather_w).  ``focal`` ((gamma, alpha); None: the calls without it, launch for launch)
+    modulates each pixel's cross entropy (ucd_seg_losses_focal / ucd_seg_losses_gather_focal, which take the weight or NULL)."""
 
     @staticmethod
-    def forward(ctx, sem, sem_old, labels, old_cl, ce_weight, kd_weight, ignore_index, kd_mode, alpha, form, sample_weight=None):
+    def forward(ctx, sem, sem_old, labels, old_cl, ce_weight, kd_weight, ignore_index, kd_mode, alpha, form, sample_weight=None,
+                focal=None):
         lib = hip.load()
         gather = form == "gather"
         # the gather form writes d_sem only where asked (the same loss bits without); the tiled forms always accumulate into it
@@ -78,7 +80,10 @@ class _FusedSegLosses(_LowResLogitLoss):
                                                                                    ctx.needs_input_grad[0] or not gather)
         name = "ucd_seg_losses_gather" if gather else "ucd_seg_losses_ex"
         sw = ()
-        if sample_weight is not None:
+        if focal is not None:
+            name = "ucd_seg_losses_gather_focal" if gather else "ucd_seg_losses_focal"
+            sw = (hip.ptr(sample_weight), float(focal[0]), float(focal[1]))
+        elif sample_weight is not None:
             name += "_w"
             sw = (hip.ptr(sample_weight),)
         nbytes = lib.ucd_seg_losses_gather_workspace_bytes(B, h, w) if gather else lib.ucd_seg_losses_workspace_bytes(B, H, W)
@@ -405,7 +410,7 @@ def seg_losses_route(H, W, h, w, Ctot, K, has_teacher, ce_old_cl=None):
 
 
 def fused_seg_losses(sem, sem_old, labels, old_cl, ce_weight=1.0, kd_weight=0.0, ignore_index=255, *, kd="unbiased", alpha=1.0,
-                     form="auto", sample_weight=None):
+                     form="auto", sample_weight=None, focal=None):
     """Returns (ce_weight*CE + kd_weight*KD [differentiable w.r.t. ``sem``], CE, KD) where CE / KD are the
     reference's ``UnbiasedCrossEntropy(old_cl)(up(sem), labels).mean()`` (``old_cl`` 1: ``nn.CrossEntropyLoss``) and
     ``UnbiasedKnowledgeDistillationLoss(alpha=alpha)(up(sem), up(sem_old))`` or, with ``kd="plain"``,
@@ -419,7 +424,12 @@ def fused_seg_losses(sem, sem_old, labels, old_cl, ce_weight=1.0, kd_weight=0.0,
     that serves (the call, and the bits, it always was) and ``"gather"`` elsewhere (``seg_losses_route``).
 
     ``sample_weight`` ([B], each in [0, 1] - the adaptive factor of ``fused_pseudo_labels``): CE becomes
-    ``1 / (BHW) sum_b sample_weight[b] sum_p CE_p``; KD is untouched.  None (the default) is the call without a weight."""
+    ``1 / (BHW) sum_b sample_weight[b] sum_p CE_p``; KD is untouched.  None (the default) is the call without a weight.
+
+    ``focal`` (``(gamma, alpha)``, ``gamma >= 0``, ``alpha > 0``): CE becomes the reference's ``FocalLoss`` on the same cross
+    entropy, ``mean(alpha (1 - exp(-CE_p))^gamma CE_p)`` over all pixels (times the image's ``sample_weight``), inside the same
+    kernels (``focal_modulate`` states the rule where ``1 - exp(-CE_p)`` rounds to 0); KD is untouched.  None (the default) is the
+    call without it; ``(0, 1)`` gives its bits."""
     if not sem.is_cuda:
         raise RuntimeError("ucd_amd.loss.fused_seg_losses runs on the GPU only (there is no CPU fallback)")
     if kd not in KD_MODES:
@@ -431,12 +441,14 @@ def fused_seg_losses(sem, sem_old, labels, old_cl, ce_weight=1.0, kd_weight=0.0,
             raise ValueError(f"sample_weight must be [{sem.shape[0]}] on {sem.device}, got {tuple(sample_weight.shape)} on "
                              f"{sample_weight.device}")
         sample_weight = sample_weight.detach().float().contiguous()
+    if focal is not None:
+        focal = _focal_check(*focal)
     if form == "auto":
         K = int(old_cl) if sem_old is None else sem_old.shape[1]
         form = seg_losses_route(labels.shape[-2], labels.shape[-1], sem.shape[2], sem.shape[3], sem.shape[1], K, sem_old is not None,
                                 max(int(old_cl), 1))
     return _FusedSegLosses.apply(sem, sem_old, labels, old_cl, ce_weight, kd_weight, ignore_index, KD_MODES[kd], float(alpha), form,
-                                 sample_weight)
+                                 sample_weight, focal)
 
 
 # ---- PLOP's pseudo-labelling (csrc/pseudo_label.hip) ------------------------------------------------------
@@ -573,6 +585,46 @@ def pseudo_median(hist, floor=0.0):
 def _wide(x):
     """fp32 arithmetic for half-precision logits; fp32 and fp64 inputs keep their type (the float64 references of the tests)."""
     return x if x.dtype in (torch.float32, torch.float64) else x.float()
+
+
+# ---- focal cross entropy (the reference's FocalLoss, utils/loss.py:6-28; DESIGN.md section 3.5.10) -----------------------------------
+def _focal_check(gamma, alpha):
+    """The domain of the focal arguments (the library's rule, for the composition too); returns them as floats."""
+    gamma, alpha = float(gamma), float(alpha)
+    if not (math.isfinite(gamma) and gamma >= 0.0):
+        raise ValueError(f"focal gamma = {gamma} must be finite and >= 0")
+    if not (math.isfinite(alpha) and alpha > 0.0):
+        raise ValueError(f"focal alpha = {alpha} must be finite and > 0")
+    return gamma, alpha
+
+
+def focal_modulate(ce_map, gamma=2.0, alpha=1.0):
+    """``alpha * u^gamma * ce`` with ``u = clamp(1 - exp(-ce), 0, 1)``, element by element, on a ``reduction='none'`` cross-entropy
+    map (an ignored pixel holds 0); differentiable.  Where ``u`` rounds to 0 the value and the gradient are 0 for ``gamma > 0``
+    (``0^(gamma-1) * ce`` is never formed: for ``gamma < 1`` it would be ``inf * 0``); ``gamma == 0`` is ``alpha * ce``.  The torch
+    composition of what ``fused_seg_losses(focal=...)`` does inside its kernels: serves CPU tensors and ``UCD_FUSED_FOCAL=0``."""
+    gamma, alpha = _focal_check(gamma, alpha)
+    if gamma == 0.0:
+        return alpha * ce_map
+    u = (1.0 - torch.exp(-ce_map)).clamp(0.0, 1.0)
+    zero = u <= 0
+    base = torch.where(zero, torch.ones_like(u), u)          # the power and its derivative never see a 0
+    return torch.where(zero, torch.zeros_like(ce_map), alpha * base.pow(gamma) * ce_map)
+
+
+class FocalLoss(nn.Module):
+    """The reference's ``FocalLoss`` (utils/loss.py:13-28) on full-resolution logits: ``alpha * (1 - p_t)^gamma * CE`` of the plain
+    cross entropy, averaged over ALL pixels (ignored ones count as 0) or summed."""
+
+    def __init__(self, alpha=1, gamma=2, size_average=True, ignore_index=255):
+        super().__init__()
+        self.gamma, self.alpha = _focal_check(gamma, alpha)
+        self.size_average, self.ignore_index = size_average, ignore_index
+
+    def forward(self, inputs, targets):
+        ce = F.cross_entropy(_wide(inputs), targets, reduction="none", ignore_index=self.ignore_index)
+        focal = focal_modulate(ce, self.gamma, self.alpha)
+        return focal.mean() if self.size_average else focal.sum()
 
 
 class UnbiasedCrossEntropy(nn.Module):

@@ -39,7 +39,7 @@ from . import switches as _switches
 from .contrastive import ucd_contrastive_loss
 from .loss import (KnowledgeDistillationLoss, UnbiasedCrossEntropy, UnbiasedKnowledgeDistillationLoss,
                    POD_SCALES, fused_attn_mse, fused_local_pod, fused_local_pod_logits, fused_pseudo_labels, fused_seg_bce,
-                   fused_seg_losses, pseudo_hist, pseudo_median)
+                   fused_seg_losses, pseudo_hist, pseudo_median, _focal_check, focal_modulate)
 
 
 def _raw(features, name):
@@ -110,6 +110,16 @@ class Trainer:
             self.pseudo_f_min = float(getattr(opts, "pseudo_adaptive_min", 0.0))
             # (trainer_state is the PREVIOUS step's: its thresholds belong to another teacher.  load_state_dict, on a resume of
             # this step, brings this step's)
+        # focal cross entropy (--focal_loss; the reference's FocalLoss): the criterion of the train step and of validation is
+        # alpha (1 - exp(-ce))^gamma ce on the step's cross entropy - plain or unbiased, after the pseudo-labels, times the adaptive
+        # factor - inside the fused logit-loss kernels (fused_seg_losses(focal=...)); UCD_FUSED_FOCAL=0, the CPU and runs without the
+        # fused losses take focal_modulate on the cross-entropy map of the up-sampled logits
+        self.focal = None
+        if getattr(opts, "focal_loss", False):
+            if self.bce:
+                raise NotImplementedError("--focal_loss with --bce / --icarl: the focal modulation is defined on the soft-max cross "
+                                          "entropy only")
+            self.focal = _focal_check(getattr(opts, "focal_loss_gamma", 2.0), getattr(opts, "focal_loss_alpha", 1.0))
         self.lkd = opts.loss_kd
         self.lkd_flag = self.lkd > 0. and model_old is not None
         self.lkd_loss = (UnbiasedKnowledgeDistillationLoss if opts.unkd else KnowledgeDistillationLoss)(alpha=opts.alpha)
@@ -135,6 +145,8 @@ class Trainer:
         any_pair = _switches.get("UCD_SEG_KD_EX", "1") != "0" and math.isfinite(self.alpha) and self.alpha != 0.0
         self.fuse_logit_losses = (getattr(opts, "fused_logit_losses", True) and device.type == "cuda"
                                   and (not self.lkd_flag or first_pair or any_pair))
+        if self.focal is not None and _switches.get("UCD_FUSED_FOCAL", "1") == "0":
+            self.fuse_logit_losses = False           # the composition over up-sampled logits
         if self.bce:
             # the student never up-samples under BCE: a --loss_kd term next to it (--method LWF --bce) comes from the fused kernel
             # too (its CE value discarded, old_cl 1 next to a teacher), which only the any-pair form of that kernel serves
@@ -386,9 +398,11 @@ class Trainer:
                                              self.old_classes if self.unce else 1, 1.0,
                                              self.lkd if self.lkd_flag else 0.0,
                                              kd=self.kd_mode if self.lkd_flag else "unbiased",
-                                             alpha=self.alpha if self.lkd_flag else 1.0, sample_weight=factor)
+                                             alpha=self.alpha if self.lkd_flag else 1.0, sample_weight=factor, focal=self.focal)
         else:
             ce = self.criterion(outputs.float() if outputs.dtype != torch.float32 else outputs, labels_ce)
+            if self.focal is not None:
+                ce = focal_modulate(ce, *self.focal)
             if factor is not None:
                 ce = ce * factor.view(-1, 1, 1)
             ce = ce.mean()
@@ -601,7 +615,8 @@ class Trainer:
                     if self.bce:
                         class_loss += fused_seg_bce(sem, None, labels)[1]
                     else:
-                        class_loss += fused_seg_losses(sem, None, labels, self.old_classes if self.unce else 1, 1.0, 0.0)[1]
+                        class_loss += fused_seg_losses(sem, None, labels, self.old_classes if self.unce else 1, 1.0, 0.0,
+                                                       focal=self.focal)[1]
                     if multi:
                         # the fused prediction is what is scored, and what on_batch sees (the rendered files show it)
                         pred = torch.empty(labels.shape, dtype=torch.int64, device=dev) if want_pred(i) else None
@@ -622,7 +637,8 @@ class Trainer:
                         # metrics without update_from_logits: the up-sampled logits only feed the arg-max, the loss stays on the kernel
                         class_loss += fused_seg_bce(sem, None, labels)[1]
                     else:
-                        class_loss += self.criterion(outputs.float(), labels.clone()).mean()
+                        ce_map = self.criterion(outputs.float(), labels.clone())
+                        class_loss += (ce_map if self.focal is None else focal_modulate(ce_map, *self.focal)).mean()
                     pred = outputs.argmax(dim=1)
                     metrics.update(labels, pred)
                     if self.bce:
