@@ -366,6 +366,52 @@ int ucd_pod_logits_forward(const void* x_s, int ld_s, const void* x_t, int ld_t,
 int ucd_pod_logits_backward(const void* x_s, int ld_s, int dtype, int B, int Ctot, int K, int h, int w, const int* scales, int n,
                             const float* g_E, const float* grad_out, float* d_x, int ld_d, ucd_stream_t stream);
 
+/* SDR's class-prototype feature losses (Michieli and Zanuttigh, CVPR 2021: prototype matching, feature clustering, prototype
+ * repulsion) on one feature level: the raw pre-logits X [M = B h w rows][C] as channels-last rows (UCD_F32 or UCD_BF16, row pitch in
+ * elements, at least C; base pointer and pitch 16-byte aligned), T classes of the step, K <= T teacher classes (csrc/proto.hip).
+ *   classify: cls[p] of the low-resolution pixel p = (b, i, j): y = labels[b, sy, sx], sy = min((int)floorf(i * ((float)H / h)), H - 1)
+ *     and sx likewise (F.interpolate(mode='nearest')); -1 where y == ignore_index or y outside [0, T); with teacher rows (sem_t [B h w]
+ *     [K] fp32, pitch ld_t >= K; NULL: no teacher) and y == 0 the first arg-max of sem_t[p, 0..K) (torch's rule; may be 0); else y.
+ *   n_c = #{p : cls_p = c}, S_c = sum_{cls_p = c} X_p, mu_c = S_c / n_c;  R_c = state_sum_c / state_n_c where state_n_c > 0 (the
+ *   running prototypes as they stood before this batch: state_sum [T, C] fp64, state_n [T] int64);  O [K, C] fp32 with old_valid [K]
+ *   bytes (non-zero: valid), the previous step's prototypes (both may be NULL for K = 0).  Every |.| is the L2 norm over C:
+ *     L_match = 1/|A|  sum_{c in A}  |mu_c - O_c|,                                  A  = {c < K : n_c > 0, valid_c}
+ *     L_attr  = 1/|Bs| sum_{c in Bs} 1/n_c sum_{cls_p = c} |X_p - R_c|^2,           Bs = {c : n_c > 0, state_n_c > 0}
+ *     L_rep   = 1/|P|  sum_{c in P}  sum_{k in P, k != c} 1 / (|mu_c - mu_k| + 1e-6),  P = {c : n_c > 0}; 0 for |P| < 2
+ *   an empty index set gives 0 and no gradient, and so does a zero distance.  X_p - R_c is formed per element: X_p == R_c on every row
+ *   gives L_attr == 0 exactly.
+ *   forward: loss_out[4] = {w_m L_match + w_a L_attr + w_r L_rep, L_match, L_attr, L_rep};  batch_sums [T, C] fp64 = S, batch_n [T]
+ *     int64 = n (what ucd_proto_update adds to the state, in a call of its own: the loss is a pure function of its arguments);
+ *     tables = a[T] | R[T, C] | G[T, C] fp32, (2 C + 1) T floats: a_c = 2 w_a / (|Bs| n_c) for c in Bs, R_c (0 where state_n_c = 0) and
+ *     G_c = d(w_m L_match + w_r L_rep) / d mu_c ALREADY divided by n_c; rows of absent classes are 0.
+ *   backward: d_x[p] = grad_out[0] * (a_c (X_p - R_c) + G_c) for c = cls_p in [0, T), 0 otherwise; d_x has the map's dtype and its own
+ *     pitch ld_d >= C.  grad_out is a device scalar.
+ *   update: state_sum += batch_sums, state_n += batch_n, element by element (fp64 and int64, no atomics).
+ * Launches: classify one; forward three - one pass over X (16-byte loads, lanes over channels; each element read once; rows in pieces
+ * of 64, ordered by class inside a piece, per-piece per-class sums of X and of (X - R_c)^2 and counts, only for the classes a piece
+ * holds), one workgroup per class that adds the pieces in index order (fp64), one workgroup per class on [T, C] (fp64 distances; the
+ * workgroup that finishes last, an integer ticket, adds the per-class values in class order); backward one (one read of X, one write
+ * of d_x, the tables from L2); update one.  |A|, |Bs| and |P| stay on the device.  Every sum has a fixed order and there is no
+ * floating-point atomic: same inputs, same bits.  No allocation, no host synchronisation: the calls capture into graphs.
+ * The plan is a pure host function (no device is touched): the forward workspace bytes (per-piece slots for min(64, T) classes: at
+ * most about 6 M C bytes, reached from T = 64 on), grid[4] = {workgroups of the pass over X, of the class kernel, of the prototype kernel, of the backward pass},
+ * lds_bytes[3] = static LDS of the three forward kernels, pieces = ceil(M / 64); output pointers may be NULL.
+ * Checked on the host before any device call, the message names the argument: UCD_EINVAL (a NULL pointer; a size below 1; a negative
+ * K; K above T; an unknown dtype; a row pitch below C, or ld_t below K), UCD_EUNSUPPORTED (C not a multiple of 8 or above 512; T above
+ * 256; M = B h w of 2^31 or more), UCD_EALIGN (x / d_x or their pitch not 16-byte aligned; another pointer not aligned to its
+ * element), UCD_EWORKSPACE (NULL, not 16-byte aligned or short workspace); else the hipError_t of a failed launch. */
+int ucd_proto_plan(long long M, int C, int T, int dtype, size_t* workspace_bytes, int* grid, int* lds_bytes, int* pieces);
+int ucd_proto_classify(const int64_t* labels, int B, int H, int W, int h, int w, int T, int K, int ignore_index, const float* sem_t,
+                       int ld_t, int32_t* cls, ucd_stream_t stream);
+int ucd_proto_forward(const void* x, int ld_x, int dtype, const int32_t* cls, long long M, int C, int T, int K, const double* state_sum,
+                      const int64_t* state_n, const float* old_proto, const unsigned char* old_valid, float w_m, float w_a, float w_r,
+                      float* loss_out, float* tables, double* batch_sums, int64_t* batch_n, void* workspace, size_t workspace_bytes,
+                      ucd_stream_t stream);
+int ucd_proto_backward(const void* x, int ld_x, int dtype, const int32_t* cls, long long M, int C, int T, const float* tables,
+                       const float* grad_out, void* d_x, int ld_d, ucd_stream_t stream);
+int ucd_proto_update(double* state_sum, int64_t* state_n, const double* batch_sums, const int64_t* batch_n, int T, int C,
+                     ucd_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Uncertainty-weighted pixel-contrastive distillation.  Replaces pre_contractive_pixel
  * (utils/utils.py:256-393; twin utils/loss.py:258-395) and PixelConLossV2.forward

@@ -27,6 +27,11 @@ METHOD_PRESETS = {
     # --pod_logits is the complete method
     "PLOP": {"pseudo": "entropy", "pseudo_adaptive": True, "pod_factor": 0.01, "pod_last_factor": 0.0005, "init_balanced": True,
              "pixcon_weight": 0.0},
+    # SDR (Michieli and Zanuttigh, CVPR 2021) without its sparsity term: MiB's unbiased losses plus prototype matching, feature
+    # clustering and prototype repulsion on the pre-logits.  The three weights are recalled from SDR's published command line and
+    # not checked against its code
+    "SDR": {"loss_kd": 10, "unce": True, "unkd": True, "init_balanced": True, "pixcon_weight": 0.0, "sdr_match": 0.01,
+            "sdr_attract": 0.001, "sdr_repel": 0.001},
 }
 NUM_CLASSES = {"voc": 21, "ade": 150, "city": 20}
 
@@ -93,6 +98,14 @@ def _focal_alpha(text):
     value = float(text)
     if not (math.isfinite(value) and value > 0.0):
         raise argparse.ArgumentTypeError(f"alpha must be finite and > 0, got {text}")
+    return value
+
+
+def _weight(text):
+    """--sdr_match / --sdr_attract / --sdr_repel: the weight of a loss term, finite and >= 0 (0: the term is off)"""
+    value = float(text)
+    if not (math.isfinite(value) and value >= 0.0):
+        raise argparse.ArgumentTypeError(f"the weight must be finite and >= 0, got {text}")
     return value
 
 
@@ -174,6 +187,11 @@ _ARGS = [
     # unbiased cross entropy is modulated, under --pseudo_adaptive the image's weight multiplies it
     _flag("--focal_loss", **_ON), _flag("--focal_loss_gamma", type=_focal_gamma, default=2.0),
     _flag("--focal_loss_alpha", type=_focal_alpha, default=1.0),
+    # SDR's class-prototype feature losses on the raw pre-logits (ucd_amd.loss.fused_proto_losses), each weight 0 = off: the batch
+    # means against the previous step's prototypes (needs a teacher), the pixels against their class's running prototype, the
+    # batch means against each other
+    _flag("--sdr_match", type=_weight, default=0.), _flag("--sdr_attract", type=_weight, default=0.),
+    _flag("--sdr_repel", type=_weight, default=0.),
     # regularisers (EWC / RW / PI; --method EWC|RW|PI): ucd_amd.regularizer, after the UCD step
     _flag("--regularizer", default=None, type=str, choices=["ewc", "rw", "pi"]),
     _flag("--reg_importance", type=float, default=1.), _flag("--reg_alpha", type=float, default=0.9),

@@ -76,7 +76,7 @@ class Conv_WgradPlan(C.Structure):
                [("workspace_bytes", C.c_size_t)]
 
 
-_p, _i, _f, _z = C.c_void_p, C.c_int, C.c_float, C.c_size_t
+_p, _i, _f, _z, _q = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_longlong
 # name -> (restype, argtypes); must list every symbol of include/ucd_hip.h (checked by the CPU tests)
 SIGNATURES = {
     "ucd_version": (_i, []),
@@ -141,6 +141,11 @@ SIGNATURES = {
     "ucd_pod_logits_plan": (_i, [_i, _i, _i, _i, _p, _i, _i, _i, _p, _p, _p]),
     "ucd_pod_logits_forward": (_i, [_p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _p, _i, _i, _f, _p, _p, _p, _z, _p]),
     "ucd_pod_logits_backward": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _p, _i, _p, _p, _p, _i, _p]),
+    "ucd_proto_plan": (_i, [_q, _i, _i, _i, _p, _p, _p, _p]),
+    "ucd_proto_classify": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _i, _p, _i, _p, _p]),
+    "ucd_proto_forward": (_i, [_p, _i, _i, _p, _q, _i, _i, _i, _p, _p, _p, _p, _f, _f, _f, _p, _p, _p, _p, _p, _z, _p]),
+    "ucd_proto_backward": (_i, [_p, _i, _i, _p, _q, _i, _i, _p, _p, _p, _i, _p]),
+    "ucd_proto_update": (_i, [_p, _p, _p, _p, _i, _i, _p]),
     "ucd_conv1x1_row_tiles": (_i, [_i]),
     "ucd_conv1x1_stats_partial_bytes": (_z, [_i, _i]),
     "ucd_conv1x1": (_i, [C.POINTER(Conv1x1Desc), _p]),
@@ -674,6 +679,65 @@ def pod_logits_plan(h, w, Ctot, K, scales=(1, 2, 4), B=1, normalize=1):
                                       C.cast(C.byref(n_E), C.c_void_p), C.cast(C.byref(nbytes), C.c_void_p), C.cast(grid, C.c_void_p)),
            "ucd_pod_logits_plan")
     return {"n_E": n_E.value, "workspace_bytes": nbytes.value, "grid": tuple(grid)}
+
+
+PROTO_MAX_C, PROTO_MAX_T = 512, 256       # what the class-prototype kernels take (csrc/proto.hip)
+
+
+def proto_plan(M, Cc, T, dtype=BF16):
+    """``ucd_proto_plan``: ``{"workspace_bytes", "grid": workgroups of (the pass over X, the class kernel, the prototype kernel, the
+    backward pass), "lds_bytes": static LDS of the three forward kernels, "pieces"}`` of the class-prototype losses on an
+    ``[M, Cc]`` map with ``T`` classes (csrc/proto.hip).  A pure host function: it answers without a GPU and raises for a shape the
+    kernels refuse."""
+    nbytes, grid, lds, pieces = C.c_size_t(0), (C.c_int * 4)(), (C.c_int * 3)(), C.c_int(0)
+    _check(load().ucd_proto_plan(int(M), int(Cc), int(T), int(dtype), C.cast(C.byref(nbytes), C.c_void_p), C.cast(grid, C.c_void_p),
+                                 C.cast(lds, C.c_void_p), C.cast(C.byref(pieces), C.c_void_p)), "ucd_proto_plan")
+    return {"workspace_bytes": nbytes.value, "grid": tuple(grid), "lds_bytes": tuple(lds), "pieces": pieces.value}
+
+
+def proto_classify(labels, sem_rows, ld_t, h, w, T, K, ignore_index=255):
+    """``ucd_proto_classify``: int32 ``cls`` [B h w] from int64 ``labels`` [B, H, W]; ``sem_rows`` are the teacher's fp32 rows
+    ``[B h w, >= K]`` with pitch ``ld_t``, or None."""
+    B, H, W = labels.shape
+    cls = torch.empty(B * h * w, dtype=torch.int32, device=labels.device)
+    with _timed("ucd_proto_classify", B * h * w * (12 + (4 * K if sem_rows is not None else 0))):
+        _check(load().ucd_proto_classify(ptr(labels), B, H, W, int(h), int(w), int(T), int(K), int(ignore_index), ptr(sem_rows), int(ld_t),
+                                         ptr(cls), stream()), "ucd_proto_classify")
+    return cls
+
+
+def proto_forward(x, ld_x, M, Cc, cls, T, K, state_sum, state_n, old_proto, old_valid, weights):
+    """``ucd_proto_forward`` on the rows ``x`` (any tensor whose storage holds ``M`` rows of pitch ``ld_x`` from its data pointer):
+    ``(loss_out [4] fp32, tables [(2 Cc + 1) T] fp32, batch_sums [T, Cc] fp64, batch_n [T] int64)``."""
+    dev = x.device
+    code = dtype_code(x)
+    out = torch.empty(4, dtype=torch.float32, device=dev)
+    tables = torch.empty((2 * Cc + 1) * T, dtype=torch.float32, device=dev)
+    sums = torch.empty(T, Cc, dtype=torch.float64, device=dev)
+    n = torch.empty(T, dtype=torch.int64, device=dev)
+    nbytes = proto_plan(M, Cc, T, code)["workspace_bytes"]
+    ws = workspace(nbytes, dev, "proto")
+    w_m, w_a, w_r = (float(v) for v in weights)
+    # one read of the map; the per-piece sums (a few classes per piece) are written and read once more
+    with _timed("ucd_proto_forward", M * Cc * x.element_size()):
+        _check(load().ucd_proto_forward(ptr(x), int(ld_x), code, ptr(cls), int(M), int(Cc), int(T), int(K), ptr(state_sum), ptr(state_n),
+                                        ptr(old_proto), ptr(old_valid), w_m, w_a, w_r, ptr(out), ptr(tables), ptr(sums), ptr(n), ptr(ws),
+                                        nbytes, stream()), "ucd_proto_forward")
+    return out, tables, sums, n
+
+
+def proto_backward(x, ld_x, M, Cc, cls, T, tables, grad_out, d_x, ld_d):
+    """``ucd_proto_backward``: writes ``d_x`` (rows of pitch ``ld_d`` in the dtype of ``x``); ``grad_out`` is a device scalar [1] fp32."""
+    with _timed("ucd_proto_backward", 2 * M * Cc * x.element_size()):
+        _check(load().ucd_proto_backward(ptr(x), int(ld_x), dtype_code(x), ptr(cls), int(M), int(Cc), int(T), ptr(tables), ptr(grad_out),
+                                         ptr(d_x), int(ld_d), stream()), "ucd_proto_backward")
+    return d_x
+
+
+def proto_update(state_sum, state_n, batch_sums, batch_n):
+    """``ucd_proto_update``: ``state_sum += batch_sums`` (fp64 [T, C]) and ``state_n += batch_n`` (int64 [T]) in one launch."""
+    T, Cc = state_sum.shape
+    _check(load().ucd_proto_update(ptr(state_sum), ptr(state_n), ptr(batch_sums), ptr(batch_n), T, Cc, stream()), "ucd_proto_update")
 
 
 def pseudo_plan(H, W, h, w, K, bins=0):

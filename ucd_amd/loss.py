@@ -451,6 +451,189 @@ def fused_seg_losses(sem, sem_old, labels, old_cl, ce_weight=1.0, kd_weight=0.0,
                                  sample_weight, focal)
 
 
+# ---- SDR's class-prototype feature losses (csrc/proto.hip) ------------------------------------------------
+def proto_classes_torch(labels, sem_t, T, K, hw, ignore_index=255):
+    """The class of every low-resolution pixel, int32 ``[B, h, w]``: the label at ``sy = min(floor(i * (float)H / h), H - 1)`` (and
+    ``sx`` likewise: ``F.interpolate(mode='nearest')``), -1 where it is ``ignore_index`` or outside ``[0, T)``; with teacher logits
+    ``sem_t`` [B, >= K, h, w] a background pixel takes the first arg-max of the teacher's first ``K`` channels.  The torch
+    composition of ``proto_classes``."""
+    h, w = int(hw[0]), int(hw[1])
+    B, H, W = labels.shape
+    dev = labels.device
+    fy, fx = torch.tensor(H, dtype=torch.float32) / h, torch.tensor(W, dtype=torch.float32) / w       # (float)H / h, in fp32
+    sy = (torch.arange(h, dtype=torch.float32) * fy).floor().long().clamp_max(H - 1).to(dev)
+    sx = (torch.arange(w, dtype=torch.float32) * fx).floor().long().clamp_max(W - 1).to(dev)
+    y = labels[:, sy][:, :, sx]
+    cls = torch.where((y == ignore_index) | (y < 0) | (y >= T), torch.full_like(y, -1), y)
+    if sem_t is not None:
+        if K < 1 or sem_t.shape[1] < K or tuple(sem_t.shape[2:]) != (h, w):
+            raise ValueError(f"teacher logits [B, >= {K}, {h}, {w}] are expected, got {tuple(sem_t.shape)}")
+        cls = torch.where(cls == 0, sem_t[:, :K].detach().float().argmax(dim=1), cls)
+    return cls.to(torch.int32)
+
+
+def proto_classes(labels, sem_t, T, K, hw, ignore_index=255):
+    """``proto_classes_torch`` as one HIP launch (ucd_proto_classify); CPU tensors, more than 256 classes and ``UCD_FUSED_PROTO=0``
+    run the composition."""
+    if labels.dim() != 3 or labels.dtype != torch.int64:
+        raise ValueError(f"int64 labels [B, H, W] are expected, got {tuple(labels.shape)} {labels.dtype}")
+    if not 0 <= K <= T:
+        raise ValueError(f"K = {K} teacher classes must be in 0 .. T = {T}")
+    h, w = int(hw[0]), int(hw[1])
+    if not labels.is_cuda or T > hip.PROTO_MAX_T or _switches.get("UCD_FUSED_PROTO", "1") == "0":
+        return proto_classes_torch(labels, sem_t, T, K, hw, ignore_index)
+    rows = None
+    if sem_t is not None:
+        if K < 1 or sem_t.shape[1] < K or tuple(sem_t.shape[2:]) != (h, w):
+            raise ValueError(f"teacher logits [B, >= {K}, {h}, {w}] are expected, got {tuple(sem_t.shape)}")
+        rows = _pseudo_rows(sem_t)
+    cls = hip.proto_classify(labels.contiguous(), rows, rows.shape[1] if rows is not None else 0, h, w, T, K, ignore_index)
+    return cls.view(labels.shape[0], h, w)
+
+
+def _safe_norm(d):
+    """L2 norm over the last dimension whose gradient at a zero distance is 0."""
+    s = (d * d).sum(dim=-1)
+    pos = s > 0
+    return torch.where(pos, torch.where(pos, s, torch.ones_like(s)).sqrt(), torch.zeros_like(s))
+
+
+def _proto_check(x, cls, state, old, weights):
+    """The argument rules of the class-prototype losses; returns (state_sum, state_n, O or None, valid or None, weights, T, K)."""
+    if x.dim() != 4:
+        raise ValueError(f"a feature map [B, C, h, w] is expected, got {tuple(x.shape)}")
+    B, Cc, h, w = x.shape
+    if tuple(cls.shape) != (B, h, w) or cls.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"cls must be an integer [{B}, {h}, {w}] map, got {tuple(cls.shape)} {cls.dtype}")
+    state_sum, state_n = state
+    if state_sum.dim() != 2 or state_sum.shape[1] != Cc or state_sum.dtype != torch.float64 or tuple(state_n.shape) != (state_sum.shape[0],) \
+            or state_n.dtype != torch.int64:
+        raise ValueError(f"the state is (float64 [T, {Cc}], int64 [T]), got {tuple(state_sum.shape)} {state_sum.dtype} and "
+                         f"{tuple(state_n.shape)} {state_n.dtype}")
+    T = state_sum.shape[0]
+    O = valid = None
+    K = 0
+    if old is not None and old[0] is not None and old[0].shape[0] > 0:
+        O, valid = old
+        K = O.shape[0]
+        if O.dim() != 2 or O.shape[1] != Cc or K > T or tuple(valid.shape) != (K,) or valid.dtype != torch.bool:
+            raise ValueError(f"the old prototypes are ([K <= {T}, {Cc}], bool [K]), got {tuple(O.shape)} and {tuple(valid.shape)} {valid.dtype}")
+    weights = tuple(float(v) for v in weights)
+    if len(weights) != 3 or not all(math.isfinite(v) and v >= 0.0 for v in weights):
+        raise ValueError(f"the weights (match, attract, repel) must be three finite values >= 0, got {weights}")
+    return state_sum, state_n, O, valid, weights, T, K
+
+
+def proto_losses_torch(x, cls, state, old, weights):
+    """``fused_proto_losses`` as a differentiable torch composition (``index_add_`` over the rows and ``[T, T, C]`` broadcasts):
+    serves CPU tensors, shapes the kernels refuse and ``UCD_FUSED_PROTO=0``.  fp64 maps stay fp64 (the tests); half-precision maps
+    compute in fp32, with the running prototypes rounded to fp32 as the kernels' tables hold them.  On the GPU ``index_add_`` adds
+    with float atomics, so two runs agree to the rounding of re-ordered sums, not bit for bit."""
+    state_sum, state_n, O, valid, (w_m, w_a, w_r), T, K = _proto_check(x, cls, state, old, weights)
+    B, Cc, h, w = x.shape
+    X = _wide(x).permute(0, 2, 3, 1).reshape(B * h * w, Cc)
+    c = cls.reshape(-1).long()
+    has = (c >= 0) & (c < T)
+    idx = torch.where(has, c, torch.zeros_like(c))
+    hasf = has.to(X.dtype)
+    n = torch.zeros(T, dtype=X.dtype, device=X.device).index_add_(0, idx, hasf)
+    S = torch.zeros(T, Cc, dtype=X.dtype, device=X.device).index_add_(0, idx, X * hasf.unsqueeze(1))
+    present = n > 0
+    nn_ = n.clamp_min(1.0)
+    mu = S / nn_.unsqueeze(1)
+    zero = X.new_zeros(())
+    l_match = zero
+    if K > 0:
+        A = present[:K] & valid.to(X.device)
+        d = _safe_norm(mu[:K] - O.to(device=X.device, dtype=X.dtype))
+        l_match = torch.where(A, d, torch.zeros_like(d)).sum() / A.sum().clamp_min(1).to(X.dtype)
+    seen = state_n.to(X.device) > 0
+    Bs = present & seen
+    R = (state_sum.to(X.device) / state_n.to(X.device).clamp_min(1).unsqueeze(1).double())
+    R = R.to(X.dtype) if X.dtype == torch.float64 else R.float().to(X.dtype)
+    R = torch.where(seen.unsqueeze(1), R, torch.zeros_like(R))
+    diff = X - R[idx]
+    sq = (diff * diff).sum(dim=1) * (has & Bs[idx]).to(X.dtype)
+    per_class = torch.zeros(T, dtype=X.dtype, device=X.device).index_add_(0, idx, sq) / nn_
+    l_attr = per_class.sum() / Bs.sum().clamp_min(1).to(X.dtype)
+    D = _safe_norm(mu.unsqueeze(1) - mu.unsqueeze(0))
+    pair = present.unsqueeze(1) & present.unsqueeze(0) & ~torch.eye(T, dtype=torch.bool, device=X.device)
+    l_rep = torch.where(pair, 1.0 / (D + 1e-6), torch.zeros_like(D)).sum() / present.sum().clamp_min(1).to(X.dtype)
+    total = w_m * l_match + w_a * l_attr + w_r * l_rep
+    parts = {"match": l_match.detach(), "attract": l_attr.detach(), "repel": l_rep.detach(),
+             "sums": S.detach().double(), "n": n.detach().round().long()}
+    return total, parts
+
+
+class _FusedProto(torch.autograd.Function):
+    """The weighted class-prototype losses on the HIP kernels (ucd_proto_forward / ucd_proto_backward, csrc/proto.hip): three
+    launches forward, one backward.  The forward keeps the tables ``a | R | G`` ((2 C + 1) T floats) and no copy of the map."""
+
+    @staticmethod
+    def forward(ctx, x, cls, state_sum, state_n, O, valid, weights):
+        xs, M, Cc, HW, ld = hip.rows_view(x.detach())
+        T = state_sum.shape[0]
+        K = 0 if O is None else O.shape[0]
+        out, tables, sums, n = hip.proto_forward(xs, ld, M, Cc, cls, T, K, state_sum, state_n, O, valid, weights)
+        ctx.save_for_backward(xs, cls, tables)
+        ctx.meta = (ld, T)
+        vals = out[1:]
+        ctx.mark_non_differentiable(vals, sums, n)
+        return out[0], vals, sums, n
+
+    @staticmethod
+    def backward(ctx, grad, *unused):
+        xs, cls, tables = ctx.saved_tensors
+        ld, T = ctx.meta
+        B, Cc, h, w = xs.shape
+        go = grad.detach().reshape(1).to(torch.float32).contiguous()
+        d = hip.empty_like_rows(xs)
+        hip.proto_backward(xs, ld, B * h * w, Cc, cls, T, tables, go, d, Cc)
+        return d, None, None, None, None, None, None
+
+
+def proto_kernels_take(x, T):
+    """Do the class-prototype kernels serve this map?  bf16 or fp32 on a GPU, C a multiple of 8 up to 512, at most 256 classes
+    (ucd_proto_plan states the same bounds)."""
+    return (x.is_cuda and x.dtype in (torch.bfloat16, torch.float32) and x.shape[1] % 8 == 0 and x.shape[1] <= hip.PROTO_MAX_C
+            and T <= hip.PROTO_MAX_T and x.shape[0] * x.shape[2] * x.shape[3] < 2 ** 31)
+
+
+def fused_proto_losses(x, cls, state, old, weights):
+    """SDR's class-prototype feature losses on the raw pre-logits ``x`` [B, C, h, w]: ``(total, parts)`` with ``total = w_m L_match +
+    w_a L_attr + w_r L_rep`` (differentiable w.r.t. ``x``) and ``parts = {"match", "attract", "repel"`` (the three unweighted values),
+    ``"sums"`` [T, C] fp64, ``"n"`` [T] int64 (this batch's per-class sums and counts: what ``proto_update`` adds to the state)``}``.
+
+    ``cls`` [B, h, w] is the class map of ``proto_classes`` (-1: none); ``state = (sum [T, C] fp64, N [T] int64)`` the running
+    prototypes as they stood before this batch; ``old = (O [K, C] fp32, valid [K] bool)`` the previous step's prototypes, or None;
+    ``weights = (w_m, w_a, w_r)``.  ``L_match`` is the mean distance of the batch means to the valid old prototypes, ``L_attr`` the
+    mean over classes of the mean squared distance of a class's pixels to its running prototype, ``L_rep`` the mean over present
+    classes of ``sum_k 1 / (|mu_c - mu_k| + 1e-6)``; an empty index set and a zero distance give 0 and no gradient.  On the GPU
+    it is three HIP launches forward and one backward (csrc/proto.hip), fixed summation order; CPU tensors, shapes the kernels
+    refuse (``proto_kernels_take``) and ``UCD_FUSED_PROTO=0`` run ``proto_losses_torch``."""
+    state_sum, state_n, O, valid, weights, T, K = _proto_check(x, cls, state, old, weights)
+    if not proto_kernels_take(x, T) or _switches.get("UCD_FUSED_PROTO", "1") == "0":
+        return proto_losses_torch(x, cls, state, old, weights)
+    dev = x.device
+    if O is not None:
+        O = O.detach().to(device=dev, dtype=torch.float32).contiguous()
+        valid = valid.to(dev).contiguous()
+    cls32 = cls.to(torch.int32).contiguous().view(-1)
+    total, vals, sums, n = _FusedProto.apply(x, cls32, state_sum.contiguous(), state_n.contiguous(), O, valid, weights)
+    return total, {"match": vals[0], "attract": vals[1], "repel": vals[2], "sums": sums, "n": n}
+
+
+def proto_update(state, parts):
+    """``sum += parts["sums"]``, ``N += parts["n"]`` in place (ucd_proto_update on the GPU: one launch, fp64 and int64)."""
+    state_sum, state_n = state
+    if state_sum.is_cuda and state_sum.shape[0] <= hip.PROTO_MAX_T and state_sum.shape[1] <= hip.PROTO_MAX_C \
+            and _switches.get("UCD_FUSED_PROTO", "1") != "0":
+        hip.proto_update(state_sum, state_n, parts["sums"].contiguous(), parts["n"].contiguous())
+    else:
+        state_sum += parts["sums"].to(state_sum.dtype)
+        state_n += parts["n"].to(state_n.dtype)
+
+
 # ---- PLOP's pseudo-labelling (csrc/pseudo_label.hip, DESIGN.md section 3.5.9) ------------------------------------------------------
 def _pseudo_check(sem_old, labels):
     if sem_old.dim() != 4 or labels.dim() != 3 or labels.shape[0] != sem_old.shape[0] or labels.dtype != torch.int64:

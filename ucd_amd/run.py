@@ -291,6 +291,12 @@ def main(opts):
         else:
             logger.info("Pseudo-label thresholds from the checkpoint: "
                         + " ".join(f"{t:.4f}" for t in trainer.pseudo_thresholds.tolist()))
+    if trainer.proto_flag and trainer.proto_w[0] > 0. and not opts.test:
+        if trainer.proto_old is None:                                     # one pass of the teacher over the training set
+            trainer.find_prototypes(train_loader, logger)
+        else:
+            logger.info(f"Class prototypes of the old model from the trainer state: {int(trainer.proto_old[1].sum())} of "
+                        f"{trainer.old_classes} classes are valid")
     ckpt_path = f"checkpoints/step/{task_name}_{opts.name}_{opts.step}.pth"
     sample_ids = None
     if rank == 0 and opts.sample_num > 0:                                 # run.py:269-273: batches whose first image is kept

@@ -36,7 +36,8 @@ DEFAULTS = {
     "UCD_FUSED_POD": "1",          # Local POD feature distillation (--pod_factor) on csrc/pod.hip: one trip over each tapped map forward, one read + one write backward; with --pod_logits also the level on the logits (0: the torch compositions local_pod_torch / local_pod_logits_torch)
     "UCD_FUSED_PSEUDO": "1",       # PLOP's pseudo-labelling (--pseudo entropy) on csrc/pseudo_label.hip: labels, per-image factor and the threshold histogram from the low-resolution teacher rows, one launch each (0: the torch composition pseudo_labels_torch / pseudo_hist_torch on the up-sampled [B, K, H, W] logits)
     "UCD_FUSED_FOCAL": "1",        # focal cross entropy (--focal_loss) inside the fused logit-loss kernels (ucd_seg_losses_focal / ucd_seg_losses_gather_focal): the modulation is a few scalar operations on the pixel's log-probability (0: the torch composition focal_modulate on the cross-entropy map of the up-sampled [B, Ctot, H, W] logits)
-    "UCD_VAL_DEVICE": "1",         # validation transforms (Resize + CenterCrop, full size) as ucd_val_image_path / ucd_val_label_path on raw samples (0: Pillow on the host per sample + the train path with the identity box; torch launches for the full image)
+    "UCD_FUSED_PROTO": "1",        # SDR's class-prototype feature losses (--sdr_match / --sdr_attract / --sdr_repel) on csrc/proto.hip: one launch for the classes of the low-resolution pixels, three forward (one pass over the pre-logits), one backward, one for the running prototypes (0: the torch compositions proto_classes_torch / proto_losses_torch)
+    "UCD_VAL_DEVICE": "1",        # validation transforms (Resize + CenterCrop, full size) as ucd_val_image_path / ucd_val_label_path on raw samples (0: Pillow on the host per sample + the train path with the identity box; torch launches for the full image)
     "UCD_STEM_EVAL_FUSED": "1",    # frozen-statistics stem (the teacher): conv1 + norm + activation + max pool as one kernel (0: two kernels)
     "UCD_STEM_FOLD": "1",          # stem norm + max-pool as one pass
     "UCD_ABN_NODE": "1",           # C++ autograd nodes

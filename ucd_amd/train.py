@@ -39,7 +39,8 @@ from . import switches as _switches
 from .contrastive import ucd_contrastive_loss
 from .loss import (KnowledgeDistillationLoss, UnbiasedCrossEntropy, UnbiasedKnowledgeDistillationLoss,
                    POD_SCALES, fused_attn_mse, fused_local_pod, fused_local_pod_logits, fused_pseudo_labels, fused_seg_bce,
-                   fused_seg_losses, pseudo_hist, pseudo_median, _focal_check, focal_modulate)
+                   fused_seg_losses, pseudo_hist, pseudo_median, _focal_check, focal_modulate, fused_proto_losses, proto_classes,
+                   proto_update)
 
 
 def _raw(features, name):
@@ -120,6 +121,24 @@ class Trainer:
                 raise NotImplementedError("--focal_loss with --bce / --icarl: the focal modulation is defined on the soft-max cross "
                                           "entropy only")
             self.focal = _focal_check(getattr(opts, "focal_loss_gamma", 2.0), getattr(opts, "focal_loss_alpha", 1.0))
+        # SDR's class-prototype feature losses (--sdr_match / --sdr_attract / --sdr_repel) on the raw pre-logits: the batch means
+        # against the previous step's prototypes (needs a teacher; alone it requests nothing), the pixels against their class's
+        # running prototype, the batch means against each other - one fused HIP operation (ucd_amd.loss.fused_proto_losses).  The
+        # running prototypes (proto_sum fp64 [T, C], proto_n int64 [T]) are device tensors allocated once: a captured step graph
+        # reads and updates them by address; they travel in the trainer state
+        self.proto_w = (float(getattr(opts, "sdr_match", 0.) or 0.) if model_old is not None else 0.,
+                        float(getattr(opts, "sdr_attract", 0.) or 0.), float(getattr(opts, "sdr_repel", 0.) or 0.))
+        self.proto_flag = any(v > 0. for v in self.proto_w)
+        self.proto_sum = self.proto_n = self.proto_old = None
+        if self.proto_flag:
+            channels = getattr(getattr(model, "module", model), "head_channels", None)
+            if channels is not None:
+                self._alloc_proto(int(channels))
+            # the previous step's state holds exactly the old model's prototypes (unlike the pseudo thresholds, which belong to the
+            # current teacher); without one, find_prototypes makes them from the teacher
+            prev = trainer_state.get("proto") if trainer_state is not None else None
+            if self.proto_w[0] > 0. and prev is not None:
+                self._old_from_state(prev)
         self.lkd = opts.loss_kd
         self.lkd_flag = self.lkd > 0. and model_old is not None
         self.lkd_loss = (UnbiasedKnowledgeDistillationLoss if opts.unkd else KnowledgeDistillationLoss)(alpha=opts.alpha)
@@ -425,7 +444,18 @@ class Trainer:
         if self.pod_flag:
             lpod = self._local_pod(features, features_old)
             loss_tot = loss_tot + lpod
+        if self.proto_flag:
+            # the class of every low-resolution pixel (a background pixel takes the teacher's arg-max), then the three terms
+            x_pl = _raw(features, "pre_logits")
+            if self.proto_sum is None:
+                self._alloc_proto(x_pl.shape[1])
+            sem_t = features_old["sem"] if model_old is not None else None
+            proto_cls = proto_classes(labels, sem_t, self.tot_classes, sem_t.shape[1] if sem_t is not None else 0, x_pl.shape[-2:])
+            lproto, proto_parts = fused_proto_losses(x_pl, proto_cls, (self.proto_sum, self.proto_n), self.proto_old, self.proto_w)
+            loss_tot = loss_tot + lproto
         loss_tot.backward()
+        if self.proto_flag:
+            proto_update((self.proto_sum, self.proto_n), proto_parts)        # the step used the state as it stood before this batch
         if hasattr(model, "finish_grad_sync"):
             model.finish_grad_sync()
         if self.regularizer_flag:
@@ -440,6 +470,8 @@ class Trainer:
             self.last["reg"] = l_reg.detach()
         if self.pod_flag:
             self.last["LPOD"] = lpod.detach()
+        if self.proto_flag:
+            self.last["PROTO"] = lproto.detach()
         if self.pseudo_flag:
             kept = pseudo_counts.sum(dim=0).float()
             self.last["pseudo_kept"] = kept[0] / kept[1].clamp_min(1.0)      # share of the candidates that took a pseudo-label
@@ -481,6 +513,9 @@ class Trainer:
             train_loader.sampler.set_epoch(cur_epoch)
         self.model.train()
         n = 0
+        multi_rank = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
+        proto_start = ((self.proto_sum.clone(), self.proto_n.clone()) if self.proto_flag and multi_rank and self.proto_sum is not None
+                       else None)
         for cur_step, (images, labels) in enumerate(train_loader):
             r = self.train_step(images, labels, optim, scheduler)
             epoch_loss += r["loss"]
@@ -495,6 +530,9 @@ class Trainer:
             if "LPOD" in r:                                     # the Local POD term counts as regularisation loss, next to lkd / lde
                 reg_loss += r["LPOD"]
                 interval += r["LPOD"]
+            if "PROTO" in r:                                    # the class-prototype terms count as regularisation loss too
+                reg_loss += r["PROTO"]
+                interval += r["PROTO"]
             n += 1
             if (cur_step + 1) % print_int == 0:
                 value = (interval / print_int).item()           # the only host sync of the interval
@@ -508,8 +546,12 @@ class Trainer:
                         # run logs what it always did
                         logger.debug(f"Loss made of: CE {r['loss'].item()}, LKD {r['lkd'].item()}, LDE {r['lde'].item()}, "
                                      f"LPOD {r['LPOD'].item()}")
+                    if "PROTO" in r and getattr(logger, "debug_flag", False):
+                        logger.debug(f"PROTO {r['PROTO'].item()}")             # --debug only: the read synchronises
                     logger.add_scalar("Loss", value, cur_epoch * len(train_loader) + cur_step + 1)
                 interval.zero_()
+        if proto_start is not None:
+            self._merge_proto(*proto_start)
         if dist.is_available() and dist.is_initialized():
             if n:
                 torch.cuda.synchronize() if dev.type == "cuda" else None
@@ -766,8 +808,99 @@ class Trainer:
             self.pseudo_thresholds = thresholds.clone()
         self.pseudo_hist = hist.to(self.device)
 
+    # -- SDR's class prototypes -------------------------------------------------------------------------------------------
+    def _alloc_proto(self, channels):
+        self.proto_sum = torch.zeros(self.tot_classes, channels, dtype=torch.float64, device=self.device)
+        self.proto_n = torch.zeros(self.tot_classes, dtype=torch.int64, device=self.device)
+
+    def _set_proto_old(self, O, valid):
+        """New values go INTO the tensors where they exist (``_set_pseudo``'s rule): a captured step graph reads them by address."""
+        O = O.to(self.device, dtype=torch.float32)
+        valid = valid.to(self.device, dtype=torch.bool)
+        if self.proto_old is not None and self.proto_old[0].shape == O.shape:
+            self.proto_old[0].copy_(O)
+            self.proto_old[1].copy_(valid)
+        else:
+            if getattr(self, "_sg", None) is not None:
+                raise RuntimeError("the old prototypes changed their shape under a captured step graph")
+            self.proto_old = (O.clone(), valid.clone())
+
+    def _old_from_state(self, prev):
+        """O and valid from rows 0 .. K-1 of a previous step's running prototypes (``state_dict()["proto"]``); a state of another
+        feature width, or of fewer classes than the teacher has, is not used."""
+        K = self.old_classes
+        s, n = prev["sum"], prev["n"]
+        if K < 1 or s.dim() != 2 or s.shape[0] < K or (self.proto_sum is not None and s.shape[1] != self.proto_sum.shape[1]):
+            return False
+        s, n = s[:K].double(), n[:K].long()
+        valid = n > 0
+        O = torch.where(valid.unsqueeze(1), s / n.clamp_min(1).unsqueeze(1).double(), torch.zeros_like(s))
+        self._set_proto_old(O, valid)
+        return True
+
+    def _merge_proto(self, start_sum, start_n):
+        """Every rank accumulated its own increments since ``start``: one all-reduce of the increments (sum and N), outside the step
+        graph, leaves the same state on every rank."""
+        inc_sum, inc_n = self.proto_sum - start_sum, self.proto_n - start_n
+        dist.all_reduce(inc_sum)
+        dist.all_reduce(inc_n)
+        self.proto_sum.copy_(start_sum + inc_sum)
+        self.proto_n.copy_(start_n + inc_n)
+
+    @torch.no_grad()
+    def find_prototypes(self, loader, logger=None):
+        """One pass of the frozen teacher (eval mode) over ``loader``: the per-class sums of ITS raw pre-logits over the classes of
+        its low-resolution pixels (a background pixel takes the teacher's arg-max, a new-class pixel none) - classify, the forward call
+        with zero weights and the update, as in a step - summed over the ranks; leaves ``proto_old = (O, valid)`` and returns the
+        number of valid classes.  Follows ``find_pseudo_thresholds``."""
+        if not (self.proto_flag and self.proto_w[0] > 0. and self.model_old is not None):
+            raise RuntimeError("find_prototypes needs --sdr_match and a teacher")
+        K = self.old_classes
+        state = None
+        self.model_old.eval()
+        if self._teacher_w16 is not None:
+            self._teacher_w16.refresh_if_stale()
+        for images, labels in loader:
+            images = images.to(self.device, dtype=torch.float32)
+            labels = labels.to(self.device, dtype=torch.long)
+            if self.device.type == "cuda":
+                images = images.contiguous(memory_format=torch.channels_last)
+            _, feats = self._teacher_eager(images, {"upsample": False} if self.fuse_logit_losses else {})
+            x_pl = _raw(feats, "pre_logits")
+            if state is None:
+                state = (torch.zeros(K, x_pl.shape[1], dtype=torch.float64, device=self.device),
+                         torch.zeros(K, dtype=torch.int64, device=self.device))
+            cls = proto_classes(labels, feats["sem"], K, K, x_pl.shape[-2:])
+            _, parts = fused_proto_losses(x_pl, cls, state, None, (0., 0., 0.))
+            proto_update(state, parts)
+        if state is None:
+            raise RuntimeError("find_prototypes: the loader is empty")
+        if dist.is_available() and dist.is_initialized():
+            dist.all_reduce(state[0])
+            dist.all_reduce(state[1])
+        self._old_from_state({"sum": state[0], "n": state[1]})
+        count = int(self.proto_old[1].sum().item())
+        if logger is not None:
+            logger.info(f"Class prototypes of the old model: {count} of {K} classes are valid")
+        return count
+
+    def _load_proto(self, state):
+        if state is None or not self.proto_flag:
+            return
+        if self.proto_sum is None:
+            self._alloc_proto(state["sum"].shape[1])
+        if state["sum"].shape == self.proto_sum.shape:          # (a state of another class split is not this step's)
+            self.proto_sum.copy_(state["sum"])
+            self.proto_n.copy_(state["n"])
+            if state.get("old") is not None and self.proto_w[0] > 0.:
+                self._set_proto_old(state["old"], state["old_valid"])
+
     def state_dict(self):
         state = {"regularizer": self.regularizer.state_dict() if self.regularizer_flag else None}
+        if self.proto_flag and self.proto_sum is not None:
+            state["proto"] = {"sum": self.proto_sum.cpu(), "n": self.proto_n.cpu(),
+                              "old": None if self.proto_old is None else self.proto_old[0].cpu(),
+                              "old_valid": None if self.proto_old is None else self.proto_old[1].cpu()}
         if self.pseudo_thresholds is not None:              # a resumed run does not repeat the pass over the training set
             state["pseudo"] = {"thresholds": self.pseudo_thresholds.cpu(), "hist": self.pseudo_hist.cpu()}
         return state
@@ -776,3 +909,4 @@ class Trainer:
         if state["regularizer"] is not None and self.regularizer is not None:
             self.regularizer.load_state_dict(state["regularizer"])
         self._load_pseudo(state.get("pseudo"))
+        self._load_proto(state.get("proto"))
